@@ -13,6 +13,11 @@ exchange + merge with its exactness rule (auriclass_amd.multigpu.sharded_sketch)
   strong scaling (--total-reads T): T reads in all, rank r owns records [r*T/N, (r+1)*T/N)
                                (BASELINE.json configs[3] / SURVEY 8(d) C4: --total-reads 80000000).
 Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the --steps steps and prints the line (`roofline`, `cpu_baseline` and
+`parity_on_sample` are null).  --full adds what takes runs of its own after the timed steps: the event-timed kernel passes
+of `roofline`, the CPU baseline with its parity check against the C oracle (N = 1), and the sharded == unsharded gate
+(N > 1).  --dump-outputs DIR writes the sketch of the last timed step as float64 .npy files (dump_outputs).
 """
 from __future__ import annotations
 
@@ -32,6 +37,22 @@ sys.path.insert(0, str(ROOT))
 from auriclass_amd import engine, multigpu, synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, hashes: np.ndarray, counts: np.ndarray) -> None:
+    """--dump-outputs: what the timed path hands its caller (the sorted sketch hashes and their multiplicities) as float64
+    arrays that two builds can be compared on exactly: every 64-bit hash split into its high and low 32 bits (both exact in
+    float64), the counts, and index.npy, the entries' positions in the sketch.  A sketch beyond the 64 MB budget is written
+    as a fixed, seeded sample of its entries (index.npy says which)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(hashes)
+    cap = (DUMP_LIMIT_BYTES - 4 * 1024) // (4 * 8)   # four float64 arrays per entry, room for their .npy headers
+    idx = np.arange(n, dtype=np.int64) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    h = hashes[idx].astype(np.uint64)
+    arrays = {"hashes_hi32": h >> np.uint64(32), "hashes_lo32": h & np.uint64(0xFFFFFFFF), "counts": counts[idx], "index": idx}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def cpu_baseline_run(sample: np.ndarray, rb: int, k: int, s: int, m: int, cores: int):
@@ -178,10 +199,16 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dump-sketch", default="", help="rank 0 saves the final sketch (hashes, counts) to this .npz")
     ap.add_argument("--no-parity", action="store_true", help="N > 1: skip the sharded == unsharded check (rank 0 re-sketches all shards)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the CPU baseline + parity (N = 1) and the sharded gate (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the sketch of the last timed step to DIR/<name>.npy (float64)")
     # ranks started by this script's own launcher get their arguments through the environment: torch.distributed.run's
     # parser claims abbreviations of its own options even behind the script name (`--s` -> "ambiguous option")
     forwarded = os.environ.get("MHX_BENCH_ARGV") if "WORLD_SIZE" in os.environ else None
     args = ap.parse_args(json.loads(forwarded)) if forwarded else ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     nproc = os.cpu_count() or 1
     try:
@@ -294,13 +321,15 @@ def main() -> None:
         total_bases = int(tb.item())
     value = total_bases / (elapsed / args.steps) / 1e9
     ranks_in_group = dist.get_world_size() if use_dist else 1
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result[0], result[1])
 
-    # ---- dominant kernel: HIP events on the engine's stream around every tile-kernel launch --
+    # ---- --full: dominant kernel: HIP events on the engine's stream around every tile-kernel launch --
     roofline = None
     cpu_baseline = None
     parity = None
     parity_kind = None
-    if rank == 0:
+    if rank == 0 and args.full:
         engine.set_profiling(True)
         ms = []
         for _ in range(3):

@@ -22,7 +22,7 @@ def _bench(*argv, gloo=True):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if gloo:
         env["MHX_DIST_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), *argv], env=env, cwd=str(ROOT), capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", *argv], env=env, cwd=str(ROOT), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     for key in CONTRACT:

@@ -174,7 +174,7 @@ def test_bench_prints_the_contract_line():
     import sys
 
     root = Path(__file__).resolve().parent.parent
-    out = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "200000",
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--reads", "200000",
                           "--cpu-sample-reads", "100000", "--cpu-cores", "2"],
                          capture_output=True, text=True, timeout=600, cwd=str(root))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -190,3 +190,32 @@ def test_bench_prints_the_contract_line():
     c = j["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 2 and c["value"] > 0
     assert j["parity_on_sample"] is True
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_sketch(tmp_path):
+    """A plain `python bench.py` (no --full) runs exactly --steps timed steps, leaves the --full extras null, and
+    --dump-outputs writes the sketch of the last timed step as float64 arrays equal to --dump-sketch's, bit for bit."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = Path(__file__).resolve().parent.parent
+    outs, npz = tmp_path / "outs", tmp_path / "sketch.npz"
+    out = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--reads", "200000",
+                          "--dump-outputs", str(outs), "--dump-sketch", str(npz)],
+                         capture_output=True, text=True, timeout=600, cwd=str(root))
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 200000 * 150 / (j["ms_per_step"] * 1e-3) / 1e9) < 0.01 * j["value"]
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity_on_sample"] is None
+    got = {p.stem: np.load(p) for p in outs.glob("*.npy")}
+    assert sorted(got) == ["counts", "hashes_hi32", "hashes_lo32", "index"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    want = np.load(npz)
+    assert len(want["hashes"]) == j["sketch_len"] == 1000
+    h = (got["hashes_hi32"].astype(np.uint64) << np.uint64(32)) | got["hashes_lo32"].astype(np.uint64)
+    assert np.array_equal(h, want["hashes"]) and np.array_equal(got["counts"], want["counts"].astype(np.float64))
+    assert np.array_equal(got["index"], np.arange(1000))

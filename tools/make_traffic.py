@@ -15,7 +15,7 @@ wr = sum(v.get("hbm_write_bytes_per_step", 0.0) for v in tile.values())
 valu = sum(v.get("SQ_INSTS_VALU", 0.0) for v in tile.values()) / steps
 gui = sum(v.get("GRBM_GUI_ACTIVE", 0.0) for v in tile.values()) / steps / 8.0   # summed over the 8 XCDs
 bl = json.loads(open(line).read().strip().splitlines()[-1])
-passes = bl["steps"] + bl["warmup"] + 3   # bench.py: warmup + timed + 3 event-timed passes
+passes = bl["steps"] + bl["warmup"] + 3   # bench.py --full: warmup + timed + 3 event-timed passes
 tile_ns = 0.0
 for r in csv.DictReader(open(trace)):
     if "sketch_tile_kernel" in r["Name"]:

@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/${TAG}_bench_line.json
-python bench.py --no-cpu-baseline --m 3 > $O/bench_m3.log 2>&1; tail -1 $O/bench_m3.log > $O/${TAG}_bench_line_m3.json
-python bench.py --no-cpu-baseline --k 27 --s 50000 --m 3 > $O/bench_k27.log 2>&1; tail -1 $O/bench_k27.log > $O/${TAG}_bench_line_k27_s50000_m3.json
+python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/${TAG}_bench_line.json
+python bench.py --full --no-cpu-baseline --m 3 > $O/bench_m3.log 2>&1; tail -1 $O/bench_m3.log > $O/${TAG}_bench_line_m3.json
+python bench.py --full --no-cpu-baseline --k 27 --s 50000 --m 3 > $O/bench_k27.log 2>&1; tail -1 $O/bench_k27.log > $O/${TAG}_bench_line_k27_s50000_m3.json
 tools/profile.sh > $O/profile.log 2>&1
 cp gpurun_out/prof/summary_pmc_summary.json $O/${TAG}_pmc_summary.json
 cp gpurun_out/prof/summary_kernel_stats_trace.csv $O/${TAG}_kernel_stats_trace.csv

@@ -9,7 +9,7 @@ cd $R
 O=gpurun_out/$TAG
 mkdir -p $O
 # sustained clocks: the same step 1200 times (> 5 s of kernels back to back)
-python bench.py --no-cpu-baseline --steps 1200 --warmup 5 2>&1 | tail -1 > $O/${TAG}_bench_line_sustained_1200_steps.json
+python bench.py --full --no-cpu-baseline --steps 1200 --warmup 5 2>&1 | tail -1 > $O/${TAG}_bench_line_sustained_1200_steps.json
 # the sharded path: merge cost on one rank with the GPU to itself, then 5 ranks sharing the GPU (gloo) through bench.py
 python tools/merge_time.py 2>&1 | grep -v amdgpu.ids > $O/${TAG}_sharded_merge_time.txt
 tools/rehearse_ranks.sh $O 5 > $O/rehearse.log 2>&1
