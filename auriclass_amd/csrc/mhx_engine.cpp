@@ -38,7 +38,7 @@ int fail(int code, const char *fmt, ...)
 }
 void clear_error() { g_err.clear(); }
 
-Engine g;
+Engine &g = *new Engine; // never deleted: see Engine
 
 int require_engine()
 {
@@ -64,9 +64,9 @@ extern "C" int mhx_init(int device)
     if (device >= n) return fail(MHX_E_ARG, "mhx_init: device %d out of range (%d visible)", device, n);
     if (g.ready) mhx_shutdown();
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&g.ev0));
-    HIPCHK(hipEventCreate(&g.ev1));
+    HIPCHK(hipStreamCreateWithFlags(g.stream.out(), hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(g.ev0.out()));
+    HIPCHK(hipEventCreate(g.ev1.out()));
     g.device = device;
     g.ready = true;
     return MHX_OK;
@@ -76,32 +76,8 @@ extern "C" void mhx_shutdown(void)
 {
     if (!g.ready) return;
     hipStreamSynchronize(g.stream);
-    if (g.fasta.sk) mhx_sketcher_destroy(g.fasta.sk);
-    for (int i = 0; i < 2; ++i) { hipFree(g.fasta.d_raw[i]); if (g.fasta.raw_ready[i]) hipEventDestroy(g.fasta.raw_ready[i]); }
-    hipFree(g.fasta.d_out); hipFree(g.fasta.d_ws); hipFree(g.fasta.d_seps);
-    if (g.fasta.h_words) hipHostFree(g.fasta.h_words);
-    hipFree(g.dist_ws);
-    if (g.dist_img) hipHostFree(g.dist_img);
-    g.dist_img = nullptr;
-    g.dist_img_cap = 0;
-    hipFree(g.dist_in);
-    for (void *p : g.ingest_pinned) hipHostFree(p);
-    for (int i = 0; i < 2; ++i) {
-        hipFree(g.ingest_slot[i]);
-        if (g.ingest_copied[i]) hipEventDestroy(g.ingest_copied[i]);
-        if (g.ingest_consumed[i]) hipEventDestroy(g.ingest_consumed[i]);
-    }
-    if (g.ingest_word) hipHostFree(g.ingest_word);
     if (g.copy_stream) hipStreamSynchronize(g.copy_stream);
-    for (int i = 0; i < Engine::kPinnedSlots; ++i) {
-        if (g.pinned[i]) hipHostFree(g.pinned[i]);
-        if (g.pinned_free[i]) hipEventDestroy(g.pinned_free[i]);
-    }
-    if (g.copy_stream) hipStreamDestroy(g.copy_stream);
-    hipEventDestroy(g.ev0);
-    hipEventDestroy(g.ev1);
-    hipStreamDestroy(g.stream);
-    g = Engine();
+    (void)std::exchange(g, Engine()); // the old state goes at the end of this statement, its streams last
 }
 
 extern "C" int mhx_device_name(char *buf, size_t cap)
@@ -139,49 +115,46 @@ struct mhx_sketcher {
     uint64_t hash_max = 0;   // largest representable hash (2^64-1 or 2^32-1)
     uint64_t t_init = 0;     // initial admission threshold (everything admitted)
     // device
-    uint64_t *d_keys = nullptr;
-    uint32_t *d_cnts = nullptr;
-    uint64_t *d_thresh = nullptr;
-    uint32_t *d_hist = nullptr;
-    uint64_t *d_acc = nullptr;
-    uint64_t *d_stats = nullptr;   // kStatReplicas x kStatCount
-    uint32_t *d_tickets = nullptr; // one per tile launch since the last reset (kTicketWords of them)
+    DevArray<uint64_t> d_keys;
+    DevArray<uint32_t> d_cnts;
+    DevArray<uint64_t> d_thresh;
+    DevArray<uint32_t> d_hist;
+    DevArray<uint64_t> d_acc;
+    DevArray<uint64_t> d_stats;   // kStatReplicas x kStatCount
+    DevArray<uint32_t> d_tickets; // one per tile launch since the last reset (kTicketWords of them)
     uint32_t tickets_used = 0;
-    uint32_t *d_done = nullptr;    // ticket of the tighten pass
-    uint8_t *d_phase_rec = nullptr; // FASTQ: phase_record() per tile of the span being pushed (chain check)
-    uint32_t phase_rec_cap = 0;
-    uint32_t *d_need = nullptr;    // FASTQ: some tile could not find its line phase by itself -> repair pass due
+    DevArray<uint32_t> d_done;    // ticket of the tighten pass
+    DevArray<uint8_t> d_phase_rec; // FASTQ: phase_record() per tile of the span being pushed (chain check)
+    DevArray<uint32_t> d_need;    // FASTQ: some tile could not find its line phase by itself -> repair pass due
     struct Span { const void *ptr; uint64_t n; };
     std::vector<Span> unsettled;   // FASTQ pushes whose repair question is still open (their buffers are valid until the next sync)
-    uint64_t *d_tile_state = nullptr;
-    size_t tile_state_cap = 0;
-    uint8_t *d_stage = nullptr;
-    size_t stage_cap = 0;
-    uint64_t *d_out_keys = nullptr;
-    uint32_t *d_out_cnts = nullptr;
-    uint32_t *d_out_n = nullptr;
-    uint32_t out_cap = 0;
+    DevArray<uint64_t> d_tile_state;
+    DevArray<uint8_t> d_stage;
+    DevArray<uint64_t> d_out_keys;
+    DevArray<uint32_t> d_out_cnts;
+    DevArray<uint32_t> d_out_n;
+    uint32_t out_cap() const { return (uint32_t)std::min(d_out_keys.cap(), d_out_cnts.cap()); }
     // sharded path: header of the shard export [n, T, flags, #(2^64-1), occupied, 0, 0, 0], accumulated on the device and
     // handed to the pinned mirror by the extract kernel itself (the entries stay in d_out_keys / d_out_cnts)
-    uint64_t *d_exp_hdr = nullptr, *h_exp_hdr = nullptr;
+    DevArray<uint64_t> d_exp_hdr;
+    PinnedArray<uint64_t> h_exp_hdr;
     uint64_t exported = 0;     // entries of the last export_begin (valid until the next push / reset)
     bool export_valid = false;
     bool merged = false;       // merge_slabs has added other shards' entries to the table: reset before the next push
-    uint64_t *d_merge_in = nullptr; // staging of gathered slabs that arrive in host memory (gloo)
-    size_t merge_in_cap = 0;
+    DevArray<uint64_t> d_merge_in; // staging of gathered slabs that arrive in host memory (gloo)
     // workspace of the binned merge (mhx_merge.hip): per-bin cursors / counts / flags (kept zero between merges by the
     // kernels), bin regions
-    uint32_t *d_mg_small = nullptr;  // [kMergeMaxBins] cursor | [kMergeMaxBins] qn | [16] flags
-    uint64_t *d_mg_keys = nullptr;
-    uint32_t *d_mg_cnts = nullptr;
-    size_t mg_entries = 0;
+    DevArray<uint32_t> d_mg_small;  // [kMergeMaxBins] cursor | [kMergeMaxBins] qn | [16] flags
+    DevArray<uint64_t> d_mg_keys;
+    DevArray<uint32_t> d_mg_cnts;
     // finish(): one device block [n, T, flags, #(2^64-1) | hashes[fin_cap] | counts[fin_cap]] and its pinned host
     // mirror, so the result comes back in ONE copy (five separate copies cost 20-60 us of idle gap each)
-    uint64_t *d_fin = nullptr, *h_fin = nullptr;
+    DevArray<uint64_t> d_fin;
+    PinnedArray<uint64_t> h_fin;
     uint32_t fin_cap = 0;
     // large sketches: a second block, the first in (almost) hash order (launch_order_block), and its bucket counters
-    uint64_t *d_fin_ordered = nullptr;
-    uint32_t *d_order_buckets = nullptr, *d_order_starts = nullptr, *d_order_groups = nullptr;
+    DevArray<uint64_t> d_fin_ordered;
+    DevArray<uint32_t> d_order_buckets, d_order_starts, d_order_groups;
     uint32_t order_log2 = 0;
     bool table_dirty = true;   // tiles have been hashed since the last EXACT tighten pass
     bool table_sampled = false; // ... but a sampled pass has run after the last of them: T is valid and ~s' solid hashes lie below it
@@ -219,23 +192,6 @@ static TableArgs table_args(mhx_sketcher *sk)
     t.sample = 1;
     t.next_cap = 0;
     return t;
-}
-
-static void free_sketcher(mhx_sketcher *sk)
-{
-    if (!sk) return;
-    hipFree(sk->d_keys); hipFree(sk->d_cnts); hipFree(sk->d_thresh); hipFree(sk->d_hist); hipFree(sk->d_acc);
-    hipFree(sk->d_stats); hipFree(sk->d_tickets); hipFree(sk->d_done); hipFree(sk->d_need); hipFree(sk->d_phase_rec); hipFree(sk->d_tile_state); hipFree(sk->d_stage);
-    hipFree(sk->d_out_keys); hipFree(sk->d_out_cnts); hipFree(sk->d_out_n);
-    hipFree(sk->d_exp_hdr); hipFree(sk->d_merge_in); hipFree(sk->d_mg_small); hipFree(sk->d_mg_keys); hipFree(sk->d_mg_cnts);
-    if (sk->h_exp_hdr) hipHostFree(sk->h_exp_hdr);
-    hipFree(sk->d_fin);
-    hipFree(sk->d_fin_ordered);
-    hipFree(sk->d_order_buckets);
-    hipFree(sk->d_order_starts);
-    hipFree(sk->d_order_groups);
-    if (sk->h_fin) hipHostFree(sk->h_fin);
-    delete sk;
 }
 
 static uint64_t next_pow2(uint64_t v)
@@ -287,7 +243,7 @@ int create_sketcher(int k, uint32_t s, uint32_t min_mult, uint64_t expected_byte
     if (!out) return fail(MHX_E_ARG, "null out pointer");
     if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
     if (s == 0) return fail(MHX_E_ARG, "sketch size must be positive");
-    mhx_sketcher *sk = new mhx_sketcher();
+    std::unique_ptr<mhx_sketcher> sk(new mhx_sketcher());
     sk->k = k; sk->s = s; sk->m = min_mult ? min_mult : 1;
     sk->hash32 = k <= 16;
     sk->hash_max = sk->hash32 ? 0xFFFFFFFFull : ~0ull;
@@ -308,46 +264,43 @@ int create_sketcher(int k, uint32_t s, uint32_t min_mult, uint64_t expected_byte
     want *= table_scale;
     if (want > (1ull << 30)) want = 1ull << 30; // 12.9 GB of table at most
     sk->nslots = next_pow2(want);
-    sk->out_cap = s * 2 + 65536;
+    const size_t out_cap = s * 2 + 65536;
     hipError_t e = hipSuccess;
-    auto A = [&](void **p, size_t n) { if (e == hipSuccess) e = hipMalloc(p, n); };
-    A((void **)&sk->d_keys, sk->nslots * sizeof(uint64_t));
-    A((void **)&sk->d_cnts, sk->nslots * sizeof(uint32_t));
-    A((void **)&sk->d_thresh, sizeof(uint64_t));
-    A((void **)&sk->d_hist, kHistBins * sizeof(uint32_t));
-    A((void **)&sk->d_acc, kAccReplicas * 8 * sizeof(uint64_t));
-    A((void **)&sk->d_stats, kStatReplicas * kStatCount * sizeof(uint64_t));
-    A((void **)&sk->d_tickets, kTicketWords * sizeof(uint32_t));
-    A((void **)&sk->d_done, sizeof(uint32_t));
-    A((void **)&sk->d_need, sizeof(uint32_t));
-    A((void **)&sk->d_out_keys, sk->out_cap * sizeof(uint64_t));
-    A((void **)&sk->d_out_cnts, sk->out_cap * sizeof(uint32_t));
-    A((void **)&sk->d_out_n, sizeof(uint32_t));
-    A((void **)&sk->d_exp_hdr, 8 * sizeof(uint64_t));
+    auto A = [&](auto &arr, size_t n) { if (e == hipSuccess) e = arr.grow(n); };
+    A(sk->d_keys, sk->nslots);
+    A(sk->d_cnts, sk->nslots);
+    A(sk->d_thresh, 1);
+    A(sk->d_hist, kHistBins);
+    A(sk->d_acc, kAccReplicas * 8);
+    A(sk->d_stats, kStatReplicas * kStatCount);
+    A(sk->d_tickets, kTicketWords);
+    A(sk->d_done, 1);
+    A(sk->d_need, 1);
+    A(sk->d_out_keys, out_cap);
+    A(sk->d_out_cnts, out_cap);
+    A(sk->d_out_n, 1);
+    A(sk->d_exp_hdr, 8);
     if (e == hipSuccess) e = hipMemset(sk->d_exp_hdr, 0, 8 * sizeof(uint64_t)); // zero between two exports (the kernel clears them)
-    if (e == hipSuccess) e = hipHostMalloc((void **)&sk->h_exp_hdr, 8 * sizeof(uint64_t), hipHostMallocDefault);
+    A(sk->h_exp_hdr, 8);
     sk->fin_cap = (s + 16u * (uint32_t)sqrt((double)s) + 4096u + 1u) & ~1u; // what a sampled threshold leaves, with room (finish())
-    const size_t fin_bytes = (4 + (size_t)sk->fin_cap + sk->fin_cap / 2) * sizeof(uint64_t);
-    A((void **)&sk->d_fin, fin_bytes);
+    const size_t fin_words = 4 + (size_t)sk->fin_cap + sk->fin_cap / 2;
+    A(sk->d_fin, fin_words);
     if (e == hipSuccess) e = hipMemset(sk->d_fin, 0, 4 * sizeof(uint64_t)); // the header words are zero between two finish() calls
     if (s >= kDeviceOrderMinSketch) { // below that the host's bucket sort costs less than three more launches
         sk->order_log2 = 12;
         while ((1u << sk->order_log2) < sk->fin_cap && sk->order_log2 < 20) ++sk->order_log2;
-        A((void **)&sk->d_fin_ordered, fin_bytes);
-        A((void **)&sk->d_order_buckets, ((size_t)1 << sk->order_log2) * sizeof(uint32_t));
-        A((void **)&sk->d_order_starts, (((size_t)1 << sk->order_log2) + 4) * sizeof(uint32_t));
-        A((void **)&sk->d_order_groups, 1024 * sizeof(uint32_t));
+        A(sk->d_fin_ordered, fin_words);
+        A(sk->d_order_buckets, (size_t)1 << sk->order_log2);
+        A(sk->d_order_starts, ((size_t)1 << sk->order_log2) + 4);
+        A(sk->d_order_groups, 1024);
         if (e == hipSuccess) e = hipMemset(sk->d_order_starts, 0, (((size_t)1 << sk->order_log2) + 4) * sizeof(uint32_t)); // [nbuckets] stays zero
         if (e == hipSuccess) e = hipMemset(sk->d_order_buckets, 0, ((size_t)1 << sk->order_log2) * sizeof(uint32_t)); // every finish() leaves them zero again
     }
-    if (e == hipSuccess) e = hipHostMalloc((void **)&sk->h_fin, fin_bytes, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        free_sketcher(sk);
-        return fail(MHX_E_HIP, "hipMalloc failed while creating the sketcher: %s", hipGetErrorString(e));
-    }
-    rc = mhx_sketcher_reset(sk);
-    if (rc) { free_sketcher(sk); return rc; }
-    *out = sk;
+    A(sk->h_fin, fin_words);
+    if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed while creating the sketcher: %s", hipGetErrorString(e));
+    rc = mhx_sketcher_reset(sk.get());
+    if (rc) return rc;
+    *out = sk.release();
     return MHX_OK;
 }
 
@@ -364,7 +317,7 @@ extern "C" int mhx_sketcher_create_scaled(int k, uint32_t s, uint32_t min_mult, 
 extern "C" void mhx_sketcher_destroy(mhx_sketcher *sk)
 {
     if (g.ready) hipStreamSynchronize(g.stream);
-    free_sketcher(sk);
+    delete sk;
 }
 
 static int read_threshold(mhx_sketcher *sk, uint64_t *T)
@@ -403,7 +356,7 @@ static int repair_unsettled(mhx_sketcher *sk)
 static int settle(mhx_sketcher *sk)
 {
     if (sk->unsettled.empty()) return MHX_OK;
-    uint32_t *need = reinterpret_cast<uint32_t *>(sk->h_fin); // pinned landing word
+    uint32_t *need = reinterpret_cast<uint32_t *>((uint64_t *)sk->h_fin); // pinned landing word
     HIPCHK(hipMemcpyAsync(need, sk->d_need, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
     if (*need) {
@@ -476,14 +429,7 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
     if (ntiles64 > 0x7FFFFFFFull) return fail(MHX_E_ARG, "span too large for one push (%llu bytes)", (unsigned long long)n);
     const uint32_t ntiles = (uint32_t)ntiles64;
     if (kfmt == 1) {
-        if (sk->tile_state_cap < ntiles) {
-            HIPCHK(hipStreamSynchronize(g.stream));
-            hipFree(sk->d_tile_state);
-            sk->d_tile_state = nullptr;
-            sk->tile_state_cap = 0;
-            HIPCHK(hipMalloc((void **)&sk->d_tile_state, (size_t)ntiles * sizeof(uint64_t)));
-            sk->tile_state_cap = ntiles;
-        }
+        HIPCHK(sk->d_tile_state.grow(ntiles, g.stream));
         HIPCHK(hipMemsetAsync(sk->d_tile_state, 0, (size_t)ntiles * sizeof(uint64_t), g.stream));
         if (sk->tickets_used + kMaxLaunchesPerPush > kTicketWords) { // every launch takes a fresh, still zero word
             HIPCHK(hipMemsetAsync(sk->d_tickets, 0, kTicketWords * sizeof(uint32_t), g.stream));
@@ -491,16 +437,7 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
         }
     }
     a.tile_state = sk->d_tile_state;
-    if (kfmt == 2 || repair) { // every tile of the span writes its record: nothing to clear
-        if (sk->phase_rec_cap < ntiles) {
-            HIPCHK(hipStreamSynchronize(g.stream));
-            hipFree(sk->d_phase_rec);
-            sk->d_phase_rec = nullptr;
-            sk->phase_rec_cap = 0;
-            HIPCHK(hipMalloc((void **)&sk->d_phase_rec, (size_t)ntiles));
-            sk->phase_rec_cap = ntiles;
-        }
-    }
+    if (kfmt == 2 || repair) HIPCHK(sk->d_phase_rec.grow(ntiles, g.stream)); // every tile of the span writes its record: nothing to clear
     a.phase_rec = sk->d_phase_rec;
     TableArgs ta = table_args(sk);
     if (sk->nslots >= (1ull << 23) && !getenv("MHX_EXACT_TIGHTEN")) ta.sample = 8; // big tables: sampled passes between chunks (finish() counts exactly)
@@ -623,14 +560,7 @@ extern "C" int mhx_sketcher_push_host(mhx_sketcher *sk, const void *h_bytes, uin
     rc = settle(sk);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
-    if (sk->stage_cap < n + 64) {
-        hipFree(sk->d_stage);
-        sk->d_stage = nullptr;
-        sk->stage_cap = 0;
-        const size_t cap = (size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1));
-        HIPCHK(hipMalloc((void **)&sk->d_stage, cap));
-        sk->stage_cap = cap;
-    }
+    if (sk->d_stage.cap() < n + 64) HIPCHK(sk->d_stage.grow((size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1))));
     HIPCHK(hipMemcpyAsync(sk->d_stage, h_bytes, n, hipMemcpyHostToDevice, g.stream));
     return mhx_sketcher_push_device(sk, sk->d_stage, n, fmt);
 }
@@ -747,16 +677,13 @@ static int extract(mhx_sketcher *sk, uint64_t limit, uint32_t min_count, std::ve
 {
     for (int attempt = 0; attempt < 2; ++attempt) {
         HIPCHK(hipMemsetAsync(sk->d_out_n, 0, sizeof(uint32_t), g.stream));
-        HIPCHK(launch_extract(table_args(sk), limit, min_count, sk->d_out_keys, sk->d_out_cnts, sk->out_cap, sk->d_out_n, nullptr, nullptr, nullptr, nullptr, g.stream));
+        HIPCHK(launch_extract(table_args(sk), limit, min_count, sk->d_out_keys, sk->d_out_cnts, sk->out_cap(), sk->d_out_n, nullptr, nullptr, nullptr, nullptr, g.stream));
         uint32_t n = 0;
         HIPCHK(hipMemcpyAsync(&n, sk->d_out_n, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
-        if (n > sk->out_cap) { // grow once and repeat
-            hipFree(sk->d_out_keys); hipFree(sk->d_out_cnts);
-            sk->d_out_keys = nullptr; sk->d_out_cnts = nullptr;
-            sk->out_cap = n + 1024;
-            HIPCHK(hipMalloc((void **)&sk->d_out_keys, (size_t)sk->out_cap * sizeof(uint64_t)));
-            HIPCHK(hipMalloc((void **)&sk->d_out_cnts, (size_t)sk->out_cap * sizeof(uint32_t)));
+        if (n > sk->out_cap()) { // grow once and repeat
+            HIPCHK(sk->d_out_keys.grow(n + 1024));
+            HIPCHK(sk->d_out_cnts.grow(n + 1024));
             continue;
         }
         keys.resize(n);
@@ -985,17 +912,14 @@ static int export_begin_impl(mhx_sketcher *sk, uint64_t *header8)
     for (int attempt = 0; attempt < 2; ++attempt) {
         // one kernel: entries to d_out_keys / d_out_cnts, the five header words accumulated on the device and stored
         // into the pinned mirror (and cleared for the next call) by the workgroup that finishes last
-        HIPCHK(launch_extract(table_args(sk), 0, 1, sk->d_out_keys, sk->d_out_cnts, sk->out_cap, (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3,
+        HIPCHK(launch_extract(table_args(sk), 0, 1, sk->d_out_keys, sk->d_out_cnts, sk->out_cap(), (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3,
                               g.stream, nullptr, 0, d, sk->h_exp_hdr, sk->d_done, d + 4, 5));
         HIPCHK(hipStreamSynchronize(g.stream));
         const uint64_t n = sk->h_exp_hdr[0];
-        if (n > sk->out_cap) { // grow (with room for the next, similar shard) and repeat once
-            hipFree(sk->d_out_keys); hipFree(sk->d_out_cnts);
-            sk->d_out_keys = nullptr; sk->d_out_cnts = nullptr;
+        if (n > sk->out_cap()) { // grow (with room for the next, similar shard) and repeat once
             if (n + n / 4 + 1024 > 0xFFFFFFF0ull) return fail(MHX_E_CAPACITY, "export: %llu entries", (unsigned long long)n);
-            sk->out_cap = (uint32_t)(n + n / 4 + 1024);
-            HIPCHK(hipMalloc((void **)&sk->d_out_keys, (size_t)sk->out_cap * sizeof(uint64_t)));
-            HIPCHK(hipMalloc((void **)&sk->d_out_cnts, (size_t)sk->out_cap * sizeof(uint32_t)));
+            HIPCHK(sk->d_out_keys.grow(n + n / 4 + 1024));
+            HIPCHK(sk->d_out_cnts.grow(n + n / 4 + 1024));
             continue;
         }
         for (int i = 0; i < 5; ++i) header8[i] = sk->h_exp_hdr[i];
@@ -1064,15 +988,8 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
     const uint64_t *d_slabs = (const uint64_t *)slabs;
     if (!slabs_on_device && (others || headers[8 * (size_t)own_rank])) {
         const size_t bytes = (size_t)n_ranks * slab_words * sizeof(uint64_t);
-        if (sk->merge_in_cap < bytes) {
-            HIPCHK(hipStreamSynchronize(g.stream));
-            hipFree(sk->d_merge_in);
-            sk->d_merge_in = nullptr;
-            sk->merge_in_cap = 0;
-            const size_t cap = (bytes + bytes / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-            HIPCHK(hipMalloc((void **)&sk->d_merge_in, cap));
-            sk->merge_in_cap = cap;
-        }
+        if (sk->d_merge_in.cap() * sizeof(uint64_t) < bytes)
+            HIPCHK(sk->d_merge_in.grow(((bytes + bytes / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1)) / sizeof(uint64_t), g.stream));
         HIPCHK(hipMemcpyAsync(sk->d_merge_in, slabs, bytes, hipMemcpyHostToDevice, g.stream));
         d_slabs = sk->d_merge_in;
     }
@@ -1096,19 +1013,13 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
         while ((uint64_t)a.table_slots * 3 / 4 < a.region) a.table_slots <<= 1;
         if (a.table_slots <= kMergeMaxSlots) {
             if (!sk->d_mg_small) {
-                HIPCHK(hipMalloc((void **)&sk->d_mg_small, (2 * (size_t)kMergeMaxBins + 16) * sizeof(uint32_t)));
+                HIPCHK(sk->d_mg_small.grow(2 * (size_t)kMergeMaxBins + 16));
                 HIPCHK(hipMemsetAsync(sk->d_mg_small, 0, (2 * (size_t)kMergeMaxBins + 16) * sizeof(uint32_t), g.stream));
             }
             const size_t need = (size_t)nbins * a.region;
-            if (sk->mg_entries < need) {
-                HIPCHK(hipStreamSynchronize(g.stream));
-                hipFree(sk->d_mg_keys); hipFree(sk->d_mg_cnts);
-                sk->d_mg_keys = nullptr; sk->d_mg_cnts = nullptr;
-                sk->mg_entries = 0;
-                const size_t want = need + need / 4;
-                HIPCHK(hipMalloc((void **)&sk->d_mg_keys, want * sizeof(uint64_t)));
-                HIPCHK(hipMalloc((void **)&sk->d_mg_cnts, want * sizeof(uint32_t)));
-                sk->mg_entries = want;
+            if (std::min(sk->d_mg_keys.cap(), sk->d_mg_cnts.cap()) < need) {
+                HIPCHK(sk->d_mg_keys.grow(need + need / 4, g.stream));
+                HIPCHK(sk->d_mg_cnts.grow(need + need / 4));
             }
             a.slabs = d_slabs; a.slab_words = slab_words; a.cap = cap_entries; a.hdr_words = hdr_words; a.nranks = n_ranks; a.min_mult = sk->m; a.t_min = t_min; a.nbins = nbins;
             uint64_t max_all = 0;
@@ -1329,14 +1240,9 @@ extern "C" int mhx_last_dist_fallback_blocks(void) { return g.last_dist_fallback
 // call cost more than the kernels of an AuriClass-sized comparison (1 query x 24 references).
 static int dist_stage(size_t bytes, uint8_t **out)
 {
-    if (g.dist_in_cap < bytes) {
-        HIPCHK(hipStreamSynchronize(g.stream));
-        hipFree(g.dist_in);
-        g.dist_in = nullptr;
-        g.dist_in_cap = 0;
+    if (g.dist_in.cap() < bytes) {
         const size_t cap = (bytes + bytes / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-        if (hipMalloc((void **)&g.dist_in, cap) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed in dist_batch (%zu bytes)", cap);
-        g.dist_in_cap = cap;
+        if (g.dist_in.grow(cap, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed in dist_batch (%zu bytes)", cap);
     }
     *out = g.dist_in;
     return MHX_OK;
@@ -1415,14 +1321,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     if (fast) {
         size_t oq, orr, oc, op;
         const size_t need = dist_work_bytes(qbatch, nr < 32 ? nr : 32, &oq, &orr, &oc, &op) + (size_t)std::min(nblocks, kBlockGroup) * 8;
-        if (g.dist_ws_cap < need) {
-            HIPCHK(hipStreamSynchronize(g.stream));
-            hipFree(g.dist_ws);
-            g.dist_ws = nullptr;
-            g.dist_ws_cap = 0;
-            if (hipMalloc((void **)&g.dist_ws, need) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the distance workspace");
-            g.dist_ws_cap = need;
-        }
+        if (g.dist_ws.grow(need, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the distance workspace");
         w.offs_q = (uint32_t *)(g.dist_ws + oq); w.offs_r = (uint32_t *)(g.dist_ws + orr);
         w.cpart = g.dist_ws + oc;
         d_params = (uint32_t *)(g.dist_ws + op); // [block][2]: shift, overflow flag

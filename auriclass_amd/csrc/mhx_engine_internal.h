@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <memory>
+#include <utility>
 #include <vector>
 
 #include "mhx_internal.h"
@@ -16,52 +18,119 @@ namespace mhx {
         if (e_ != hipSuccess) return fail(MHX_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// ---- owners of HIP resources ----------------------------------------------------------
+// Move-only; each releases what it holds in its destructor and when it is assigned to.  They convert to the raw handle,
+// so kernels and copies take them as they are.
+template <class T, bool Pinned>
+class HipArray { // device (Pinned = false) or pinned host array of T, with its capacity in elements
+  public:
+    HipArray() = default;
+    HipArray(T *p, size_t n) : p_(p), n_(n) {} // takes over an allocation of n elements of the same kind
+    HipArray(HipArray &&o) noexcept { *this = std::move(o); }
+    HipArray &operator=(HipArray &&o) noexcept
+    {
+        if (this != &o) { reset(); p_ = std::exchange(o.p_, nullptr); n_ = std::exchange(o.n_, 0); }
+        return *this;
+    }
+    ~HipArray() { reset(); }
+    operator T *() const { return p_; }
+    size_t cap() const { return n_; }
+    T *release() { n_ = 0; return std::exchange(p_, nullptr); }
+    void reset()
+    {
+        if (p_) { if (Pinned) hipHostFree(p_); else hipFree(p_); }
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // room for n elements: nothing to do if there is; otherwise `sync` (if any) is synchronised, the old array freed and n
+    // elements allocated -- the caller decides n.  On failure the array is empty.
+    hipError_t grow(size_t n, hipStream_t sync = nullptr)
+    {
+        if (n_ >= n) return hipSuccess;
+        if (sync) { const hipError_t e = hipStreamSynchronize(sync); if (e != hipSuccess) return e; }
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void **)&p_, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p_, n * sizeof(T));
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        n_ = n;
+        return hipSuccess;
+    }
+
+  private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+template <class T> using DevArray = HipArray<T, false>;
+template <class T> using PinnedArray = HipArray<T, true>;
+
+inline void hip_destroy(hipEvent_t e) { hipEventDestroy(e); }
+inline void hip_destroy(hipStream_t s) { hipStreamDestroy(s); }
+template <class H>
+class HipHandle { // a hipEvent_t or a hipStream_t
+  public:
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept { *this = std::move(o); }
+    HipHandle &operator=(HipHandle &&o) noexcept
+    {
+        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); }
+        return *this;
+    }
+    ~HipHandle() { reset(); }
+    operator H() const { return h_; }
+    H *out() { reset(); return &h_; } // for the create call: hipEventCreate(ev.out())
+    void reset() { if (h_) hip_destroy(h_); h_ = nullptr; }
+
+  private:
+    H h_ = nullptr;
+};
+using HipEvent = HipHandle<hipEvent_t>;
+using HipStream = HipHandle<hipStream_t>;
+
+struct SketcherDestroy { void operator()(mhx_sketcher *sk) const { mhx_sketcher_destroy(sk); } };
+using SketcherPtr = std::unique_ptr<mhx_sketcher, SketcherDestroy>;
+
 // FASTA through the device parser (mhx_files.cpp), kept between files and calls: device buffers sized to the largest file
 // seen, one sketcher per (k, s) that is reset between files (no hipMalloc / hipFree and no 200 MB table set-up per file)
 constexpr uint32_t kFastaSepsInline = 4096; // record positions that come back with the first synchronisation
 struct FastaCtx {
-    uint8_t *d_raw[2] = {nullptr, nullptr}; // file i uses d_raw[i & 1]: file i + 1 is copied in while file i is parsed and sketched
-    hipEvent_t raw_ready[2] = {nullptr, nullptr};
-    uint8_t *d_out = nullptr, *d_ws = nullptr;
-    uint64_t *d_seps = nullptr;
-    size_t raw_cap = 0, ws_cap = 0;
-    uint32_t seps_cap = 0;
-    uint64_t *h_words = nullptr; // pinned: [0] stream size, [1] {format flag, #separators}, [2 ..) the first kFastaSepsInline separators
-    mhx_sketcher *sk = nullptr;
+    DevArray<uint8_t> d_raw[2]; // file i uses d_raw[i & 1]: file i + 1 is copied in while file i is parsed and sketched
+    HipEvent raw_ready[2];
+    DevArray<uint8_t> d_out, d_ws;
+    DevArray<uint64_t> d_seps;
+    PinnedArray<uint64_t> h_words; // [0] stream size, [1] {format flag, #separators}, [2 ..) the first kFastaSepsInline separators
+    SketcherPtr sk;
     int k = 0;
     uint32_t s = 0;
     uint64_t scale = 0;
 };
 
 // ---- engine state ---------------------------------------------------------------------
+// The streams come first: they are released last.  The one Engine (g) is never destroyed -- at exit the HIP runtime may
+// be gone already; mhx_shutdown releases everything while it is not.
 struct Engine {
+    HipStream stream;
+    HipStream copy_stream; // bulk file ingest and the FASTA loader (created on first use)
     bool ready = false;
     int device = -1;
-    hipStream_t stream = nullptr;
     bool profiling = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HipEvent ev0, ev1;
     double last_dist_ms = 0.0;
-    uint8_t *dist_ws = nullptr; // workspace of the all-vs-refs distance path
-    size_t dist_ws_cap = 0;
-    uint8_t *dist_in = nullptr; // staging of a host-pointer distance batch (rows, lengths, outputs)
-    size_t dist_in_cap = 0;
+    DevArray<uint8_t> dist_ws; // workspace of the all-vs-refs distance path
+    DevArray<uint8_t> dist_in; // staging of a host-pointer distance batch (rows, lengths, outputs)
     int last_dist_fallbacks = 0;
-    uint8_t *dist_img = nullptr; // pinned image of the reference sketch file of mhx_dist_files
-    size_t dist_img_cap = 0;
-    // bulk file ingest: pinned staging ring + copy stream (allocated on first use, kept)
+    PinnedArray<uint8_t> dist_img; // pinned image of the reference sketch file of mhx_dist_files
+    // bulk file ingest: pinned staging ring (allocated on first use, kept)
     static constexpr int kPinnedSlots = 4;
-    uint8_t *pinned[kPinnedSlots] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t pinned_free[kPinnedSlots] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
+    PinnedArray<uint8_t> pinned[kPinnedSlots];
+    HipEvent pinned_free[kPinnedSlots];
     FastaCtx fasta;
     // chunked ingest (.gz FASTQ): pinned host buffers kept between calls, two device slots with their events, a pinned word
     static constexpr size_t kIngestPinnedKeep = 12;
-    std::vector<void *> ingest_pinned;
-    uint8_t *ingest_slot[2] = {nullptr, nullptr};
-    hipEvent_t ingest_copied[2] = {nullptr, nullptr}, ingest_consumed[2] = {nullptr, nullptr};
-    uint32_t *ingest_word = nullptr;
+    std::vector<PinnedArray<uint8_t>> ingest_pinned;
+    DevArray<uint8_t> ingest_slot[2];
+    HipEvent ingest_copied[2], ingest_consumed[2];
+    PinnedArray<uint32_t> ingest_word;
 };
-extern Engine g;
+extern Engine &g;
 int require_engine();
 
 } // namespace mhx

@@ -129,7 +129,7 @@ class BufPool {
     ~BufPool()
     {
         for (auto &b : spare_) {
-            if (b.pinned && g.ready && g.ingest_pinned.size() < Engine::kIngestPinnedKeep) g.ingest_pinned.push_back(b.p);
+            if (b.pinned && g.ready && g.ingest_pinned.size() < Engine::kIngestPinnedKeep) g.ingest_pinned.emplace_back(b.p, bytes_);
             else if (b.pinned) hipHostFree(b.p);
             else free(b.p);
         }
@@ -143,7 +143,7 @@ class BufPool {
             cv_.wait(lk);
         }
         ++allocated_;
-        if (!g.ingest_pinned.empty()) { HostBuf b{(uint8_t *)g.ingest_pinned.back(), true}; g.ingest_pinned.pop_back(); return b; }
+        if (!g.ingest_pinned.empty()) { HostBuf b{g.ingest_pinned.back().release(), true}; g.ingest_pinned.pop_back(); return b; }
         lk.unlock();
         HostBuf b;
         static const bool no_pin = getenv("MHX_INGEST_PAGEABLE") != nullptr;
@@ -227,8 +227,8 @@ class ChunkQueue {
   private:
     std::mutex m_;
     std::condition_variable ready_, room_;
+    BufPool pool_; // before q_: chunks still queued (after an abort) hand their buffers back to it
     std::deque<IngestChunk> q_;
-    BufPool pool_;
     int live_ = 0;
     bool abort_ = false;
 };
@@ -612,7 +612,7 @@ namespace {
 constexpr size_t kBulkBlock = 64u << 20;
 
 struct BulkFile {
-    uint8_t *d_buf = nullptr;
+    DevArray<uint8_t> d_buf;
     uint64_t size = 0;
     std::vector<uint8_t> head; // first bytes of the file (record name / comment)
     std::vector<uint8_t> tail; // its last bytes (is the last record complete?)
@@ -620,10 +620,10 @@ struct BulkFile {
 
 static int ensure_pinned_ring()
 {
-    if (!g.copy_stream) HIPCHK(hipStreamCreateWithFlags(&g.copy_stream, hipStreamNonBlocking));
+    if (!g.copy_stream) HIPCHK(hipStreamCreateWithFlags(g.copy_stream.out(), hipStreamNonBlocking));
     for (int i = 0; i < Engine::kPinnedSlots; ++i) {
-        if (!g.pinned[i]) HIPCHK(hipHostMalloc((void **)&g.pinned[i], kBulkBlock, hipHostMallocDefault));
-        if (!g.pinned_free[i]) HIPCHK(hipEventCreateWithFlags(&g.pinned_free[i], hipEventDisableTiming));
+        HIPCHK(g.pinned[i].grow(kBulkBlock));
+        if (!g.pinned_free[i]) HIPCHK(hipEventCreateWithFlags(g.pinned_free[i].out(), hipEventDisableTiming));
     }
     return MHX_OK;
 }
@@ -668,10 +668,9 @@ static int bulk_load_plain(const char *path, BulkFile *f)
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(MHX_E_IO, "ERROR: could not open %s for reading", path);
     f->size = (uint64_t)sb.st_size;
-    if (hipMalloc((void **)&f->d_buf, f->size + 64) != hipSuccess) { // tolerated: forget the sticky error, take the chunked path
+    if (f->d_buf.grow(f->size + 64) != hipSuccess) { // tolerated: forget the sticky error, take the chunked path
         (void)hipGetLastError();
         close(fd);
-        f->d_buf = nullptr;
         return MHX_OK;
     }
     int nthreads = std::min(16, ingest_thread_budget()); // pread threads: beyond 16 the page cache copy does not get faster
@@ -681,13 +680,14 @@ static int bulk_load_plain(const char *path, BulkFile *f)
     while (off < f->size && !rc) {
         const size_t len = (size_t)std::min<uint64_t>(kBulkBlock, f->size - off);
         if (hipEventSynchronize(g.pinned_free[slot]) != hipSuccess) { rc = fail(MHX_E_HIP, "pinned slot wait failed"); break; }
-        if (!parallel_pread(fd, g.pinned[slot], off, len, len >= (8u << 20) ? nthreads : 1)) { rc = fail(MHX_E_IO, "ERROR: reading %s failed", path); break; }
-        if (off == 0) f->head.assign(g.pinned[slot], g.pinned[slot] + std::min<size_t>(len, 1u << 20));
+        uint8_t *const block = g.pinned[slot];
+        if (!parallel_pread(fd, block, off, len, len >= (8u << 20) ? nthreads : 1)) { rc = fail(MHX_E_IO, "ERROR: reading %s failed", path); break; }
+        if (off == 0) f->head.assign(block, block + std::min<size_t>(len, 1u << 20));
         if (off + len >= f->size) { // the last block: keep the file's last bytes (and what the block before it contributed, if this one is short)
             const size_t keep = std::min<size_t>(len, 1u << 16);
-            f->tail.assign(g.pinned[slot] + len - keep, g.pinned[slot] + len);
+            f->tail.assign(block + len - keep, block + len);
         }
-        if (hipMemcpyAsync(f->d_buf + off, g.pinned[slot], len, hipMemcpyHostToDevice, g.copy_stream) != hipSuccess ||
+        if (hipMemcpyAsync(f->d_buf + off, block, len, hipMemcpyHostToDevice, g.copy_stream) != hipSuccess ||
             hipEventRecord(g.pinned_free[slot], g.copy_stream) != hipSuccess) { rc = fail(MHX_E_HIP, "H2D copy failed"); break; }
         off += len;
         slot = (slot + 1) % Engine::kPinnedSlots;
@@ -695,7 +695,7 @@ static int bulk_load_plain(const char *path, BulkFile *f)
     close(fd);
     if (!rc && hipMemsetAsync(f->d_buf + f->size, 0, 64, g.copy_stream) != hipSuccess) rc = fail(MHX_E_HIP, "memset failed");
     if (!rc && hipStreamSynchronize(g.copy_stream) != hipSuccess) rc = fail(MHX_E_HIP, "copy stream sync failed");
-    if (rc) { hipStreamSynchronize(g.copy_stream); hipFree(f->d_buf); f->d_buf = nullptr; }
+    if (rc) { hipStreamSynchronize(g.copy_stream); f->d_buf.reset(); }
     return rc;
 }
 
@@ -764,7 +764,6 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
     // pushing them again into a larger sketcher instead of reading the files a second time.
     std::vector<int> queued; // files that go through an inflate thread instead
     std::vector<BulkFile> resident;
-    auto free_resident = [&]() { for (auto &b : resident) hipFree(b.d_buf); resident.clear(); };
     for (int i = 0; i < n_paths && !rc && !fallback; ++i) {
         if (is_gzip_file(paths[i]) || getenv("MHX_NO_BULK")) { queued.push_back(i); continue; }
         BulkFile bf;
@@ -787,12 +786,12 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
     std::vector<FileIngestState> st(n_paths);
     if (!rc && !fallback && !queued.empty()) {
         for (int i = 0; i < 2 && !rc; ++i) {
-            if (!g.ingest_slot[i] && hipMalloc((void **)&g.ingest_slot[i], kIngestChunk + GzInflater::kOvershoot + 64) != hipSuccess) rc = fail(MHX_E_HIP, "hipMalloc failed for the ingest slot");
-            if (!rc && !g.ingest_copied[i] && hipEventCreateWithFlags(&g.ingest_copied[i], hipEventDisableTiming) != hipSuccess) rc = fail(MHX_E_HIP, "event creation failed");
-            if (!rc && !g.ingest_consumed[i] && hipEventCreateWithFlags(&g.ingest_consumed[i], hipEventDisableTiming) != hipSuccess) rc = fail(MHX_E_HIP, "event creation failed");
+            if (g.ingest_slot[i].grow(kIngestChunk + GzInflater::kOvershoot + 64) != hipSuccess) rc = fail(MHX_E_HIP, "hipMalloc failed for the ingest slot");
+            if (!rc && !g.ingest_copied[i] && hipEventCreateWithFlags(g.ingest_copied[i].out(), hipEventDisableTiming) != hipSuccess) rc = fail(MHX_E_HIP, "event creation failed");
+            if (!rc && !g.ingest_consumed[i] && hipEventCreateWithFlags(g.ingest_consumed[i].out(), hipEventDisableTiming) != hipSuccess) rc = fail(MHX_E_HIP, "event creation failed");
         }
-        if (!rc && !g.ingest_word && hipHostMalloc((void **)&g.ingest_word, 64, hipHostMallocDefault) != hipSuccess) rc = fail(MHX_E_HIP, "hipHostMalloc failed");
-        if (!rc && !g.copy_stream && hipStreamCreateWithFlags(&g.copy_stream, hipStreamNonBlocking) != hipSuccess) rc = fail(MHX_E_HIP, "stream creation failed");
+        if (!rc && g.ingest_word.grow(16) != hipSuccess) rc = fail(MHX_E_HIP, "hipHostMalloc failed");
+        if (!rc && !g.copy_stream && hipStreamCreateWithFlags(g.copy_stream.out(), hipStreamNonBlocking) != hipSuccess) rc = fail(MHX_E_HIP, "stream creation failed");
     }
     if (!rc && !fallback && !queued.empty()) {
         ChunkQueue q(2 * queued.size() + 4);
@@ -846,7 +845,7 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
     bool own_failed = false;
     for (auto &f : st) own_failed = own_failed || f.own_inflate_failed;
     if (own_failed && !force_zlib) { // the engine's own decoder refused a stream: let zlib have the last word
-            free_resident();
+        resident.clear();
         mhx_sketcher_destroy(sk);
         clear_error();
         return stream_fastq_reference(paths, n_paths, k, s, m, hashes, counts, kmers, records, fname, fcomment, handled, true);
@@ -884,7 +883,6 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
         counts.resize(n);
         *handled = !rc;
     }
-    free_resident();
     if (sk) mhx_sketcher_destroy(sk);
     return rc;
 }
@@ -902,12 +900,6 @@ constexpr int kFastaNotForDevice = 1;
 struct FastaInfo {
     uint64_t records = 0, total_length = 0;
     std::string first_name, first_comment;
-};
-
-struct DeviceBuf {
-    void *p = nullptr;
-    ~DeviceBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n); }
 };
 
 // header line number `idx` (0-based, counting lines that start with '>') of a FASTA held in memory
@@ -928,8 +920,6 @@ bool nth_header(const uint8_t *b, size_t n, uint64_t idx, std::string &name, std
 }
 } // namespace
 
-// One FASTA file, bytes in host memory (a pinned staging slot or a vector) -> its reference sketch.  Device buffers and the
-// sketcher live in g.fasta between files and calls; two stream synchronisations per file (record layout, sketch).
 // device buffers of the FASTA path for files of up to n bytes (both raw buffers, the stream, the workspace), the pinned
 // word block, the record positions, the two "raw bytes are in place" events
 static int ensure_fasta_buffers(uint64_t n)
@@ -937,41 +927,32 @@ static int ensure_fasta_buffers(uint64_t n)
     FastaCtx &c = g.fasta;
     size_t os, oi, oo, of;
     const size_t ws_bytes = fasta_workspace_bytes(n, &os, &oi, &oo, &of);
-    if (!c.h_words) HIPCHK(hipHostMalloc((void **)&c.h_words, (2 + (size_t)kFastaSepsInline) * sizeof(uint64_t), hipHostMallocDefault));
+    HIPCHK(c.h_words.grow(2 + (size_t)kFastaSepsInline));
     for (int i = 0; i < 2; ++i)
-        if (!c.raw_ready[i]) HIPCHK(hipEventCreateWithFlags(&c.raw_ready[i], hipEventDisableTiming));
-    if (c.raw_cap < n + 64 || c.ws_cap < ws_bytes) { // grow with room: the next assembly is about as large as this one
+        if (!c.raw_ready[i]) HIPCHK(hipEventCreateWithFlags(c.raw_ready[i].out(), hipEventDisableTiming));
+    if (c.d_raw[0].cap() < n + 64 || c.d_ws.cap() < ws_bytes) { // grow with room: the next assembly is about as large as this one
         HIPCHK(hipStreamSynchronize(g.stream));
         if (g.copy_stream) HIPCHK(hipStreamSynchronize(g.copy_stream));
-        hipFree(c.d_raw[0]); hipFree(c.d_raw[1]); hipFree(c.d_out); hipFree(c.d_ws);
-        c.d_raw[0] = c.d_raw[1] = c.d_out = c.d_ws = nullptr;
-        c.raw_cap = c.ws_cap = 0;
+        c.d_raw[0].reset(); c.d_raw[1].reset(); c.d_out.reset(); c.d_ws.reset(); // all four go before any is allocated again
         const size_t want = (size_t)(n + n / 4 + (1u << 20));
         size_t os2, oi2, oo2, of2;
         const size_t ws_want = fasta_workspace_bytes(want, &os2, &oi2, &oo2, &of2);
-        if (hipMalloc((void **)&c.d_raw[0], want + 64) != hipSuccess || hipMalloc((void **)&c.d_raw[1], want + 64) != hipSuccess ||
-            hipMalloc((void **)&c.d_out, want + 64) != hipSuccess || hipMalloc((void **)&c.d_ws, ws_want) != hipSuccess)
+        // (d_ws last: after a failure it is empty, and the next call grows all four again)
+        if (c.d_raw[0].grow(want + 64) || c.d_raw[1].grow(want + 64) || c.d_out.grow(want + 64) || c.d_ws.grow(ws_want))
             return fail(MHX_E_HIP, "hipMalloc failed for the FASTA buffers (%llu bytes)", (unsigned long long)n);
-        c.raw_cap = want + 64;
-        c.ws_cap = ws_want;
     }
-    if (!c.d_seps) {
-        c.seps_cap = 1u << 16;
-        if (hipMalloc((void **)&c.d_seps, (size_t)c.seps_cap * 8) != hipSuccess) { c.seps_cap = 0; return fail(MHX_E_HIP, "hipMalloc failed for the FASTA record positions"); }
-    }
+    if (c.d_seps.grow(1u << 16) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the FASTA record positions");
     return MHX_OK;
 }
 
 // One FASTA file, bytes in host memory (a pinned staging slot or a vector) -> its reference sketch.  Device buffers and the
 // sketcher live in g.fasta between files and calls; two stream synchronisations per file (record layout, sketch).
-// which: the raw buffer of this file (d_raw[which]); on_device: the loader has already copied the bytes there on the copy
-// stream (raw_ready[which] says when)
+// Only for files that pass fasta_for_device, with ensure_fasta_buffers(n) done.  which: the raw buffer of this file
+// (d_raw[which]); on_device: the loader has already copied the bytes there on the copy stream (raw_ready[which] says when)
+static bool fasta_for_device(const uint8_t *raw, uint64_t n) { return n != 0 && raw[0] == '>' && n <= 0x7FFFFFFF00ull; }
 static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, int k, uint32_t s, std::vector<uint64_t> &hashes, FastaInfo &info)
 {
-    if (n == 0 || raw[0] != '>' || n > 0x7FFFFFFF00ull) return kFastaNotForDevice;
     FastaCtx &c = g.fasta;
-    int rc0 = ensure_fasta_buffers(n);
-    if (rc0) return rc0;
     size_t os, oi, oo, of;
     fasta_workspace_bytes(n, &os, &oi, &oo, &of);
     const uint64_t ntiles = (n + kFastaTile - 1) / kFastaTile;
@@ -981,25 +962,22 @@ static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, boo
     uint64_t total = 0;
     uint32_t nsep = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        HIPCHK(launch_fasta_compact(d_raw, n, c.d_ws, c.d_out, c.d_seps, c.seps_cap, g.stream));
+        const uint32_t seps_cap = (uint32_t)c.d_seps.cap();
+        HIPCHK(launch_fasta_compact(d_raw, n, c.d_ws, c.d_out, c.d_seps, seps_cap, g.stream));
         HIPCHK(hipMemcpyAsync(&c.h_words[0], c.d_ws + oo + 8 * ntiles, 8, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipMemcpyAsync(&c.h_words[1], c.d_ws + of, 8, hipMemcpyDeviceToHost, g.stream));
         // the record positions of an assembly (tens to hundreds of contigs) ride along with the same synchronisation
-        HIPCHK(hipMemcpyAsync(&c.h_words[2], c.d_seps, (size_t)std::min(c.seps_cap, kFastaSepsInline) * 8, hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(&c.h_words[2], c.d_seps, (size_t)std::min(seps_cap, kFastaSepsInline) * 8, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
         total = c.h_words[0];
         uint32_t fl[2];
         memcpy(fl, &c.h_words[1], 8);
         if (fl[0] & 1u) return kFastaNotForDevice;
         nsep = fl[1];
-        if (nsep <= c.seps_cap) break;
+        if (nsep <= seps_cap) break;
         if (attempt) return fail(MHX_E_INTERNAL, "FASTA record list kept growing");
-        hipFree(c.d_seps); // more records than there was room for: once more with room for all of them
-        c.d_seps = nullptr;
-        c.seps_cap = 0;
-        const uint32_t want = nsep + nsep / 4 + 16;
-        if (hipMalloc((void **)&c.d_seps, (size_t)want * 8) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for %u FASTA record positions", want);
-        c.seps_cap = want;
+        const uint32_t want = nsep + nsep / 4 + 16; // more records than there was room for: once more with room for all of them
+        if (c.d_seps.grow(want) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for %u FASTA record positions", want);
     }
     // records: separator i sits in front of record i; its length is the distance to the next separator (or the end)
     std::vector<uint64_t> seps(nsep);
@@ -1026,20 +1004,21 @@ static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, boo
     for (int attempt = 0; attempt < 6; ++attempt) {
         int rc = MHX_OK;
         if (!c.sk || c.k != k || c.s != s || c.scale != boost) { // one sketcher per (k, s), reset between files
-            if (c.sk) mhx_sketcher_destroy(c.sk);
-            c.sk = nullptr;
-            rc = create_sketcher(k, s, 1, 0, boost, &c.sk);
+            c.sk.reset();
+            mhx_sketcher *sk = nullptr;
+            rc = create_sketcher(k, s, 1, 0, boost, &sk);
             if (rc) return rc;
+            c.sk.reset(sk);
             c.k = k; c.s = s; c.scale = boost;
         } else {
-            rc = mhx_sketcher_reset(c.sk);
+            rc = mhx_sketcher_reset(c.sk.get());
             if (rc) return rc;
         }
-        rc = mhx_sketcher_push_device(c.sk, c.d_out, total, MHX_FMT_SEQ);
+        rc = mhx_sketcher_push_device(c.sk.get(), c.d_out, total, MHX_FMT_SEQ);
         uint32_t nh = 0;
         if (!rc) {
             hashes.resize(s);
-            rc = mhx_sketcher_finish(c.sk, hashes.data(), nullptr, &nh);
+            rc = mhx_sketcher_finish(c.sk.get(), hashes.data(), nullptr, &nh);
         }
         if (rc == MHX_E_CAPACITY) { boost *= 16; continue; }
         if (rc) return rc;
@@ -1238,19 +1217,29 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
         struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{loader};
         auto start_loader = [&](int j) { // file j on its way while file j - 1 is on the GPU; without a thread to be had: loaded here and now
             try {
-                loader = std::thread(load_fasta_input, paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.raw_cap, g.fasta.raw_ready[j & 1]);
+                loader = std::thread(load_fasta_input, paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), (hipEvent_t)g.fasta.raw_ready[j & 1]);
             } catch (const std::system_error &) {
-                load_fasta_input(paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.raw_cap, g.fasta.raw_ready[j & 1]);
+                load_fasta_input(paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), g.fasta.raw_ready[j & 1]);
             }
         };
-        load_fasta_input(paths[0], 0, pinned_ok, &inputs[0], raw_of(0), g.fasta.raw_cap, g.fasta.raw_ready[0]);
+        load_fasta_input(paths[0], 0, pinned_ok, &inputs[0], raw_of(0), g.fasta.d_raw[0].cap(), g.fasta.raw_ready[0]);
         for (int i = 0; i < n_paths; ++i) {
             if (loader.joinable()) loader.join();
-            if (i + 1 < n_paths) start_loader(i + 1);
             FastaInput &in = inputs[i];
             err += std::string("Sketching ") + paths[i] + "...\n";
             if (in.rc) return fail(in.rc, "%s", in.error.c_str());
-            if (!getenv("MHX_HOST_FASTA")) { // plain FASTA: parsed on the device
+            // The FASTA device buffers regrow only while no loader holds one of them: file i's are sized here, before file
+            // i + 1's loader is handed its raw buffer.  Bytes that went to a buffer that has since been regrown are copied
+            // again from the host.
+            const bool device_parser = !getenv("MHX_HOST_FASTA") && fasta_for_device(in.data, in.n);
+            if (device_parser) {
+                const size_t raw_cap = g.fasta.d_raw[i & 1].cap();
+                rc = ensure_fasta_buffers(in.n);
+                if (rc) return rc;
+                if (g.fasta.d_raw[i & 1].cap() != raw_cap) in.on_device = false;
+            }
+            if (i + 1 < n_paths) start_loader(i + 1);
+            if (device_parser) { // plain FASTA: parsed on the device
                 RefSketch ref;
                 FastaInfo info;
                 rc = sketch_fasta_on_device(in.data, in.n, i, in.on_device, k, s, ref.hashes, info);
@@ -1314,15 +1303,10 @@ static int mhx_dist_files_impl(const char *ref_msh, const char *qry_msh, char *s
         const size_t len = (size_t)sb.st_size;
         uint8_t *img = nullptr;
         if (len >= (1u << 20) && len <= (256u << 20)) { // a pinned block of its own, kept between calls (larger files, or MHX_DIST_PAGEABLE=1: the heap)
-            if (g.dist_img_cap < len && !getenv("MHX_DIST_PAGEABLE")) {
-                if (g.dist_img) hipHostFree(g.dist_img);
-                g.dist_img = nullptr;
-                g.dist_img_cap = 0;
-                const size_t cap = (len + len / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-                if (hipHostMalloc((void **)&g.dist_img, cap, hipHostMallocDefault) == hipSuccess) g.dist_img_cap = cap;
-                else { g.dist_img = nullptr; (void)hipGetLastError(); }
-            }
-            if (g.dist_img_cap >= len) img = g.dist_img;
+            if (g.dist_img.cap() < len && !getenv("MHX_DIST_PAGEABLE") &&
+                g.dist_img.grow((len + len / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1)) != hipSuccess)
+                (void)hipGetLastError();
+            if (g.dist_img.cap() >= len) img = g.dist_img;
         }
         if (!img) { ref_heap.resize(len); img = ref_heap.data(); }
         const bool ok = len == 0 || parallel_pread(fd, img, 0, len, len >= (4u << 20) ? std::min(8, ingest_thread_budget()) : 1);

@@ -132,3 +132,25 @@ def test_bgzf_and_plain_gz_assemblies(tmp_path, monkeypatch):
         got = mo.read_msh(tmp_path / "z.msh").references[0]
         assert np.array_equal(got.hashes, osk.references[0].hashes) and got.length == 2_000_000
         assert got.comment == osk.references[0].comment
+
+
+@pytest.mark.parametrize("order", [("big", "small"), ("small", "big", "small2")])
+def test_gz_assembly_larger_than_the_plain_files_beside_it(tmp_path, monkeypatch, order):
+    """The device buffers are sized up front for the largest PLAIN file; a .fa.gz that inflates beyond that regrows them.
+    That must happen before the loader of the next file is handed a raw buffer, or the next file is copied into a freed
+    buffer and parsed from a fresh one.  (The .gz inflates to more than 1.25 x the largest plain file + 1 MiB, and to more
+    than the 3 Mb assembly of the first test here leaves the buffers at.)"""
+    import gzip
+
+    files = {
+        "big": ("big.fa.gz", gzip.compress(synth.genome_fasta(synth.make_genome(8_000_000, seed=31), n_contigs=9), 1)),
+        "small": ("small.fa", synth.genome_fasta(synth.make_genome(200_000, seed=32), n_contigs=3)),
+        "small2": ("small2.fa", synth.genome_fasta(synth.make_genome(200_000, seed=33), n_contigs=2)),
+    }
+    paths = []
+    for key in order:
+        name, data = files[key]
+        paths.append(tmp_path / name)
+        paths[-1].write_bytes(data)
+    osk = _three_ways(tmp_path, paths, 21, 1000, monkeypatch)
+    assert [r.length for r in osk.references] == [8_000_000 if key == "big" else 200_000 for key in order]
