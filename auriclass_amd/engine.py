@@ -121,6 +121,8 @@ def load() -> ctypes.CDLL:
                                            c.c_void_p, c.c_void_p, u32p]
     L.mhx_gunzip_buffer.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     L.mhx_gunzip_buffer_mt.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_int]
+    L.mhx_gunzip_device.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    L.mhx_last_inflate_stats.argtypes = [c.c_void_p]
     _lib = L
     return L
 
@@ -409,6 +411,41 @@ def gunzip(data: bytes, threads: int = 1, size_hint: int = 0) -> bytes:
     if rc:
         raise EngineError(rc, L.mhx_last_error().decode())
     return out.raw[:need.value]
+
+
+def gunzip_device(data: bytes, out=None):
+    """Inflate an in-memory .gz (all members) on the GPU (mhx_gunzip_device) into a torch.uint8 tensor on the engine's
+    device.  out: a contiguous uint8 CUDA tensor to inflate into (the result is a view of it), else one is allocated --
+    sized from the last trailer's ISIZE, so a single member under 4 GiB is decoded once; a second call with the size the
+    first one reported follows only when that guess is short.  Bytes and errors are those of gunzip(): the host decoder
+    has the last word."""
+    import torch
+
+    init()
+    L = load()
+    data = bytes(data)
+    need = ctypes.c_size_t(0)
+    torch.cuda.synchronize()  # the call runs on the engine's stream
+    if out is not None:
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+        _check(L.mhx_gunzip_device(data, len(data), ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(need)))
+        return out[:need.value]
+    guess = int.from_bytes(data[-4:], "little") if len(data) >= 18 else 0
+    out = torch.empty(max(1, guess), dtype=torch.uint8, device=f"cuda:{torch.cuda.current_device()}")
+    rc = L.mhx_gunzip_device(data, len(data), ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(need))
+    if rc == MHX_E_CAPACITY:
+        out = torch.empty(max(1, need.value), dtype=torch.uint8, device=out.device)
+        rc = L.mhx_gunzip_device(data, len(data), ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.byref(need))
+    _check(rc)
+    return out[:need.value]
+
+
+def inflate_stats() -> dict:
+    """Counters of the last gunzip_device call."""
+    v = np.zeros(8, dtype=np.uint64)
+    _check(load().mhx_last_inflate_stats(v.ctypes.data))
+    keys = ("members", "segments", "redone", "hops", "host_bytes", "inflated", "ms", "reserved")
+    return {k: int(x) for k, x in zip(keys, v)}
 
 
 def set_profiling(on: bool) -> None:

@@ -215,6 +215,23 @@ int mhx_gunzip_buffer(const void *gz, size_t n, void *out, size_t cap, size_t *o
  * unknown 32 KiB windows, resolution; the result is byte-identical or the call fails); small inputs and threads < 2 take
  * the sequential decoder. */
 int mhx_gunzip_buffer_mt(const void *gz, size_t n, void *out, size_t cap, size_t *out_n, int threads);
+/* The same on the GPU: all members of the host-resident gzip buffer gz, inflated into DEVICE memory d_out; complete when
+ * it returns.  A member is cut into segments (MHX_DINFLATE_SEGMENT compressed bytes apart, default 64 KiB) that the device
+ * searches for block starts, decodes symbolically, chains, resolves and checks (CRC-32 per segment, joined on the host,
+ * and ISIZE), in rounds that start at 16 segments and double up to 1024 (MHX_DINFLATE_ROUND).  Members go to the device
+ * while at least MHX_DINFLATE_MIN (1 MiB) compressed bytes remain from their start and the member before was at least
+ * that large; the first smaller member is decoded there too, and what follows it, a BGZF block (bgzip output: its run of
+ * blocks goes to the host's block reader) or a header the host decoder refuses go through the host decoders.  Not
+ * used by the FASTQ ingest (mhx_sketch_files).
+ * The host has the last word: whenever the device path fails (no consistent chain within the pass bound, an invalid
+ * code, a CRC or length mismatch, no room) the whole buffer goes through mhx_gunzip_buffer, whose bytes and error are
+ * the result -- this call never returns bytes or an error that mhx_gunzip_buffer would not.  d_out == NULL or cap too
+ * small: *out_n still receives the inflated size (MHX_E_CAPACITY in the second case).  MHX_E_NO_DEVICE without an engine. */
+int mhx_gunzip_device(const void *gz, size_t n, void *d_out, size_t cap, size_t *out_n);
+/* the last mhx_gunzip_device: [0] members decoded on the device, [1] segments, [2] segments redone after a false start,
+ * [3] resolution hops (segments resolved), [4] compressed bytes handed to the host decoder, [5] inflated bytes, [6] ms of
+ * the call (profiling on), [7] reserved (0) */
+int mhx_last_inflate_stats(uint64_t *out8);
 
 #ifdef __cplusplus
 }
