@@ -51,6 +51,10 @@ hipError_t launch_cap_threshold(uint64_t *thresh, uint64_t cap, uint64_t *stats,
 hipError_t launch_order_block(const uint64_t *blk, uint32_t cap, uint32_t log2_buckets, uint32_t *cursor, uint32_t *starts,
                               uint32_t *group_total, uint64_t *grouped, uint64_t *host_blk, hipStream_t st);
 hipError_t launch_phase_verify(const uint8_t *rec, uint32_t ntiles, uint64_t *stats, hipStream_t st);
+// record check of the FASTQ span [begin, end) of base (mhx_fqcheck.hip): raises kFlagBadFastq in stats; scratch holds
+// fastq_check_scratch_bytes(begin, end)
+size_t fastq_check_scratch_bytes(uint64_t begin, uint64_t end);
+hipError_t launch_fastq_check(const uint8_t *base, uint64_t begin, uint64_t end, void *scratch, uint64_t *stats, hipStream_t st);
 hipError_t launch_extract(const TableArgs &a, uint64_t limit, uint32_t min_count, uint64_t *out_keys,
                           uint32_t *out_cnts, uint32_t cap, uint32_t *out_n, uint64_t *flags_out, const uint64_t *limit_dev,
                           uint64_t *limit_out, uint64_t *maxkey_out, hipStream_t st, uint32_t *order_cursor = nullptr, uint32_t order_log2 = 0,

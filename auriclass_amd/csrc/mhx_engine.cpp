@@ -141,6 +141,7 @@ struct mhx_sketcher {
     uint64_t exported = 0;     // entries of the last export_begin (valid until the next push / reset)
     bool export_valid = false;
     bool merged = false;       // merge_slabs has added other shards' entries to the table: reset before the next push
+    bool verify_fastq = false; // file-level callers: FASTQ4 pushes also run the record check (sketcher_verify_fastq)
     DevArray<uint64_t> d_merge_in; // staging of gathered slabs that arrive in host memory (gloo)
     // workspace of the binned merge (mhx_merge.hip): per-bin cursors / counts / flags (kept zero between merges by the
     // kernels), bin regions
@@ -339,6 +340,7 @@ static int read_threshold(mhx_sketcher *sk, uint64_t *T)
 // settle() reads at the next synchronisation point; the repair pass then runs format 1 over the same span with only
 // those tiles doing work.  (MHX_NO_SELFSYNC=1: format 1 for everything, as in round 1.)
 static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt, bool repair);
+static int check_fastq_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n);
 
 static int repair_unsettled(mhx_sketcher *sk)
 {
@@ -398,6 +400,10 @@ extern "C" int mhx_sketcher_push_device(mhx_sketcher *sk, const void *d_bytes, u
     if (n == 0) return MHX_OK;
     sk->export_valid = false;
     if (fmt == MHX_FMT_SEQ) return push_span(sk, d_bytes, n, 0, false);
+    if (sk->verify_fastq) {
+        rc = check_fastq_span(sk, d_bytes, n);
+        if (rc) return rc;
+    }
     static const bool no_selfsync = getenv("MHX_NO_SELFSYNC") != nullptr;
     if (no_selfsync) return push_span(sk, d_bytes, n, 1, false);
     if (sk->unsettled.size() >= 4096) { // thousands of small pushes without a synchronisation point: settle what there is
@@ -407,6 +413,23 @@ extern "C" int mhx_sketcher_push_device(mhx_sketcher *sk, const void *d_bytes, u
     rc = push_span(sk, d_bytes, n, 2, false);
     if (!rc) sk->unsettled.push_back({d_bytes, n});
     return rc;
+}
+
+void sketcher_verify_fastq(mhx_sketcher *sk, bool on)
+{
+    if (sk) sk->verify_fastq = on;
+}
+
+// the record check of a FASTQ4 push (mhx_fqcheck.h); its verdict lands in the flags finish() reads
+static int check_fastq_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n)
+{
+    const uintptr_t p = (uintptr_t)d_bytes;
+    const uintptr_t base = p & ~(uintptr_t)15;
+    const uint64_t begin = p - base, end = begin + n;
+    // one workspace for every sketcher (all of them run on the engine stream); earlier checks may still use the old one
+    HIPCHK(g.fqcheck_ws.grow(fastq_check_scratch_bytes(begin, end), g.stream));
+    HIPCHK(launch_fastq_check((const uint8_t *)base, begin, end, g.fqcheck_ws, sk->d_stats, g.stream));
+    return MHX_OK;
 }
 
 static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt, bool repair)

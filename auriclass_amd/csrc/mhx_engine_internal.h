@@ -129,6 +129,8 @@ struct Engine {
     DevArray<uint8_t> ingest_slot[2];
     HipEvent ingest_copied[2], ingest_consumed[2];
     PinnedArray<uint32_t> ingest_word;
+    int last_fastq_route = 0; // mhx_last_fastq_route
+    DevArray<uint8_t> fqcheck_ws; // per-workgroup summaries of the FASTQ record check (mhx_fqcheck.hip), kept between calls
 };
 extern Engine &g;
 int require_engine();
@@ -145,3 +147,8 @@ int sketcher_release_push(mhx_sketcher *sk, const void *d_bytes, hipStream_t sid
 
 // sketcher with `table_scale` times the default candidate table and admission budget
 int create_sketcher(int k, uint32_t s, uint32_t min_mult, uint64_t expected_bytes, uint64_t table_scale, mhx_sketcher **out);
+
+// File-level callers only: every MHX_FMT_FASTQ4 push of this sketcher also runs the record check of mhx_fqcheck.h over
+// its bytes (a record the kseq reader would read differently raises kFlagBadFastq, finish() returns MHX_E_FORMAT).
+// Each push must then start at a record start.  Off by default: the public push API trusts its caller.
+void sketcher_verify_fastq(mhx_sketcher *sk, bool on);

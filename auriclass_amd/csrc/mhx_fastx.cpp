@@ -165,11 +165,13 @@ void first_header(const uint8_t *buf, size_t n, std::string &name, std::string &
 // Cheap host-side plausibility test for the device FASTQ parser: starts with '@', and the
 // first record has the 4-line shape.  The device verifies every record (kFlagBadFastq).
 // Is the LAST record of a 4-line FASTQ complete in kseq's sense?  t: the last bytes of the stream.  A record that has its
-// '+' line but no quality string, or one of another length than its sequence, makes kseq_read return -2 (the oracle
-// raises "truncated quality string"): the device parser, which checks the four-line layout but not the quality lengths,
-// must not sketch such a file -- the caller hands it to the host record parser, which reports it.  A header without
-// anything behind it, or a sequence line without a '+' line, is a record to kseq (it reads it as FASTA).  true when the
-// record is complete or the tail cannot tell (no record start among its last four lines).
+// '+' line but no quality string, or one with another count of non-blank bytes (> 0x20, != 0x7F: what kseq counts)
+// than its sequence has bases, makes kseq_read return -2 (the oracle raises "truncated quality string"): the device
+// parser must not sketch such a file -- the caller hands it to the host record parser, which reports it.  So does a
+// blank inside the sequence line (kseq drops it and joins the bases on either side; the device parser would not): such
+// a record counts as incomplete too.  A header without anything behind it, or a sequence line without a '+' line, is a
+// record to kseq (it reads it as FASTA).  true when the record is complete or the tail cannot tell (no record start
+// among its last four lines).
 bool fastq_tail_complete(const uint8_t *t, size_t n)
 {
     size_t ls[5], le[5]; // the last (up to five) lines, newest first: [start, end) without the newline
@@ -185,7 +187,16 @@ bool fastq_tail_complete(const uint8_t *t, size_t n)
         e = b - 1;
     }
     auto first = [&](int i) { return ls[i] < le[i] ? t[ls[i]] : (uint8_t)0; };
-    auto length = [&](int i) { size_t l = le[i] - ls[i]; if (l && t[le[i] - 1] == '\r') --l; return l; };
+    auto bases = [&](int i) { // non-blank bytes of line i
+        size_t l = 0;
+        for (size_t q = ls[i]; q < le[i]; ++q) l += t[q] > ' ' && t[q] != 127;
+        return l;
+    };
+    auto clean_seq = [&](int i) { // no blank inside but one '\r' that ends the line
+        for (size_t q = ls[i]; q < le[i]; ++q)
+            if ((t[q] <= ' ' || t[q] == 127) && !(t[q] == '\r' && q + 1 == le[i])) return false;
+        return true;
+    };
     // the record start nearest to the end: a line that begins with '@', whose successor (if any) begins with neither '@'
     // nor '+', and whose second successor (if any) begins with '+'  (index 0 = last line; successors have smaller indices)
     for (int i = 0; i < nl && i < 4; ++i) {
@@ -193,8 +204,8 @@ bool fastq_tail_complete(const uint8_t *t, size_t n)
         if (i >= 1 && (first(i - 1) == '@' || first(i - 1) == '+')) continue;
         if (i >= 2 && first(i - 2) != '+') continue;
         if (i <= 1) return true;                                  // header only, or header + sequence: a record without qualities
-        if (i == 2) return length(1) == 0;                        // '+' line, nothing behind it
-        return length(0) == length(2);                            // i == 3: quality against sequence
+        if (i == 2) return clean_seq(1) && bases(1) == 0;         // '+' line, nothing behind it
+        return clean_seq(2) && bases(0) == bases(2);              // i == 3: quality against sequence
     }
     return true;
 }

@@ -71,11 +71,13 @@ static int sketch_reference(const std::vector<Loaded *> &inputs, int k, uint32_t
         mhx_sketcher *sk = nullptr;
         int rc = create_sketcher(k, s, m, total, boost, &sk);
         if (rc) return rc;
+        sketcher_verify_fastq(sk, true); // a whole-file FASTQ4 push starts at the file's first record
         for (auto *in : inputs) {
             if (device_fastq && in->fastq4) {
                 rc = mhx_sketcher_push_host(sk, in->raw.data(), in->raw.size(), MHX_FMT_FASTQ4);
             } else {
                 if (in->rec.records_seen == 0 && in->rec.seq.empty()) {
+                    if (allow_device_fastq) g.last_fastq_route = MHX_ROUTE_RECORD_PARSER; // (a reads call: mhx_last_fastq_route)
                     rc = parse_fastx(in->raw.data(), in->raw.size(), k, in->rec);
                     if (rc) { mhx_sketcher_destroy(sk); return rc; } // the record parser's verdict is final (not the device parser's MHX_E_FORMAT, which sends the file HERE)
                 }
@@ -757,6 +759,7 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
     mhx_sketcher *sk = nullptr;
     int rc = mhx_sketcher_create(k, s, m, expected, &sk);
     if (rc) return rc;
+    sketcher_verify_fastq(sk, true); // bulk pushes start at '@' (checked below), chunks at a record start
     bool fallback = false;
     HeaderPick header;
     // 1. uncompressed files: whole file -> one device buffer -> one push (see bulk_load_plain).  The buffers
@@ -868,6 +871,7 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
             mhx_sketcher_destroy(sk);
             sk = nullptr;
             rc = create_sketcher(k, s, m, expected, scale, &sk);
+            sketcher_verify_fastq(sk, true);
             for (size_t i = 0; i < resident.size() && !rc; ++i) rc = mhx_sketcher_push_device(sk, resident[i].d_buf, resident[i].size, MHX_FMT_FASTQ4);
             if (!rc) rc = mhx_sketcher_finish(sk, hashes.data(), counts.data(), &n);
         }
@@ -1123,6 +1127,7 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
         return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", p);
     };
     if (reads) {
+        g.last_fastq_route = 0;
         RefSketch ref;
         uint64_t kmers = 0, count = 0;
         std::string fname, fcomment;
@@ -1148,6 +1153,8 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
         bool any = streamed;
         std::string fb_name, fb_comment;
         bool have_fb = false;
+        if (streamed) g.last_fastq_route = MHX_ROUTE_DEVICE_STREAMED;
+        else if (g.last_fastq_route == 0) g.last_fastq_route = MHX_ROUTE_DEVICE_WHOLE; // (sketch_reference notes the record parser)
         for (auto &l : loaded) {
             if (streamed) break;
             if (l.rec.records_seen || !l.rec.seq.empty()) {
@@ -1401,6 +1408,8 @@ extern "C" int mhx_sketch_files(const char *const *paths, int n_paths, int k, ui
         return fail(MHX_E_INTERNAL, "mhx_sketch_files: %s", e.what());
     }
 }
+
+extern "C" int mhx_last_fastq_route(void) { return g.last_fastq_route; }
 
 extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
 {

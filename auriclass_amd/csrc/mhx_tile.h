@@ -27,7 +27,10 @@
 #define MHX_HD __host__ __device__ __forceinline__
 #else
 #define MHX_HD inline
+#ifndef MHX_HOST_UINT4
+#define MHX_HOST_UINT4
 struct uint4 { uint32_t x, y, z, w; };
+#endif
 #endif
 
 #include "mhx_device_consts.h"

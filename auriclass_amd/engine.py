@@ -123,6 +123,8 @@ def load() -> ctypes.CDLL:
     L.mhx_gunzip_buffer_mt.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_int]
     L.mhx_gunzip_device.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     L.mhx_last_inflate_stats.argtypes = [c.c_void_p]
+    L.mhx_last_fastq_route.argtypes = []
+    L.mhx_last_fastq_route.restype = c.c_int
     _lib = L
     return L
 
@@ -446,6 +448,15 @@ def inflate_stats() -> dict:
     _check(load().mhx_last_inflate_stats(v.ctypes.data))
     keys = ("members", "segments", "redone", "hops", "host_bytes", "inflated", "ms", "reserved")
     return {k: int(x) for k, x in zip(keys, v)}
+
+
+FASTQ_ROUTES = {0: None, 1: "device-streamed", 2: "device-whole", 3: "record-parser"}
+
+
+def last_fastq_route():
+    """Parser the last sketch_files(..., reads=True) call took (see mhx_last_fastq_route): "device-streamed",
+    "device-whole", "record-parser", or None."""
+    return FASTQ_ROUTES[load().mhx_last_fastq_route()]
 
 
 def set_profiling(on: bool) -> None:

@@ -392,7 +392,9 @@ def sketch_fastq_files(paths, k: int, s: int, min_mult: int, out_msh, device: to
     what bounds such inputs anyway).  Each rank sketches what it took on its GPU, ONE exchange merges the partial results
     (sharded_sketch), rank 0 writes the .msh -- the same bytes `engine.sketch_files(..., reads=True)` writes on one GPU.
     Returns (stderr text, estimated genome size) on every rank.  Strict 4-line FASTQ only (what the device parser
-    takes); anything else: use the single-GPU call."""
+    takes); anything else: use the single-GPU call.  Only the tail of each file is checked here (fastq_tail_complete):
+    the record check of the single-GPU call (mhx_fqcheck.hip: blanks in a sequence line, quality lengths of every
+    record) does not run on this path, so a file damaged in its middle may be sketched where mash refuses it."""
     world, rank = dist.get_world_size(), dist.get_rank()
     pieces = []
     for i, p in enumerate(paths):

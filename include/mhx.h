@@ -52,6 +52,12 @@ extern "C" {
 /* input stream formats for mhx_sketcher_push_* */
 #define MHX_FMT_SEQ 0     /* dense sequence bytes; any non-ACGT byte (e.g. '\n') ends a k-mer run */
 #define MHX_FMT_FASTQ4 1  /* strict 4-line FASTQ records, parsed on the device                      */
+/* A MHX_FMT_FASTQ4 push trusts its caller that every record is clean in the kseq reader's sense: the device checks
+ * only that record lines start with '@' and '+'.  A sequence line holding blanks (bytes <= 0x20 or 0x7F, but for one
+ * '\r' before its newline) or beginning with '>', '@' or '+', or a quality line with another count of non-blank bytes
+ * than its sequence, is read differently by mash and gives a different sketch.  mhx_sketch_files verifies every
+ * record of the files it pushes (a separate pass over the bytes, outside the sketch kernel) and hands a file that
+ * fails to the host record parser, whose result or refusal is mash's. */
 
 /* ---- library ---------------------------------------------------------------------- */
 int mhx_init(int device);              /* selects the GPU, creates the stream; idempotent */
@@ -83,9 +89,16 @@ int mhx_fasta_total_bases(const char *path, uint64_t *total);
 int mhx_sniff_fastq(const char *path);
 int mhx_sniff_fasta(const char *path);
 /* the end of a 4-line FASTQ stream (its last bytes, up to 64 KiB are enough): 1 when the last record is complete in kseq's
- * sense, 0 when it has its '+' line but no, or a differently long, quality string (kseq_read: -2; such a file is refused
- * by mhx_sketch_files); callers that push byte ranges of a file themselves ask here for its tail */
+ * sense, 0 when it has its '+' line but no quality string, one with another count of non-blank bytes than its sequence
+ * (kseq_read: -2; such a file is refused by mhx_sketch_files), or a sequence line with a blank inside; callers that push byte ranges of a file themselves ask here for its tail */
 int mhx_fastq_tail_complete(const void *tail, size_t n);
+/* which parser the last mhx_sketch_files call with reads != 0 took: 0 none (it failed early),
+ * MHX_ROUTE_DEVICE_STREAMED (device FASTQ parser, streamed ingest), MHX_ROUTE_DEVICE_WHOLE (device FASTQ parser,
+ * whole files), MHX_ROUTE_RECORD_PARSER (host record parser for at least one file) */
+#define MHX_ROUTE_DEVICE_STREAMED 1
+#define MHX_ROUTE_DEVICE_WHOLE 2
+#define MHX_ROUTE_RECORD_PARSER 3
+int mhx_last_fastq_route(void);
 
 /* ---- buffer level: the hot path itself ------------------------------------------------ */
 typedef struct mhx_sketcher mhx_sketcher;

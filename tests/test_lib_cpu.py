@@ -437,3 +437,47 @@ def test_fastq_tail_completeness_rule(lib):
         for lead in (body, b"", body * 3):
             data = lead + tail
             assert f(data, len(data)) == want, (tail[:20], len(lead))
+    _check_tail_blank_rule()
+
+
+def _oracle_refuses(data: bytes) -> bool:
+    try:
+        mo.Sketcher(21, 100).add_fastx(data)
+    except ValueError:
+        return True
+    return False
+
+
+def _check_tail_blank_rule():
+    """Blanks in the last record (`fastq_tail_complete` counts what kseq counts: bytes > 0x20 and != 0x7F): a file the
+    oracle refuses is never called complete; a blank inside the last sequence line (kseq joins the bases on either
+    side, the device parser would not) is incomplete too; a clean last record -- CRLF, no final newline -- stays
+    complete, so ordinary files keep the device path."""
+    seq = b"ACGTACGTAC"
+    qual = b"IIIIIIIIII"
+    lead = b"@r1 x\n" + seq * 4 + b"\n+\n" + qual * 4 + b"\n"
+
+    def with_blank(line, at, b):
+        return line[:at] + b + line[at:]
+
+    incomplete = []   # (header, sequence line, '+' line, quality line), each without its newline
+    for b in (b" ", b"\t", b"\r", b"\x7f", b"\x00"):
+        incomplete += [
+            (b"@l", seq, b"+", with_blank(qual[:-1], 4, b)),       # raw length as the sequence's, one base short
+            (b"@l", with_blank(seq, 5, b), b"+", qual),            # a blank inside the sequence
+            (b"@l", with_blank(seq, 5, b), b"+", qual + b"I"),
+        ]
+    incomplete += [(b"@l", b"", b"+", b"II"), (b"@l", b"", b"+", b"I"), (b"@l", seq + b"\r\r", b"+", qual),
+                   (b"@l", seq, b"+", b"IIII IIIII"), (b"@l", seq, b"+", b"IIII\tIIIII")]
+    clean = [(b"@l", seq, b"+", qual), (b"@l", seq, b"+", qual + b"  "), (b"@l", seq, b"+", with_blank(qual, 4, b"\t")),
+             (b"@l", seq, b"+", b" " + qual + b"\t"), (b"@l", seq, b"+", b"IIII IIIIII"), (b"@l", b"", b"+", b""),
+             (b"@l", b"", b"+", b"  "), (b"@l", seq, b"+", qual + b"\r")]
+    for recs, want in ((incomplete, False), (clean, True)):
+        for rec in recs:
+            for final in (b"\n", b""):
+                for eol in (b"\n", b"\r\n"):
+                    data = lead + eol.join(rec) + final
+                    got = engine.fastq_tail_complete(data)
+                    if _oracle_refuses(data):
+                        assert not got, (rec, final, eol)
+                    assert got == want, (rec, final, eol)
