@@ -27,16 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#ifndef MHX_HD
-#define MHX_HD __host__ __device__ __forceinline__
-#endif
-#else
-#ifndef MHX_HD
-#define MHX_HD inline
-#endif
-#endif
+#include "mhx_deflate.h"
 
 #include <algorithm>
 #include <vector>
@@ -44,40 +35,16 @@
 namespace mhx {
 namespace dinf {
 
+using namespace deflate;
+
 constexpr uint32_t kWin = 32768;
 constexpr uint16_t kMarker = 0x8000;
 constexpr uint64_t kNoBit = ~0ull;         // "no candidate" / "no stop target"
-constexpr int kLitBits = 11, kDistBits = 8;
-constexpr int kLitCap = (1 << kLitBits) + 288 * 16, kDistCap = (1 << kDistBits) + 32 * 128;
-constexpr int kLaneWords = kLitCap + kDistCap + 320 / 4; // per-lane workspace: both tables and the code lengths
+constexpr int kLaneWords = kLitCap + kDistCap + kLensBytes / 4; // per-lane workspace: both tables and the code lengths
 constexpr int kMaxPasses = 16;
 
 // segment status
 enum : uint32_t { kSegOk = 0, kSegData = 1, kSegEnd = 2 };
-
-// table entries (the layout of the host decoder, mhx_inflate_impl.h): bits 0..7 bits to consume (or index bits of the
-// sub-table), 8 literal, 9 end of block, 10 sub-table link, 11 invalid, 12 length/distance base, 13..16 extra bits,
-// 17..31 the literal, base or sub-table offset
-constexpr uint32_t kLiteral = 0x0100, kEnd = 0x0200, kSub = 0x0400, kInvalid = 0x0800, kBase = 0x1000;
-constexpr int kValShift = 17, kExtraShift = 13;
-
-MHX_HD uint32_t len_base(int i)
-{
-    const uint16_t t[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-    return t[i];
-}
-MHX_HD uint32_t len_extra(int i) { return i < 8 || i == 28 ? 0u : (uint32_t)((i - 4) >> 2); }
-MHX_HD uint32_t dist_base(int i)
-{
-    const uint16_t t[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-    return t[i];
-}
-MHX_HD uint32_t dist_extra(int i) { return i < 4 ? 0u : (uint32_t)((i - 2) >> 1); }
-MHX_HD int clen_order(int i)
-{
-    const uint8_t t[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-    return t[i];
-}
 
 // ---- bit input: reads past the n bytes return zero bits; pos() > 8 n tells that it happened ----
 struct Bits {
@@ -121,104 +88,13 @@ struct Bits {
         return v;
     }
     MHX_HD uint64_t pos() const { return next * 8 - (uint64_t)cnt; }
-    MHX_HD bool over() const { return pos() > n * 8; }
+    MHX_HD bool overrun() const { return pos() > n * 8; }
+    MHX_HD bool fill(int k) // read_dynamic's refill: reads past the input are harmless here, its overrun() tests catch them
+    {
+        if (cnt < k) refill();
+        return true;
+    }
 };
-
-// ---- the code-length code: decoded bit by bit from counts (19 symbols, 7 bits at most) ----
-struct ClenCode {
-    uint8_t count[8];
-    uint8_t sym[19];
-};
-// false: over-subscribed (complete: Kraft sum exactly 1)
-MHX_HD bool clen_build(const uint8_t *lens19, ClenCode &c, bool *complete)
-{
-    for (int l = 0; l < 8; ++l) c.count[l] = 0;
-    for (int i = 0; i < 19; ++i) c.count[lens19[i] & 7]++;
-    int left = 1;
-    for (int l = 1; l < 8; ++l) {
-        left <<= 1;
-        left -= c.count[l];
-        if (left < 0) return false;
-    }
-    *complete = left == 0;
-    uint8_t offs[8];
-    offs[1] = 0;
-    for (int l = 1; l < 7; ++l) offs[l + 1] = (uint8_t)(offs[l] + c.count[l]);
-    for (int i = 0; i < 19; ++i)
-        if (lens19[i]) c.sym[offs[lens19[i] & 7]++] = (uint8_t)i;
-    return true;
-}
-// symbol or -1 (no code of <= 7 bits matches: incomplete code)
-MHX_HD int clen_decode(Bits &b, const ClenCode &c)
-{
-    if (b.cnt < 8) b.refill();
-    int code = 0, first = 0, index = 0;
-    for (int l = 1; l < 8; ++l) {
-        code |= (int)(b.buf & 1);
-        b.drop(1);
-        const int count = c.count[l];
-        if (code - count < first) return c.sym[(index + (code - first)) % 19];
-        index += count;
-        first += count;
-        first <<= 1;
-        code <<= 1;
-    }
-    return -1;
-}
-
-// Reads HLIT/HDIST/HCLEN, the code-length code and the code lengths.  lens (320 bytes) receives the literal/length
-// lengths at [0, 288) and the distance lengths at [288, 320) when non-null; kraft[0]/[1] receive the Kraft sums (in units of
-// 2^-15) of the literal/length and distance codes, eob whether symbol 256 has a code.  Returns false on an invalid header.
-MHX_HD bool read_dynamic(Bits &b, uint8_t *lens, bool strict, uint32_t *kraft, bool *eob)
-{
-    if (b.cnt < 14) b.refill();
-    const int nlit = (int)b.take(5) + 257, ndist = (int)b.take(5) + 1, nclen = (int)b.take(4) + 4;
-    if (nlit > 286 || ndist > 30) return false;
-    uint8_t cl[19];
-    for (int i = 0; i < 19; ++i) cl[i] = 0;
-    for (int i = 0; i < nclen; ++i) cl[clen_order(i)] = (uint8_t)b.take(3);
-    if (b.over()) return false;
-    ClenCode cc;
-    bool complete = false;
-    if (!clen_build(cl, cc, &complete)) return false;
-    if (strict && !complete) return false;
-    uint32_t k0 = 0, k1 = 0;
-    int prev = 0;
-    bool has_eob = false;
-    int i = 0;
-    while (i < nlit + ndist) {
-        const int sym = clen_decode(b, cc);
-        if (sym < 0) return false;
-        int rep = 1, val = sym;
-        if (sym == 16) {
-            if (i == 0) return false;
-            val = prev;
-            rep = 3 + (int)b.take(2);
-        } else if (sym == 17) { val = 0; rep = 3 + (int)b.take(3); }
-        else if (sym == 18) { val = 0; rep = 11 + (int)b.take(7); }
-        if (i + rep > nlit + ndist) return false;
-        if (b.over()) return false;
-        for (int r = 0; r < rep; ++r, ++i) {
-            if (i < nlit) {
-                if (val) k0 += 1u << (15 - val);
-                if (i == 256) has_eob = val != 0;
-                if (lens) lens[i] = (uint8_t)val;
-            } else {
-                if (val) k1 += 1u << (15 - val);
-                if (lens) lens[288 + i - nlit] = (uint8_t)val;
-            }
-        }
-        prev = val;
-    }
-    if (lens) {
-        for (int j = nlit; j < 288; ++j) lens[j] = 0;
-        for (int j = ndist; j < 32; ++j) lens[288 + j] = 0;
-    }
-    kraft[0] = k0;
-    kraft[1] = k1;
-    *eob = has_eob;
-    return true;
-}
 
 // Search test: is `bit` the start of a dynamic-Huffman block header that a real encoder could have written?
 MHX_HD bool header_candidate(const uint8_t *in, uint64_t n, uint64_t bit)
@@ -228,79 +104,10 @@ MHX_HD bool header_candidate(const uint8_t *in, uint64_t n, uint64_t bit)
     b.drop(1); // BFINAL: either
     if (b.take(2) != 2) return false;
     uint32_t kraft[2];
-    bool eob = false;
-    if (!read_dynamic(b, nullptr, true, kraft, &eob)) return false;
-    if (!eob || kraft[0] != 32768u) return false;
+    if (read_dynamic(b, nullptr, true, kraft) != kHeaderOk || kraft[0] != 32768u) return false;
     // distances: complete, or the single one-bit code that encoders write for a block with one distance (or none)
     if (kraft[1] != 32768u && kraft[1] != 16384u) return false;
-    return !b.over();
-}
-
-// ---- decode tables (the host decoder's construction): false for an over-subscribed code or a table overflow ----
-MHX_HD uint32_t payload(int kind, int s)
-{
-    if (kind == 0) { // literal/length
-        if (s < 256) return kLiteral | ((uint32_t)s << kValShift);
-        if (s == 256) return kEnd;
-        if (s > 285) return kInvalid;
-        return kBase | (len_base(s - 257) << kValShift) | (len_extra(s - 257) << kExtraShift);
-    }
-    if (s > 29) return kInvalid;
-    return kBase | (dist_base(s) << kValShift) | (dist_extra(s) << kExtraShift);
-}
-MHX_HD bool build_table(const uint8_t *lens, int nsym, int first_bits, uint32_t *table, int cap, int kind)
-{
-    int count[16];
-    for (int l = 0; l < 16; ++l) count[l] = 0;
-    for (int i = 0; i < nsym; ++i) ++count[lens[i] & 15];
-    count[0] = 0;
-    int max_len = 15;
-    while (max_len > 0 && count[max_len] == 0) --max_len;
-    uint32_t next_code[16];
-    uint32_t code = 0;
-    int left = 1;
-    next_code[0] = 0;
-    for (int l = 1; l <= 15; ++l) {
-        left <<= 1;
-        left -= count[l];
-        if (left < 0) return false;
-        code = (code + (uint32_t)count[l - 1]) << 1;
-        next_code[l] = code;
-    }
-    const int first_size = 1 << first_bits;
-    for (int i = 0; i < first_size; ++i) table[i] = kInvalid | 1u;
-    int sub_next = first_size;
-    const int sub_bits = max_len > first_bits ? max_len - first_bits : 0;
-    for (int sym = 0; sym < nsym; ++sym) {
-        const int l = lens[sym] & 15;
-        if (!l) continue;
-        const uint32_t c = next_code[l]++;
-        uint32_t r = 0;
-        for (int i = 0; i < l; ++i) r |= ((c >> i) & 1u) << (l - 1 - i);
-        if (l <= first_bits) {
-            const uint32_t e = payload(kind, sym) | (uint32_t)l;
-            for (uint32_t i = r; i < (uint32_t)first_size; i += 1u << l) table[i] = e;
-        } else {
-            const uint32_t lo = r & (uint32_t)(first_size - 1);
-            uint32_t head = table[lo];
-            if (!(head & kSub)) {
-                if (sub_next + (1 << sub_bits) > cap) return false;
-                head = kSub | (uint32_t)sub_bits | ((uint32_t)sub_next << kValShift);
-                table[lo] = head;
-                for (int i = 0; i < (1 << sub_bits); ++i) table[sub_next + i] = kInvalid | 1u;
-                sub_next += 1 << sub_bits;
-            }
-            const uint32_t base = head >> kValShift;
-            const uint32_t e = payload(kind, sym) | (uint32_t)(l - first_bits);
-            for (uint32_t i = r >> first_bits; i < (1u << sub_bits); i += 1u << (l - first_bits)) table[base + i] = e;
-        }
-    }
-    return true;
-}
-MHX_HD void fixed_lens(uint8_t *lens)
-{
-    for (int i = 0; i < 288; ++i) lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
-    for (int i = 0; i < 32; ++i) lens[288 + i] = 5;
+    return !b.overrun();
 }
 
 // ---- one segment, symbolically ----
@@ -325,7 +132,7 @@ MHX_HD void decode_segment(const uint8_t *in, uint64_t n, uint64_t start_bit, ui
     uint32_t status = kSegOk, final_block = 0;
     const uint64_t hist = window ? kWin : 0;
     while (!final_block && b.pos() < stop_target) {
-        if (b.over()) { status = kSegEnd; break; }
+        if (b.overrun()) { status = kSegEnd; break; }
         if (b.cnt < 3) b.refill();
         final_block = b.take(1);
         const uint32_t type = b.take(2);
@@ -333,7 +140,7 @@ MHX_HD void decode_segment(const uint8_t *in, uint64_t n, uint64_t start_bit, ui
             b.drop(b.cnt & 7);
             if (b.cnt < 32) b.refill();
             const uint32_t len = b.take(16), nlen = b.take(16);
-            if (b.over()) { status = kSegEnd; break; }
+            if (b.overrun()) { status = kSegEnd; break; }
             if ((len ^ nlen) != 0xFFFFu) { status = kSegData; break; }
             if (b.pos() / 8 + len > n) { status = kSegEnd; break; }
             for (uint32_t i = 0; i < len; ++i) {
@@ -345,42 +152,38 @@ MHX_HD void decode_segment(const uint8_t *in, uint64_t n, uint64_t start_bit, ui
         }
         if (type == 3) { status = kSegData; break; }
         if (type == 1) fixed_lens(lens);
-        else {
-            uint32_t kraft[2];
-            bool eob = false;
-            if (!read_dynamic(b, lens, false, kraft, &eob) || !eob) { status = b.over() ? kSegEnd : kSegData; break; }
-        }
-        if (!build_table(lens, 288, kLitBits, lit, kLitCap, 0) || !build_table(lens + 288, 32, kDistBits, dist, kDistCap, 1)) {
+        else if (read_dynamic(b, lens, false, nullptr) != kHeaderOk) { status = b.overrun() ? kSegEnd : kSegData; break; }
+        if (!build_table(lens, 288, kLitBits, lit, kLitCap, kLitLenTable) || !build_table(lens + 288, 32, kDistBits, dist, kDistCap, kDistTable)) {
             status = kSegData;
             break;
         }
         // the symbol loop of one block; each pass consumes at least one bit, so it ends within the input
         for (;;) {
             if (b.cnt < 48) b.refill();
-            if (b.over()) { status = kSegEnd; break; }
+            if (b.overrun()) { status = kSegEnd; break; }
             uint32_t e = lit[b.buf & ((1u << kLitBits) - 1)];
-            if (e & kSub) {
+            if (e & kKindSub) {
                 b.drop(kLitBits);
                 e = lit[((e >> kValShift) + (uint32_t)(b.buf & ((1ull << (e & 0xFF)) - 1))) % kLitCap];
             }
-            if (e & kInvalid) { status = kSegData; break; }
+            if (e & kKindInvalid) { status = kSegData; break; }
             b.drop((int)(e & 0xFF));
-            if (e & kLiteral) {
+            if (e & kKindLiteral) {
                 if (o < cap) sym[o] = (uint16_t)(e >> kValShift);
                 ++o;
                 continue;
             }
-            if (e & kEnd) break;
+            if (e & kKindEnd) break;
             const int le = (int)((e >> kExtraShift) & 15u);
             const uint32_t len = (e >> kValShift) + (uint32_t)(b.buf & ((1ull << le) - 1));
             b.drop(le);
             if (b.cnt < 32) b.refill();
             uint32_t d = dist[b.buf & ((1u << kDistBits) - 1)];
-            if (d & kSub) {
+            if (d & kKindSub) {
                 b.drop(kDistBits);
                 d = dist[((d >> kValShift) + (uint32_t)(b.buf & ((1ull << (d & 0xFF)) - 1))) % kDistCap];
             }
-            if (!(d & kBase)) { status = kSegData; break; }
+            if (!(d & kKindBase)) { status = kSegData; break; }
             b.drop((int)(d & 0xFF));
             const int de = (int)((d >> kExtraShift) & 15u);
             const uint32_t distance = (d >> kValShift) + (uint32_t)(b.buf & ((1ull << de) - 1));
@@ -393,7 +196,7 @@ MHX_HD void decode_segment(const uint8_t *in, uint64_t n, uint64_t start_bit, ui
         }
         if (status != kSegOk) break;
     }
-    if (status == kSegOk && b.over()) status = kSegEnd;
+    if (status == kSegOk && b.overrun()) status = kSegEnd;
     res->stop_bit = b.pos();
     res->n_sym = o;
     res->status = status;
@@ -413,11 +216,7 @@ MHX_HD bool resolve_symbol(uint16_t s, const uint8_t *out, uint64_t seg_out, uin
 // ---- CRC-32 (gzip polynomial), table driven ----
 MHX_HD void crc_table(uint32_t *t)
 {
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = c & 1 ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        t[i] = c;
-    }
+    for (uint32_t i = 0; i < 256; ++i) t[i] = crc_entry(i);
 }
 MHX_HD uint32_t crc_update(const uint32_t *t, uint32_t crc, const uint8_t *p, uint64_t n)
 {
@@ -428,43 +227,12 @@ MHX_HD uint32_t crc_update(const uint32_t *t, uint32_t crc, const uint8_t *p, ui
 
 // ---- host side: the gzip member header and the round driver, shared by the HIP host code and the emulator ----
 
-// Offset of the DEFLATE data of the member at in[0], 0 when there is no member there (fewer than 18 bytes or no gzip magic:
-// the host decoder ends there too), -1 for a member header the host decoder refuses.
+// Offset of the DEFLATE data of the member at in[0], 0 when there is no member there (the host decoder ends there too),
+// -1 for a member header the host decoder refuses.
 inline int64_t member_data_offset(const uint8_t *in, size_t n)
 {
-    if (n < 18 || in[0] != 0x1f || in[1] != 0x8b) return 0;
-    if (in[2] != 8) return -1;
-    const uint8_t flg = in[3];
-    size_t p = 10;
-    if (flg & 4) {
-        if (n - p < 2) return -1;
-        const size_t xlen = in[p] | (in[p + 1] << 8);
-        p += 2;
-        if (n - p < xlen) return -1;
-        p += xlen;
-    }
-    for (int bit = 8; bit <= 16; bit <<= 1) {
-        if (!(flg & bit)) continue;
-        const void *z = memchr(in + p, 0, n - p);
-        if (!z) return -1;
-        p = (size_t)((const uint8_t *)z - in) + 1;
-    }
-    if (flg & 2) { if (n - p < 2) return -1; p += 2; }
-    return (int64_t)p;
-}
-
-// Is the member at in[0] a BGZF block (bgzip: FEXTRA with a 'BC' subfield announcing the block size)?
-inline bool member_is_bgzf(const uint8_t *in, size_t n)
-{
-    if (n < 18 || in[0] != 0x1f || in[1] != 0x8b || in[2] != 8 || !(in[3] & 4)) return false;
-    const size_t xlen = in[10] | (in[11] << 8);
-    if (n < 12 + xlen) return false;
-    for (size_t p = 12; p + 4 <= 12 + xlen;) {
-        const size_t slen = in[p + 2] | (in[p + 3] << 8);
-        if (in[p] == 'B' && in[p + 1] == 'C' && slen == 2) return true;
-        p += 4 + slen;
-    }
-    return false;
+    const int64_t h = gzip_member(in, n);
+    return h < 0 ? -1 : h;
 }
 
 // What the driver asks of a backend (the kernels, or the emulator):

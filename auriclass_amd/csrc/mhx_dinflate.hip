@@ -89,11 +89,7 @@ __global__ __launch_bounds__(64) void dinf_crc_kernel(const uint8_t *out, uint32
                                                       uint32_t *crcs)
 {
     __shared__ uint32_t table[256];
-    for (int i = threadIdx.x; i < 256; i += 64) {
-        uint32_t c = (uint32_t)i;
-        for (int k = 0; k < 8; ++k) c = c & 1 ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        table[i] = c;
-    }
+    for (int i = threadIdx.x; i < 256; i += 64) table[i] = crc_entry((uint32_t)i);
     __syncthreads();
     const uint32_t j = blockIdx.x * 64 + threadIdx.x;
     if (j >= nseg) return;
@@ -271,7 +267,7 @@ extern "C" int mhx_gunzip_device(const void *gz, size_t n, void *d_out, size_t c
         while (off < n) {
             const int64_t h = member_data_offset(in + off, n - off);
             if (h == 0) break; // no further member: the host decoder ignores what is left, so does this
-            if (h < 0 || n - off < min_member || member_is_bgzf(in + off, n - off)) break;
+            if (h < 0 || n - off < min_member || bgzf_block_size(in + off, n - off)) break;
             if (!uploaded) {
                 if (!be.ok(d_in.grow(n + kInPad)) || !be.ok(hipMemsetAsync(d_in + n, 0, kInPad, st)) ||
                     !be.ok(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, st)))

@@ -22,16 +22,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define MHX_FQ_HD __host__ __device__ __forceinline__
-#else
-#define MHX_FQ_HD inline
-#ifndef MHX_HOST_UINT4
-#define MHX_HOST_UINT4
-struct uint4 { uint32_t x, y, z, w; };
-#endif
-#endif
+#include "mhx_hd.h"
 
 namespace mhx {
 
@@ -49,7 +40,7 @@ template <class I> struct FqSum {
     I v[4];          // share of S in front of the first record end (bit q of flags)
 };
 
-template <class I> MHX_FQ_HD FqSum<I> fq_identity()
+template <class I> MHX_HD FqSum<I> fq_identity()
 {
     FqSum<I> s;
     s.nl = 0; s.flags = 0;
@@ -58,11 +49,11 @@ template <class I> MHX_FQ_HD FqSum<I> fq_identity()
 }
 
 // x[i] by selects: an array in registers indexed at run time would go to scratch memory
-template <class J> MHX_FQ_HD J fq_pick(const J (&x)[4], int i) { return i == 0 ? x[0] : i == 1 ? x[1] : i == 2 ? x[2] : x[3]; }
+template <class J> MHX_HD J fq_pick(const J (&x)[4], int i) { return i == 0 ? x[0] : i == 1 ? x[1] : i == 2 ? x[2] : x[3]; }
 
 // a then b.  All record ends of a piece must see the same S (0 once the prefix is added); b's first one is
 // compared with a's.
-template <class I, class J> MHX_FQ_HD FqSum<I> fq_combine(const FqSum<I> &a, const FqSum<J> &b)
+template <class I, class J> MHX_HD FqSum<I> fq_combine(const FqSum<I> &a, const FqSum<J> &b)
 {
     FqSum<I> r;
     r.nl = (a.nl + b.nl) & 3u;
@@ -82,27 +73,27 @@ template <class I, class J> MHX_FQ_HD FqSum<I> fq_combine(const FqSum<I> &a, con
 }
 
 // the span's verdict: its summary starts at line 0
-template <class I> MHX_FQ_HD bool fq_span_bad(const FqSum<I> &s)
+template <class I> MHX_HD bool fq_span_bad(const FqSum<I> &s)
 {
     return ((s.flags >> 4) & 1u) || s.t[0] != 0 || ((s.flags & 1u) && s.v[0] != 0);
 }
 
 // ---- bytes -> bit masks (exact per byte: no borrow crosses a byte) -----------------------
-MHX_FQ_HD uint32_t fq_eq(uint32_t v, uint32_t pattern) // 0x80 in every byte equal to the pattern's
+MHX_HD uint32_t fq_eq(uint32_t v, uint32_t pattern) // 0x80 in every byte equal to the pattern's
 {
     const uint32_t y = v ^ pattern;
     return ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u;
 }
 // bytes the kseq reader counts: > 0x20 and != 0x7F (unsigned)
-MHX_FQ_HD uint32_t fq_nonblank(uint32_t v)
+MHX_HD uint32_t fq_nonblank(uint32_t v)
 {
     const uint32_t ge21 = ((v | 0x80808080u) - 0x21212121u) & 0x80808080u; // low seven bits >= 0x21
     return (v & 0x80808080u) | (ge21 & ~fq_eq(v, 0x7F7F7F7Fu));
 }
 // the 0x80 flags of two dwords (bytes 0..3, 4..7) -> 8 bits in byte order
-MHX_FQ_HD uint32_t fq_pack(uint32_t f_lo, uint32_t f_hi) { return (((f_lo >> 4) | f_hi) * 0x00204081u) >> 24; }
+MHX_HD uint32_t fq_pack(uint32_t f_lo, uint32_t f_hi) { return (((f_lo >> 4) | f_hi) * 0x00204081u) >> 24; }
 
-MHX_FQ_HD uint32_t fq_prefix_xor_excl(uint32_t x)
+MHX_HD uint32_t fq_prefix_xor_excl(uint32_t x)
 {
     x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
     return x << 1;
@@ -114,26 +105,26 @@ MHX_FQ_HD uint32_t fq_prefix_xor_excl(uint32_t x)
 // behind every eight chunks puts the lanes of a 16-lane group on 16 different 16-byte bank groups (a stride of 144 bytes
 // instead of 128, which would put them on two).
 constexpr int kFqChunks = kFqTileBytes / 16 + 2;
-MHX_FQ_HD constexpr int fq_slot(int c) { return c + ((c + 7) >> 3); }
+MHX_HD constexpr int fq_slot(int c) { return c + ((c + 7) >> 3); }
 constexpr int kFqSlots = fq_slot(kFqChunks - 1) + 1;
 struct FqSmem {
     uint4 bytes[kFqSlots];
     FqSum<int32_t> red[kFqBlock];
 };
 // byte x of the tile (-16 <= x < kFqTileBytes + 16)
-MHX_FQ_HD uint8_t fq_byte(const FqSmem &sm, int x)
+MHX_HD uint8_t fq_byte(const FqSmem &sm, int x)
 {
     return reinterpret_cast<const uint8_t *>(sm.bytes)[16 * fq_slot((x + 16) >> 4) + ((x + 16) & 15)];
 }
 
 // Stage lane tid's chunks of the step at tile_off.  Readable are the 16-byte chunks of [0, lim), lim = end rounded up
 // to 16 (as for the sketch kernel); chunks outside are zero.
-MHX_FQ_HD bool fq_chunk_readable(uint64_t tile_off, int c, uint64_t lim)
+MHX_HD bool fq_chunk_readable(uint64_t tile_off, int c, uint64_t lim)
 {
     const uint64_t at = tile_off + 16u * (uint64_t)c; // + 16: offset of the chunk's end
     return at >= 16u && at - 16u < lim;
 }
-MHX_FQ_HD void fq_stage(FqSmem &sm, int tid, const uint8_t *base, uint64_t tile_off, uint64_t lim)
+MHX_HD void fq_stage(FqSmem &sm, int tid, const uint8_t *base, uint64_t tile_off, uint64_t lim)
 {
     const uint4 *src = reinterpret_cast<const uint4 *>(base + tile_off - 16u); // (chunk 0; used when readable)
     constexpr int kPer = (kFqChunks - 2) / kFqBlock;
@@ -158,7 +149,7 @@ MHX_FQ_HD void fq_stage(FqSmem &sm, int tid, const uint8_t *base, uint64_t tile_
 // One 32-byte word at tile byte L: w = its eight dwords, in = bits of its bytes inside the span, prev_start = the byte in
 // front of bit 0 is a newline or lies in front of the span, next_end = the byte behind bit 31 is a newline or lies
 // behind the span.
-MHX_FQ_HD FqSum<int32_t> fq_word(const FqSmem &sm, int L, const uint32_t (&w)[8], uint32_t in, bool prev_start, bool next_end)
+MHX_HD FqSum<int32_t> fq_word(const FqSmem &sm, int L, const uint32_t (&w)[8], uint32_t in, bool prev_start, bool next_end)
 {
     uint32_t nl = 0, nb = 0;
 #pragma unroll
@@ -212,7 +203,7 @@ MHX_FQ_HD FqSum<int32_t> fq_word(const FqSmem &sm, int L, const uint32_t (&w)[8]
 }
 
 // bits of the 32-byte word at absolute offset A (from base) that lie inside [begin, end)
-MHX_FQ_HD uint32_t fq_inrange(uint64_t A, uint64_t begin, uint64_t end)
+MHX_HD uint32_t fq_inrange(uint64_t A, uint64_t begin, uint64_t end)
 {
     uint32_t m = 0xFFFFFFFFu;
     if (begin > A) { const uint64_t lo = begin - A; m = lo >= 32 ? 0u : (m << lo); }
@@ -221,7 +212,7 @@ MHX_FQ_HD uint32_t fq_inrange(uint64_t A, uint64_t begin, uint64_t end)
 }
 
 // One lane's 128 bytes of the staged step (read as 16-byte pieces: see FqSmem).
-MHX_FQ_HD FqSum<int32_t> fq_thread(const FqSmem &sm, int tid, uint64_t tile_off, uint64_t begin, uint64_t end)
+MHX_HD FqSum<int32_t> fq_thread(const FqSmem &sm, int tid, uint64_t tile_off, uint64_t begin, uint64_t end)
 {
     const uint4 *mine = sm.bytes + fq_slot(8 * tid + 1);
     FqSum<int32_t> acc = fq_identity<int32_t>();

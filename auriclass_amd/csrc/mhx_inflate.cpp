@@ -49,27 +49,11 @@ bool GzInflater::Impl::read_member_header()
     // header are ignored, as gzread does.
     r.byte_align();
     r.unread(); // whole unread bytes go back so that r.in is the true position
-    const uint8_t *in = r.in, *const in_end = r.in_end;
-    if (in_end - in < 18) { state = kDone; return true; }
-    if (in[0] != 0x1f || in[1] != 0x8b) { state = kDone; return true; }
-    if (in[2] != 8) return fail("unsupported gzip compression method");
-    const uint8_t flg = in[3];
-    const uint8_t *p = in + 10;
-    if (flg & 4) { // FEXTRA
-        if (in_end - p < 2) return fail("truncated gzip header");
-        const size_t xlen = p[0] | (p[1] << 8);
-        p += 2;
-        if ((size_t)(in_end - p) < xlen) return fail("truncated gzip header");
-        p += xlen;
-    }
-    for (int bit = 8; bit <= 16; bit <<= 1) { // FNAME, FCOMMENT: zero-terminated
-        if (!(flg & bit)) continue;
-        const void *z = memchr(p, 0, (size_t)(in_end - p));
-        if (!z) return fail("truncated gzip header");
-        p = (const uint8_t *)z + 1;
-    }
-    if (flg & 2) { if (in_end - p < 2) return fail("truncated gzip header"); p += 2; } // FHCRC
-    r.in = p;
+    const int64_t h = gzip_member(r.in, r.in_end > r.in ? (size_t)(r.in_end - r.in) : 0);
+    if (h == kGzNone) { state = kDone; return true; }
+    if (h == kGzMethod) return fail("unsupported gzip compression method");
+    if (h == kGzTruncated) return fail("truncated gzip header");
+    r.in += h;
     crc = 0;
     member_out = 0;
     state = kBlockHeader;
@@ -106,11 +90,7 @@ bool GzInflater::Impl::read_trailer()
 static uint32_t g_crc_table[8][256];
 static void build_crc_tables()
 {
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1)));
-        g_crc_table[0][i] = c;
-    }
+    for (uint32_t i = 0; i < 256; ++i) g_crc_table[0][i] = crc_entry(i);
     for (uint32_t i = 0; i < 256; ++i)
         for (int t = 1; t < 8; ++t) g_crc_table[t][i] = (g_crc_table[t - 1][i] >> 8) ^ g_crc_table[0][g_crc_table[t - 1][i] & 0xFF];
 }

@@ -229,29 +229,6 @@ struct ParallelGunzip::Impl {
     void worker();
 };
 
-// gzip member header at z[0..): returns the offset of the deflate stream or 0
-static size_t member_header_len(const uint8_t *z, size_t n)
-{
-    if (n < 18 || z[0] != 0x1f || z[1] != 0x8b || z[2] != 8) return 0;
-    const uint8_t flg = z[3];
-    size_t p = 10;
-    if (flg & 4) {
-        if (n - p < 2) return 0;
-        const size_t xlen = z[p] | (z[p + 1] << 8);
-        p += 2;
-        if (n - p < xlen) return 0;
-        p += xlen;
-    }
-    for (int bit = 8; bit <= 16; bit <<= 1) {
-        if (!(flg & bit)) continue;
-        const void *e = memchr(z + p, 0, n - p);
-        if (!e) return 0;
-        p = (size_t)((const uint8_t *)e - z) + 1;
-    }
-    if (flg & 2) { if (n - p < 2) return 0; p += 2; }
-    return p < n ? p : 0;
-}
-
 // First bit position in [from_bit, to_bit) at which a non-final dynamic-Huffman block starts: its header parses (a complete
 // code-length code, valid length runs, an end-of-block symbol), the whole block decodes (symbolically) and a second
 // dynamic header follows.
@@ -546,7 +523,8 @@ bool ParallelGunzip::start(const uint8_t *z, size_t n, int threads, size_t min_b
     p.z = z;
     p.n = n;
     p.nthreads = threads;
-    p.deflate_off = member_header_len(z, n);
+    const int64_t h = gzip_member(z, n);
+    p.deflate_off = h > 0 && (size_t)h < n ? (size_t)h : 0; // 0: no member, or one the sequential decoder reports on
     // small inputs: the sequential decoder is as fast (MHX_PINFLATE_MIN / MHX_PINFLATE_SEGMENT: test knobs)
     const size_t min_env = getenv("MHX_PINFLATE_MIN") ? (size_t)atol(getenv("MHX_PINFLATE_MIN")) : 0;
     const size_t min_bytes = min_env ? min_env : (min_bytes_arg ? min_bytes_arg : (8u << 20));
@@ -680,23 +658,6 @@ struct BgzfReader::Impl {
     std::string error;
     size_t cur_group = 0, cur_off = 0;         // consumer position
 
-    // size of the BGZF block at z[off..), 0 if there is none
-    static uint32_t block_size(const uint8_t *z, size_t n, size_t off)
-    {
-        if (n - off < 28 || z[off] != 0x1f || z[off + 1] != 0x8b || z[off + 2] != 8 || !(z[off + 3] & 4)) return 0;
-        const uint32_t xlen = z[off + 10] | (z[off + 11] << 8);
-        if (n - off < 12 + (size_t)xlen) return 0;
-        for (uint32_t p = 0; p + 4 <= xlen;) {
-            const uint8_t *f = z + off + 12 + p;
-            const uint32_t slen = f[2] | (f[3] << 8);
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2 && p + 6 <= xlen) {
-                const uint32_t total = (uint32_t)(f[4] | (f[5] << 8)) + 1u;
-                return total >= 12 + xlen + 8 && total <= n - off ? total : 0;
-            }
-            p += 4 + slen;
-        }
-        return 0;
-    }
     void worker()
     {
         GzInflater inf;
@@ -754,7 +715,7 @@ bool BgzfReader::start(const uint8_t *z, size_t n, int threads)
     size_t off = 0;
     uint32_t in_group = 0;
     while (off < n) {
-        const uint32_t len = Impl::block_size(z, n, off);
+        const uint32_t len = bgzf_block_size(z + off, n - off);
         if (!len) break;
         const uint8_t *t = z + off + len - 4;
         const uint32_t isize = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);

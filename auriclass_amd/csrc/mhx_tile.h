@@ -22,17 +22,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define MHX_HD __host__ __device__ __forceinline__
-#else
-#define MHX_HD inline
-#ifndef MHX_HOST_UINT4
-#define MHX_HOST_UINT4
-struct uint4 { uint32_t x, y, z, w; };
-#endif
-#endif
-
+#include "mhx_hd.h"
 #include "mhx_device_consts.h"
 
 // rare branches are laid out of line: the hot path falls through instead of jumping over the cold block

@@ -13,13 +13,13 @@ from auriclass_amd import synth
 
 ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tests" / "emul" / "dinflate_emul.cpp"
-HDR = ROOT / "auriclass_amd" / "csrc" / "mhx_dinflate.h"
+HDR = [ROOT / "auriclass_amd" / "csrc" / h for h in ("mhx_dinflate.h", "mhx_deflate.h", "mhx_hd.h")]
 SO = ROOT / "tests" / "emul" / "_dinflate_emul.so"
 
 
 @pytest.fixture(scope="module")
 def emul():
-    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, HDR.stat().st_mtime):
+    if not SO.exists() or SO.stat().st_mtime < max(p.stat().st_mtime for p in [SRC, *HDR]):
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC), "-lz"], check=True)
     L = ctypes.CDLL(str(SO))
     L.emul_gunzip.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,

@@ -23,7 +23,7 @@ SPECIAL = np.frombuffer(b"\n\n\n@+>\r ANacgt" + b" \t\r\x7f\x00", np.uint8)
 def tile_emul():
     src, so = ROOT / "tests" / "emul" / "tile_emul.cpp", ROOT / "tests" / "emul" / "_tile_emul.so"
     hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_tile.h"
-    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, hdr.stat().st_mtime):
+    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
     L = ctypes.CDLL(str(so))
     L.emul_sketch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
@@ -34,7 +34,7 @@ def tile_emul():
 @pytest.fixture(scope="module")
 def fq():
     hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_fqcheck.h"
-    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime):
+    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
     L = ctypes.CDLL(str(SO))
     L.emul_fqcheck.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]

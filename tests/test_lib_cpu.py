@@ -189,6 +189,62 @@ def test_gunzip_never_reads_stored_block_lengths_from_the_pad(lib):
     assert engine.gunzip(z) == b"ACGT"
 
 
+class _BitWriter:
+    """DEFLATE bit order: fields least significant bit first, Huffman codes most significant bit first."""
+
+    def __init__(self):
+        self.acc, self.n = 0, 0
+
+    def put(self, v, k):
+        self.acc |= v << self.n
+        self.n += k
+        return self
+
+    def code(self, c, k):
+        return self.put(int(format(c, f"0{k}b")[::-1], 2), k)
+
+    def bytes(self):
+        return self.acc.to_bytes((self.n + 7) // 8, "little")
+
+
+def test_gunzip_error_texts(lib):
+    """Each corrupt stream gets zlib's text for the first check it fails."""
+    hdr = bytes([0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3])
+
+    def member(deflate: bytes) -> bytes:
+        return hdr + deflate + bytes(16)   # room behind the stream: no check runs out of input first
+
+    def dynamic(hlit=0, hdist=0, clens=(0, 0, 0, 0)):
+        w = _BitWriter().put(1, 1).put(2, 2).put(hlit, 5).put(hdist, 5).put(len(clens) - 4, 4)
+        for l in clens:                    # in the order 16, 17, 18, 0, 8, 7, ...
+            w.put(l, 3)
+        return w
+
+    good = _gz(b"ACGT" * 10)
+    cases = {
+        "invalid block type": member(_BitWriter().put(1, 1).put(3, 2).bytes()),
+        "stored block length check failed": member(_BitWriter().put(1, 1).put(0, 2).bytes() + b"\x04\x00\x00\x00ACGT"),
+        "too many length or distance symbols": member(dynamic(hlit=30).bytes()),
+        "invalid code lengths set": member(dynamic(clens=[1] * 19).bytes()),
+        # code-length code {0: '0', 16: '1'}; the first length is a repeat of nothing
+        "invalid bit length repeat": member(dynamic(clens=(1, 0, 0, 1)).put(1, 1).bytes()),
+        # code-length code {0: '00'}; '11' is no code of it
+        "invalid code length code": member(dynamic(clens=(0, 0, 0, 2)).put(3, 2).bytes()),
+        # code-length code {0: '0', 18: '1'}: 138 + 120 zero lengths, none for the end-of-block symbol
+        "invalid code -- missing end-of-block": member(dynamic(clens=(0, 0, 1, 1)).put(1, 1).put(127, 7).put(1, 1).put(109, 7).bytes()),
+        # fixed Huffman: length 3 (code 257), distance 1 (code 0) with no output yet
+        "invalid distance too far back": member(_BitWriter().put(1, 1).put(1, 2).code(1, 7).code(0, 5).code(0, 7).bytes()),
+        "incorrect data check": good[:-8] + bytes([good[-8] ^ 1]) + good[-7:],
+        "incorrect length check": good[:-4] + bytes([good[-4] ^ 1]) + good[-3:],
+        "unsupported gzip compression method": bytes([0x1f, 0x8b, 7]) + hdr[3:] + bytes(16),
+        "truncated gzip header": bytes([0x1f, 0x8b, 8, 8]) + hdr[4:] + b"reads.fq.gz",   # FNAME without its terminator
+    }
+    for text, z in cases.items():
+        with pytest.raises(engine.EngineError) as e:
+            engine.gunzip(z)
+        assert e.value.message == "gunzip: " + text, text
+
+
 def test_gunzip_header_truncation_sweep(lib):
     """Every prefix of a multi-block .gz (cut inside the member header, the HLIT/HDIST/HCLEN fields, the code-length
     code, the length runs, the data, the trailer) is refused or -- cut between members -- decodes to a prefix; none

@@ -18,7 +18,7 @@ MAXT = 2 ** 64 - 1
 @pytest.fixture(scope="module")
 def emul():
     hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_tile.h"
-    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime):
+    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
     L = ctypes.CDLL(str(SO))
     L.emul_sketch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
