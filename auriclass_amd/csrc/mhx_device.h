@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mhx_device_consts.h"
+#include "mhx_dist.h"
 
 namespace mhx {
 
@@ -123,27 +124,22 @@ struct DistArgs {
 };
 hipError_t launch_dist_pairs(const DistArgs &a, hipStream_t st);
 
-// all-vs-refs fast path (nr <= 32): value-range partition + LDS hash probe
-#ifndef MHX_DIST_RANGES
-#define MHX_DIST_RANGES 1024
-#endif
-#ifndef MHX_DIST_SLOTS
-#define MHX_DIST_SLOTS 2048
-#endif
-constexpr int kDistRanges = MHX_DIST_RANGES;     // value ranges the hash space is cut into
-constexpr int kDistTableSlots = MHX_DIST_SLOTS; // LDS table of one range (refs' hashes of that range)
+// all-vs-refs fast path (nr <= 32): value-range partition + LDS hash probe.  kDistRanges, kDistTableSlots, kDistSegs and
+// the geometry rule (dist_windows) are in mhx_dist.h, with the logic the kernels share with the CPU emulator.
 #ifndef MHX_DIST_QCHUNKS
 #define MHX_DIST_QCHUNKS 4
 #endif
 constexpr int kDistQueryChunks = MHX_DIST_QCHUNKS;   // query chunks per range (grid.y of the range kernel)
-constexpr int kDistSegs = 16;         // finish kernel: ranges are summed in 16 segments first
 struct DistWork {
-    uint32_t *offs_q;   // [nq][kDistRanges + 1] first index of every range in each query list
-    uint32_t *offs_r;   // [nr][kDistRanges + 1]
-    uint8_t *cpart;     // [nq][kDistRanges][4 * ceil(nr / 4)] shared hashes per (query, range, ref), one byte each
+    uint32_t *offs_q;   // [nq][ranges + 1] first index of every range in each query list
+    uint32_t *offs_r;   // [nr][ranges + 1]
+    uint8_t *cpart;     // [nq][ranges][4 * ceil(nr / 4)] shared hashes per (query, range, ref), one byte each
     uint32_t *params;   // [0] shift, [1] overflow flag
+    uint32_t *wtot;     // windowed form only: [nq][ranges / kDistWindowRanges][4 * ceil(nr / 4)] shared hashes per (query, window, ref)
+    uint32_t ranges;    // kDistRanges * W (mhx_dist.h: dist_windows); kDistRanges = the base form, whose kernels do not read this
 };
-size_t dist_work_bytes(uint32_t nq, uint32_t nr, size_t *off_q, size_t *off_r, size_t *off_c, size_t *off_p);
+// workspace of one (query batch, reference slice) block; with ranges == kDistRanges the layout of the base form (no wtot)
+size_t dist_work_bytes(uint32_t nq, uint32_t nr, uint32_t ranges, size_t *off_q, size_t *off_r, size_t *off_c, size_t *off_w, size_t *off_p);
 hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t st);
 
 } // namespace mhx

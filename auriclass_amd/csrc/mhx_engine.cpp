@@ -1258,6 +1258,7 @@ extern "C" int mhx_merge_shard_partials(const uint64_t *hashes, const uint32_t *
 // ---- batched distance ------------------------------------------------------------------
 extern "C" double mhx_last_dist_kernel_ms(void) { return g.last_dist_ms; }
 extern "C" int mhx_last_dist_fallback_blocks(void) { return g.last_dist_fallbacks; }
+extern "C" int mhx_last_dist_ranges(void) { return g.last_dist_ranges; }
 
 // Persistent device staging of the host-pointer form (one buffer, grown on demand): six hipMalloc / hipFree pairs per
 // call cost more than the kernels of an AuriClass-sized comparison (1 query x 24 references).
@@ -1334,19 +1335,33 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     // word, all of them come back with ONE copy behind the last launch.
     // (few pairs of LONG lists take it too -- AuriClass's own call, 1 query x 24 references at s = 50 000: 0.48 ms in the
     // generic kernel, whose 24 workgroups each walk 100 000 elements)
-    const bool fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)s >= 400000)) && getenv("MHX_DIST_GENERIC") == nullptr;
+    // The number of value ranges follows the longest list of the call (its length, never its values; the row stride where
+    // the lengths are on the device): 1024 x W, W = 1 up to 65 536 entries -- the kernels, grids and workspace of round 3 --
+    // up to 16 at 2^20 (mhx_dist.h: dist_windows), so that sketches of up to 1 000 000 hashes keep slices of at most 64
+    // entries and stay on this path; longer lists have no geometry and go to the generic kernel.
+    uint32_t longest = stride;
+    if (!device_ptrs) {
+        longest = 0;
+        for (uint32_t i = 0; i < nq; ++i) longest = std::max(longest, q_len[i]);
+        for (uint32_t i = 0; i < nr; ++i) longest = std::max(longest, r_len[i]);
+    }
+    const uint32_t windows = dist_windows(longest), ranges = (uint32_t)kDistRanges * windows;
+    const bool fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)s >= 400000)) && windows != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
     uint32_t qbatch = nq;
     if (const char *e = getenv("MHX_DIST_QBATCH")) { const long v = atol(e); if (v > 0 && (uint64_t)v < nq) qbatch = (uint32_t)v; }
+    if (windows > 1) qbatch = std::min(qbatch, dist_wide_max_queries(nr < 32 ? nr : 32, ranges)); // the workspace stays below kDistWideWorkLimit
     const uint32_t nslices = (nr + 31) / 32, nbatches = (nq + qbatch - 1) / qbatch, nblocks = nslices * nbatches;
     DistWork w{};
     uint32_t *d_params = nullptr;
     constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together (a reference set of 131 072 sketches per group)
     if (fast) {
-        size_t oq, orr, oc, op;
-        const size_t need = dist_work_bytes(qbatch, nr < 32 ? nr : 32, &oq, &orr, &oc, &op) + (size_t)std::min(nblocks, kBlockGroup) * 8;
+        size_t oq, orr, oc, ow, op;
+        const size_t need = dist_work_bytes(qbatch, nr < 32 ? nr : 32, ranges, &oq, &orr, &oc, &ow, &op) + (size_t)std::min(nblocks, kBlockGroup) * 8;
         if (g.dist_ws.grow(need, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the distance workspace");
         w.offs_q = (uint32_t *)(g.dist_ws + oq); w.offs_r = (uint32_t *)(g.dist_ws + orr);
         w.cpart = g.dist_ws + oc;
+        w.wtot = (uint32_t *)(g.dist_ws + ow);
+        w.ranges = ranges;
         d_params = (uint32_t *)(g.dist_ws + op); // [block][2]: shift, overflow flag
     }
     auto block_args = [&](uint32_t b) {
@@ -1368,6 +1383,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     hipError_t le = hipSuccess;
     if (!fast) { le = launch_dist_pairs(a, g.stream); g.last_dist_fallbacks = -1; }
     if (fast) g.last_dist_fallbacks = 0;
+    g.last_dist_ranges = 0;
     for (uint32_t b0 = 0; fast && b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
         const uint32_t b1 = std::min(nblocks, b0 + kBlockGroup);
         for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b) {
@@ -1383,6 +1399,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
             if (flags[2 * (b - b0) + 1]) { le = launch_dist_pairs(block_args(b), g.stream); ++g.last_dist_fallbacks; } // a value range overflowed the LDS table
     }
     hipEventRecord(g.ev1, g.stream);
+    if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges; // (0: the generic kernel did all the work)
     if (le != hipSuccess) return fail(MHX_E_HIP, "dist kernel launch failed: %s", hipGetErrorString(le));
     hipError_t se = hipSuccess;
     if (!device_ptrs) {

@@ -117,6 +117,7 @@ struct Engine {
     DevArray<uint8_t> dist_ws; // workspace of the all-vs-refs distance path
     DevArray<uint8_t> dist_in; // staging of a host-pointer distance batch (rows, lengths, outputs)
     int last_dist_fallbacks = 0;
+    int last_dist_ranges = 0;    // value ranges per block of the last distance call (0: generic kernel only)
     PinnedArray<uint8_t> dist_img; // pinned image of the reference sketch file of mhx_dist_files
     // bulk file ingest: pinned staging ring (allocated on first use, kept)
     static constexpr int kPinnedSlots = 4;

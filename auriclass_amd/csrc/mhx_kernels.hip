@@ -963,15 +963,26 @@ hipError_t launch_dist_pairs(const DistArgs &a, hipStream_t st)
 
 // ---------------------------------------------------------------------------------------
 // All-vs-refs distance, fast path.  Hash values are uniform, so cutting the value space into
-// 512 equal ranges cuts every sorted list into 512 short, aligned sub-lists (offsets by
-// binary search).  For one range, ALL references' hashes (<= 32 refs) go into one LDS hash
+// R equal ranges cuts every sorted list into R short, aligned sub-lists (offsets by one pass
+// over the list).  R = kDistRanges (1024) x W, W chosen on the host from the length of the
+// call's longest list (mhx_dist.h: dist_windows; W = 1 up to 65 536 entries, 16 at 2^20), so
+// that a slice holds at most 64 entries on average whatever the sketch size.  The scale is
+// rounded to a power of two, so between R / 2 + 1 and R of the ranges are really in use.
+// For one range, ALL references' hashes (<= 32 refs) go into one LDS hash
 // table: key -> bit mask of the references that contain it.  Every query element is then
 // probed ONCE and yields its shared-hash bits for all references at the same time (ballot +
 // popcount per reference), instead of being merged 24 times.  A last kernel walks the
 // per-range counts of each (query, ref) pair to the range where the union reaches s and
 // finishes that one short range exactly with the sequential two-pointer rule.
+// The shift, split and range kernels are templates with two instantiations: <false> is the
+// base form (W = 1: kDistRanges is a compile-time constant -- the code of round 3, instruction
+// for instruction), <true> the windowed form (R = w.ranges), which also has a level between
+// pair and range in the finish pass (dist_window_kernel, dist_finish_wide_kernel).
+// The rules themselves are the host+device functions of mhx_dist.h.
 // ---------------------------------------------------------------------------------------
-__global__ void dist_shift_kernel(const DistArgs a, DistWork w)
+template <bool kWide> __device__ __forceinline__ uint32_t dist_ranges(const DistWork &w) { return kWide ? w.ranges : (uint32_t)kDistRanges; }
+
+template <bool kWide> __global__ void dist_shift_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long gmax;
     if (threadIdx.x == 0) gmax = 0;
@@ -989,20 +1000,18 @@ __global__ void dist_shift_kernel(const DistArgs a, DistWork w)
     atomicMax(&gmax, m);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int bits = gmax ? 64 - __builtin_clzll(gmax) : 1;
-        const int lg = 31 - __builtin_clz((unsigned)kDistRanges);
-        w.params[0] = bits > lg ? bits - lg : 0; // value >> shift is a range index < kDistRanges
+        w.params[0] = dist_shift_for(gmax, dist_ranges<kWide>(w)); // value >> shift is a range index < R
         w.params[1] = 0;
     }
 }
 
-// offs[list][p] = first element of the list whose range index (value >> shift) is >= p, for p = 0 .. kDistRanges.
+// offs[list][p] = first element of the list whose range index (value >> shift) is >= p, for p = 0 .. R.
 // One thread per ELEMENT: it compares its range index with its left neighbour's and writes the few offsets that fall
 // between the two (none at all for 98 % of the elements: a range holds ~49 of them).  Every list is read once, coalesced --
 // the per-offset binary searches of round 1 moved 709 MB per C5 call for 419 MB of lists and ran at the HBM limit.
-__global__ __launch_bounds__(256) void dist_split_kernel(const DistArgs a, DistWork w, uint32_t list0)
+template <bool kWide> __global__ __launch_bounds__(256) void dist_split_kernel(const DistArgs a, DistWork w, uint32_t list0)
 {
-    const uint32_t list = blockIdx.x + list0, per = kDistRanges + 1; // lists along x (no 65 535 limit), element blocks along y
+    const uint32_t list = blockIdx.x + list0, per = dist_ranges<kWide>(w) + 1; // lists along x (no 65 535 limit), element blocks along y
     const bool isq = list < a.nq;
     const uint32_t li = isq ? list : list - a.nq;
     const uint32_t n = isq ? a.q_len[li] : a.r_len[li];
@@ -1026,14 +1035,11 @@ __global__ __launch_bounds__(256) void dist_split_kernel(const DistArgs a, DistW
         e0 = v[i];
         if (two) e1 = v[i + 1];
     }
-    const uint32_t r0 = (uint32_t)(e0 >> shift), r1 = two ? (uint32_t)(e1 >> shift) : r0;
+    const uint32_t r0 = dist_range_of(e0, shift), r1 = two ? dist_range_of(e1, shift) : r0;
     // offsets p in (range of the left neighbour, range of this element] point at this element; the list's first element
     // also serves p = 0 .. its own range, the last one leaves everything above its range at n
-    uint32_t from = i == 0 ? 0u : (uint32_t)(v[i - 1] >> shift) + 1u;
-    for (uint32_t p = from; p <= r0 && p < per; ++p) offs[p] = i;
-    if (two) for (uint32_t p = r0 + 1; p <= r1 && p < per; ++p) offs[p] = i + 1;
-    if (i + 2 >= n)
-        for (uint32_t p = r1 + 1; p < per; ++p) offs[p] = n;
+    const uint32_t from = i == 0 ? 0u : dist_range_of(v[i - 1], shift) + 1u;
+    dist_split_offsets(offs, per, i, n, two, from, r0, r1);
 }
 
 // Sum over the wave of a word of four byte counters (no carry between the bytes as long as every total stays < 256),
@@ -1056,12 +1062,11 @@ __device__ __forceinline__ uint32_t wave_sum_bytes(uint32_t v)
 // instead of 0.05 for AuriClass's own 1 x 24 comparison, 62 ms instead of 0.4 for 1024 queries).  The probe sequence is
 // bounded by the table size, so a table that does fill up (non-uniform values) ends the build instead of hanging it; the
 // caller checks `ndistinct` against kDistTableLimit behind the barrier and gives the range up.
-constexpr uint32_t kDistTableLimit = (kDistTableSlots * 3) / 4;
 // returns the number of keys this call added (0 or 1; kDistTableSlots when the table had no room at all): the callers sum
 // it per thread and add the wave totals to the shared count once, behind the build (dist_table_count)
 __device__ __forceinline__ uint32_t dist_table_insert(unsigned long long *keys, uint32_t *masks, uint64_t v, uint32_t r)
 {
-    uint32_t sl = (uint32_t)((v * 0x9E3779B97F4A7C15ull) >> 40) & (kDistTableSlots - 1);
+    uint32_t sl = dist_slot_of(v);
 #pragma nounroll
     for (int probe = 0; probe < kDistTableSlots; ++probe) {
         const unsigned long long prev = atomicCAS(&keys[sl], (unsigned long long)kEmptyKey, (unsigned long long)v);
@@ -1077,19 +1082,18 @@ __device__ __forceinline__ void dist_table_count(uint32_t *ndistinct, uint32_t m
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(ndistinct, mine);
 }
 
-__global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistWork w)
+template <bool kWide> __global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long keys[kDistTableSlots];
     __shared__ uint32_t masks[kDistTableSlots];
     __shared__ uint32_t too_big;
     // neighbouring ranges share the cache lines their slices begin and end in: consecutive workgroups go round the eight
     // XCDs, so this order puts ranges p, p + 1, ... of one eighth of the value space on ONE XCD (its L2), close in time
-    const uint32_t p = (blockIdx.x & 7u) * (kDistRanges / 8) + (blockIdx.x >> 3), per = kDistRanges + 1;
+    const uint32_t R = dist_ranges<kWide>(w), p = dist_range_of_block(blockIdx.x, R), per = R + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < kDistTableSlots; i += 256) { keys[i] = kEmptyKey; masks[i] = 0; }
     if (tid == 0) too_big = 0; // number of distinct keys in the table
     __syncthreads();
-    auto slot_of = [](uint64_t x) { return (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> 40) & (kDistTableSlots - 1); };
     // build: wave w inserts references w, w+4, ...; a reference's slice of this range is a
     // few dozen hashes, so all slices of the wave are loaded first, then inserted
     {
@@ -1111,6 +1115,10 @@ __global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistW
             const uint32_t r = wave + 4 * g;
             if (r >= a.nr) continue;
             const uint32_t b = w.offs_r[r * per + p], e = w.offs_r[r * per + p + 1];
+            // windowed form: a reference slice of more than 255 entries is no uniform input either -- it is not inserted
+            // (a crowded range of a large sketch holds 10^5 entries and more, each of which would probe a full table from end
+            // to end) and counts as a table overflow
+            if (kWide && e - b > kDistSliceLimit) { added += (uint32_t)kDistTableSlots; continue; }
             for (uint32_t i = b + lane; i < e; i += 64) {
                 const uint64_t v = (i == b + lane && have[g]) ? x[g] : a.r[(uint64_t)r * a.stride + i];
                 added += dist_table_insert(keys, masks, v, r);
@@ -1158,19 +1166,13 @@ __global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistW
                 uint32_t m = 0;
                 if (i0 + lane < ee[g]) {
                     const uint64_t v = i0 == bb[g] ? x[g] : a.q[(uint64_t)q * a.stride + i0 + lane];
-                    uint32_t sl = slot_of(v);
-                    for (;;) {
-                        const unsigned long long kx = keys[sl];
-                        if (kx == v) { m = masks[sl]; break; }
-                        if (kx == kEmptyKey) break;
-                        sl = (sl + 1) & (kDistTableSlots - 1);
-                    }
+                    m = dist_table_probe(keys, masks, v);
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) // bits 4j .. 4j+3 of the mask -> the low bit of four bytes
-                    if (j < (int)nwords) acc[j] += (((m >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u;
+                    if (j < (int)nwords) acc[j] += dist_spread4(m, j);
             }
-            uint8_t *dst = w.cpart + ((uint64_t)q * kDistRanges + p) * (4 * nwords);
+            uint8_t *dst = w.cpart + ((uint64_t)q * R + p) * (4 * nwords);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 if (j >= (int)nwords) break;
@@ -1192,12 +1194,12 @@ __global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistW
 #define MHX_DIST_LANE_BLOCK 512
 #endif
 constexpr int kLaneBlock = MHX_DIST_LANE_BLOCK; // queries (= threads) per workgroup: they share one table build
-__global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistArgs a, DistWork w)
+template <bool kWide> __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long keys[kDistTableSlots];
     __shared__ uint32_t masks[kDistTableSlots];
     __shared__ uint32_t ndistinct; // keys in the table
-    const uint32_t p = (blockIdx.x & 7u) * (kDistRanges / 8) + (blockIdx.x >> 3), per = kDistRanges + 1;
+    const uint32_t R = dist_ranges<kWide>(w), p = dist_range_of_block(blockIdx.x, R), per = R + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // where range p begins and ends in every reference: lane r of EVERY wave holds reference r's pair (nr <= 32), so all
     // reference loads of the build are issued together -- two HBM round trips for the whole build instead of two per
@@ -1206,7 +1208,6 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
     if ((uint32_t)lane < a.nr) { rb = w.offs_r[lane * per + p]; re = w.offs_r[lane * per + p + 1]; }
     for (int i = tid; i < kDistTableSlots; i += kLaneBlock) { keys[i] = kEmptyKey; masks[i] = 0; }
     if (tid == 0) ndistinct = 0;
-    auto slot_of = [](uint64_t x) { return (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> 40) & (kDistTableSlots - 1); };
     uint32_t added = 0;
     auto insert = [&](uint64_t v, uint32_t r) { added += dist_table_insert(keys, masks, v, r); };
     constexpr int kWaves = kLaneBlock / 64, kPerWave = (32 + kWaves - 1) / kWaves;
@@ -1217,6 +1218,7 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
         const uint32_t r = (uint32_t)wave + (uint32_t)kWaves * t;
         const uint32_t b = __shfl(rb, (int)(r & 31u)), e = __shfl(re, (int)(r & 31u));
         rv[t] = 0;
+        if (kWide && r < a.nr && e - b > kDistSliceLimit) { added += (uint32_t)kDistTableSlots; continue; } // (see dist_range_kernel: counts as a table overflow)
         if (r < a.nr && b + lane < e) { rv[t] = a.r[(uint64_t)r * a.stride + b + lane]; have |= 1u << t; }
     }
     __syncthreads(); // the table is clear
@@ -1225,6 +1227,7 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
         if ((have >> t) & 1u) insert(rv[t], (uint32_t)wave + (uint32_t)kWaves * t);
     for (uint32_t r = wave; r < a.nr; r += kWaves) { // slices of more than 64 elements (rare with uniform hashes)
         const uint32_t b = __shfl(rb, (int)r), e = __shfl(re, (int)r);
+        if (kWide && e - b > kDistSliceLimit) continue;
         for (uint32_t i = b + 64u + lane; i < e; i += 64) insert(a.r[(uint64_t)r * a.stride + i], r);
     }
     dist_table_count(&ndistinct, added);
@@ -1237,7 +1240,7 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
     if (q >= a.nq) return;
     const uint32_t nwords = (a.nr + 3) / 4;
     const uint32_t b = w.offs_q[q * per + p], e = w.offs_q[q * per + p + 1];
-    uint32_t *dst = reinterpret_cast<uint32_t *>(w.cpart + ((uint64_t)q * kDistRanges + p) * (4 * nwords));
+    uint32_t *dst = reinterpret_cast<uint32_t *>(w.cpart + ((uint64_t)q * R + p) * (4 * nwords));
     if (e - b > 255u) { // a byte counter could overflow: not a uniform input, the generic kernel takes over
         atomicOr(&w.params[1], 1u);
         return;
@@ -1245,16 +1248,10 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
     const uint64_t *row = a.q + (uint64_t)q * a.stride;
     uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto one = [&](uint64_t v) {
-        uint32_t sl = slot_of(v), m = 0;
-        for (;;) {
-            const unsigned long long kx = keys[sl];
-            if (kx == v) { m = masks[sl]; break; }
-            if (kx == kEmptyKey) break;
-            sl = (sl + 1) & (kDistTableSlots - 1);
-        }
+        const uint32_t m = dist_table_probe(keys, masks, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) // bits 4j .. 4j+3 of the mask -> the low bit of four bytes
-            if (j < (int)nwords) acc[j] += (((m >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u;
+            if (j < (int)nwords) acc[j] += dist_spread4(m, j);
     };
 #ifndef MHX_DIST_LINE64
     if ((reinterpret_cast<uintptr_t>(row) & 127) == 0 && (a.stride & 15u) == 0) {
@@ -1322,6 +1319,7 @@ __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistA
 // only needs to know where its FIRST range begins (dist_segstart_kernel: one binary search per kDistWalk ranges), walks
 // on from there -- the next range starts where the value's range index changes -- and leaves the range starts behind for
 // the finish kernel (offs_q).  The line a range ends in is still in the lane's registers when the next range begins.
+// Base form only: a windowed call (W > 1) is never sent here, whatever MHX_DIST_WALK_MIN says.
 #ifndef MHX_DIST_WALK
 #define MHX_DIST_WALK 4
 #endif
@@ -1435,64 +1433,9 @@ __global__ __launch_bounds__(256) void dist_walk_kernel(const DistArgs a, DistWo
     }
 }
 
-// 16 pairs per workgroup; thread (seg, pair) first sums its 64 ranges, then the 16 threads of
-// segment 0 locate the cut segment, walk it range by range and finish the cut range with the
-// sequential two-pointer rule.
-__global__ __launch_bounds__(256) void dist_finish_kernel(const DistArgs a, DistWork w)
+// what the finish pass writes for one pair
+__device__ __forceinline__ void dist_store(const DistArgs &a, uint32_t q, uint32_t r, uint32_t common, uint32_t denom)
 {
-    __shared__ uint32_t seg_uni[kDistSegs][16], seg_com[kDistSegs][16];
-    constexpr int RPS = kDistRanges / kDistSegs; // ranges per segment
-    // the range kernel gave up on this slice (a value range too crowded for its table or for byte counters): cpart holds
-    // cells it never wrote, the host discards this result and runs the generic kernel -- nothing to do here, and
-    // nothing to be walked on the strength of stale counts
-    if (w.params[1] != 0) return;
-    const uint32_t pl = threadIdx.x & 15, seg = threadIdx.x >> 4;
-    const uint32_t pair = blockIdx.x * 16 + pl;
-    const bool live = pair < a.nq * a.nr;
-    const uint32_t q = live ? pair / a.nr : 0, r = live ? pair % a.nr : 0, per = kDistRanges + 1;
-    const uint32_t *oq = w.offs_q + q * per, *orr = w.offs_r + r * per;
-    // shared hashes per range of this pair: bytes, [query][range][4 * ceil(nr / 4)], 24 bytes apart from range to range
-    const uint32_t cstride = 4 * ((a.nr + 3) / 4);
-    const uint8_t *cp = w.cpart + (uint64_t)q * kDistRanges * cstride + r;
-    {
-        uint32_t com = 0;
-        for (uint32_t p = seg * RPS; p < (seg + 1) * RPS; ++p) com += cp[(uint64_t)p * cstride];
-        const uint32_t p0 = seg * RPS, p1 = (seg + 1) * RPS;
-        seg_com[seg][pl] = com;
-        seg_uni[seg][pl] = (orr[p1] - orr[p0]) + (oq[p1] - oq[p0]) - com;
-    }
-    __syncthreads();
-    if (seg != 0 || !live) return;
-    const uint32_t S = a.s;
-    uint32_t uni = 0, common = 0, sg = 0;
-    for (; sg < kDistSegs; ++sg) {
-        if (uni + seg_uni[sg][pl] >= S) break;
-        uni += seg_uni[sg][pl];
-        common += seg_com[sg][pl];
-    }
-    uint32_t denom;
-    if (sg == kDistSegs) denom = uni; // union smaller than s: everything counts
-    else {
-        uint32_t p = sg * RPS;
-        for (; p + 1 < (sg + 1) * RPS; ++p) { // the cut range is inside this segment (its last range is the cut at the latest)
-            const uint32_t c = cp[(uint64_t)p * cstride];
-            const uint32_t u = (orr[p + 1] - orr[p]) + (oq[p + 1] - oq[p]) - c;
-            if (uni + u >= S) break;
-            uni += u;
-            common += c;
-        }
-        const uint64_t *A = a.r + (uint64_t)r * a.stride, *B = a.q + (uint64_t)q * a.stride;
-        uint32_t i = orr[p], j = oq[p];
-        const uint32_t ie = orr[p + 1], je = oq[p + 1];
-        while (uni < S && i < ie && j < je) {
-            const uint64_t x = A[i], y = B[j];
-            if (x < y) ++i;
-            else if (y < x) ++j;
-            else { ++i; ++j; ++common; }
-            ++uni;
-        }
-        denom = S; // this range holds enough further union elements by construction
-    }
     const uint64_t out = (uint64_t)q * a.out_stride + a.out_off + r; // the references may be a slice of a wider batch
     a.common[out] = common;
     a.denom[out] = denom;
@@ -1509,20 +1452,133 @@ __global__ __launch_bounds__(256) void dist_finish_kernel(const DistArgs a, Dist
     }
 }
 
-size_t dist_work_bytes(uint32_t nq, uint32_t nr, size_t *off_q, size_t *off_r, size_t *off_c, size_t *off_p)
+// 16 pairs per workgroup; thread (seg, pair) first sums its 64 ranges, then the 16 threads of
+// segment 0 locate the cut segment, walk it range by range and finish the cut range with the
+// sequential two-pointer rule.
+__global__ __launch_bounds__(256) void dist_finish_kernel(const DistArgs a, DistWork w)
+{
+    __shared__ uint32_t seg_uni[kDistSegs][16], seg_com[kDistSegs][16];
+    constexpr int RPS = kDistRanges / kDistSegs; // ranges per segment
+    // the range kernel gave up on this slice (a value range too crowded for its table or for byte counters): cpart holds
+    // cells it never wrote, the host discards this result and runs the generic kernel -- nothing to do here, and
+    // nothing to be walked on the strength of stale counts
+    if (w.params[1] != 0) return;
+    const uint32_t pl = threadIdx.x & 15, seg = threadIdx.x >> 4;
+    const uint32_t pair = blockIdx.x * 16 + pl;
+    const bool live = pair < a.nq * a.nr;
+    const uint32_t q = live ? pair / a.nr : 0, r = live ? pair % a.nr : 0, per = kDistRanges + 1;
+    // shared hashes per range of this pair: bytes, [query][range][4 * ceil(nr / 4)], 24 bytes apart from range to range
+    const uint32_t cstride = 4 * ((a.nr + 3) / 4);
+    const DistPair x{w.cpart + (uint64_t)q * kDistRanges * cstride + r, cstride, w.offs_q + q * per, w.offs_r + r * per,
+                     a.r + (uint64_t)r * a.stride, a.q + (uint64_t)q * a.stride, a.s};
+    {
+        uint32_t com = 0;
+        for (uint32_t p = seg * RPS; p < (seg + 1) * RPS; ++p) com += x.cp[(uint64_t)p * cstride];
+        seg_com[seg][pl] = com;
+        seg_uni[seg][pl] = dist_range_union(x, seg * RPS, (seg + 1) * RPS, com);
+    }
+    __syncthreads();
+    if (seg != 0 || !live) return;
+    uint32_t uni = 0, common = 0, denom;
+    const uint32_t sg = dist_scan_totals(&seg_uni[0][pl], &seg_com[0][pl], 16, 0, kDistSegs, a.s, uni, common);
+    if (sg == kDistSegs) denom = uni; // union smaller than s: everything counts
+    else {
+        const uint32_t p = dist_scan_ranges(x, sg * RPS, (sg + 1) * RPS, uni, common); // the cut range is inside this segment
+        dist_two_pointer(x, p, uni, common);
+        denom = a.s; // this range holds enough further union elements by construction
+    }
+    dist_store(a, q, r, common, denom);
+}
+
+// ---- the finish pass of the windowed form ---------------------------------------------------------------------------------
+// With R = 16 384 ranges the 16 threads of a pair would each sum 1024 byte cells.  A level between pair and range keeps
+// the work per thread where it is in the base form: dist_window_kernel sums every window of kDistWindowRanges (64)
+// ranges once, for the four references of a word at a time -- cpart is read once, word-wise, by neighbouring threads --
+// and the finish kernel works on windows: thread (group, pair) sums the 16 window totals of its group of 1024 ranges,
+// thread (0, pair) walks the <= 16 group totals to the cut group, its 16 windows to the cut window, that window's 64
+// ranges to the cut range (dist_scan_* of mhx_dist.h) and finishes the cut range with the two-pointer rule.
+__global__ __launch_bounds__(256) void dist_window_kernel(const DistArgs a, DistWork w)
+{
+    if (w.params[1] != 0) return; // (see dist_finish_kernel)
+    const uint32_t nwords = (a.nr + 3) / 4, nwin = w.ranges / kDistWindowRanges;
+    const uint32_t id = blockIdx.x * 256 + threadIdx.x; // (query, window, word), the word fastest
+    if (id >= a.nq * nwin * nwords) return;
+    const uint32_t j = id % nwords, qw = id / nwords; // qw = q * nwin + window
+    uint32_t tot[4];
+    dist_window_sum(reinterpret_cast<const uint32_t *>(w.cpart) + (uint64_t)qw * kDistWindowRanges * nwords + j, nwords, kDistWindowRanges, tot);
+    *reinterpret_cast<uint4 *>(w.wtot + ((uint64_t)qw * nwords + j) * 4) = make_uint4(tot[0], tot[1], tot[2], tot[3]);
+}
+
+__global__ __launch_bounds__(256) void dist_finish_wide_kernel(const DistArgs a, DistWork w)
+{
+    constexpr uint32_t kGroupWindows = kDistRanges / kDistWindowRanges; // a group: 16 windows, kDistRanges ranges
+    __shared__ uint32_t grp_uni[kDistMaxWindows][16], grp_com[kDistMaxWindows][16];
+    if (w.params[1] != 0) return; // (see dist_finish_kernel)
+    const uint32_t R = w.ranges, ngroups = R / kDistRanges, per = R + 1;
+    const uint32_t pl = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const uint32_t pair = blockIdx.x * 16 + pl;
+    const bool live = pair < a.nq * a.nr;
+    const uint32_t q = live ? pair / a.nr : 0, r = live ? pair % a.nr : 0;
+    const uint32_t cstride = 4 * ((a.nr + 3) / 4);
+    const DistPair x{w.cpart + (uint64_t)q * R * cstride + r, cstride, w.offs_q + q * per, w.offs_r + r * per,
+                     a.r + (uint64_t)r * a.stride, a.q + (uint64_t)q * a.stride, a.s};
+    const uint32_t *wt = w.wtot + (uint64_t)q * (R / kDistWindowRanges) * cstride + r; // this pair's window totals, cstride words apart
+    if (grp < ngroups) {
+        uint32_t com = 0;
+        for (uint32_t t = grp * kGroupWindows; t < (grp + 1) * kGroupWindows; ++t) com += wt[(uint64_t)t * cstride];
+        grp_com[grp][pl] = com;
+        grp_uni[grp][pl] = dist_range_union(x, grp * kDistRanges, (grp + 1) * kDistRanges, com);
+    }
+    __syncthreads();
+    if (grp != 0 || !live) return;
+    uint32_t uni = 0, common = 0, denom;
+    const uint32_t cg = dist_scan_totals(&grp_uni[0][pl], &grp_com[0][pl], 16, 0, ngroups, a.s, uni, common);
+    if (cg == ngroups) denom = uni; // union smaller than s: everything counts
+    else {
+        const uint32_t cw = dist_scan_windows(x, wt, cstride, cg * kGroupWindows, (cg + 1) * kGroupWindows, uni, common);
+        const uint32_t p = dist_scan_ranges(x, cw * kDistWindowRanges, (cw + 1) * kDistWindowRanges, uni, common);
+        dist_two_pointer(x, p, uni, common);
+        denom = a.s; // this range holds enough further union elements by construction
+    }
+    dist_store(a, q, r, common, denom);
+}
+
+size_t dist_work_bytes(uint32_t nq, uint32_t nr, uint32_t ranges, size_t *off_q, size_t *off_r, size_t *off_c, size_t *off_w, size_t *off_p)
 {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t cell = 4 * ((nr + 3) / 4);
     size_t o = 0;
-    *off_q = o; o += up((size_t)nq * (kDistRanges + 1) * 4);
-    *off_r = o; o += up((size_t)nr * (kDistRanges + 1) * 4);
-    *off_c = o; o += up((size_t)kDistRanges * nq * 4 * ((nr + 3) / 4));
+    *off_q = o; o += up((size_t)nq * (ranges + 1) * 4);
+    *off_r = o; o += up((size_t)nr * (ranges + 1) * 4);
+    *off_c = o; o += up((size_t)ranges * nq * cell);
+    *off_w = o; if (ranges != (uint32_t)kDistRanges) o += up((size_t)(ranges / kDistWindowRanges) * nq * cell * 4);
     *off_p = o; // behind it: two words per (query batch, reference slice) block, sized by the caller
     return o;
 }
 
+// the windowed form (w.ranges = kDistRanges * W, W > 1): the same passes with R as a launch parameter.  The caller bounds
+// the batch (dist_work_bytes <= kDistWideWorkLimit), which keeps every q * (R + 1) product of the kernels below 2^32.
+static hipError_t launch_dist_ranges_wide(const DistArgs &a, const DistWork &w, hipStream_t st)
+{
+    const uint32_t R = w.ranges;
+    hipLaunchKernelGGL(dist_shift_kernel<true>, dim3(1), dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(dist_split_kernel<true>, dim3(a.nq + a.nr, (a.stride + 511) / 512), dim3(256), 0, st, a, w, 0u);
+    if (a.nq >= 128 && getenv("MHX_DIST_NO_LANE") == nullptr)
+        hipLaunchKernelGGL(dist_range_lane_kernel<true>, dim3(R, (a.nq + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, a, w);
+    else { // a workgroup serves 32 queries per round: no more chunks than there are rounds (a chunk without queries only builds the table)
+        const uint32_t chunks = std::min<uint32_t>(kDistQueryChunks, (a.nq + 31) / 32);
+        hipLaunchKernelGGL(dist_range_kernel<true>, dim3(R, chunks), dim3(256), 0, st, a, w);
+    }
+    const uint32_t cells = a.nq * (R / kDistWindowRanges) * ((a.nr + 3) / 4), pairs = a.nq * a.nr;
+    hipLaunchKernelGGL(dist_window_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, a, w);
+    hipLaunchKernelGGL(dist_finish_wide_kernel, dim3((pairs + 15) / 16), dim3(256), 0, st, a, w);
+    return hipGetLastError();
+}
+
 hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t st)
 {
-    hipLaunchKernelGGL(dist_shift_kernel, dim3(1), dim3(256), 0, st, a, w);
+    if (w.ranges != (uint32_t)kDistRanges) return launch_dist_ranges_wide(a, w, st);
+    hipLaunchKernelGGL(dist_shift_kernel<false>, dim3(1), dim3(256), 0, st, a, w);
     const bool no_lane = getenv("MHX_DIST_NO_LANE") != nullptr, no_walk = getenv("MHX_DIST_NO_WALK") != nullptr;
     // rows of whole 128-byte lines (the walk reads a row line by line), enough queries to fill the lanes.
     // Measured with 128-byte lines in both forms (C5 rows, profiles/r03_dist_line128_ab.txt): 1024 queries 0.40 ms lane
@@ -1537,14 +1593,14 @@ hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t 
 #endif
     const bool walk = !no_lane && !no_walk && a.nq >= walk_min && whole_lines;
     if (walk) {
-        hipLaunchKernelGGL(dist_split_kernel, dim3(a.nr, (a.stride + 511) / 512), dim3(256), 0, st, a, w, a.nq); // the references only
+        hipLaunchKernelGGL(dist_split_kernel<false>, dim3(a.nr, (a.stride + 511) / 512), dim3(256), 0, st, a, w, a.nq); // the references only
         constexpr uint32_t G = kDistRanges / kDistWalk;
         hipLaunchKernelGGL(dist_segstart_kernel, dim3((a.nq * (G + 1) + 255) / 256), dim3(256), 0, st, a, w);
         hipLaunchKernelGGL(dist_walk_kernel, dim3(G, (a.nq + 255) / 256), dim3(256), 0, st, a, w);
     } else {
-        hipLaunchKernelGGL(dist_split_kernel, dim3(a.nq + a.nr, (a.stride + 511) / 512), dim3(256), 0, st, a, w, 0u);
-        if (a.nq >= 128 && !no_lane) hipLaunchKernelGGL(dist_range_lane_kernel, dim3(kDistRanges, (a.nq + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, a, w);
-        else hipLaunchKernelGGL(dist_range_kernel, dim3(kDistRanges, kDistQueryChunks), dim3(256), 0, st, a, w);
+        hipLaunchKernelGGL(dist_split_kernel<false>, dim3(a.nq + a.nr, (a.stride + 511) / 512), dim3(256), 0, st, a, w, 0u);
+        if (a.nq >= 128 && !no_lane) hipLaunchKernelGGL(dist_range_lane_kernel<false>, dim3(kDistRanges, (a.nq + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, a, w);
+        else hipLaunchKernelGGL(dist_range_kernel<false>, dim3(kDistRanges, kDistQueryChunks), dim3(256), 0, st, a, w);
     }
     const uint32_t pairs = a.nq * a.nr;
     hipLaunchKernelGGL(dist_finish_kernel, dim3((pairs + 15) / 16), dim3(256), 0, st, a, w);

@@ -108,6 +108,7 @@ def load() -> ctypes.CDLL:
                                  c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
     L.mhx_last_dist_kernel_ms.restype = c.c_double
     L.mhx_last_dist_fallback_blocks.restype = c.c_int
+    L.mhx_last_dist_ranges.restype = c.c_int
     L.mhx_p_value.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, c.c_int, c.c_uint64]
     L.mhx_p_value.restype = c.c_double
     L.mhx_msh_write.argtypes = [c.c_char_p, c.c_int, c.c_uint32, c.c_uint32, c.POINTER(c.c_char_p), c.POINTER(c.c_char_p),

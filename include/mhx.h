@@ -211,6 +211,11 @@ double mhx_last_dist_kernel_ms(void);
 /* diagnostics of the last mhx_dist_batch / mhx_dist_files call: -1 = the generic pair kernel did all the work (tiny batch),
  * else the number of (query batch, reference slice) blocks the all-vs-refs fast path gave up to it (0 for uniform hashes) */
 int mhx_last_dist_fallback_blocks(void);
+/* value ranges every (query batch, reference slice) block of that call was cut into: 1024 x W, W = the smallest power of two
+ * with longest list / (1024 W) <= 64 (1024 for lists of up to 65 536 hashes, 16 384 for 1 000 000; the longest list is taken
+ * from q_len / r_len, from `stride` when they are device pointers).  0 = the generic pair kernel did all the work: a tiny
+ * batch, lists of more than 2^20 hashes, or every block gave up */
+int mhx_last_dist_ranges(void);
 
 /* scalar pieces of the dist row (host): mash pValue() */
 double mhx_p_value(uint64_t common, uint64_t len_ref, uint64_t len_qry, int k, uint64_t denom);

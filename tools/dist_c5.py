@@ -77,7 +77,8 @@ def main():
     out = {"config": f"{args.nq} queries x {args.nr} refs, s={args.s}, k={args.k}", "pairs": pairs,
            "kernel_ms": round(kernel_ms, 4), "wall_ms_per_call": round(wall * 1e3, 3), "pairs_per_s": round(pairs / (kernel_ms / 1e3)),
            "algorithmic_bytes": alg_bytes, "achieved_GBps": round(alg_bytes / (kernel_ms / 1e3) / 1e9, 2), "hbm_peak_GBps": 8000.0,
-           "roofline_frac": round(alg_bytes / (kernel_ms / 1e3) / 1e9 / 8000.0, 5)}
+           "roofline_frac": round(alg_bytes / (kernel_ms / 1e3) / 1e9 / 8000.0, 5),
+           "fallback_blocks": engine.load().mhx_last_dist_fallback_blocks(), "ranges": engine.load().mhx_last_dist_ranges()}
     print(json.dumps(out))
 
 

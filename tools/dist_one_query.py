@@ -16,4 +16,4 @@ from oracle import mash_oracle as mo
 for it in range(4):
     c, d, x = engine.dist_batch(Q, ql, R, rl, 27, s)
     ok = all(mo.compare(R[j, :rl[j]], Q[0, :ql[0]], s, 27)[:2] == (int(c[0, j]), int(d[0, j])) for j in (0, 3, 11, 23))
-    print(os.environ.get("MHX_DIST_GENERIC", "default"), "s", s, "oracle ok", ok, "fallback blocks", engine.load().mhx_last_dist_fallback_blocks(), "kernel ms", round(engine.load().mhx_last_dist_kernel_ms(), 4), c[0, :4], d[0, :4])
+    print(os.environ.get("MHX_DIST_GENERIC", "default"), "s", s, "oracle ok", ok, "fallback blocks", engine.load().mhx_last_dist_fallback_blocks(), "ranges", engine.load().mhx_last_dist_ranges(), "kernel ms", round(engine.load().mhx_last_dist_kernel_ms(), 4), c[0, :4], d[0, :4])
