@@ -91,7 +91,12 @@ class BasicAuriclass:
         """All references against the query sketch; fills `mash_output` (+ a Clade column keyed
         on the reference names stored inside the sketch)."""
         logging.info(add_tag("mash dist", f"mash dist {self.reference_sketch_path} {self.query_sketch_path}"))
-        table_text = engine.dist_files(self.reference_sketch_path, self.query_sketch_path)
+        return self.set_mash_output(engine.dist_files(self.reference_sketch_path, self.query_sketch_path))
+
+    def set_mash_output(self, table_text: str) -> pd.DataFrame:
+        """`mash dist` stdout of THIS sample -> `mash_output`.  The text is read on its own, whoever produced it
+        (run_mash_dist, or a batch that cut it out of one multi-query call): pandas infers the column types from a
+        sample's own rows, and they show in the report."""
         table = pd.read_csv(StringIO(table_text), sep="\t", header=None, names=_DIST_COLUMNS)
         table["Clade"] = table["Reference"].map(self.clade_dict["clade"])
         self.mash_output = table

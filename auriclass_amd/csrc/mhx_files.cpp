@@ -1286,17 +1286,24 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
     return put_text(err, stderr_buf, stderr_cap, stderr_need);
 }
 
-static int mhx_dist_files_impl(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
+// `mash dist REF QUERY [QUERY ...]`: mhx_dist_files is the n_qry == 1 case.  The reference file is read, parsed, checked and
+// staged once per call, and the sketches of ALL query files go to the device together, so that a run of samples reaches
+// the all-vs-refs kernels in the shape they were made for (many queries x few references) instead of 1 x nr per sample.
+static int mhx_dist_files_impl(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
 {
     clear_error();
     int rc = require_engine();
     if (rc) return rc;
-    if (!ref_msh || !qry_msh) return fail(MHX_E_ARG, "dist: two sketch paths required");
+    if (n_qry == 1 && (!ref_msh || !qry_msh || !qry_msh[0])) return fail(MHX_E_ARG, "dist: two sketch paths required");
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "dist: a reference sketch path and at least one query sketch path required");
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "dist: query sketch path %d is null", i);
     // The reference sketch file (9.6 MB at AuriClass's defaults: 24 x 50 000 hashes) is read ONCE, into a pinned block,
     // parsed where it is (64-bit hash lists stay views into the image), checked for order on a few threads and copied
     // row by row from the pinned image into the device staging area: one pass over the bytes on the host instead of
     // five (file buffer, segment copies, hash vectors, padded matrix, pageable H2D staging): 5.6 -> 2 ms per call.
-    SketchSet R, Q;
+    SketchSet R;
+    std::vector<SketchSet> Q((size_t)n_qry);
     std::vector<uint8_t> ref_heap;
     static const bool timing = getenv("MHX_DIST_TIMING") != nullptr; // phase times of a call on stderr
     const auto t_start = std::chrono::steady_clock::now();
@@ -1340,21 +1347,34 @@ static int mhx_dist_files_impl(const char *ref_msh, const char *qry_msh, char *s
             if (bad[i]) return fail(MHX_E_FORMAT, "%s: hash list of reference %zu is not ascending", ref_msh, i);
         lap("order checked");
     }
-    rc = msh_read_file(qry_msh, Q);
-    if (rc) return rc;
+    uint64_t nq_all = 0;
+    for (int i = 0; i < n_qry; ++i) {
+        rc = msh_read_file(qry_msh[i], Q[i]);
+        if (rc) return rc;
+        if (R.kmer_size != Q[i].kmer_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", Q[i].kmer_size, R.kmer_size);
+        if (R.hash_seed != Q[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
+        if (Q[i].sketch_size != Q[0].sketch_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", qry_msh[0], qry_msh[i],
+                        Q[0].sketch_size, Q[i].sketch_size);
+        nq_all += Q[i].refs.size();
+    }
     lap("query read");
-    if (R.kmer_size != Q.kmer_size)
-        return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", Q.kmer_size, R.kmer_size);
-    if (R.hash_seed != Q.hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
     const int k = (int)R.kmer_size;
-    const uint32_t s = R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size;
-    const uint32_t nr = (uint32_t)R.refs.size(), nq = (uint32_t)Q.refs.size();
+    const uint32_t s = R.sketch_size < Q[0].sketch_size ? R.sketch_size : Q[0].sketch_size;
+    const uint32_t nr = (uint32_t)R.refs.size();
+    if (nq_all * (nr ? nr : 1) > 0x7FFFFFFFull) return fail(MHX_E_ARG, "too many pairs for one call");
+    const uint32_t nq = (uint32_t)nq_all;
     std::string text;
     if (nr && nq) {
+        std::vector<const RefSketch *> qs;
+        qs.reserve(nq);
+        for (const SketchSet &set : Q)
+            for (const RefSketch &q : set.refs) qs.push_back(&q);
         std::vector<const uint64_t *> rrows(nr), qrows(nq);
         std::vector<uint32_t> rl(nr), ql(nq);
         for (uint32_t i = 0; i < nr; ++i) { rrows[i] = R.refs[i].hash_data(); rl[i] = (uint32_t)R.refs[i].hash_count(); }
-        for (uint32_t i = 0; i < nq; ++i) { qrows[i] = Q.refs[i].hash_data(); ql[i] = (uint32_t)Q.refs[i].hash_count(); }
+        for (uint32_t i = 0; i < nq; ++i) { qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count(); }
         std::vector<uint32_t> common((size_t)nq * nr), denom((size_t)nq * nr);
         std::vector<double> dist((size_t)nq * nr);
         rc = dist_batch_rows(qrows.data(), ql.data(), nq, rrows.data(), rl.data(), nr, k, s, common.data(), denom.data(), dist.data());
@@ -1363,10 +1383,11 @@ static int mhx_dist_files_impl(const char *ref_msh, const char *qry_msh, char *s
         for (uint32_t qi = 0; qi < nq; ++qi)
             for (uint32_t ri = 0; ri < nr; ++ri) {
                 const size_t p = (size_t)qi * nr + ri;
-                const double pv = mhx_p_value(common[p], R.refs[ri].length, Q.refs[qi].length, k, denom[p]);
-                text += R.refs[ri].name + "\t" + Q.refs[qi].name + "\t" + fmt_g(dist[p]) + "\t" + fmt_g(pv) + "\t" +
+                const double pv = mhx_p_value(common[p], R.refs[ri].length, qs[qi]->length, k, denom[p]);
+                text += R.refs[ri].name + "\t" + qs[qi]->name + "\t" + fmt_g(dist[p]) + "\t" + fmt_g(pv) + "\t" +
                         std::to_string(common[p]) + "/" + std::to_string(denom[p]) + "\n";
             }
+        lap("text written");
     }
     return put_text(text, stdout_buf, cap, need);
 }
@@ -1411,14 +1432,23 @@ extern "C" int mhx_sketch_files(const char *const *paths, int n_paths, int k, ui
 
 extern "C" int mhx_last_fastq_route(void) { return g.last_fastq_route; }
 
-extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
+static int dist_files_guarded(const char *what, const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
 {
     try {
-        return mhx_dist_files_impl(ref_msh, qry_msh, stdout_buf, cap, need);
+        return mhx_dist_files_impl(ref_msh, qry_msh, n_qry, stdout_buf, cap, need);
     } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_files: out of host memory");
+        return fail(MHX_E_INTERNAL, "%s: out of host memory", what);
     } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_files: %s", e.what());
+        return fail(MHX_E_INTERNAL, "%s: %s", what, e.what());
     }
 }
 
+extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
+{
+    return dist_files_guarded("mhx_dist_files", ref_msh, &qry_msh, 1, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
+{
+    return dist_files_guarded("mhx_dist_files_multi", ref_msh, qry_msh, n_qry, stdout_buf, cap, need);
+}

@@ -80,6 +80,7 @@ def load() -> ctypes.CDLL:
     L.mhx_sketch_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.c_int, c.c_uint32, c.c_int, c.c_uint32, c.c_char_p,
                                    c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t), c.POINTER(c.c_double)]
     L.mhx_dist_files.argtypes = [c.c_char_p, c.c_char_p, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    L.mhx_dist_files_multi.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
     L.mhx_bounds.argtypes = [c.c_int, c.c_double, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
     L.mhx_fasta_total_bases.argtypes = [c.c_char_p, u64p]
     L.mhx_sniff_fastq.argtypes = [c.c_char_p]
@@ -199,6 +200,17 @@ def dist_files(ref_msh, qry_msh) -> str:
     """`mash dist REF QUERY` stdout."""
     init()
     return _text_call(load().mhx_dist_files, os.fsencode(str(ref_msh)), os.fsencode(str(qry_msh)))
+
+
+def dist_files_multi(ref_msh, qry_paths: Sequence) -> str:
+    """`mash dist REF QUERY [QUERY ...]` stdout: the rows of dist_files(ref, q) for every q, in argument order, from ONE
+    call that reads and stages the reference once and compares all query sketches together.  The first buffer holds
+    64 KiB per query file (25 times the 24 rows of an AuriClass reference set); a larger reference set costs the
+    second, correct-but-slower call of _text_call."""
+    init()
+    paths = [os.fsencode(str(p)) for p in qry_paths]
+    arr = (ctypes.c_char_p * len(paths))(*paths)
+    return _text_call(load().mhx_dist_files_multi, os.fsencode(str(ref_msh)), arr, len(paths), guess=max(1, len(paths)) << 16)
 
 
 def bounds(k: int, p: float) -> str:

@@ -8,6 +8,7 @@
  *   mhx_sketch_files  <- `mash sketch [-r -m M] -o OUT -k K -s S files...`
  *                        auriclass/classes.py:576-596 (FASTQ) and :696-713 (FASTA)
  *   mhx_dist_files    <- `mash dist REF.msh QUERY.msh`      auriclass/classes.py:92-104
+ *   mhx_dist_files_multi <- `mash dist REF.msh QUERY.msh [QUERY.msh ...]` (a run of samples, one call)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_init          <- `mash -h` dependency probe         auriclass/general.py:198-205
  *
@@ -79,6 +80,18 @@ int mhx_sketch_files(const char *const *paths, int n_paths, int k, uint32_t s, i
 
 /* `mash dist REF QUERY` stdout: rows "ref\tquery\tdist\tp\tcommon/denom\n", query-major. */
 int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need);
+
+/* `mash dist REF QUERY [QUERY ...]` stdout: the rows of mhx_dist_files(ref, qry[0]), then those of
+ * qry[1], ... -- query-major in argument order, every sketch of a query file in the file's order.
+ * The reference file is read, parsed, order-checked and staged once per call and the sketches of all
+ * query files are compared in one device call (mhx_dist_files is the n_qry == 1 case).  n_qry < 1 or a
+ * null entry: MHX_E_ARG.  A query file that cannot be read or parsed, or whose k or hash seed differs from
+ * the reference's, fails the whole call as it fails mhx_dist_files.  Query files whose sketch sizes differ
+ * from each other are refused with MHX_E_MISMATCH: what mash prints for such a set is not pinned by any
+ * recorded output, and a run of samples sketched with one setting never produces one.  The effective
+ * sketch size is min(reference, query); more than 2^31 - 1 pairs per call are refused (MHX_E_ARG). */
+int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry,
+                         char *stdout_buf, size_t cap, size_t *need);
 
 /* `mash bounds -k K -p P` stdout. */
 int mhx_bounds(int k, double p, char *buf, size_t cap, size_t *need);
