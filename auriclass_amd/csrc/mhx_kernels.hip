@@ -178,6 +178,11 @@ __device__ __forceinline__ uint32_t block_scan_excl(uint32_t value, uint32_t *wa
 }
 
 // ---------------------------------------------------------------------------------------
+#ifdef MHX_PARSE_LOOPS   // A/B builds: every FASTQ tile parses with the per-newline loops of phase_good
+constexpr bool kParseLoops = true;
+#else
+constexpr bool kParseLoops = false;
+#endif
 #ifndef MHX_MIN_WAVES
 #define MHX_MIN_WAVES 7   // 72 VGPRs: seven waves per SIMD, matching the seven workgroups per CU the LDS footprint admits
 #endif
@@ -229,11 +234,16 @@ template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_M
 
     MHX_STAMP(); // 1: classify
     uint32_t line_base = 0, excl = 0, tile_total = 0;
+    bool fast_parse = false;
     // the format look-ahead may only read staged bytes that belong to the span
     const uint64_t span_left = a.end > tile_off ? a.end - tile_off : 0;
     const uint32_t check_limit = span_left < (uint64_t)(kTileBytes + kHaloBytes) ? (uint32_t)span_left : (uint32_t)(kTileBytes + kHaloBytes);
     if (FASTQ) {
         excl = block_scan_excl(st.nlcount, sm.cnt, tile_total); // barrier inside: the newline map is complete
+        // good map without a trip per newline (mhx_tile.h): the newline positions are listed now, next to thread 0's
+        // phase search; the barrier that follows it puts them in front of phase_good_events.  Workgroup-uniform.
+        fast_parse = !kParseLoops && parse_events_fit(tile_total);
+        if (fast_parse) phase_events(sm, tid, st, excl);
         // the tile that holds the start of the span begins a record there; every other tile looks at its own first lines
         if (tid == 0) sm.misc[0] = tile == a.first_tile ? 0u : phase_selfsync(sm, check_limit);
         __syncthreads();
@@ -241,7 +251,7 @@ template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_M
         if (SELFSYNC) {
             if (self_phase == 4u) { // lines too long to tell: left to the look-back pass, nothing of this tile is counted now
                 if (tid == 0) { a.phase_rec[tile - a.first_tile] = 0; atomicOr(a.need_lookback, 1u); }
-                return;
+                return; // (the newline list phase_events has just written goes unused: listing before the phase is known saves a barrier)
             }
             if (tid == 0) a.phase_rec[tile - a.first_tile] = phase_record(self_phase, tile_total);
             line_base = self_phase;
@@ -251,7 +261,7 @@ template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_M
                     st_state(&a.tile_state[tile], (2ull << 32) | (uint64_t)(self_phase + tile_total));
                     a.phase_rec[tile - a.first_tile] = phase_record(self_phase, tile_total);
                 }
-                return;
+                return; // (the newline list phase_events has just written goes unused: listing before the phase is known saves a barrier)
             }
             if (tid < 64) {
                 const uint32_t lb = lookback_wave(a.tile_state, tile, a.first_tile, tile_total, stats);
@@ -264,7 +274,9 @@ template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_M
     }
     MHX_STAMP(); // 2: newline scan + look-back
     bool bad = false;
-    const uint32_t long_records = phase_good<FASTQ>(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
+    const uint32_t long_records = fast_parse
+        ? phase_good_events(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K)
+        : phase_good<FASTQ>(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
     if (FASTQ && bad) atomicOr(&stats[kStatFlags], (unsigned long long)kFlagBadFastq);
     if (FASTQ && long_records) atomicAdd(&sm.misc[5], long_records);
     __syncthreads();

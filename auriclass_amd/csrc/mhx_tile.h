@@ -338,19 +338,25 @@ MHX_HD uint32_t admission_limit(uint64_t T)
     const uint32_t th = (uint32_t)(T >> 32);
     return th == 0xFFFFFFFFu ? th : th + 1u;
 }
+constexpr uint64_t kMurmurSeed = 42; // mash's hash seed
 // w: the K bytes as little-endian dwords, bytes beyond K zero
 template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
 {
     constexpr uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
     constexpr int NBLK = K / 16, TAIL = K & 15;
-    uint64_t h1 = 42, h2 = 42;
+    uint64_t h1 = kMurmurSeed, h2 = kMurmurSeed;
     uint32_t zero = 0; // see mul64c
 #pragma unroll
     for (int b = 0; b < NBLK; ++b) {
         uint64_t k1 = make64(w[4 * b], w[4 * b + 1]);
         uint64_t k2 = make64(w[4 * b + 2], w[4 * b + 3]);
         k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); h1 ^= k1;
-        h1 = rotl64<27>(h1); h1 += h2; h1 = times5_plus(h1, 0x52dce729u);
+        h1 = rotl64<27>(h1);
+        // block 0: h2 is still the seed, and (x + seed) * 5 + c = x * 5 + (c + 5 * seed) with a constant that fits 32 bits
+        // still -- the 64-bit add of the seed (two instructions and a zero register per window) is folded away
+        static_assert(0x52dce729ull + 5ull * kMurmurSeed <= 0xFFFFFFFFull, "folded constant of block 0 must fit times5_plus' 32-bit addend");
+        if (b == 0) h1 = times5_plus(h1, (uint32_t)(0x52dce729ull + 5ull * kMurmurSeed));
+        else { h1 += h2; h1 = times5_plus(h1, 0x52dce729u); }
         k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); h2 ^= k2;
         h2 = rotl64<31>(h2); h2 += h1; h2 = times5_plus(h2, 0x38495ab5u);
     }
@@ -516,6 +522,115 @@ MHX_HD uint32_t phase_good(TileSmem &sm, int tid, const ThreadState &st, uint32_
         tile_good(sm)[kTileBytes / 32 + 3] = 0;
     }
     return lc.count;
+}
+
+// ---- P2c for FASTQ without a trip per newline -------------------------------------------
+// seqline_mask walks the newlines of a word one by one, and a wave sits through as many trips as its busiest lane
+// needs: the '+' line puts two newlines two bytes apart, so on ordinary reads EVERY wave takes two trips per word (and
+// one more of the length loop), each with an LDS round trip inside.  The form below gives the same good map, bad-format
+// flag and record count (tests/emul/tile_parse_emul.cpp compares them tile by tile) in two loop-free parts:
+//   mask    the line index of byte i is line + popcount(nl below i): its two low bits are prefix parities of the
+//           newline mask, pure register arithmetic (seqline_mask_bits);
+//   checks  the newlines of the tile are listed by position (phase_events; sm.valid is free until phase_runs), and
+//           after the barrier lane e takes newline e: the line that starts behind it has index line_base + e + 1, which
+//           says what to test there ('@', '+', or the length of a sequence line) -- one lane per line instead of one
+//           loop trip per line.
+// The list holds kEventCap positions; a tile with more newlines (lines of under 16 bytes on average) keeps phase_good.
+constexpr uint32_t kEventCap = kGroupsPerTile / 2; // 16-bit entries of sm.valid: one per 16 tile bytes
+static_assert(kEventCap * 2 == sizeof(TileSmem::valid) && kEventCap % kBlock == 0, "event list = sm.valid");
+static_assert(kTileBytes + kHaloBytes <= 65536, "event positions are 16-bit");
+MHX_HD bool parse_events_fit(uint32_t tile_total) { return tile_total <= kEventCap; }
+
+// bit i = parity of the bits of x below i
+MHX_HD uint32_t prefix_parity_excl(uint32_t x)
+{
+    x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
+    return x << 1;
+}
+// seqline_mask's result (bytes of lines with index 1 mod 4, newlines excluded) by bit arithmetic
+MHX_HD uint32_t seqline_mask_bits(uint32_t nl, uint32_t line)
+{
+    const uint32_t b0 = prefix_parity_excl(nl) ^ (0u - (line & 1u));               // low bit of every byte's line index
+    const uint32_t b1 = prefix_parity_excl(nl & b0) ^ (0u - ((line >> 1) & 1u));   // second bit: flips where the low bit carries
+    return b0 & ~b1 & ~nl;
+}
+
+// tile positions of this thread's newlines -> events[excl ..) (16-bit entries in sm.valid).  Two per word without a
+// loop -- ordinary reads never have more in 32 bytes --, the rest in a loop no wave of such a file enters.
+// Needs parse_events_fit(tile_total): excl + rank < tile_total <= kEventCap.
+MHX_HD void phase_events(TileSmem &sm, int tid, const ThreadState &st, uint32_t excl)
+{
+    uint16_t *ev = reinterpret_cast<uint16_t *>(sm.valid);
+    uint32_t at = excl;
+#pragma unroll
+    for (int w = 0; w < kWordsPerThread; ++w) {
+        const uint32_t off = (uint32_t)tid * kBytesPerThread + 32u * w;
+        uint32_t nl = st.nl[w];
+        if (nl) {
+            ev[at] = (uint16_t)(off + (uint32_t)__builtin_ctz(nl));
+            nl &= nl - 1u;
+            if (nl) {
+                ev[at + 1u] = (uint16_t)(off + (uint32_t)__builtin_ctz(nl));
+                nl &= nl - 1u;
+                for (uint32_t j = 2; MHX_UNLIKELY(nl != 0); ++j, nl &= nl - 1u) ev[at + j] = (uint16_t)(off + (uint32_t)__builtin_ctz(nl));
+            }
+        }
+        at += (uint32_t)__builtin_popcount(st.nl[w]);
+    }
+}
+
+// LineLenCheck's test for the sequence line that starts at tile position pos: does the record count?
+MHX_HD bool seqline_is_long(const uint32_t *nlmap, const uint8_t *tile_bytes, uint32_t pos, uint64_t tile_off, uint64_t end, uint32_t k)
+{
+    const uint32_t wq = pos >> 5, sh = pos & 31u;
+    const uint32_t window = funnel_bits(nlmap[wq + 1], nlmap[wq], sh); // newline bits of bytes pos..pos+31
+    const uint32_t first_k = k >= 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
+    if ((window & first_k) != 0 || tile_off + pos + k > end) return false;
+    // the CR rule of seqline_mask: a '\r' in front of the line end is not a base
+    const uint32_t after = pos + k;
+    const bool ends_here = tile_off + after >= end || ((nlmap[after >> 5] >> (after & 31u)) & 1u);
+    return !(tile_bytes[after - 1u] == '\r' && ends_here);
+}
+
+// phase_good<true> for a tile whose newlines phase_events has listed (a barrier in between); the sum of the return
+// values over the workgroup is the tile's number of long records (which lane counts a record differs from phase_good)
+MHX_HD uint32_t phase_good_events(TileSmem &sm, int tid, const ThreadState &st, uint32_t line_base, uint32_t excl,
+                                  uint32_t tile_total, uint32_t check_limit, bool &bad_format, uint64_t tile_off, uint64_t end, uint32_t k)
+{
+    uint32_t line = line_base + excl;
+#pragma unroll
+    for (int w = 0; w < kWordsPerThread; ++w) {
+        tile_good(sm)[tid * kWordsPerThread + w] = st.in[w] & seqline_mask_bits(st.nl[w], line);
+        line += (uint32_t)__builtin_popcount(st.nl[w]);
+    }
+    if (tid == 0) {
+        uint32_t hl = line_base + tile_total;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            tile_good(sm)[kTileBytes / 32 + w] = st.hin[w] & seqline_mask_bits(st.hnl[w], hl);
+            hl += (uint32_t)__builtin_popcount(st.hnl[w]);
+        }
+        tile_good(sm)[kTileBytes / 32 + 2] = 0;
+        tile_good(sm)[kTileBytes / 32 + 3] = 0;
+    }
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(sm.bytes);
+    const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
+    uint32_t count = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < kEventCap / kBlock; ++r) { // unrolled; ordinary reads (lines of 64 bytes and more) need the first round only
+        if (r == 1 && tile_total <= (uint32_t)kBlock) break; // workgroup-uniform
+        const uint32_t e = r * kBlock + (uint32_t)tid;
+        if (e < tile_total) {
+            const uint32_t pos = (uint32_t)ev[e] + 1u;     // first byte of the line behind newline e (<= kTileBytes: staged)
+            const uint32_t idx = (line_base + e + 1u) & 3u; // that line's index
+            if (idx == 1u) {
+                if (seqline_is_long(tile_nlmap(sm), tb, pos, tile_off, end, k)) ++count;
+            } else if (idx != 3u && pos < check_limit) {
+                if (tb[pos] != (idx == 0u ? '@' : '+')) bad_format = true;
+            }
+        }
+    }
+    return count;
 }
 
 // P3: valid k-mer starts of this thread's positions -> sm.valid, #items -> sm.cnt
