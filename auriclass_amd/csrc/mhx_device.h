@@ -26,6 +26,7 @@ struct HashArgs {
     uint32_t repair;         // FMT 1: repair pass -- tiles that CAN find their phase by themselves only publish it
     uint32_t queue_candidates; // kernel form: windows that pass the admission test are queued and finished after the hash loop (large sketches)
     uint8_t *phase_rec;      // FMT 2 / repair: one phase_record() per tile of the span (0: phase unknown), for phase_verify_kernel
+    uint32_t probe;          // containment screen: keys / cnts are a screen table (mhx_screen.h) and the launch takes the probing kernels
 };
 
 struct TableArgs {
@@ -61,6 +62,24 @@ hipError_t launch_extract(const TableArgs &a, uint64_t limit, uint32_t min_count
                           uint64_t *limit_out, uint64_t *maxkey_out, hipStream_t st, uint32_t *order_cursor = nullptr, uint32_t order_log2 = 0,
                           uint64_t *hdr_dev = nullptr, uint64_t *hdr_host = nullptr, uint32_t *ticket = nullptr,
                           uint64_t *occ_out = nullptr, uint32_t nhdr = 4, uint64_t *hdr_copy = nullptr);
+
+// containment screen (mhx_screen.h): the screen table of a reference set, and what the reads left in it
+struct ScreenArgs {
+    const uint64_t *rows;   // [nr][stride] reference hash lists (ascending, unique within a row)
+    const uint32_t *len;    // [nr] valid entries per row
+    uint32_t nr, stride;
+    uint64_t *keys;         // screen table
+    uint32_t *cnts;
+    uint64_t nslots;
+    uint64_t *thresh;       // T_screen: the largest reference hash
+    uint64_t *stats;        // the prober's counters (kStatReplicas x kStatCount)
+    uint32_t *counts;       // tally: [nr][stride] count of every reference entry
+    uint32_t *shared;       // tally: [nr] entries with a non-zero count
+    uint32_t *median;       // tally: [nr] element [shared / 2] of the ascending non-zero counts (0: none)
+};
+hipError_t launch_screen_build(const ScreenArgs &a, hipStream_t st);  // vacates the table, inserts every reference hash, sets T_screen, then clears as launch_screen_clear
+hipError_t launch_screen_clear(const ScreenArgs &a, uint32_t *tickets, uint32_t ntickets, uint32_t *need_lookback, hipStream_t st); // counters to zero, keys kept
+hipError_t launch_screen_tally(const ScreenArgs &a, hipStream_t st);
 
 // sharded path: the other ranks' gathered partial results go into this rank's candidate table (slab_insert_kernel)
 constexpr uint32_t kMaxMergeRanks = 64; // ranks per launch (more: several launches)

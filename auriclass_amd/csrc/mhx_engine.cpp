@@ -21,6 +21,7 @@
 #include "mhx_device.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
+#include "mhx_screen.h"
 
 namespace mhx {
 
@@ -175,6 +176,13 @@ struct mhx_sketcher {
     bool established = false;  // as of the last finish(): a tighten pass has lowered T from solid (count >= m) entries
     uint64_t occupied = 0;     // table occupancy reported by the last tighten pass
     uint64_t solid = 0;        // entries <= T with count >= m reported by the last tighten pass
+    // containment screen (mhx_screener below): d_keys / d_cnts are a screen table built from reference sketches and
+    // d_thresh holds T_screen, which never moves -- a push is ONE launch of the probing kernels, no tighten pass, no stages
+    bool screen = false;
+    uint64_t screen_T = 0;     // T_screen as the host knows it (chooses the kernel form)
+    // file-level screen: the prober of a screener rides along with the sketcher the ingest feeds -- every span pushed here is
+    // pushed there too, and whatever settles this sketcher's pushes settles the follower's (sketcher_set_follower)
+    mhx_sketcher *follower = nullptr;
 };
 
 static constexpr int kMaxLaunchesPerPush = 64;
@@ -208,6 +216,7 @@ extern "C" int mhx_sketcher_reset(mhx_sketcher *sk)
     int rc = require_engine();
     if (rc) return rc;
     if (!sk) return fail(MHX_E_ARG, "null sketcher");
+    if (sk->screen) return fail(MHX_E_ARG, "a screener's prober is reset through mhx_screener_reset");
     // Admission threshold: everything is admitted at first.  For m = 1 the first tighten pass already
     // finds s entries; for m > 1 push_device keeps the table safe until s solid hashes exist.
     sk->t_init = sk->hash_max;
@@ -357,6 +366,10 @@ static int repair_unsettled(mhx_sketcher *sk)
 // at a synchronisation point that is not finish(): is a repair pass due for the pushes since the last one?
 static int settle(mhx_sketcher *sk)
 {
+    if (sk->follower) {
+        const int rc = settle(sk->follower);
+        if (rc) return rc;
+    }
     if (sk->unsettled.empty()) return MHX_OK;
     uint32_t *need = reinterpret_cast<uint32_t *>((uint64_t *)sk->h_fin); // pinned landing word
     HIPCHK(hipMemcpyAsync(need, sk->d_need, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
@@ -373,6 +386,10 @@ static int settle(mhx_sketcher *sk)
 int sketcher_release_push(mhx_sketcher *sk, const void *d_bytes, hipStream_t side, uint32_t *word)
 {
     if (!sk) return MHX_OK;
+    if (sk->follower) {
+        const int rc = sketcher_release_push(sk->follower, d_bytes, side, word);
+        if (rc) return rc;
+    }
     size_t at = sk->unsettled.size();
     for (size_t i = 0; i < sk->unsettled.size(); ++i)
         if (sk->unsettled[i].ptr == d_bytes) { at = i; break; }
@@ -399,6 +416,10 @@ extern "C" int mhx_sketcher_push_device(mhx_sketcher *sk, const void *d_bytes, u
     if (sk->merged) return fail(MHX_E_ARG, "this sketcher holds a merged (multi-shard) table: mhx_sketcher_reset() before the next push");
     if (n == 0) return MHX_OK;
     sk->export_valid = false;
+    if (sk->follower) { // the same span for the prober that rides along (its own launch over the same resident bytes)
+        rc = mhx_sketcher_push_device(sk->follower, d_bytes, n, fmt);
+        if (rc) return rc;
+    }
     if (fmt == MHX_FMT_SEQ) return push_span(sk, d_bytes, n, 0, false);
     if (sk->verify_fastq) {
         rc = check_fastq_span(sk, d_bytes, n);
@@ -446,6 +467,7 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
     a.keys = sk->d_keys; a.cnts = sk->d_cnts; a.slot_mask = sk->nslots - 1; a.stats = sk->d_stats;
     a.need_lookback = sk->d_need;
     a.repair = repair ? 1u : 0u;
+    a.probe = sk->screen ? 1u : 0u;
     static const char *force_queue = getenv("MHX_QUEUE_CANDIDATES"); // "0" / "1": diagnostic override
     a.queue_candidates = force_queue ? (uint32_t)(force_queue[0] == '1') : (uint32_t)(sk->s >= kDeviceOrderMinSketch);
     const uint64_t ntiles64 = (a.end + kTileBytes - 1) / kTileBytes;
@@ -462,6 +484,39 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
     a.tile_state = sk->d_tile_state;
     if (kfmt == 2 || repair) HIPCHK(sk->d_phase_rec.grow(ntiles, g.stream)); // every tile of the span writes its record: nothing to clear
     a.phase_rec = sk->d_phase_rec;
+    // Kernel form of a launch (process_group_regs) from the share of the windows that will pass the admission test:
+    // candidates are queued when many will -- a large sketch, or a threshold above ~3 candidates in 10^4 windows --, and
+    // finished where they are found otherwise.
+    // (a sequence stream fills the work list -- every group of a tile is an item --, which leaves the queue no room;
+    // above ~0.15 candidates per window the ~1100 free entries of a FASTQ tile's list overflow and the tile would do
+    // its work twice, see sketch_tile_kernel: such launches finish their candidates inline)
+    auto queue_form = [&](long double expected_rate) {
+        return (uint32_t)(kfmt != 0 && expected_rate <= 0.1L && (sk->s >= kDeviceOrderMinSketch || expected_rate > 3e-4L));
+    };
+    auto timed_launch = [&]() -> int {
+        if (g.profiling) HIPCHK(hipEventRecord(g.ev0, g.stream));
+        HIPCHK(launch_hash(sk->k, kfmt, a, g.stream));
+        if (g.profiling) {
+            HIPCHK(hipEventRecord(g.ev1, g.stream));
+            HIPCHK(hipEventSynchronize(g.ev1));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
+            sk->hash_ms += ms;
+        }
+        ++sk->launches;
+        return MHX_OK;
+    };
+    if (sk->screen) { // the screen table never grows and T_screen never moves: one launch, nothing behind it
+        if (!force_queue) a.queue_candidates = queue_form((long double)sk->screen_T / (long double)sk->hash_max);
+        a.tile0 = 0;
+        a.ntiles = ntiles;
+        a.ticket = sk->d_tickets + sk->tickets_used++;
+        const int rc = timed_launch();
+        if (rc) return rc;
+        if (!repair) sk->bytes_pushed += n;
+        if (kfmt == 2 || repair) HIPCHK(launch_phase_verify(sk->d_phase_rec, ntiles, sk->d_stats, g.stream));
+        return MHX_OK;
+    }
     TableArgs ta = table_args(sk);
     if (sk->nslots >= (1ull << 23) && !getenv("MHX_EXACT_TIGHTEN")) ta.sample = 8; // big tables: sampled passes between chunks (finish() counts exactly)
     // a repair pass runs the same staged schedule on counters of its own (it may be the first time any k-mer is admitted)
@@ -527,24 +582,13 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
             long double expected_rate = bytes_pushed ? std::min(1.0L, (long double)sk->s / (0.4L * (long double)bytes_pushed)) : 1.0L;
             // staged phase of the multiplicity filter: the threshold sits at the byte-count cap until solid hashes take over
             if (cur.cap) expected_rate = std::max(expected_rate, (long double)cur.cap / (long double)sk->hash_max);
-            // (a sequence stream fills the work list -- every group of a tile is an item --, which leaves the queue no room;
-            // above ~0.15 candidates per window the ~1100 free entries of a FASTQ tile's list overflow and the tile would do
-            // its work twice, see sketch_tile_kernel: such launches finish their candidates inline)
-            a.queue_candidates = (uint32_t)(kfmt != 0 && expected_rate <= 0.1L && (sk->s >= kDeviceOrderMinSketch || expected_rate > 3e-4L));
+            a.queue_candidates = queue_form(expected_rate);
         }
         a.tile0 = tile;
         a.ntiles = cur.take;
         a.ticket = sk->d_tickets + sk->tickets_used++;
-        if (g.profiling) HIPCHK(hipEventRecord(g.ev0, g.stream));
-        HIPCHK(launch_hash(sk->k, kfmt, a, g.stream));
-        if (g.profiling) {
-            HIPCHK(hipEventRecord(g.ev1, g.stream));
-            HIPCHK(hipEventSynchronize(g.ev1));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, g.ev0, g.ev1));
-            sk->hash_ms += ms;
-        }
-        ++sk->launches;
+        const int lrc = timed_launch();
+        if (lrc) return lrc;
         ++launch;
         tile += cur.take;
         sk->table_dirty = true;
@@ -766,6 +810,11 @@ static int mhx_sketcher_finish_impl(mhx_sketcher *sk, uint64_t *hashes, uint32_t
     int rc = require_engine();
     if (rc) return rc;
     if (!sk || !hashes || !n_out) return fail(MHX_E_ARG, "null argument");
+    if (sk->screen) return fail(MHX_E_ARG, "a screener's prober has no sketch");
+    if (sk->follower) { // its spans are the ones pushed here: settled while they are still in place
+        rc = settle(sk->follower);
+        if (rc) return rc;
+    }
     // One batch on the stream, one copy, one synchronisation: final (exact) tighten unless the last pass already was
     // one, extract with the threshold read on the device into the result block, the block to its pinned mirror.
     const uint32_t cap = sk->fin_cap;
@@ -1451,6 +1500,234 @@ int dist_batch_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32
     return dist_batch_core(nullptr, q_len, nq, nullptr, r_len, nr, stride, k, s, common, denom, dist, 0, q_rows, r_rows);
 }
 } // namespace mhx
+
+// ---- containment screen ----------------------------------------------------------------
+// `mash screen`: which share of every REFERENCE sketch occurs in a read set, and how often.  A screener is the sketcher's
+// push machinery with another table behind it (mhx_screen.h): its prober is an mhx_sketcher in screen mode, so the FASTQ
+// line phase, the repair pass for long reads, the chain check, the device flags and the sync contract are the sketcher's
+// own code.  For the set size of the mixture it owns an ordinary sketcher (k, s_ref, m = 1) that sees every span too.
+struct mhx_screener {
+    SketcherPtr probe, setsk;
+    int k = 0;
+    uint32_t nr = 0, stride = 0, s_ref = 0;
+    DevArray<uint64_t> d_rows;
+    DevArray<uint32_t> d_len, d_counts, d_res; // d_res: shared[nr] | median[nr]
+};
+
+static ScreenArgs screen_args(mhx_screener *sc)
+{
+    mhx_sketcher *p = sc->probe.get();
+    ScreenArgs a;
+    a.rows = sc->d_rows; a.len = sc->d_len; a.nr = sc->nr; a.stride = sc->stride;
+    a.keys = p->d_keys; a.cnts = p->d_cnts; a.nslots = p->nslots; a.thresh = p->d_thresh; a.stats = p->d_stats;
+    a.counts = sc->d_counts; a.shared = sc->d_res; a.median = sc->d_res + sc->nr;
+    return a;
+}
+
+// counts, counters, tickets and the "repair due" word of the prober to zero; the keys stay
+static int screener_clear(mhx_screener *sc)
+{
+    mhx_sketcher *p = sc->probe.get();
+    HIPCHK(launch_screen_clear(screen_args(sc), p->d_tickets, kTicketWords, p->d_need, g.stream));
+    p->tickets_used = 0;
+    p->unsettled.clear();
+    p->bytes_pushed = 0;
+    p->hash_ms = 0.0;
+    p->launches = 0;
+    return MHX_OK;
+}
+
+static int screener_create_impl(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
+                                int with_set_size, int device_ptrs, mhx_screener **out)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!out) return fail(MHX_E_ARG, "null out pointer");
+    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+    if (nr && (!ref_rows || !ref_len || stride == 0)) return fail(MHX_E_ARG, "null reference rows");
+    if (s_ref == 0) return fail(MHX_E_ARG, "sketch size must be positive");
+    const uint64_t entries = (uint64_t)nr * stride;
+    if (entries > (1ull << 31)) return fail(MHX_E_ARG, "reference set too large for one screen table (%llu entries)", (unsigned long long)entries);
+    std::unique_ptr<mhx_screener> sc(new mhx_screener());
+    sc->k = k; sc->nr = nr; sc->stride = stride ? stride : 1; sc->s_ref = s_ref;
+    std::unique_ptr<mhx_sketcher> p(new mhx_sketcher());
+    p->k = k; p->s = s_ref; p->m = 1;
+    p->hash32 = k <= 16;
+    p->hash_max = p->hash32 ? 0xFFFFFFFFull : ~0ull;
+    p->screen = true;
+    p->nslots = screen_table_slots(entries);
+    hipError_t e = hipSuccess;
+    auto A = [&](auto &arr, size_t n) { if (e == hipSuccess) e = arr.grow(n); };
+    A(p->d_keys, p->nslots);
+    A(p->d_cnts, p->nslots);
+    A(p->d_thresh, 1);
+    A(p->d_stats, kStatReplicas * kStatCount);
+    A(p->d_tickets, kTicketWords);
+    A(p->d_need, 1);
+    A(p->h_fin, 8); // the pinned landing word of settle()
+    A(sc->d_rows, std::max<uint64_t>(entries, 1));
+    A(sc->d_len, std::max<uint32_t>(nr, 1));
+    A(sc->d_counts, std::max<uint64_t>(entries, 1));
+    A(sc->d_res, 2 * (size_t)std::max<uint32_t>(nr, 1));
+    if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed while creating the screener: %s", hipGetErrorString(e));
+    sc->probe.reset(p.release());
+    if (!device_ptrs)
+        for (uint32_t i = 0; i < nr; ++i)
+            if (ref_len[i] > stride) return fail(MHX_E_ARG, "ref_len[%u] exceeds stride", i);
+    const hipMemcpyKind kind = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (entries) HIPCHK(hipMemcpyAsync(sc->d_rows, ref_rows, entries * sizeof(uint64_t), kind, g.stream));
+    if (nr) HIPCHK(hipMemcpyAsync(sc->d_len, ref_len, (size_t)nr * sizeof(uint32_t), kind, g.stream));
+    HIPCHK(hipMemsetAsync(sc->d_counts, 0, std::max<uint64_t>(entries, 1) * sizeof(uint32_t), g.stream));
+    HIPCHK(hipMemsetAsync(sc->probe->d_stats, 0, kStatReplicas * kStatCount * sizeof(uint64_t), g.stream));
+    HIPCHK(launch_screen_build(screen_args(sc.get()), g.stream));
+    uint64_t T = 0, flags = 0;
+    HIPCHK(hipMemcpyAsync(&T, sc->probe->d_thresh, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(&flags, sc->probe->d_stats + kStatFlags, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream)); // (the caller's rows are free again)
+    if (flags & kFlagTableFull) return fail(MHX_E_INTERNAL, "screen table overflowed while it was built");
+    sc->probe->screen_T = T;
+    sc->probe->last_T = T;
+    rc = screener_clear(sc.get());
+    if (rc) return rc;
+    if (with_set_size) {
+        mhx_sketcher *ss = nullptr;
+        rc = create_sketcher(k, s_ref, 1, 0, 1, &ss);
+        if (rc) return rc;
+        sc->setsk.reset(ss);
+    }
+    *out = sc.release();
+    return MHX_OK;
+}
+
+extern "C" int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
+                                   int with_set_size, int device_ptrs, mhx_screener **out)
+{
+    try {
+        return screener_create_impl(k, ref_rows, ref_len, nr, stride, s_ref, with_set_size, device_ptrs, out);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_create: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_create: %s", e.what());
+    }
+}
+
+extern "C" void mhx_screener_destroy(mhx_screener *sc)
+{
+    if (g.ready) hipStreamSynchronize(g.stream);
+    delete sc;
+}
+
+extern "C" int mhx_screener_reset(mhx_screener *sc)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!sc) return fail(MHX_E_ARG, "null screener");
+    rc = screener_clear(sc);
+    if (rc) return rc;
+    return sc->setsk ? mhx_sketcher_reset(sc->setsk.get()) : MHX_OK;
+}
+
+extern "C" int mhx_screener_push_device(mhx_screener *sc, const void *d_bytes, uint64_t n, int fmt)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!sc) return fail(MHX_E_ARG, "null argument");
+    rc = mhx_sketcher_push_device(sc->probe.get(), d_bytes, n, fmt);
+    if (rc || !sc->setsk) return rc;
+    return mhx_sketcher_push_device(sc->setsk.get(), d_bytes, n, fmt); // a second launch over the same resident bytes
+}
+
+extern "C" int mhx_screener_push_host(mhx_screener *sc, const void *h_bytes, uint64_t n, int fmt)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!sc || (!h_bytes && n)) return fail(MHX_E_ARG, "null argument");
+    if (n == 0) return MHX_OK;
+    mhx_sketcher *p = sc->probe.get();
+    // one staging buffer (the prober's) for both: earlier pushes of either that may still read it come first
+    rc = settle(p);
+    if (!rc && sc->setsk) rc = settle(sc->setsk.get());
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    if (p->d_stage.cap() < n + 64) HIPCHK(p->d_stage.grow((size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1))));
+    HIPCHK(hipMemcpyAsync(p->d_stage, h_bytes, n, hipMemcpyHostToDevice, g.stream));
+    return mhx_screener_push_device(sc, p->d_stage, n, fmt);
+}
+
+extern "C" int mhx_screener_sync(mhx_screener *sc)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!sc) return fail(MHX_E_ARG, "null argument");
+    rc = mhx_sketcher_sync(sc->probe.get());
+    if (rc || !sc->setsk) return rc;
+    return mhx_sketcher_sync(sc->setsk.get());
+}
+
+namespace mhx {
+double set_size_estimate(int k, const uint64_t *hashes, size_t n)
+{
+    return n ? pow(2.0, k > 16 ? 64.0 : 32.0) * (double)n / (double)hashes[n - 1] : 0.0;
+}
+mhx_sketcher *screener_prober(mhx_screener *sc) { return sc ? sc->probe.get() : nullptr; }
+} // namespace mhx
+
+void sketcher_set_follower(mhx_sketcher *sk, mhx_sketcher *follower)
+{
+    if (sk) sk->follower = follower;
+}
+
+static int screener_finish_impl(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!sc || (sc->nr && (!shared || !median))) return fail(MHX_E_ARG, "null argument");
+    mhx_sketcher *p = sc->probe.get();
+    rc = settle(p); // the repair pass of long reads, if one is due
+    if (rc) return rc;
+    uint64_t st[kStatCount];
+    rc = fetch_stats(p, st);
+    if (rc) return rc;
+    rc = check_flags(st[kStatFlags]);
+    if (rc) return rc;
+    if (st[kStatFlags] & kFlagCountWrap) return fail(MHX_E_CAPACITY, "a multiplicity counter of the screen table reached its limit");
+    if (sc->nr) {
+        HIPCHK(launch_screen_tally(screen_args(sc), g.stream));
+        std::vector<uint32_t> res(2 * (size_t)sc->nr);
+        HIPCHK(hipMemcpyAsync(res.data(), sc->d_res, res.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        if (counts) HIPCHK(hipMemcpyAsync(counts, sc->d_counts, (size_t)sc->nr * sc->stride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+        memcpy(shared, res.data(), (size_t)sc->nr * sizeof(uint32_t));
+        memcpy(median, res.data() + sc->nr, (size_t)sc->nr * sizeof(uint32_t));
+    }
+    double size = 0.0;
+    if (sc->setsk) {
+        std::vector<uint64_t> h(sc->s_ref);
+        uint32_t n = 0;
+        rc = mhx_sketcher_finish(sc->setsk.get(), h.data(), nullptr, &n);
+        if (rc) return rc;
+        size = set_size_estimate(sc->k, h.data(), n);
+    }
+    if (set_size) *set_size = size;
+    return MHX_OK;
+}
+
+extern "C" int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
+{
+    try {
+        return screener_finish_impl(sc, shared, median, set_size, counts);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_finish: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_finish: %s", e.what());
+    }
+}
 
 extern "C" int mhx_sketcher_finish(mhx_sketcher *sk, uint64_t *hashes, uint32_t *counts, uint32_t *n_out)
 {

@@ -153,3 +153,13 @@ int create_sketcher(int k, uint32_t s, uint32_t min_mult, uint64_t expected_byte
 // its bytes (a record the kseq reader would read differently raises kFlagBadFastq, finish() returns MHX_E_FORMAT).
 // Each push must then start at a record start.  Off by default: the public push API trusts its caller.
 void sketcher_verify_fastq(mhx_sketcher *sk, bool on);
+
+// Containment screen at file level: `follower` (the prober of a screener, screener_prober) sees every span that is pushed
+// to sk from now on, and every call that settles sk's pushes settles its own.  nullptr: nobody rides along.  The caller
+// resets the screener before it attaches its prober to another sketcher.
+void sketcher_set_follower(mhx_sketcher *sk, mhx_sketcher *follower);
+namespace mhx {
+mhx_sketcher *screener_prober(mhx_screener *sc);
+// "Estimated genome size" of a reads-mode sketch: 2^bits * n / largest hash (0 for an empty sketch)
+double set_size_estimate(int k, const uint64_t *hashes, size_t n);
+} // namespace mhx

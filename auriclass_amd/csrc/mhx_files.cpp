@@ -58,10 +58,21 @@ struct Loaded {
     bool fastq4 = false;
 };
 
+// `mash screen` at file level: the prober of `scr` rides along with the sketcher the ingest is about to feed (every span
+// reaches both), starting from zero counts -- an attempt that was given up leaves nothing behind.
+static int attach_screen(mhx_sketcher *sk, mhx_screener *scr)
+{
+    if (!scr || !sk) return MHX_OK;
+    const int rc = mhx_screener_reset(scr);
+    if (rc) return rc;
+    sketcher_set_follower(sk, screener_prober(scr));
+    return MHX_OK;
+}
+
 // One reference from one or more inputs on the device.  On a 4-line violation or a too
 // tight admission bound the whole reference is redone (record parser / bigger table).
 static int sketch_reference(const std::vector<Loaded *> &inputs, int k, uint32_t s, uint32_t m, bool allow_device_fastq,
-                            std::vector<uint64_t> &hashes, std::vector<uint32_t> &counts, uint64_t *kmers)
+                            std::vector<uint64_t> &hashes, std::vector<uint32_t> &counts, uint64_t *kmers, mhx_screener *scr = nullptr)
 {
     uint64_t total = 0;
     for (auto *in : inputs) total += in->raw.size();
@@ -72,6 +83,8 @@ static int sketch_reference(const std::vector<Loaded *> &inputs, int k, uint32_t
         int rc = create_sketcher(k, s, m, total, boost, &sk);
         if (rc) return rc;
         sketcher_verify_fastq(sk, true); // a whole-file FASTQ4 push starts at the file's first record
+        rc = attach_screen(sk, scr);
+        if (rc) { mhx_sketcher_destroy(sk); return rc; }
         for (auto *in : inputs) {
             if (device_fastq && in->fastq4) {
                 rc = mhx_sketcher_push_host(sk, in->raw.data(), in->raw.size(), MHX_FMT_FASTQ4);
@@ -751,7 +764,7 @@ struct HeaderPick {
 // *handled = false means "not strict FASTQ / could not size": use the whole-file path.
 static int stream_fastq_reference(const char *const *paths, int n_paths, int k, uint32_t s, uint32_t m, std::vector<uint64_t> &hashes,
                                   std::vector<uint32_t> &counts, uint64_t *kmers, uint64_t *records, std::string *fname,
-                                  std::string *fcomment, bool *handled, bool force_zlib = false)
+                                  std::string *fcomment, bool *handled, bool force_zlib = false, mhx_screener *scr = nullptr)
 {
     *handled = false;
     uint64_t expected = 0;
@@ -760,6 +773,8 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
     int rc = mhx_sketcher_create(k, s, m, expected, &sk);
     if (rc) return rc;
     sketcher_verify_fastq(sk, true); // bulk pushes start at '@' (checked below), chunks at a record start
+    rc = attach_screen(sk, scr);
+    if (rc) { mhx_sketcher_destroy(sk); return rc; }
     bool fallback = false;
     HeaderPick header;
     // 1. uncompressed files: whole file -> one device buffer -> one push (see bulk_load_plain).  The buffers
@@ -851,7 +866,7 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
         resident.clear();
         mhx_sketcher_destroy(sk);
         clear_error();
-        return stream_fastq_reference(paths, n_paths, k, s, m, hashes, counts, kmers, records, fname, fcomment, handled, true);
+        return stream_fastq_reference(paths, n_paths, k, s, m, hashes, counts, kmers, records, fname, fcomment, handled, true, scr);
     }
     for (auto &f : st) {
         if (!f.error.empty() && !rc) rc = fail(MHX_E_IO, "%s", f.error.c_str());
@@ -872,6 +887,7 @@ static int stream_fastq_reference(const char *const *paths, int n_paths, int k, 
             sk = nullptr;
             rc = create_sketcher(k, s, m, expected, scale, &sk);
             sketcher_verify_fastq(sk, true);
+            if (!rc) rc = attach_screen(sk, scr);
             for (size_t i = 0; i < resident.size() && !rc; ++i) rc = mhx_sketcher_push_device(sk, resident[i].d_buf, resident[i].size, MHX_FMT_FASTQ4);
             if (!rc) rc = mhx_sketcher_finish(sk, hashes.data(), counts.data(), &n);
         }
@@ -1107,6 +1123,74 @@ static void load_fasta_input_impl(const char *path, int slot, bool pinned_ok, Fa
     in->n = in->owned.size();
 }
 
+// The read set of a reads-mode call (all files = one mixture) through the ingest: streamed where it can be, whole files
+// otherwise, the host record parser for what is not strict 4-line FASTQ.  ref receives the bottom-s sketch (hashes and
+// counts), count the records of at least k bases, fname / fcomment the header of the first of them.  scr: a screener
+// whose prober sees every span the sketcher sees (mhx_screen_files).
+static int sketch_read_set(const char *const *paths, int n_paths, int k, uint32_t s, uint32_t m, mhx_screener *scr, RefSketch &ref,
+                           uint64_t &kmers, uint64_t &count, std::string &fname, std::string &fcomment)
+{
+    int rc = MHX_OK;
+    std::vector<Loaded> loaded(n_paths);
+    g.last_fastq_route = 0;
+    bool streamed = false;
+    if (!getenv("MHX_NO_STREAMING")) {
+        rc = stream_fastq_reference(paths, n_paths, k, s, m, ref.hashes, ref.counts, &kmers, &count, &fname, &fcomment, &streamed, false, scr);
+        if (rc) return rc;
+    }
+    std::vector<Loaded *> in;
+    if (!streamed) {
+        for (int i = 0; i < n_paths; ++i) {
+            rc = read_all_maybe_gz(paths[i], loaded[i].raw);
+            if (rc) return rc;
+            loaded[i].fastq4 = looks_like_fastq4(loaded[i].raw.data(), loaded[i].raw.size());
+            in.push_back(&loaded[i]);
+        }
+        rc = sketch_reference(in, k, s, m, true, ref.hashes, ref.counts, &kmers, scr);
+        if (rc) return rc;
+    }
+    // name / comment / count: the first counted record and the number of counted ones (sequence of at least
+    // k bytes) -- from the record parser where it ran, from a 4-line walk over the raw bytes where the stream
+    // went to the device parser untouched
+    bool any = streamed;
+    std::string fb_name, fb_comment;
+    bool have_fb = false;
+    if (streamed) g.last_fastq_route = MHX_ROUTE_DEVICE_STREAMED;
+    else if (g.last_fastq_route == 0) g.last_fastq_route = MHX_ROUTE_DEVICE_WHOLE; // (sketch_reference notes the record parser)
+    for (auto &l : loaded) {
+        if (streamed) break;
+        if (l.rec.records_seen || !l.rec.seq.empty()) {
+            if (!any && l.rec.records) { fname = l.rec.first_name; fcomment = l.rec.first_comment; any = true; }
+            count += l.rec.records;
+        } else if (!l.raw.empty()) {
+            const uint8_t *b = l.raw.data();
+            const size_t n = l.raw.size();
+            if (!have_fb) { first_header(b, n, fb_name, fb_comment); have_fb = true; }
+            size_t p = 0;
+            while (p < n) { // one record: header, sequence, '+', quality
+                const uint8_t *e0 = (const uint8_t *)memchr(b + p, '\n', n - p);
+                if (!e0) break;
+                const size_t s0 = (size_t)(e0 - b) + 1;
+                const uint8_t *e1 = s0 < n ? (const uint8_t *)memchr(b + s0, '\n', n - s0) : nullptr;
+                const size_t s1 = e1 ? (size_t)(e1 - b) : n;
+                const size_t len = s1 - s0 - ((s1 > s0 && b[s1 - 1] == '\r') ? 1 : 0);
+                if (len >= (size_t)k) {
+                    if (!any) { first_header(b + p, s1 - p, fname, fcomment); any = true; }
+                    ++count;
+                }
+                size_t q = s1 + 1;
+                for (int i = 0; i < 2 && q < n; ++i) {
+                    const uint8_t *e = (const uint8_t *)memchr(b + q, '\n', n - q);
+                    q = e ? (size_t)(e - b) + 1 : n;
+                }
+                p = q;
+            }
+        }
+    }
+    if (!any && have_fb) { fname = fb_name; fcomment = fb_comment; }
+    return MHX_OK;
+}
+
 static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, uint32_t s, int reads, uint32_t min_mult,
                                 const char *out_msh, char *stderr_buf, size_t stderr_cap, size_t *stderr_need,
                                 double *est_genome_size)
@@ -1127,65 +1211,11 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
         return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", p);
     };
     if (reads) {
-        g.last_fastq_route = 0;
         RefSketch ref;
         uint64_t kmers = 0, count = 0;
         std::string fname, fcomment;
-        bool streamed = false;
-        if (!getenv("MHX_NO_STREAMING")) {
-            rc = stream_fastq_reference(paths, n_paths, k, s, min_mult ? min_mult : 1, ref.hashes, ref.counts, &kmers, &count, &fname, &fcomment, &streamed);
-            if (rc) return rc;
-        }
-        std::vector<Loaded *> in;
-        if (!streamed) {
-            for (int i = 0; i < n_paths; ++i) {
-                rc = read_all_maybe_gz(paths[i], loaded[i].raw);
-                if (rc) return rc;
-                loaded[i].fastq4 = looks_like_fastq4(loaded[i].raw.data(), loaded[i].raw.size());
-                in.push_back(&loaded[i]);
-            }
-            rc = sketch_reference(in, k, s, min_mult ? min_mult : 1, true, ref.hashes, ref.counts, &kmers);
-            if (rc) return rc;
-        }
-        // name / comment / count: the first counted record and the number of counted ones (sequence of at least
-        // k bytes) -- from the record parser where it ran, from a 4-line walk over the raw bytes where the stream
-        // went to the device parser untouched
-        bool any = streamed;
-        std::string fb_name, fb_comment;
-        bool have_fb = false;
-        if (streamed) g.last_fastq_route = MHX_ROUTE_DEVICE_STREAMED;
-        else if (g.last_fastq_route == 0) g.last_fastq_route = MHX_ROUTE_DEVICE_WHOLE; // (sketch_reference notes the record parser)
-        for (auto &l : loaded) {
-            if (streamed) break;
-            if (l.rec.records_seen || !l.rec.seq.empty()) {
-                if (!any && l.rec.records) { fname = l.rec.first_name; fcomment = l.rec.first_comment; any = true; }
-                count += l.rec.records;
-            } else if (!l.raw.empty()) {
-                const uint8_t *b = l.raw.data();
-                const size_t n = l.raw.size();
-                if (!have_fb) { first_header(b, n, fb_name, fb_comment); have_fb = true; }
-                size_t p = 0;
-                while (p < n) { // one record: header, sequence, '+', quality
-                    const uint8_t *e0 = (const uint8_t *)memchr(b + p, '\n', n - p);
-                    if (!e0) break;
-                    const size_t s0 = (size_t)(e0 - b) + 1;
-                    const uint8_t *e1 = s0 < n ? (const uint8_t *)memchr(b + s0, '\n', n - s0) : nullptr;
-                    const size_t s1 = e1 ? (size_t)(e1 - b) : n;
-                    const size_t len = s1 - s0 - ((s1 > s0 && b[s1 - 1] == '\r') ? 1 : 0);
-                    if (len >= (size_t)k) {
-                        if (!any) { first_header(b + p, s1 - p, fname, fcomment); any = true; }
-                        ++count;
-                    }
-                    size_t q = s1 + 1;
-                    for (int i = 0; i < 2 && q < n; ++i) {
-                        const uint8_t *e = (const uint8_t *)memchr(b + q, '\n', n - q);
-                        q = e ? (size_t)(e - b) + 1 : n;
-                    }
-                    p = q;
-                }
-            }
-        }
-        if (!any && have_fb) { fname = fb_name; fcomment = fb_comment; }
+        rc = sketch_read_set(paths, n_paths, k, s, min_mult ? min_mult : 1, nullptr, ref, kmers, count, fname, fcomment);
+        if (rc) return rc;
         // mash stops when no record holds k bases.  (`kmers` is not that question: the device counts every window of k BYTES
         // inside one line, and a CRLF file of reads one base shorter than k has such windows -- 31 bases and the '\r' --
         // although none of them is a k-mer.)
@@ -1390,6 +1420,76 @@ static int mhx_dist_files_impl(const char *ref_msh, const char *const *qry_msh, 
         lap("text written");
     }
     return put_text(text, stdout_buf, cap, need);
+}
+
+// `mash screen REF.msh reads...`: the reference sketches become a screen table on the device (mhx_screen.h), the read set
+// goes through the ingest of a reads-mode sketch -- with the reference file's k and sketch size and m = 1, which is the
+// bottom-s sketch mash keeps beside the counting for the set size -- and the screener's prober sees every span on its
+// way (sketch_read_set).  Tally on the device, columns on the host.
+struct ScreenerDestroy { void operator()(mhx_screener *sc) const { mhx_screener_destroy(sc); } };
+
+static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
+                                 double *set_size_out)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!ref_msh || !paths || n_paths <= 0) return fail(MHX_E_ARG, "screen: a reference sketch path and at least one read file required");
+    for (int i = 0; i < n_paths; ++i)
+        if (!paths[i]) return fail(MHX_E_ARG, "screen: read file path %d is null", i);
+    SketchSet R;
+    rc = msh_read_file(ref_msh, R);
+    if (rc) return rc;
+    if (R.hash_seed != 42) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches use hash seed %u; reads are hashed with seed 42", R.hash_seed);
+    if (R.alphabet != "ACGT" || R.noncanonical) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches are not canonical nucleotide sketches");
+    const int k = (int)R.kmer_size;
+    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+    const uint32_t nr = (uint32_t)R.refs.size();
+    uint32_t stride = 1, s_ref = R.sketch_size;
+    std::vector<uint32_t> len(nr);
+    for (uint32_t i = 0; i < nr; ++i) {
+        if (!check_ascending(R.refs[i].hash_data(), R.refs[i].hash_count()))
+            return fail(MHX_E_FORMAT, "%s: hash list of reference %u is not ascending", ref_msh, i);
+        len[i] = (uint32_t)R.refs[i].hash_count();
+        stride = std::max(stride, len[i]);
+    }
+    s_ref = std::max<uint32_t>(std::max(s_ref, stride), 1);
+    std::vector<uint64_t> rows((size_t)nr * stride, 0);
+    for (uint32_t i = 0; i < nr; ++i)
+        if (len[i]) memcpy(rows.data() + (size_t)i * stride, R.refs[i].hash_data(), (size_t)len[i] * sizeof(uint64_t));
+    mhx_screener *raw = nullptr;
+    rc = mhx_screener_create(k, rows.data(), len.data(), nr, stride, s_ref, 0, 0, &raw);
+    if (rc) return rc;
+    std::unique_ptr<mhx_screener, ScreenerDestroy> scr(raw);
+    RefSketch mix;
+    uint64_t kmers = 0, count = 0;
+    std::string fname, fcomment;
+    rc = sketch_read_set(paths, n_paths, k, s_ref, 1, scr.get(), mix, kmers, count, fname, fcomment);
+    if (rc) return rc;
+    // (no record of k bases at all: mash warns and prints its rows; the sketch is empty and the set size 0)
+    const double set_size = set_size_estimate(k, mix.hashes.data(), mix.hashes.size());
+    std::vector<uint32_t> shared(nr), median(nr);
+    rc = mhx_screener_finish(scr.get(), shared.data(), median.data(), nullptr, nullptr);
+    if (rc) return rc;
+    std::string text;
+    for (uint32_t i = 0; i < nr; ++i)
+        text += fmt_g(mhx_screen_identity(shared[i], len[i], k)) + "\t" + std::to_string(shared[i]) + "/" + std::to_string(len[i]) + "\t" +
+                std::to_string(median[i]) + "\t" + fmt_g(mhx_screen_p_value(shared[i], len[i], set_size, k)) + "\t" + R.refs[i].name + "\t" +
+                R.refs[i].comment + "\n";
+    if (set_size_out) *set_size_out = set_size;
+    return put_text(text, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
+                                double *set_size_out)
+{
+    try {
+        return mhx_screen_files_impl(ref_msh, paths, n_paths, stdout_buf, cap, need, set_size_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_screen_files: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_screen_files: %s", e.what());
+    }
 }
 
 extern "C" int mhx_msh_write(const char *path, int k, uint32_t s, uint32_t n_refs, const char *const *names,

@@ -15,7 +15,10 @@
 // Replaces the loops inside the `mash sketch` / `mash dist` child processes that
 // /root/reference/auriclass/classes.py:576-596, 696-713 and 92-104 spawn.
 #include "mhx_device.h"
+#include "mhx_screen.h"
 #include "mhx_tile.h"
+
+#include <type_traits>
 
 namespace mhx {
 
@@ -48,9 +51,33 @@ struct DeviceInserter {
     }
 };
 
+// The same place in the kernel for the containment screen (mhx_screen.h): keys / cnts are a screen table, built before the
+// launch and only read here.  An admitted window counts where its hash is a key and changes nothing otherwise: plain
+// loads along the probe sequence, one atomic add on a hit.  A type of its own, and with it kernels of their own
+// (sketch_tile_kernel<.., PROBE = true>): a run-time switch inside DeviceInserter costs the inline form of the sketch
+// kernel four VGPRs (68 -> 72 at k = 21), wherever the switch is kept.
+struct ScreenProber {
+    unsigned long long *keys;
+    uint32_t *cnts;
+    uint64_t mask;
+    unsigned long long *stats; // this block's replica
+    __device__ __forceinline__ void operator()(uint64_t h)
+    {
+        if (h == kEmptyKey) {
+            atomicAdd(&stats[kStatMaxKey], 1ull);
+            return;
+        }
+        const uint64_t at = screen_find(reinterpret_cast<const uint64_t *>(keys), mask, h);
+        if (at != kScreenAbsent && !screen_count_stands(atomicAdd(&cnts[at], 1u))) {
+            atomicSub(&cnts[at], 1u);
+            atomicOr(&stats[kStatFlags], (unsigned long long)kFlagCountWrap);
+        }
+    }
+};
+
 // Not inlined on purpose: the window finished here needs ~40 registers of its own (two strands, eight words each, and
 // the hash); inside the kernel body they would be the hash loop's problem.
-template <int K> __device__ __noinline__ uint32_t finish_candidate(const TileSmem &sm, uint32_t code, uint64_t T, DeviceInserter ins)
+template <int K, class Ins> __device__ __noinline__ uint32_t finish_candidate(const TileSmem &sm, uint32_t code, uint64_t T, Ins ins)
 {
     return process_deferred<K>(sm, code, T, ins);
 }
@@ -186,7 +213,7 @@ constexpr bool kParseLoops = false;
 #ifndef MHX_MIN_WAVES
 #define MHX_MIN_WAVES 7   // 72 VGPRs: seven waves per SIMD, matching the seven workgroups per CU the LDS footprint admits
 #endif
-template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_MIN_WAVES) void sketch_tile_kernel(const HashArgs a)
+template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(kBlock, MHX_MIN_WAVES) void sketch_tile_kernel(const HashArgs a)
 {
     __shared__ TileSmem sm;
     constexpr bool FASTQ = (FMT != 0), LOOKBACK = (FMT == 1), SELFSYNC = (FMT == 2);
@@ -294,7 +321,7 @@ template <int K, int FMT, bool QUEUE> __global__ __launch_bounds__(kBlock, MHX_M
 
     const uint64_t T = *a.thresh;
     const uint32_t limit = admission_limit(T);
-    DeviceInserter ins{reinterpret_cast<unsigned long long *>(a.keys), a.cnts, a.slot_mask, stats};
+    std::conditional_t<PROBE, ScreenProber, DeviceInserter> ins{reinterpret_cast<unsigned long long *>(a.keys), a.cnts, a.slot_mask, stats};
     const uint32_t qcap = (uint32_t)kGroupsPerTile - nitems; // QUEUE: the work list's unused tail holds the candidate queue
     CandidateQueue queue{sm, nitems, qcap};
     uint32_t ninsert = 0;
@@ -331,12 +358,15 @@ template <int K> static hipError_t launch_k(int fmt, const HashArgs &a, hipStrea
 {
     // a.queue_candidates: large sketches (many windows pass the admission test) finish their candidates after the hash
     // loop, one per lane; small ones where they are found (process_group_regs)
-#define MHX_LAUNCH(FMT_) do { if (a.queue_candidates) hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, true>), dim3(a.ntiles), dim3(kBlock), 0, st, a); \
-                              else hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, false>), dim3(a.ntiles), dim3(kBlock), 0, st, a); } while (0)
+    // a.probe: the kernels of the containment screen (ScreenProber in the place of DeviceInserter)
+#define MHX_LAUNCH_FORM(FMT_, QUEUE_) do { if (a.probe) hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, true>), dim3(a.ntiles), dim3(kBlock), 0, st, a); \
+                                           else hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, false>), dim3(a.ntiles), dim3(kBlock), 0, st, a); } while (0)
+#define MHX_LAUNCH(FMT_) do { if (a.queue_candidates) MHX_LAUNCH_FORM(FMT_, true); else MHX_LAUNCH_FORM(FMT_, false); } while (0)
     if (fmt == 1) MHX_LAUNCH(1);
     else if (fmt == 2) MHX_LAUNCH(2);
     else MHX_LAUNCH(0);
 #undef MHX_LAUNCH
+#undef MHX_LAUNCH_FORM
     return hipGetLastError();
 }
 
@@ -358,6 +388,122 @@ hipError_t launch_hash(int k, int fmt, const HashArgs &a, hipStream_t st)
 #undef X
     default: return hipErrorInvalidValue;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// Containment screen (mhx_screen.h).  Build: the table is vacated by one kernel and filled by the next (a CAS claims a slot,
+// duplicates across references meet the key they share); T_screen = the largest reference hash, one atomic per thread.
+// Clear: counters and control words to zero, keys kept.  Tally: one workgroup per reference looks every entry up, writes
+// its count, counts the non-zero ones and selects their median by four histogram passes over the counts it has written.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void screen_vacate_kernel(const ScreenArgs a)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nslots; i += (uint64_t)gridDim.x * blockDim.x) a.keys[i] = kEmptyKey;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.thresh = 0;
+}
+
+__global__ __launch_bounds__(256) void screen_clear_kernel(const ScreenArgs a, uint32_t *tickets, uint32_t ntickets, uint32_t *need_lookback)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.nslots; i += (uint64_t)gridDim.x * blockDim.x) a.cnts[i] = 0;
+    if (blockIdx.x == 0) {
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(kStatReplicas * kStatCount); i += blockDim.x) a.stats[i] = 0;
+        for (uint32_t i = threadIdx.x; i < ntickets; i += blockDim.x) tickets[i] = 0;
+        if (threadIdx.x == 0) *need_lookback = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void screen_build_kernel(const ScreenArgs a)
+{
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(a.keys);
+    auto claim = [keys](uint64_t slot, uint64_t h) { return (uint64_t)atomicCAS(&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)h); };
+    const uint64_t total = (uint64_t)a.nr * a.stride;
+    uint64_t top = 0;
+    bool any = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / a.stride), j = (uint32_t)(i % a.stride);
+        if (j >= a.len[r]) continue;
+        const uint64_t h = a.rows[i];
+        any = true;
+        top = h > top ? h : top;
+        if (h != kEmptyKey && screen_insert(a.nslots - 1, h, claim) == kScreenAbsent)
+            atomicOr(reinterpret_cast<unsigned long long *>(a.stats) + kStatFlags, (unsigned long long)kFlagTableFull);
+    }
+    if (any) atomicMax(reinterpret_cast<unsigned long long *>(a.thresh), (unsigned long long)top);
+}
+
+__global__ __launch_bounds__(256) void screen_tally_kernel(const ScreenArgs a)
+{
+    __shared__ uint32_t hist[kScreenSelectBins];
+    __shared__ unsigned long long maxkey_s;
+    __shared__ uint32_t shared_s, prefix_s, rank_s;
+    const uint32_t r = blockIdx.x, n = a.len[r] < a.stride ? a.len[r] : a.stride, tid = threadIdx.x;
+    const uint64_t *row = a.rows + (uint64_t)r * a.stride;
+    uint32_t *out = a.counts + (uint64_t)r * a.stride;
+    if (tid == 0) { maxkey_s = 0; shared_s = 0; }
+    __syncthreads();
+    if (tid < kStatReplicas) {
+        const uint64_t c = a.stats[tid * kStatCount + kStatMaxKey];
+        if (c) atomicAdd(&maxkey_s, (unsigned long long)c);
+    }
+    __syncthreads();
+    const uint64_t maxkey = maxkey_s;
+    uint32_t nz = 0;
+    for (uint32_t i = tid; i < n; i += blockDim.x) {
+        const uint32_t c = screen_count_of(a.keys, a.cnts, a.nslots - 1, row[i], maxkey);
+        out[i] = c;
+        nz += c != 0u ? 1u : 0u;
+    }
+    if (nz) atomicAdd(&shared_s, nz);
+    __syncthreads(); // (also: every count of this row is written and visible to the workgroup)
+    const uint32_t shared = shared_s;
+    if (tid == 0) { a.shared[r] = shared; prefix_s = 0; rank_s = shared / 2; }
+    if (shared == 0) {
+        if (tid == 0) a.median[r] = 0;
+        return;
+    }
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (uint32_t i = tid; i < (uint32_t)kScreenSelectBins; i += blockDim.x) hist[i] = 0;
+        __syncthreads();
+        const uint32_t prefix = prefix_s;
+        for (uint32_t i = tid; i < n; i += blockDim.x) {
+            const uint32_t c = out[i];
+            if (screen_select_match(c, prefix, shift)) atomicAdd(&hist[screen_select_digit(c, shift)], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t rank = rank_s;
+            const uint32_t d = screen_select_step(hist, rank);
+            rank_s = rank;
+            prefix_s = (prefix << 8) | d;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) a.median[r] = prefix_s;
+}
+
+static unsigned screen_blocks(uint64_t items)
+{
+    uint64_t blocks = (items + 256 * 8 - 1) / (256 * 8);
+    return (unsigned)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks);
+}
+
+hipError_t launch_screen_clear(const ScreenArgs &a, uint32_t *tickets, uint32_t ntickets, uint32_t *need_lookback, hipStream_t st)
+{
+    hipLaunchKernelGGL(screen_clear_kernel, dim3(screen_blocks(a.nslots)), dim3(256), 0, st, a, tickets, ntickets, need_lookback);
+    return hipGetLastError();
+}
+
+hipError_t launch_screen_build(const ScreenArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(screen_vacate_kernel, dim3(screen_blocks(a.nslots)), dim3(256), 0, st, a);
+    if ((uint64_t)a.nr * a.stride) hipLaunchKernelGGL(screen_build_kernel, dim3(screen_blocks((uint64_t)a.nr * a.stride)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_screen_tally(const ScreenArgs &a, hipStream_t st)
+{
+    if (a.nr) hipLaunchKernelGGL(screen_tally_kernel, dim3(a.nr), dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------

@@ -120,6 +120,23 @@ extern "C" double mhx_p_value(uint64_t common, uint64_t len_ref, uint64_t len_qr
     return binomial_sf_ge(common, r, denom);
 }
 
+// `mash screen` columns (Mash 2.x CommandScreen.cpp: estimateIdentity(), pValueWithin()).  mash keeps the set size in a
+// uint64_t, hence the floor.
+extern "C" double mhx_screen_identity(uint64_t shared, uint64_t n, int k)
+{
+    if (shared == n) return 1.0;
+    if (shared == 0) return 0.0;
+    return pow((double)shared / (double)n, 1.0 / (double)k);
+}
+
+extern "C" double mhx_screen_p_value(uint64_t shared, uint64_t n, double set_size, int k)
+{
+    if (shared == 0) return 1.0;
+    const double size = set_size > 0.0 ? (double)(uint64_t)set_size : 0.0;
+    const double r = 1.0 / (1.0 + pow(4.0, k) / size);
+    return binomial_sf_ge(shared, r, n);
+}
+
 extern "C" int mhx_bounds(int k, double p, char *buf, size_t cap, size_t *need)
 {
     clear_error();

@@ -127,6 +127,22 @@ def load() -> ctypes.CDLL:
     L.mhx_last_inflate_stats.argtypes = [c.c_void_p]
     L.mhx_last_fastq_route.argtypes = []
     L.mhx_last_fastq_route.restype = c.c_int
+    if hasattr(L, "mhx_screen_files"):   # (MHX_LIB may name an experiment build older than the screen: tools/ab.py)
+        L.mhx_screen_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t),
+                                       c.POINTER(c.c_double)]
+        L.mhx_screener_create.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_int, c.c_int,
+                                          c.POINTER(c.c_void_p)]
+        L.mhx_screener_destroy.argtypes = [c.c_void_p]
+        L.mhx_screener_destroy.restype = None
+        L.mhx_screener_reset.argtypes = [c.c_void_p]
+        L.mhx_screener_push_device.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64, c.c_int]
+        L.mhx_screener_push_host.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64, c.c_int]
+        L.mhx_screener_sync.argtypes = [c.c_void_p]
+        L.mhx_screener_finish.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_double), c.c_void_p]
+        L.mhx_screen_identity.argtypes = [c.c_uint64, c.c_uint64, c.c_int]
+        L.mhx_screen_identity.restype = c.c_double
+        L.mhx_screen_p_value.argtypes = [c.c_uint64, c.c_uint64, c.c_double, c.c_int]
+        L.mhx_screen_p_value.restype = c.c_double
     _lib = L
     return L
 
@@ -211,6 +227,26 @@ def dist_files_multi(ref_msh, qry_paths: Sequence) -> str:
     paths = [os.fsencode(str(p)) for p in qry_paths]
     arr = (ctypes.c_char_p * len(paths))(*paths)
     return _text_call(load().mhx_dist_files_multi, os.fsencode(str(ref_msh)), arr, len(paths), guess=max(1, len(paths)) << 16)
+
+
+def screen_files(ref_msh, paths: Sequence) -> Tuple[str, float]:
+    """`mash screen REF.msh paths...` -> (stdout text, estimated set size of the read set): one row per reference,
+    "identity\\tshared/n\\tmedian\\tp\\tname\\tcomment".  All paths form one read set."""
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    size = ctypes.c_double(0.0)
+    text = _text_call(lambda buf, cap, need: load().mhx_screen_files(os.fsencode(str(ref_msh)), arr, len(files), buf, cap, need,
+                                                                     ctypes.byref(size)))
+    return text, size.value
+
+
+def screen_identity(shared: int, n: int, k: int) -> float:
+    return load().mhx_screen_identity(shared, n, k)
+
+
+def screen_p_value(shared: int, n: int, set_size: float, k: int) -> float:
+    return load().mhx_screen_p_value(shared, n, set_size, k)
 
 
 def bounds(k: int, p: float) -> str:
@@ -397,6 +433,66 @@ class Sketcher:
                 continue
             _check(rc)
             return hashes[:n.value].copy(), counts[:n.value].copy()
+
+
+class Screener:
+    """Containment screen of a fixed reference set (`mash screen` at buffer level): rows is [nr, stride] uint64 with
+    lens[i] valid ascending hashes in row i, as dist_batch takes them.  Push the read set as into a Sketcher, then
+    finish() -> (shared[nr], median[nr], set_size, counts or None)."""
+
+    def __init__(self, k: int, rows: np.ndarray, lens: np.ndarray, s_ref: int, with_set_size: bool = True):
+        init()
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        assert rows.ndim == 2 and lens.shape == (rows.shape[0],)
+        self.k, self.nr, self.stride, self.s_ref = k, rows.shape[0], rows.shape[1], s_ref
+        self.lens = lens.copy()
+        h = ctypes.c_void_p()
+        _check(load().mhx_screener_create(k, rows.ctypes.data, lens.ctypes.data, self.nr, self.stride, s_ref, int(with_set_size), 0,
+                                          ctypes.byref(h)))
+        self._h = h
+        self._keep: list = []
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.mhx_screener_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """Multiplicities back to zero; the table built from the references is kept."""
+        _check(load().mhx_screener_reset(self._h))
+        self._keep.clear()
+
+    def push_device(self, ptr: int, nbytes: int, fmt: int, keep=None) -> None:
+        """As Sketcher.push_device (same lifetime rule for the pushed bytes)."""
+        _check(load().mhx_screener_push_device(self._h, ctypes.c_void_p(ptr), nbytes, fmt))
+        if keep is not None:
+            self._keep.append(keep)
+
+    def push_host(self, data, fmt: int) -> None:
+        a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        a = np.ascontiguousarray(a)
+        _check(load().mhx_screener_push_host(self._h, a.ctypes.data, a.size, fmt))
+
+    def sync(self) -> None:
+        _check(load().mhx_screener_sync(self._h))
+        self._keep.clear()
+
+    def finish(self, with_counts: bool = False):
+        shared = np.zeros(self.nr, dtype=np.uint32)
+        median = np.zeros(self.nr, dtype=np.uint32)
+        counts = np.zeros((self.nr, self.stride), dtype=np.uint32) if with_counts else None
+        size = ctypes.c_double(0.0)
+        _check(load().mhx_screener_finish(self._h, shared.ctypes.data, median.ctypes.data, ctypes.byref(size),
+                                          counts.ctypes.data if with_counts else None))
+        self._keep.clear()
+        return shared, median, size.value, counts
 
 
 def gunzip(data: bytes, threads: int = 1, size_hint: int = 0) -> bytes:

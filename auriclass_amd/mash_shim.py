@@ -2,7 +2,7 @@
 `mash` launcher (auriclass_amd/bin) first on PATH and the reference's five subprocess call sites
 (/root/reference/auriclass/general.py:198-205 `mash -h`; classes.py:576-596 and 696-706
 `mash sketch`; classes.py:92-97 `mash dist`; classes.py:305-312 `mash bounds`) run on the GPU
-engine.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
+engine.  `mash screen REF.msh reads...` (containment; AuriClass itself does not call it) is served too.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
 codes follow mash (sketch: exit 1 with 'ERROR: Did not find fasta records in ...')."""
 from __future__ import annotations
 
@@ -25,6 +25,8 @@ Commands:
   bounds    Print a table of Mash error bounds.
 
   dist      Estimate the distance of query sequences to references.
+
+  screen    Determine whether query sequences are within a larger pool of sequences.
 
   sketch    Create sketches (reduced representations for fast operations).
 
@@ -72,6 +74,18 @@ def main(argv: List[str] = None) -> int:
                 sys.stderr.write("ERROR: mash dist <reference> <query>\n")
                 return 1
             sys.stdout.write(engine.dist_files(args[0], args[1]))
+            return 0
+        if cmd == "screen":
+            for flag in ("-w", "-i", "-v", "-a"):
+                if flag in args:
+                    sys.stderr.write(f"ERROR: mash screen {flag} is not supported by the mhx shim\n")
+                    return 1
+            _take(args, "-p", 1, int)   # threads: the engine has its own
+            if len(args) < 2:
+                sys.stderr.write("ERROR: mash screen <reference.msh> <reads> [<reads> ...]\n")
+                return 1
+            text, _ = engine.screen_files(args[0], args[1:])
+            sys.stdout.write(text)
             return 0
         if cmd == "bounds":
             k = _take(args, "-k", 21, int)

@@ -10,6 +10,8 @@
  *   mhx_dist_files    <- `mash dist REF.msh QUERY.msh`      auriclass/classes.py:92-104
  *   mhx_dist_files_multi <- `mash dist REF.msh QUERY.msh [QUERY.msh ...]` (a run of samples, one call)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
+ *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
+ *                        distance check cannot answer, docs/faq.md entries 3 and 4)
  *   mhx_init          <- `mash -h` dependency probe         auriclass/general.py:198-205
  *
  * The remaining entry points expose the same hot path at buffer granularity (device
@@ -92,6 +94,23 @@ int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, s
  * sketch size is min(reference, query); more than 2^31 - 1 pairs per call are refused (MHX_E_ARG). */
 int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry,
                          char *stdout_buf, size_t cap, size_t *need);
+
+/* `mash screen REF.msh reads...` stdout (Mash 2.x defaults -i 0 -v 1, nucleotides, no -w): one row per reference of the
+ * sketch file, in its order, "identity\tshared/n\tmedian\tp\tname\tcomment\n".  All paths form ONE read set (FASTQ or
+ * FASTA, plain or gzip / BGZF), read by the ingest of mhx_sketch_files(..., reads = 1, ...): every route, the record check
+ * and the hand-over to the host record parser included (mhx_last_fastq_route reports this call's route too).
+ *   shared   = hashes of the reference sketch that occur in the read set (n = the sketch's length),
+ *   median   = element [shared / 2] of the ascending multiplicities of those hashes (0: none),
+ *   identity = mhx_screen_identity(shared, n, k),  p = mhx_screen_p_value(shared, n, set size, k),
+ *   set size = the estimated number of distinct k-mers of the read set: the "Estimated genome size" of
+ *              mhx_sketch_files(paths, k, s, 1, 1, ...) with the reference file's k and sketch size s; handed back in
+ *              *set_size_out (may be NULL).
+ * A multiplicity is the number of windows (k bytes A/C/G/T inside one record) with that canonical hash, as the sketcher
+ * counts them.  A read set without any valid k-mer is no error here: set size 0, rows "0\t0/n\t0\t1\t...".  A reference file
+ * with another hash seed than 42 or another alphabet: MHX_E_MISMATCH.  Not pinned by mash output (none is recorded): the
+ * rule is Mash's CommandScreen restated, see DESIGN.md section 6. */
+int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
+                     double *set_size_out);
 
 /* `mash bounds -k K -p P` stdout. */
 int mhx_bounds(int k, double p, char *buf, size_t cap, size_t *need);
@@ -232,6 +251,34 @@ int mhx_last_dist_ranges(void);
 
 /* scalar pieces of the dist row (host): mash pValue() */
 double mhx_p_value(uint64_t common, uint64_t len_ref, uint64_t len_qry, int k, uint64_t denom);
+
+/* ---- containment screen at buffer level -------------------------------------------------- */
+typedef struct mhx_screener mhx_screener;
+
+/* The screen table of a reference set, built once on the device: ref_rows is row-major [nr][stride] with ref_len[i]
+ * valid, ascending, duplicate-free hashes in row i (values < 2^32 for k <= 16), as mhx_dist_batch takes them;
+ * device_ptrs != 0 => both are device pointers.  The rows are copied: the caller's are free when the call returns.
+ * s_ref: the sketch size of the reference set (sizes the set-size sketch).  with_set_size != 0: the screener also keeps a
+ * bottom-s_ref sketch of everything pushed (a second launch per push over the same bytes); 0: mhx_screener_finish
+ * reports a set size of 0 and the caller computes no p-value from it. */
+int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
+                        int with_set_size, int device_ptrs, mhx_screener **out);
+void mhx_screener_destroy(mhx_screener *sc);
+int mhx_screener_reset(mhx_screener *sc);   /* multiplicities to zero; the table is kept */
+/* the contract of mhx_sketcher_push_device / _push_host / _sync (formats, alignment, lifetime of the pushed bytes) */
+int mhx_screener_push_device(mhx_screener *sc, const void *d_bytes, uint64_t n, int fmt);
+int mhx_screener_push_host(mhx_screener *sc, const void *h_bytes, uint64_t n, int fmt);
+int mhx_screener_sync(mhx_screener *sc);
+/* shared[nr], median[nr] as in mhx_screen_files, tallied on the device; *set_size (may be NULL) as there, 0 without the
+ * set-size sketch.  counts: NULL, or [nr][stride] words that receive the multiplicity of every reference hash (entries
+ * beyond ref_len[i] are 0).  MHX_E_CAPACITY when a multiplicity reached the counter's limit (0xF0000000).  May be called
+ * again after further pushes. */
+int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts);
+/* scalar pieces of the screen row (host), Mash's estimateIdentity() and pValueWithin():
+ * identity = 1 if shared == n, 0 if shared == 0, else pow(shared / n, 1 / k);
+ * p = 1 if shared == 0, else P[Binomial(n, r) >= shared] with r = 1 / (1 + 4^k / floor(set_size)). */
+double mhx_screen_identity(uint64_t shared, uint64_t n, int k);
+double mhx_screen_p_value(uint64_t shared, uint64_t n, double set_size, int k);
 
 /* .msh container access for callers that hold sketches in memory */
 int mhx_msh_write(const char *path, int k, uint32_t s, uint32_t n_refs, const char *const *names,
