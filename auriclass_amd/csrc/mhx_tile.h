@@ -115,6 +115,25 @@ MHX_HD uint32_t funnel_bits(uint32_t hi, uint32_t lo, uint32_t bit_shift)
     return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> bit_shift);
 #endif
 }
+// WIDTH bits of v from bit `shift` on (shift + WIDTH <= 32, WIDTH < 32): one v_bfe_u32 with a run-time offset
+template <uint32_t WIDTH> MHX_HD uint32_t bit_field(uint32_t v, uint32_t shift)
+{
+    static_assert(WIDTH > 0 && WIDTH < 32, "field width");
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ubfe(v, shift, WIDTH);
+#else
+    return (v >> shift) & ((1u << WIDTH) - 1u);
+#endif
+}
+// a ^ b ^ c as one v_bitop3_b32 (truth table 0x96); hipcc's own choice for two chained xors is two v_xor_b32
+MHX_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
 
 // 0x80 in every byte of v that equals the byte replicated in `pattern` (exact).  One instruction less than
 // zero_byte_flags(v ^ pattern): the xor-ed word itself is never needed, only its low seven bits per byte (one v_bitop3:
@@ -255,7 +274,7 @@ template <int K, int NWD> MHX_HD void run_starts(const uint32_t (&w)[NWD + 1], u
 //  * a product is made opaque before it is rotated: left to itself the compiler turns rotl(k * c, r) into a SECOND
 //    64x64 multiplication by (c << r) plus the shifted high word (10 instructions where 4 + 2 do);
 //  * rotations and the fmix shift-xors are written on the 32-bit halves (2 v_alignbit / v_lshrrev + v_xor);
-//  * h * 5 + c is one v_mad_u64_u32 for the low word and a shift-add for the high word.
+//  * h * 5 + c is v_lshl_add_u64 (5h, asm) and a 64-bit add: times5_plus.
 MHX_HD uint64_t opaque64(uint64_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -276,12 +295,28 @@ MHX_HD uint64_t xorshift33(uint64_t k)
     const uint32_t lo = (uint32_t)k, hi = (uint32_t)(k >> 32);
     return make64(lo ^ (hi >> 1), hi);
 }
+// h * 5 + c.  The compiler's own best is three instructions (v_lshl_add_u32 for the high word, v_mad_u64_u32, and a 64-bit add
+// of c); gfx950's v_lshl_add_u64 d, h, 2, h gives 5h in one, but no C++ spelling reaches it (h * 5 + c and (h << 2) + h + c both
+// come out two instructions LONGER per window), so that one instruction is asm and the add of c is left to the compiler:
+// two.  It pays only together with rotated() below.  Timed against the compiler's form at K = 21 and at K = 27 (m = 1 and 3):
+// faster at each (profiles/canonical_select_ab.txt), so there is one device form for every K; the host path keeps plain C++.
 MHX_HD uint64_t times5_plus(uint64_t h, uint32_t c)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t r;
+    asm("v_lshl_add_u64 %0, %1, 2, %1" : "=v"(r) : "v"(h));
+    return r + c;
+#else
     const uint32_t lo = (uint32_t)h, hi = (uint32_t)(h >> 32);
     const uint64_t t = (uint64_t)lo * 5u + c;
     return make64((uint32_t)t, ((hi << 2) + hi) + (uint32_t)(t >> 32));
+#endif
 }
+// A rotation's result on its way into `+= h` and times5_plus.  make64's `hi << 32 | lo` is an addition to the compiler, which
+// reassociates it with the `+= h` behind it: {lo, 0} + h + {0, hi}, a v_mov and two 64-bit adds where one add does -- unseen
+// as long as times5_plus took the halves apart anyway, and exactly what ate the gain of the asm form there.  Opaque, the
+// rotation's two v_alignbit write a register pair and the sum is one v_lshl_add_u64.
+MHX_HD uint64_t rotated(uint64_t x) { return opaque64(x); }
 // x * C mod 2^64 for a constant C.  hipcc's own sequence is v_mad_u64_u32 (lo * C_lo, 64 bits) + 2 x v_mul_lo_u32 (the cross
 // terms) + v_add3_u32: four quarter-rate VALU instructions (4 cycles each per wave64 in isolation,
 // profiles/r02_valu_class_rates_microbench.txt).  -DMHX_ASM_MUL64 selects an experiment of round 3 instead: three of them
@@ -338,6 +373,13 @@ MHX_HD uint32_t admission_limit(uint64_t T)
     const uint32_t th = (uint32_t)(T >> 32);
     return th == 0xFFFFFFFFu ? th : th + 1u;
 }
+// h ^ k ^ K (the length K fits the low word).  h is made opaque before it is split: left to see that only the halves of
+// h are used, the compiler takes the times5_plus in front apart as well and pays two v_mov per window for it.
+template <int K> MHX_HD uint64_t xor_tail_len(uint64_t h, uint64_t k)
+{
+    h = opaque64(h);
+    return make64(xor3((uint32_t)h, (uint32_t)k, (uint32_t)K), (uint32_t)(h >> 32) ^ (uint32_t)(k >> 32));
+}
 constexpr uint64_t kMurmurSeed = 42; // mash's hash seed
 // w: the K bytes as little-endian dwords, bytes beyond K zero
 template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
@@ -351,24 +393,28 @@ template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
         uint64_t k1 = make64(w[4 * b], w[4 * b + 1]);
         uint64_t k2 = make64(w[4 * b + 2], w[4 * b + 3]);
         k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); h1 ^= k1;
-        h1 = rotl64<27>(h1);
+        h1 = rotated(rotl64<27>(h1));
         // block 0: h2 is still the seed, and (x + seed) * 5 + c = x * 5 + (c + 5 * seed) with a constant that fits 32 bits
         // still -- the 64-bit add of the seed (two instructions and a zero register per window) is folded away
         static_assert(0x52dce729ull + 5ull * kMurmurSeed <= 0xFFFFFFFFull, "folded constant of block 0 must fit times5_plus' 32-bit addend");
         if (b == 0) h1 = times5_plus(h1, (uint32_t)(0x52dce729ull + 5ull * kMurmurSeed));
         else { h1 += h2; h1 = times5_plus(h1, 0x52dce729u); }
         k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); h2 ^= k2;
-        h2 = rotl64<31>(h2); h2 += h1; h2 = times5_plus(h2, 0x38495ab5u);
+        h2 = rotated(rotl64<31>(h2)); h2 += h1; h2 = times5_plus(h2, 0x38495ab5u);
     }
+    // the tail block's xor and the xor of the length meet in the low word: h ^ k ^ K there is one three-input operation
     if (TAIL > 8) {
         uint64_t k2 = make64(w[(4 * NBLK + 2) & 7], w[(4 * NBLK + 3) & 7]);
-        k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); h2 ^= k2;
+        k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); h2 = xor_tail_len<K>(h2, k2);
+    } else {
+        h2 ^= (uint64_t)K;
     }
     if (TAIL > 0) {
         uint64_t k1 = make64(w[(4 * NBLK) & 7], w[(4 * NBLK + 1) & 7]);
-        k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); h1 ^= k1;
+        k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); h1 = xor_tail_len<K>(h1, k1);
+    } else {
+        h1 ^= (uint64_t)K;
     }
-    h1 ^= (uint64_t)K; h2 ^= (uint64_t)K;
     h1 += h2; h2 += h1;
     const uint64_t a = fmix64_head(h1, zero), b = fmix64_head(h2, zero);
     return Murmur3Tail{a, b};
@@ -742,15 +788,28 @@ MHX_HD void canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND 
             }
             rc = rc_less;
         }
-        // select the source dwords first, extract once
-        uint32_t S[NW + 1];
+        // select the source dwords first, extract once.  The last word keeps TB bytes, and a strand whose byte shift s has
+        // s + TB <= 4 takes them all from S[NW - 1]: what it would pull in from S[NW] is masked away.  Both shifts are
+        // compile-time constants (only WHICH of them applies is a per-lane run-time value, so the compiler cannot see it):
+        //   neither strand reads S[NW]: it is not selected, and the last word is one bit-field extract of S[NW - 1];
+        //   one strand reads it: that strand's dword is taken as it is, the other strand's garbage is masked away.
+        constexpr int TB = K - 4 * (NW - 1); // 1..4
+        constexpr bool need_f = OF % 4 + TB > 4, need_r = OR % 4 + TB > 4;
+        uint32_t S[NW];
 #pragma unroll
-        for (int i = 0; i < NW + 1; ++i) S[i] = rc ? R[OR / 4 + i] : U[OF / 4 + i];
+        for (int i = 0; i < NW; ++i) S[i] = rc ? R[OR / 4 + i] : U[OF / 4 + i];
         const uint32_t sh = rc ? 8u * (OR % 4) : 8u * (OF % 4);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            w[i] = i < NW ? funnel_bits(S[i + 1], S[i], sh) : 0u;
-        if (K % 4) w[NW - 1] &= (1u << (8 * (K % 4))) - 1u;
+            w[i] = i < NW - 1 ? funnel_bits(S[i + 1], S[i], sh) : 0u;
+        if constexpr (!need_f && !need_r) {
+            if constexpr (TB == 4) w[NW - 1] = S[NW - 1]; // both shifts are 0
+            else w[NW - 1] = bit_field<8 * TB>(S[NW - 1], sh);
+        } else {
+            const uint32_t last = need_f && need_r ? (rc ? R[OR / 4 + NW] : U[OF / 4 + NW]) : need_f ? U[OF / 4 + NW] : R[OR / 4 + NW];
+            w[NW - 1] = funnel_bits(last, S[NW - 1], sh);
+            if constexpr (TB < 4) w[NW - 1] &= (1u << (8 * TB)) - 1u;
+        }
     } else {
         uint32_t wf[8], wr[8];
         extract_words<K, OF>(U, wf);
@@ -766,6 +825,23 @@ template <int K> struct GroupGeom {
     static constexpr int NB = kGroup + K - 1; // bytes touched
     static constexpr int ND = (NB + 3) / 4;   // dwords loaded
 };
+
+// The four views of a group's chunk that canonical_words takes (one dword of zero padding behind each)
+template <int ND>
+MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint32_t (&R)[ND + 1], uint32_t (&Wr)[ND + 1], uint32_t (&Cc)[ND + 1])
+{
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        U[d] = src[d] & 0xDFDFDFDFu; // fold case: mash upper-cases before hashing
+        Cc[d] = complement4(U[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        R[d] = __builtin_bswap32(Cc[ND - 1 - d]);
+        Wr[d] = __builtin_bswap32(U[ND - 1 - d]);
+    }
+    U[ND] = R[ND] = Wr[ND] = Cc[ND] = 0;
+}
 
 // Cold path, reached by one window in ~2^64 / T: are bytes J .. J+K-1 of the chunk all A/C/G/T (either case)?
 // mash skips every window that holds anything else (Sketch.cpp addMinHashes).
@@ -792,17 +868,7 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
 {
     constexpr int ND = GroupGeom<K>::ND;
     uint32_t U[ND + 1], R[ND + 1], Wr[ND + 1], Cc[ND + 1];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        U[d] = src[d] & 0xDFDFDFDFu; // fold case: mash upper-cases before hashing
-        Cc[d] = complement4(U[d]);
-    }
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        R[d] = __builtin_bswap32(Cc[ND - 1 - d]);
-        Wr[d] = __builtin_bswap32(U[ND - 1 - d]);
-    }
-    U[ND] = R[ND] = Wr[ND] = Cc[ND] = 0;
+    strand_views<ND>(src, U, R, Wr, Cc);
     constexpr bool kHash32 = K <= 16; // mash keeps 32 bits when 4^k <= 2^32
     uint32_t ninserted = 0;
 #define MHX_WINDOW(J)                                                                         \

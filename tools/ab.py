@@ -73,12 +73,18 @@ def main():
             env = dict(os.environ, MHX_LIB=str(lib))
             cmd = [sys.executable, __file__, "--child", "--reads", str(args.reads), "--iters", str(args.iters), "--k", str(args.k),
                    "--s", str(args.s), "--m", str(args.m)] + (["--parity"] if rd == 0 else [])
-            p = subprocess.run(cmd, env=env, capture_output=True, text=True)
+            # nothing more is started on a GPU that a run may have faulted or hung: the failure is looked into first
+            try:
+                p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+            except subprocess.TimeoutExpired as e:
+                # what a timed-out child had written can arrive as bytes even with text=True
+                so, se = (x.decode(errors="replace") if isinstance(x, bytes) else x or "" for x in (e.stdout, e.stderr))
+                print(f"{n}: FAILED, no result after {e.timeout:.0f} s\n{so[-500:]}\n{se[-1500:]}", flush=True)
+                raise SystemExit(f"{n} hung in round {rd}: stopped")
             line = [x for x in p.stdout.splitlines() if x.startswith("ABRESULT ")]
             if p.returncode != 0 or not line:
                 print(f"{n}: FAILED rc={p.returncode}\n{p.stdout[-500:]}\n{p.stderr[-1500:]}", flush=True)
-                res[n].append(None)
-                continue
+                raise SystemExit(f"{n} failed in round {rd}: stopped")
             r = json.loads(line[0][9:])
             res[n].append(r)
             if "parity" in r:
@@ -89,12 +95,8 @@ def main():
     base = None
     print("---- medians over rounds ----")
     for n in args.names:
-        ok = [r for r in res[n] if r]
-        if not ok:
-            print(f"{n:24s} no data")
-            continue
-        km = statistics.median(r["kernel_ms"] for r in ok)
-        sm = statistics.median(r["step_ms"] for r in ok)
+        km = statistics.median(r["kernel_ms"] for r in res[n])
+        sm = statistics.median(r["step_ms"] for r in res[n])
         if base is None:
             base = (km, sm)
         print(f"{n:24s} kernel {km:.3f} ms ({100 * (km / base[0] - 1):+.1f}%)  step {sm:.3f} ms ({100 * (sm / base[1] - 1):+.1f}%)  "
