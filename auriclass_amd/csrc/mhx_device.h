@@ -12,7 +12,7 @@ struct HashArgs {
     const uint8_t *base;   // 16-byte aligned; tiles are laid over base + [0, ...)
     uint64_t begin, end;   // logical span, byte offsets from base
     uint32_t tile0;        // first tile of this launch
-    uint32_t ntiles;       // tiles in this launch (== gridDim.x)
+    uint32_t ntiles;       // tiles in this launch (gridDim.x == ntiles * split)
     uint32_t first_tile;   // first tile of the push (its line phase is 0)
     uint32_t hash32;       // 1: keep the low 32 bits of the hash (k <= 16)
     uint32_t *ticket;      // zeroed before every launch
@@ -27,6 +27,8 @@ struct HashArgs {
     uint32_t queue_candidates; // kernel form: windows that pass the admission test are queued and finished after the hash loop (large sketches)
     uint8_t *phase_rec;      // FMT 2 / repair: one phase_record() per tile of the span (0: phase unknown), for phase_verify_kernel
     uint32_t probe;          // containment screen: keys / cnts are a screen table (mhx_screen.h) and the launch takes the probing kernels
+    uint32_t split;          // workgroups per tile, a power of two <= 8 (1: the usual launch).  > 1: each one parses the tile and hashes one slice
+                             // of its work list -- the first launch of a sketcher, inline kernels of formats 0 and 2 only (sketch_tile_kernel<.., SPLIT>)
 };
 
 struct TableArgs {
@@ -43,11 +45,13 @@ struct TableArgs {
     uint32_t sketch_size;
     uint32_t sample;     // tighten pass looks at one 256-slot block in `sample` (1 = exact pass)
     uint64_t next_cap;   // tighten pass, m > 1: byte-count cap to apply behind the new threshold (0: none), see cap_threshold_kernel
+    const uint8_t *verify_rec; // tighten pass: HashArgs::phase_rec of the push it ends, whose chain it checks as phase_verify_kernel does (nullptr: no check)
+    uint32_t verify_ntiles;    // ... and the number of tiles of that push
 };
 
 // launchers (mhx_kernels.hip)
 hipError_t launch_hash(int k, int fmt, const HashArgs &a, hipStream_t st);
-hipError_t launch_tighten(const TableArgs &a, hipStream_t st);
+hipError_t launch_tighten(const TableArgs &a, uint32_t cus, hipStream_t st); // cus: compute units of the device (bounds the grid)
 hipError_t launch_reset(const TableArgs &a, uint64_t t_init, uint32_t *tickets, uint32_t ntickets, uint32_t *out_n, hipStream_t st);
 hipError_t launch_cap_threshold(uint64_t *thresh, uint64_t cap, uint64_t *stats, hipStream_t st);
 hipError_t launch_order_block(const uint64_t *blk, uint32_t cap, uint32_t log2_buckets, uint32_t *cursor, uint32_t *starts,

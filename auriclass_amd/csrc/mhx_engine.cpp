@@ -65,6 +65,9 @@ extern "C" int mhx_init(int device)
     if (device >= n) return fail(MHX_E_ARG, "mhx_init: device %d out of range (%d visible)", device, n);
     if (g.ready) mhx_shutdown();
     HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    g.cu_count = prop.multiProcessorCount;
     HIPCHK(hipStreamCreateWithFlags(g.stream.out(), hipStreamNonBlocking));
     HIPCHK(hipEventCreate(g.ev0.out()));
     HIPCHK(hipEventCreate(g.ev1.out()));
@@ -200,6 +203,8 @@ static TableArgs table_args(mhx_sketcher *sk)
     t.hist = sk->d_hist; t.acc = sk->d_acc; t.stats = sk->d_stats; t.done = sk->d_done; t.need_lookback = sk->d_need; t.min_mult = sk->m; t.sketch_size = sk->s;
     t.sample = 1;
     t.next_cap = 0;
+    t.verify_rec = nullptr;
+    t.verify_ntiles = 0;
     return t;
 }
 
@@ -469,6 +474,11 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
     a.repair = repair ? 1u : 0u;
     a.probe = sk->screen ? 1u : 0u;
     static const char *force_queue = getenv("MHX_QUEUE_CANDIDATES"); // "0" / "1": diagnostic override
+    // MHX_FIRST_SPLIT=1|2|4|8: diagnostic override of the first launch's split (read per push: the tests change it between sketches)
+    const char *split_env = getenv("MHX_FIRST_SPLIT");
+    const long split_val = split_env ? atol(split_env) : 0;
+    const uint32_t force_split = (uint32_t)(split_val == 1 || split_val == 2 || split_val == 4 || split_val == 8 ? split_val : 0);
+    a.split = 1;
     a.queue_candidates = force_queue ? (uint32_t)(force_queue[0] == '1') : (uint32_t)(sk->s >= kDeviceOrderMinSketch);
     const uint64_t ntiles64 = (a.end + kTileBytes - 1) / kTileBytes;
     if (ntiles64 > 0x7FFFFFFFull) return fail(MHX_E_ARG, "span too large for one push (%llu bytes)", (unsigned long long)n);
@@ -570,6 +580,7 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
     };
     uint32_t tile = 0;
     int launch = 0;
+    bool verified = false; // the FASTQ phase chain of this push has been checked by its last tighten pass
     Plan cur = plan(0, 0);
     if (cur.cap) HIPCHK(launch_cap_threshold(sk->d_thresh, cur.cap, sk->d_stats, g.stream)); // first launch of a push: a launch of its own
     while (tile < ntiles) {
@@ -586,6 +597,14 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
         }
         a.tile0 = tile;
         a.ntiles = cur.take;
+        // The first launch of a fresh sketcher admits every window: each lane hashes AND inserts window after window, on
+        // a chunk of at most nslots / 4 bytes -- a few dozen workgroups on an otherwise empty device.  It gets S workgroups
+        // per tile (HashArgs::split), the smallest power of two that brings the grid up to the CU count.
+        a.split = 1;
+        if (kfmt != 1 && !repair && pushed_before == 0 && launch == 0 && !cur.cap && !a.queue_candidates) { // (inline form: the split kernels are)
+            if (force_split) a.split = force_split;
+            else while (a.split < 8 && (uint64_t)cur.take * a.split < (uint64_t)g.cu_count) a.split *= 2;
+        }
         a.ticket = sk->d_tickets + sk->tickets_used++;
         const int lrc = timed_launch();
         if (lrc) return lrc;
@@ -608,11 +627,17 @@ static int push_span(mhx_sketcher *sk, const void *d_bytes, uint64_t n, int kfmt
         // with a multiplicity filter the cap in front of the next launch is decided before the pass can report solid
         // hashes.  What remains safe saves < 1 % of a step; the passes stay in stream order.)
         ta.next_cap = tile < ntiles ? cur.cap : 0;
-        HIPCHK(launch_tighten(ta, g.stream));
+        // the pass behind the last launch also checks the phase chain of the push (a push of one tile has no chain)
+        if (tile >= ntiles && (kfmt == 2 || repair) && ntiles >= 2) {
+            ta.verify_rec = sk->d_phase_rec;
+            ta.verify_ntiles = ntiles;
+            verified = true;
+        }
+        HIPCHK(launch_tighten(ta, (uint32_t)g.cu_count, g.stream));
         if (ta.sample == 1) sk->table_dirty = false;
         else sk->table_sampled = true;
     }
-    if (kfmt == 2 || repair) HIPCHK(launch_phase_verify(sk->d_phase_rec, ntiles, sk->d_stats, g.stream));
+    if ((kfmt == 2 || repair) && !verified) HIPCHK(launch_phase_verify(sk->d_phase_rec, ntiles, sk->d_stats, g.stream));
     return MHX_OK;
 }
 
@@ -727,7 +752,7 @@ extern "C" int mhx_sketcher_threshold(mhx_sketcher *sk, uint64_t *threshold)
     if (!sk || !threshold) return fail(MHX_E_ARG, "null argument");
     rc = settle(sk);
     if (rc) return rc;
-    HIPCHK(launch_tighten(table_args(sk), g.stream));
+    HIPCHK(launch_tighten(table_args(sk), (uint32_t)g.cu_count, g.stream));
     return read_threshold(sk, threshold);
 }
 
@@ -827,7 +852,7 @@ static int mhx_sketcher_finish_impl(mhx_sketcher *sk, uint64_t *hashes, uint32_t
     // big tables: the sampled pass behind the last launch left T at about the (s + 8 sqrt(s))-th solid hash, the block holds
     // twice that, and the host keeps the first s -- a second pass over the table only if that turns out not to be so
     if (sk->table_dirty && (want_exact || !sk->table_sampled)) {
-        HIPCHK(launch_tighten(table_args(sk), g.stream));
+        HIPCHK(launch_tighten(table_args(sk), (uint32_t)g.cu_count, g.stream));
         sk->table_dirty = false;
         sk->table_sampled = false;
     }

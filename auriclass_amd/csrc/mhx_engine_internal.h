@@ -111,6 +111,7 @@ struct Engine {
     HipStream copy_stream; // bulk file ingest and the FASTA loader (created on first use)
     bool ready = false;
     int device = -1;
+    int cu_count = 0;      // compute units of the device (mhx_init): sizes the split of a sketcher's first launch
     bool profiling = false;
     HipEvent ev0, ev1;
     double last_dist_ms = 0.0;

@@ -17,6 +17,7 @@
 #include "mhx_device.h"
 #include "mhx_screen.h"
 #include "mhx_tile.h"
+#include "mhx_tighten.h"
 
 #include <type_traits>
 
@@ -213,7 +214,7 @@ constexpr bool kParseLoops = false;
 #ifndef MHX_MIN_WAVES
 #define MHX_MIN_WAVES 7   // 72 VGPRs: seven waves per SIMD, matching the seven workgroups per CU the LDS footprint admits
 #endif
-template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(kBlock, MHX_MIN_WAVES) void sketch_tile_kernel(const HashArgs a)
+template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__ __launch_bounds__(kBlock, MHX_MIN_WAVES) void sketch_tile_kernel(const HashArgs a)
 {
     __shared__ TileSmem sm;
     constexpr bool FASTQ = (FMT != 0), LOOKBACK = (FMT == 1), SELFSYNC = (FMT == 2);
@@ -223,6 +224,15 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
     // and more waves per SIMD are in VALU-dense code at any time (-2 % kernel time)
     __builtin_amdgcn_s_setprio(3);
 
+    // split launch (SPLIT: HashArgs::split > 1, a power of two): `split` workgroups per tile, all of which stage and parse
+    // it, and each of which then hashes one slice of the work list.  What a tile does once -- counters, phase record,
+    // repair word, format flag -- is left to slice 0.  A form of its own, for the inline kernels of formats 0 and 2 only:
+    // as a run-time stride in every kernel it cost the queue forms a VGPR (60 -> 61 at k = 21, 67 -> 68 at k = 27).
+    static_assert(!SPLIT || (!LOOKBACK && !QUEUE && !PROBE), "split launches: inline sketch kernels of formats 0 and 2");
+    const uint32_t split_log2 = SPLIT ? (uint32_t)__builtin_ctz(a.split) : 0u;
+    const uint32_t slice = SPLIT ? blockIdx.x & (a.split - 1u) : 0u;
+    const uint32_t it0 = slice * kBlock + (uint32_t)tid, it_step = (uint32_t)kBlock << split_log2;
+    const bool once = slice == 0; // this workgroup speaks for the tile
     // tile id: in ticket order for FASTQ (look-back needs started-before ordering)
     uint32_t tile;
     if (LOOKBACK) {
@@ -230,7 +240,7 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
         __syncthreads();
         tile = sm.misc[2];
     } else {
-        tile = a.tile0 + blockIdx.x;
+        tile = a.tile0 + (blockIdx.x >> split_log2);
     }
     const uint64_t tile_off = (uint64_t)tile * kTileBytes;
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(a.stats) + (tile % kStatReplicas) * kStatCount;
@@ -277,10 +287,10 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
         const uint32_t self_phase = sm.misc[0];
         if (SELFSYNC) {
             if (self_phase == 4u) { // lines too long to tell: left to the look-back pass, nothing of this tile is counted now
-                if (tid == 0) { a.phase_rec[tile - a.first_tile] = 0; atomicOr(a.need_lookback, 1u); }
+                if (tid == 0 && once) { a.phase_rec[tile - a.first_tile] = 0; atomicOr(a.need_lookback, 1u); }
                 return; // (the newline list phase_events has just written goes unused: listing before the phase is known saves a barrier)
             }
-            if (tid == 0) a.phase_rec[tile - a.first_tile] = phase_record(self_phase, tile_total);
+            if (tid == 0 && once) a.phase_rec[tile - a.first_tile] = phase_record(self_phase, tile_total);
             line_base = self_phase;
         } else {
             if (a.repair && self_phase != 4u) { // repair pass: this tile was done in the first pass, it only publishes its phase
@@ -304,7 +314,7 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
     const uint32_t long_records = fast_parse
         ? phase_good_events(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K)
         : phase_good<FASTQ>(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
-    if (FASTQ && bad) atomicOr(&stats[kStatFlags], (unsigned long long)kFlagBadFastq);
+    if (FASTQ && bad && once) atomicOr(&stats[kStatFlags], (unsigned long long)kFlagBadFastq);
     if (FASTQ && long_records) atomicAdd(&sm.misc[5], long_records);
     __syncthreads();
     MHX_STAMP(); // 3: good-base map
@@ -325,14 +335,14 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
     const uint32_t qcap = (uint32_t)kGroupsPerTile - nitems; // QUEUE: the work list's unused tail holds the candidate queue
     CandidateQueue queue{sm, nitems, qcap};
     uint32_t ninsert = 0;
-    for (uint32_t it = tid; it < nitems; it += kBlock) ninsert += process_group<K, QUEUE>(sm, sm.list[it], T, limit, ins, queue);
+    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE>(sm, sm.list[it], T, limit, ins, queue);
     if (QUEUE) {
         __syncthreads();
         const uint32_t ncand = sm.misc[7];
         if (ncand <= qcap) { // the candidates the loop has queued, one per lane
             for (uint32_t c = tid; c < ncand; c += kBlock) ninsert += finish_candidate<K>(sm, sm.list[nitems + c], T, ins);
         } else { // the queue overflowed (T still admits a large share of all hashes): every valid window, whole hash, exact test
-            for (uint32_t it = tid; it < nitems; it += kBlock) {
+            for (uint32_t it = it0; it < nitems; it += it_step) {
                 const uint32_t g = sm.list[it];
                 uint32_t vmask = reinterpret_cast<const uint8_t *>(sm.valid)[g];
                 while (vmask) {
@@ -347,10 +357,10 @@ template <int K, int FMT, bool QUEUE, bool PROBE> __global__ __launch_bounds__(k
     __syncthreads();
     MHX_STAMP(); // 5: work loop
     if (tid == 0) {
-        if (sm.misc[3]) atomicAdd(&stats[kStatKmers], (unsigned long long)sm.misc[3]);
-        if (sm.misc[4]) atomicAdd(&stats[kStatInserts], (unsigned long long)sm.misc[4]);
-        if (FASTQ && tile_total) atomicAdd(&stats[kStatLines], (unsigned long long)tile_total);
-        if (FASTQ && sm.misc[5]) atomicAdd(&stats[kStatRecords], (unsigned long long)sm.misc[5]);
+        if (once && sm.misc[3]) atomicAdd(&stats[kStatKmers], (unsigned long long)sm.misc[3]);
+        if (sm.misc[4]) atomicAdd(&stats[kStatInserts], (unsigned long long)sm.misc[4]); // per slice: every slice adds its own
+        if (once && FASTQ && tile_total) atomicAdd(&stats[kStatLines], (unsigned long long)tile_total);
+        if (once && FASTQ && sm.misc[5]) atomicAdd(&stats[kStatRecords], (unsigned long long)sm.misc[5]);
     }
 }
 
@@ -359,8 +369,15 @@ template <int K> static hipError_t launch_k(int fmt, const HashArgs &a, hipStrea
     // a.queue_candidates: large sketches (many windows pass the admission test) finish their candidates after the hash
     // loop, one per lane; small ones where they are found (process_group_regs)
     // a.probe: the kernels of the containment screen (ScreenProber in the place of DeviceInserter)
-#define MHX_LAUNCH_FORM(FMT_, QUEUE_) do { if (a.probe) hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, true>), dim3(a.ntiles), dim3(kBlock), 0, st, a); \
-                                           else hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, false>), dim3(a.ntiles), dim3(kBlock), 0, st, a); } while (0)
+    if (a.split > 1) { // the split forms: inline, non-probing, formats 0 and 2 (FMT 1 takes its tiles by ticket: one workgroup each)
+        if (fmt == 1 || a.queue_candidates || a.probe) return hipErrorInvalidValue;
+        if (fmt == 2) hipLaunchKernelGGL((sketch_tile_kernel<K, 2, false, false, true>), dim3(a.ntiles * a.split), dim3(kBlock), 0, st, a);
+        else hipLaunchKernelGGL((sketch_tile_kernel<K, 0, false, false, true>), dim3(a.ntiles * a.split), dim3(kBlock), 0, st, a);
+        return hipGetLastError();
+    }
+    const unsigned grid = a.ntiles;
+#define MHX_LAUNCH_FORM(FMT_, QUEUE_) do { if (a.probe) hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, true>), dim3(grid), dim3(kBlock), 0, st, a); \
+                                           else hipLaunchKernelGGL((sketch_tile_kernel<K, FMT_, QUEUE_, false>), dim3(grid), dim3(kBlock), 0, st, a); } while (0)
 #define MHX_LAUNCH(FMT_) do { if (a.queue_candidates) MHX_LAUNCH_FORM(FMT_, true); else MHX_LAUNCH_FORM(FMT_, false); } while (0)
     if (fmt == 1) MHX_LAUNCH(1);
     else if (fmt == 2) MHX_LAUNCH(2);
@@ -382,6 +399,7 @@ bool hash_k_supported(int k) { return k >= 1 && k <= 32; }
 hipError_t launch_hash(int k, int fmt, const HashArgs &a, hipStream_t st)
 {
     if (a.ntiles == 0) return hipSuccess;
+    if (a.split == 0 || (a.split & (a.split - 1)) || a.split > 8 || (uint64_t)a.ntiles * a.split > 0x7FFFFFFFull) return hipErrorInvalidValue;
     switch (k) {
 #define X(KK) case KK: return launch_k<KK>(fmt, a, st);
         MHX_K_LIST(X)
@@ -516,46 +534,99 @@ hipError_t launch_screen_tally(const ScreenArgs &a, hipStream_t st)
 // through memory-side atomics (the flush, the ticket) and agent-scope loads / stores in the last workgroup (which also
 // clear the bins for the next pass), with an agent-scope release in front of the ticket, so no cache of another XCD is
 // ever trusted.
+// Geometry (launch_tighten): at most one workgroup per CU, each with kTightenLoads independent key loads in flight per
+// thread -- the pass costs a launch, the stream of the key array, one ticket per workgroup and the last workgroup's tail;
+// a grid of several workgroups per CU only adds arrivals at the ticket word (10-20 ns each, one after the other) and
+// release fences.  A workgroup that counted nothing below T -- the usual case from the second pass of a push on, when
+// qualifying entries are one slot in thousands -- has nothing to flush.
+// TableArgs::verify_rec: the pass that push_span launches last also checks the FASTQ phase chain of the push
+// (phase_verify_kernel's work, one launch and one kernel boundary less).
+#ifndef MHX_TIGHTEN_LOADS
+#define MHX_TIGHTEN_LOADS 16
+#endif
+#ifndef MHX_TIGHTEN_PER_CU
+#define MHX_TIGHTEN_PER_CU 1
+#endif
+constexpr int kTightenLoads = MHX_TIGHTEN_LOADS;
+#ifdef MHX_TIGHTEN_STAMPS // diagnostic builds: wall-clock ticks (10 ns) per phase of the pass, summed over workgroups
+#define MHX_TSTAMP(IDX_)                                                                                                   \
+    do {                                                                                                                   \
+        if (threadIdx.x == 0) {                                                                                            \
+            const uint64_t now_ = wall_clock64();                                                                          \
+            atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + (1 + blockIdx.x % (kStatReplicas - 1)) * kStatCount + kStatStamp0 + (IDX_), \
+                      (unsigned long long)(now_ - tstamp_prev));                                                           \
+            tstamp_prev = now_;                                                                                            \
+        }                                                                                                                  \
+    } while (0)
+#else
+#define MHX_TSTAMP(IDX_) do { } while (0)
+#endif
 __global__ __launch_bounds__(256) void table_tighten_kernel(const TableArgs a)
 {
     __shared__ uint32_t h[kHistBins];
     __shared__ uint32_t occ_s, solid_s, last_s, cut_s;
     __shared__ uint32_t wave_sums[4];
     __shared__ unsigned long long tot_s[2];
+#ifdef MHX_TIGHTEN_STAMPS
+    uint64_t tstamp_prev = wall_clock64();
+#endif
     for (int i = threadIdx.x; i < kHistBins; i += blockDim.x) h[i] = 0;
-    if (threadIdx.x == 0) { occ_s = 0; solid_s = 0; cut_s = 0xFFFFFFFFu; tot_s[0] = 0; tot_s[1] = 0; }
+    if (threadIdx.x == 0) { occ_s = 0; solid_s = 0; cut_s = kNoCut; tot_s[0] = 0; tot_s[1] = 0; }
     __syncthreads();
     const uint64_t T = *a.thresh;
-    const int lz = T ? __builtin_clzll(T) : 63;
+    const int lz = tighten_lz(T);
+    // FASTQ, self-synchronising form: do the line phases the tiles of the push found form one chain?
+    if (a.verify_rec)
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x + 1u; i < a.verify_ntiles; i += gridDim.x * blockDim.x)
+            if (phase_chain_broken(a.verify_rec[i - 1], a.verify_rec[i]))
+                atomicOr(reinterpret_cast<unsigned long long *>(a.stats) + kStatFlags, (unsigned long long)kFlagBadFastq);
+    MHX_TSTAMP(0); // 0: LDS clear, T, phase chain
     uint32_t occ = 0, solid = 0;
     // sample = 1: every slot; sample = 8: one 256-slot block in eight (slots are hash-addressed, so
     // any fixed subset of blocks is a uniform sample of the entries)
     const uint64_t nblocks256 = a.nslots / 256;
     const uint64_t step = a.sample > 1 ? a.sample : 1;
-    // four independent key loads in flight per thread: with one, the pass is a chain of L2/HBM round trips
+    // kTightenLoads independent key loads in flight per thread: with one, the pass is a chain of L2/HBM round trips
     const uint64_t stride = (uint64_t)gridDim.x * step;
-    for (uint64_t b0 = (uint64_t)blockIdx.x * step; b0 < nblocks256; b0 += 4 * stride) {
-        uint64_t key[4];
+    for (uint64_t b0 = (uint64_t)blockIdx.x * step; b0 < nblocks256; b0 += kTightenLoads * stride) {
+        uint64_t key[kTightenLoads];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < kTightenLoads; ++u) {
             const uint64_t b = b0 + u * stride;
             key[u] = b < nblocks256 ? a.keys[b * 256 + threadIdx.x] : kEmptyKey;
         }
+        // ... and the counts of the entries <= T likewise, all of them issued before the first is looked at: behind the
+        // first launch of a sketch every entry qualifies, and a count fetched inside the branch that tests it made that
+        // pass a chain of one round trip per key.  m = 1: an occupied slot has been counted at least once, nothing to fetch.
+        uint32_t cnt[kTightenLoads];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < kTightenLoads; ++u) {
+            const bool fetch = a.min_mult > 1 && key[u] != kEmptyKey && key[u] <= T;
+            cnt[u] = fetch ? a.cnts[(b0 + u * stride) * 256 + threadIdx.x] : 1u;
+        }
+#pragma unroll
+        for (int u = 0; u < kTightenLoads; ++u) {
             if (key[u] == kEmptyKey) continue;
             ++occ;
-            if (key[u] <= T && a.cnts[(b0 + u * stride) * 256 + threadIdx.x] >= a.min_mult) {
+            if (key[u] <= T && cnt[u] >= a.min_mult) {
                 ++solid;
-                atomicAdd(&h[(key[u] << lz) >> (64 - 11)], 1u);
+                atomicAdd(&h[tighten_bin(key[u], lz)], 1u);
             }
         }
     }
     if (occ) atomicAdd(&occ_s, occ);
     if (solid) atomicAdd(&solid_s, solid);
     __syncthreads();
-    for (int i = threadIdx.x; i < kHistBins; i += blockDim.x)
-        if (h[i]) atomicAdd(&a.hist[i], h[i]);
+    MHX_TSTAMP(1); // 1: key loop
+    if (solid_s) { // (workgroup-uniform) nothing counted: every bin is zero
+        // two neighbouring bins per 64-bit atomic: half the atomics of the first pass of a sketch, when every entry
+        // qualifies and every workgroup has something in every bin (a bin's total is at most nslots < 2^32: no carry)
+        unsigned long long *hist2 = reinterpret_cast<unsigned long long *>(a.hist);
+        for (int i = threadIdx.x; i < kHistBins / 2; i += blockDim.x) {
+            const uint32_t lo = h[2 * i], hi = h[2 * i + 1];
+            if (lo | hi) atomicAdd(&hist2[i], (unsigned long long)lo | ((unsigned long long)hi << 32));
+        }
+    }
     if (threadIdx.x == 0) {
         // 64 replicas, 64 bytes apart: a thousand workgroups adding to ONE word serialise at ~10-20 ns each
         unsigned long long *acc = reinterpret_cast<unsigned long long *>(a.acc) + (blockIdx.x % kAccReplicas) * 8;
@@ -566,88 +637,70 @@ __global__ __launch_bounds__(256) void table_tighten_kernel(const TableArgs a)
     // (256 threads fencing cost 60 us per pass)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    MHX_TSTAMP(2); // 2: flushes
     if (threadIdx.x == 0) {
         __threadfence();
         last_s = atomicAdd(a.done, 1u) == gridDim.x - 1;
     }
     __syncthreads();
+    MHX_TSTAMP(3); // 3: release + ticket
+#ifdef MHX_TIGHTEN_STAMPS
+    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + (1 + blockIdx.x % (kStatReplicas - 1)) * kStatCount + kStatStamp0 + 5, 1ull); // 5: workgroups
+#endif
     if (!last_s) return;
 
-    // ---- last workgroup: first bin where the cumulative count reaches s ----------------------------------------
-    // T only ever decreases, and only to a value below which at least s entries with count >= m already exist, so
-    // every hash of the final sketch stays admitted (and therefore fully counted) for the whole run.
+    // ---- last workgroup: first bin where the cumulative count reaches s (mhx_tighten.h) ------------------------
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     constexpr int kPer = kHistBins / 256; // bins per thread, in value order
     uint32_t c[kPer], mine = 0;
-    // agent-scope loads + stores: served past the caches, like the look-back words.  All loads first (one round trip for
-    // the eight of them instead of eight), then the stores that clear the bins for the next pass.
+    // agent-scope loads + stores: served past the caches, like the look-back words.  All loads first -- the eight bins
+    // and this pass's totals in one round trip --, then the stores that clear the words for the next pass.
 #pragma unroll
     for (int j = 0; j < kPer; ++j) c[j] = __hip_atomic_load(&a.hist[kPer * t + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint64_t o = 0, so = 0;
+    if (t < kAccReplicas) {
+        o = __hip_atomic_load(&a.acc[t * 8], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        so = __hip_atomic_load(&a.acc[t * 8 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
-        __hip_atomic_store(&a.hist[kPer * t + j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c[j]) __hip_atomic_store(&a.hist[kPer * t + j], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         mine += c[j];
+    }
+    if (t < kAccReplicas) {
+        if (o) __hip_atomic_store(&a.acc[t * 8], (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (so) __hip_atomic_store(&a.acc[t * 8 + 1], (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (o) atomicAdd(&tot_s[0], (unsigned long long)o);
+        if (so) atomicAdd(&tot_s[1], (unsigned long long)so);
     }
     uint32_t incl = mine;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
+    for (int o2 = 1; o2 < 64; o2 <<= 1) {
+        const uint32_t v = __shfl_up(incl, o2);
+        if (lane >= o2) incl += v;
     }
     if (lane == 63) wave_sums[wave] = incl;
     __syncthreads();
     uint32_t before = incl - mine;
     for (int w = 0; w < wave; ++w) before += wave_sums[w];
-    // sampled pass: counts are ~Binomial(truth, 1/sample); ask for the expected s/sample plus six
-    // standard deviations (+16 for small s) so that the sampling error cannot push T below the true
-    // s-th qualifying hash (~1e-9 per pass; finish() counts exactly and refuses a short result below a lowered T)
-    uint32_t s = a.sketch_size;
-    if (a.sample > 1) {
-        const float mean = (float)a.sketch_size / (float)a.sample;
-        s = (uint32_t)(mean + 6.0f * sqrtf(mean)) + 16u;
-    }
-    if (before < s && before + mine >= s) { // the cut lies in one of my bins (exactly one thread gets here)
-        uint32_t run = before;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            if (run < s && run + c[j] >= s) cut_s = (uint32_t)(kPer * t + j);
-            run += c[j];
-        }
-    }
-    if (t < kAccReplicas) { // this pass's totals
-        uint64_t *acc = a.acc + t * 8;
-        const uint64_t o = __hip_atomic_load(&acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint64_t so = __hip_atomic_load(&acc[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&acc[0], (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&acc[1], (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (o) atomicAdd(&tot_s[0], (unsigned long long)o);
-        if (so) atomicAdd(&tot_s[1], (unsigned long long)so);
-    }
+    const uint32_t s = tighten_target(a.sketch_size, a.sample);
+    if (before < s && before + mine >= s) cut_s = tighten_cut_among(c, kPer, (uint32_t)(kPer * t), before, s); // exactly one thread gets here
     __syncthreads();
     if (t == 0) {
         const uint64_t occupied = tot_s[0] * (a.sample > 1 ? a.sample : 1), solid = tot_s[1] * (a.sample > 1 ? a.sample : 1);
         a.stats[kStatOccupied] = occupied;
         a.stats[kStatSolid] = solid;
         *a.done = 0;
-        const uint32_t cut = cut_s;
-        uint64_t now = T;
-        bool established = a.min_mult > 1 && a.stats[kStatEstablished];
-        if (cut != 0xFFFFFFFFu && lz <= 52) {
-            const uint64_t edge = (((uint64_t)cut + 1) << (53 - lz)) - 1; // last value of bin `cut`
-            if (edge < T) {
-                now = edge;
-                if (a.min_mult > 1) { a.stats[kStatEstablished] = 1; established = true; } // from now on T follows the solid hashes: no more caps
-            }
-        }
-        // the byte-count cap in front of the NEXT launch of the same push (cap_threshold_kernel's rule, without its launch)
-        if (a.next_cap && !established && !(occupied > 0 && solid * 5 >= occupied) && now > a.next_cap) {
-            now = a.next_cap;
-            a.stats[kStatBounded] = 1;
-        }
+        const bool was_established = a.min_mult > 1 && a.stats[kStatEstablished];
+        bool established = was_established, bounded = false;
+        const uint64_t now = tighten_threshold(T, lz, cut_s, a.min_mult, a.next_cap, occupied, solid, established, bounded);
+        if (established && !was_established) a.stats[kStatEstablished] = 1; // from now on T follows the solid hashes: no more caps
+        if (bounded) a.stats[kStatBounded] = 1;
         // (atomic: a pass between two launches of a push runs beside the next launch's cap_threshold_kernel, and T must
         // never rise -- a hash that is admitted now must have been admitted on every earlier occurrence)
         if (now < T) atomicMin(reinterpret_cast<unsigned long long *>(a.thresh), (unsigned long long)now);
     }
+    MHX_TSTAMP(4); // 4: the last workgroup's tail
 }
 
 // Cap of the admission threshold that follows the bytes seen (multiplicity filter, before s solid hashes exist):
@@ -684,11 +737,14 @@ hipError_t launch_cap_threshold(uint64_t *thresh, uint64_t cap, uint64_t *stats,
     return hipGetLastError();
 }
 
-hipError_t launch_tighten(const TableArgs &a, hipStream_t st)
+hipError_t launch_tighten(const TableArgs &a, uint32_t cus, hipStream_t st)
 {
-    // few, long-running workgroups: each one flushes its 2048-bin LDS histogram with global atomics
-    uint64_t blocks = a.nslots / 256 / 16;
-    if (blocks > 1024) blocks = 1024;
+    // few, long-running workgroups (see table_tighten_kernel): no more than the device has CUs, and none with less than one
+    // full round of loads
+    const uint64_t step = a.sample > 1 ? a.sample : 1;
+    uint64_t blocks = a.nslots / 256 / step / kTightenLoads;
+    const uint64_t most = (uint64_t)(cus ? cus : 256) * MHX_TIGHTEN_PER_CU;
+    if (blocks > most) blocks = most;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(table_tighten_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     return hipGetLastError();
