@@ -11,8 +11,8 @@
 //   runs      candidate k-mer starts = K bytes inside one line   -> 1 bit per position
 //   compact   groups of 8 start positions with any candidate     -> LDS work list
 //   work      each lane takes a group: 8 windows share one 28..39 byte register chunk;
-//             canonical strand by big-endian compare, MurmurHash3_x64_128(seed 42) up to its
-//             last two steps, a 32-bit necessary test against the global threshold; the few
+//             canonical strand by big-endian compare, MurmurHash3_x64_128(seed 42) up to the last
+//             multiplication, a 32-bit necessary test against the global threshold; the few
 //             windows that pass finish the hash, are checked base by base (A/C/G/T, either
 //             case -- mash skips every window holding anything else) and go into the table.
 // The base check is deferred on purpose: one window in 10^4..10^6 is ever a candidate, so
@@ -349,29 +349,46 @@ template <uint64_t C> MHX_HD uint64_t mul64c(uint64_t x, uint32_t &zero)
     return opaque64(x * C);
 #endif
 }
-// fmix64 without its last step (k ^= k >> 33 changes only the low word, see Murmur3Tail::finish)
+// fmix64 without its last two steps, the multiplication by kFmixC2 and k ^= k >> 33 (see Murmur3Tail)
+constexpr uint64_t kFmixC2 = 0xc4ceb9fe1a85ec53ull;
 MHX_HD uint64_t fmix64_head(uint64_t k, uint32_t &zero)
 {
     k = xorshift33(k);
     k = mul64c<0xff51afd7ed558ccdull>(k, zero);
-    k = xorshift33(k);
-    return mul64c<0xc4ceb9fe1a85ec53ull>(k, zero);
+    return xorshift33(k);
 }
-// The hash up to its last two steps: h = xorshift33(a) + xorshift33(b).  The high word of h is
-// hi(a) + hi(b) or that plus one, so `h <= T` implies hi(a) + hi(b) + 1 <= hi(T) + 1 (mod 2^32, see
-// admission_limit): one 32-bit add and one compare reject all but ~T / 2^64 of the windows without the
-// two shift-xors and the 64-bit add.
+// The hash up to the last multiplication of its two fmix64: with a = ka * C2 and b = kb * C2 (C2 = kFmixC2, mod 2^64)
+// the hash is h = xorshift33(a) + xorshift33(b).  Nearly every window is only tested against the threshold, h <= T,
+// and that test needs neither product.  Multiplication distributes over addition mod 2^64: s = (ka + kb) * C2 = a + b, so
+//   hi(s) = hi(a) + hi(b) + c1,  c1 = the carry of lo(a) + lo(b),
+//   hi(h) = hi(a) + hi(b) + c2,  c2 = the carry of the two shift-xored low words (xorshift33 leaves the high words alone),
+// and hi(h) is one of hi(s) - 1, hi(s), hi(s) + 1 (mod 2^32).  h <= T gives hi(h) <= hi(T), hence
+//   (hi(s) + 1) mod 2^32 <= hi(T) + 2
+// as long as the right side does not wrap; from hi(T) = 0xFFFFFFFD on the test says nothing and admission_limit
+// saturates.  That is a necessary condition of h <= T for one 64-bit add, the high word of ONE multiplication, one add
+// and one compare (5 instructions where the two whole products and an add of their high words took 9); it lets through
+// (hi(T) + 3) / 2^32 of the windows where the exact test passes T / 2^64 of them.  Only those few do the two
+// multiplications, the shift-xors and the 64-bit add (finish).  32-bit hashes (k <= 16) are tested by their exact low
+// word, which needs both products whole: low32.
 struct Murmur3Tail {
-    uint64_t a, b;
-    MHX_HD uint64_t finish() const { return xorshift33(a) + xorshift33(b); }
-    MHX_HD uint32_t low32() const { return (uint32_t)xorshift33(a) + (uint32_t)xorshift33(b); } // 32-bit hashes (k <= 16)
-    MHX_HD uint32_t high_bound() const { return (uint32_t)(a >> 32) + (uint32_t)(b >> 32) + 1u; }
+    uint64_t ka, kb;
+    MHX_HD uint64_t finish() const
+    {
+        uint32_t zero = 0; // see mul64c
+        return xorshift33(mul64c<kFmixC2>(ka, zero)) + xorshift33(mul64c<kFmixC2>(kb, zero));
+    }
+    MHX_HD uint32_t low32() const // 32-bit hashes (k <= 16)
+    {
+        uint32_t zero = 0;
+        return (uint32_t)xorshift33(mul64c<kFmixC2>(ka, zero)) + (uint32_t)xorshift33(mul64c<kFmixC2>(kb, zero));
+    }
+    MHX_HD uint32_t high_bound() const { return (uint32_t)(((ka + kb) * kFmixC2) >> 32) + 1u; }
 };
 // largest value of Murmur3Tail::high_bound() a hash <= T can have
 MHX_HD uint32_t admission_limit(uint64_t T)
 {
     const uint32_t th = (uint32_t)(T >> 32);
-    return th == 0xFFFFFFFFu ? th : th + 1u;
+    return th >= 0xFFFFFFFDu ? 0xFFFFFFFFu : th + 2u;
 }
 // h ^ k ^ K (the length K fits the low word).  h is made opaque before it is split: left to see that only the halves of
 // h are used, the compiler takes the times5_plus in front apart as well and pays two v_mov per window for it.
@@ -416,8 +433,12 @@ template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
         h1 ^= (uint64_t)K;
     }
     h1 += h2; h2 += h1;
-    const uint64_t a = fmix64_head(h1, zero), b = fmix64_head(h2, zero);
-    return Murmur3Tail{a, b};
+    uint64_t ka = fmix64_head(h1, zero), kb = fmix64_head(h2, zero);
+    // 64-bit hashes add the two (Murmur3Tail::high_bound).  The shift-xor's make64 is an addition to the compiler (see rotated()),
+    // which reassociates it with that sum -- two v_mov and a second 64-bit add per window in the queue form; opaque, each
+    // is a register pair and the sum one v_lshl_add_u64.  32-bit hashes never add them and keep the code they had.
+    if (K > 16) { ka = opaque64(ka); kb = opaque64(kb); }
+    return Murmur3Tail{ka, kb};
 }
 template <int K> MHX_HD uint64_t murmur3_h1(const uint32_t (&w)[8]) { return murmur3_core<K>(w).finish(); }
 
@@ -826,14 +847,42 @@ template <int K> struct GroupGeom {
     static constexpr int ND = (NB + 3) / 4;   // dwords loaded
 };
 
+// complement4 of a group's dwords without the index shift: v & 0x06060606 (bits 1..2 of every byte where they stand; the
+// case bit is not among them, so the raw bytes do) already tells 'A','C','T','G' apart, as the even selectors 0, 2, 4, 6
+// of v_perm_b32's EIGHT-byte table: {'T', -, 'G', -} in the low dword, {'A', -, 'C', -} in the high one.  v_and + v_perm
+// where base_index + perm_lut take v_lshrrev + v_and + v_perm, and the same byte for every input byte.  The two halves of
+// the table differ and a VOP3 instruction of gfx950 reads one scalar operand, so the low half lives in a VGPR for the
+// whole hash loop (opaque, or the compiler folds it back into a literal and a v_mov in front of every v_perm).
+constexpr uint32_t kLutComp8Lo = 0x00470054u, kLutComp8Hi = 0x00430041u;
+MHX_HD uint32_t complement_lut_lo()
+{
+    uint32_t lo = kLutComp8Lo;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(lo));
+#endif
+    return lo;
+}
+MHX_HD uint32_t complement4_raw(uint32_t v, uint32_t lut_lo)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(kLutComp8Hi, lut_lo, v & 0x06060606u);
+#else // the same look-up byte by byte: selectors 0..3 take the low dword's bytes, 4..7 the high one's
+    const uint64_t lut = ((uint64_t)kLutComp8Hi << 32) | lut_lo;
+    uint32_t o = 0;
+    for (int i = 0; i < 4; ++i) o |= (uint32_t)((lut >> (8 * ((v >> (8 * i)) & 6u))) & 0xFFu) << (8 * i);
+    return o;
+#endif
+}
+
 // The four views of a group's chunk that canonical_words takes (one dword of zero padding behind each)
 template <int ND>
 MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint32_t (&R)[ND + 1], uint32_t (&Wr)[ND + 1], uint32_t (&Cc)[ND + 1])
 {
+    const uint32_t lut_lo = complement_lut_lo();
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
         U[d] = src[d] & 0xDFDFDFDFu; // fold case: mash upper-cases before hashing
-        Cc[d] = complement4(U[d]);
+        Cc[d] = complement4_raw(src[d], lut_lo);
     }
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
@@ -876,13 +925,14 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
         uint32_t w[8];                                                                        \
         canonical_words<K, J, ND>(U, R, Wr, Cc, w);                                           \
         const Murmur3Tail tail = murmur3_core<K>(w);                                          \
-        /* necessary condition of h <= T, one add + one compare (32-bit hashes: the exact low word) */ \
-        const bool candidate = kHash32 ? tail.low32() <= (uint32_t)T : tail.high_bound() <= limit; \
+        /* necessary condition of h <= T, see Murmur3Tail (32-bit hashes: the exact low word) */ \
+        const uint32_t low = kHash32 ? tail.low32() : 0u;                                     \
+        const bool candidate = kHash32 ? low <= (uint32_t)T : tail.high_bound() <= limit;     \
         if (MHX_UNLIKELY(candidate)) {                                                        \
             if constexpr (QUEUE) {                                                            \
                 if ((vm >> J) & 1u) cand(vm >> 8, J);                                         \
             } else {                                                                          \
-                const uint64_t h = kHash32 ? (uint64_t)tail.low32() : tail.finish();          \
+                const uint64_t h = kHash32 ? (uint64_t)low : tail.finish();                   \
                 if (((vm >> J) & 1u) && h <= T && window_is_acgt<K, J, ND>(U)) { ins(h); ++ninserted; } \
             }                                                                                 \
         }                                                                                     \
