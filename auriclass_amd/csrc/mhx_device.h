@@ -84,6 +84,9 @@ struct ScreenArgs {
 hipError_t launch_screen_build(const ScreenArgs &a, hipStream_t st);  // vacates the table, inserts every reference hash, sets T_screen, then clears as launch_screen_clear
 hipError_t launch_screen_clear(const ScreenArgs &a, uint32_t *tickets, uint32_t ntickets, uint32_t *need_lookback, hipStream_t st); // counters to zero, keys kept
 hipError_t launch_screen_tally(const ScreenArgs &a, hipStream_t st);
+// winner-take-all: win [nslots + 1] winner words at kScreenNobody, prio [nr] (screen_priorities), maxkey the occurrences of 2^64-1
+hipError_t launch_screen_winner(const ScreenArgs &a, uint32_t *win, const uint32_t *prio, uint64_t maxkey, hipStream_t st);
+hipError_t launch_screen_tally_winner(const ScreenArgs &a, const uint32_t *win, const uint32_t *prio, hipStream_t st);
 
 // sharded path: the other ranks' gathered partial results go into this rank's candidate table (slab_insert_kernel)
 constexpr uint32_t kMaxMergeRanks = 64; // ranks per launch (more: several launches)

@@ -1537,6 +1537,7 @@ struct mhx_screener {
     uint32_t nr = 0, stride = 0, s_ref = 0;
     DevArray<uint64_t> d_rows;
     DevArray<uint32_t> d_len, d_counts, d_res; // d_res: shared[nr] | median[nr]
+    DevArray<uint32_t> d_win, d_prio;          // winner-take-all (mhx_screen.h): win[nslots + 1], prio[nr]; allocated by the first winner finish
 };
 
 static ScreenArgs screen_args(mhx_screener *sc)
@@ -1707,7 +1708,35 @@ void sketcher_set_follower(mhx_sketcher *sk, mhx_sketcher *follower)
     if (sk) sk->follower = follower;
 }
 
-static int screener_finish_impl(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
+// Winner-take-all behind the plain tally, which has just been launched: its shared[] comes to the host and becomes the
+// priority order, the winner words go back to "nobody" (the counts have changed since the last call), every entry claims
+// its key, and the tally runs again in its winner form into the same result buffers.
+static int screener_winner_passes(mhx_screener *sc, const uint64_t *ref_length, uint64_t maxkey)
+{
+    mhx_sketcher *p = sc->probe.get();
+    const uint32_t nr = sc->nr;
+    std::vector<uint32_t> shared0(nr), len(nr), prio(nr);
+    HIPCHK(hipMemcpyAsync(shared0.data(), sc->d_res, (size_t)nr * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipMemcpyAsync(len.data(), sc->d_len, (size_t)nr * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    screen_priorities(shared0.data(), len.data(), ref_length, nr, prio.data());
+    if (!sc->d_win.cap()) {
+        hipError_t e = sc->d_win.grow(p->nslots + 1);
+        if (e == hipSuccess) e = sc->d_prio.grow(nr);
+        if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the winner words of the screener: %s", hipGetErrorString(e));
+    }
+    HIPCHK(hipMemcpyAsync(sc->d_prio, prio.data(), (size_t)nr * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
+    static_assert(kScreenNobody == 0, "the winner words are vacated by a memset");
+    HIPCHK(hipMemsetAsync(sc->d_win, 0, (size_t)(p->nslots + 1) * sizeof(uint32_t), g.stream));
+    const ScreenArgs a = screen_args(sc);
+    HIPCHK(launch_screen_winner(a, sc->d_win, sc->d_prio, maxkey, g.stream));
+    HIPCHK(launch_screen_tally_winner(a, sc->d_win, sc->d_prio, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream)); // (prio is free again)
+    return MHX_OK;
+}
+
+static int screener_finish_impl(mhx_screener *sc, bool winner, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
+                                uint32_t *counts)
 {
     clear_error();
     int rc = require_engine();
@@ -1724,6 +1753,10 @@ static int screener_finish_impl(mhx_screener *sc, uint32_t *shared, uint32_t *me
     if (st[kStatFlags] & kFlagCountWrap) return fail(MHX_E_CAPACITY, "a multiplicity counter of the screen table reached its limit");
     if (sc->nr) {
         HIPCHK(launch_screen_tally(screen_args(sc), g.stream));
+        if (winner) {
+            rc = screener_winner_passes(sc, ref_length, st[kStatMaxKey]);
+            if (rc) return rc;
+        }
         std::vector<uint32_t> res(2 * (size_t)sc->nr);
         HIPCHK(hipMemcpyAsync(res.data(), sc->d_res, res.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
         if (counts) HIPCHK(hipMemcpyAsync(counts, sc->d_counts, (size_t)sc->nr * sc->stride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
@@ -1746,11 +1779,23 @@ static int screener_finish_impl(mhx_screener *sc, uint32_t *shared, uint32_t *me
 extern "C" int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
 {
     try {
-        return screener_finish_impl(sc, shared, median, set_size, counts);
+        return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts);
     } catch (const std::bad_alloc &) {
         return fail(MHX_E_INTERNAL, "mhx_screener_finish: out of host memory");
     } catch (const std::exception &e) {
         return fail(MHX_E_INTERNAL, "mhx_screener_finish: %s", e.what());
+    }
+}
+
+extern "C" int mhx_screener_finish_winner(mhx_screener *sc, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
+                                          uint32_t *counts)
+{
+    try {
+        return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: %s", e.what());
     }
 }
 

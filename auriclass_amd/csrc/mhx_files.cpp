@@ -1425,15 +1425,23 @@ static int mhx_dist_files_impl(const char *ref_msh, const char *const *qry_msh, 
 // `mash screen REF.msh reads...`: the reference sketches become a screen table on the device (mhx_screen.h), the read set
 // goes through the ingest of a reads-mode sketch -- with the reference file's k and sketch size and m = 1, which is the
 // bottom-s sketch mash keeps beside the counting for the set size -- and the screener's prober sees every span on its
-// way (sketch_read_set).  Tally on the device, columns on the host.
+// way (sketch_read_set).  Tally on the device (opts->winner: winner-take-all), columns and the -i / -v filters on the host.
 struct ScreenerDestroy { void operator()(mhx_screener *sc) const { mhx_screener_destroy(sc); } };
 
-static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
-                                 double *set_size_out)
+static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
+                                 size_t cap, size_t *need, double *set_size_out)
 {
     clear_error();
     int rc = require_engine();
     if (rc) return rc;
+    bool winner = false;
+    double min_identity = -1.0, max_p = 1.0;
+    if (opts) {
+        if (opts->struct_size != sizeof(mhx_screen_opts)) return fail(MHX_E_ARG, "screen: mhx_screen_opts of %u bytes, expected %zu", opts->struct_size, sizeof(mhx_screen_opts));
+        if (!(opts->min_identity <= 1.0)) return fail(MHX_E_ARG, "screen: minimum identity must be at most 1");
+        if (!(opts->max_p_value >= 0.0 && opts->max_p_value <= 1.0)) return fail(MHX_E_ARG, "screen: maximum p-value must be within [0, 1]");
+        winner = opts->winner != 0; min_identity = opts->min_identity; max_p = opts->max_p_value;
+    }
     if (!ref_msh || !paths || n_paths <= 0) return fail(MHX_E_ARG, "screen: a reference sketch path and at least one read file required");
     for (int i = 0; i < n_paths; ++i)
         if (!paths[i]) return fail(MHX_E_ARG, "screen: read file path %d is null", i);
@@ -1469,27 +1477,42 @@ static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, 
     // (no record of k bases at all: mash warns and prints its rows; the sketch is empty and the set size 0)
     const double set_size = set_size_estimate(k, mix.hashes.data(), mix.hashes.size());
     std::vector<uint32_t> shared(nr), median(nr);
-    rc = mhx_screener_finish(scr.get(), shared.data(), median.data(), nullptr, nullptr);
+    if (winner) {
+        std::vector<uint64_t> length(nr);
+        for (uint32_t i = 0; i < nr; ++i) length[i] = R.refs[i].length;
+        rc = mhx_screener_finish_winner(scr.get(), length.data(), shared.data(), median.data(), nullptr, nullptr);
+    } else {
+        rc = mhx_screener_finish(scr.get(), shared.data(), median.data(), nullptr, nullptr);
+    }
     if (rc) return rc;
     std::string text;
-    for (uint32_t i = 0; i < nr; ++i)
-        text += fmt_g(mhx_screen_identity(shared[i], len[i], k)) + "\t" + std::to_string(shared[i]) + "/" + std::to_string(len[i]) + "\t" +
-                std::to_string(median[i]) + "\t" + fmt_g(mhx_screen_p_value(shared[i], len[i], set_size, k)) + "\t" + R.refs[i].name + "\t" +
-                R.refs[i].comment + "\n";
+    for (uint32_t i = 0; i < nr; ++i) {
+        const double identity = mhx_screen_identity(shared[i], len[i], k), p = mhx_screen_p_value(shared[i], len[i], set_size, k);
+        // mash screen -i / -v: -i 0 keeps identities above zero only, -i -1 everything
+        if (!(min_identity == 0.0 ? identity > 0.0 : identity >= min_identity) || !(p <= max_p)) continue;
+        text += fmt_g(identity) + "\t" + std::to_string(shared[i]) + "/" + std::to_string(len[i]) + "\t" + std::to_string(median[i]) + "\t" +
+                fmt_g(p) + "\t" + R.refs[i].name + "\t" + R.refs[i].comment + "\n";
+    }
     if (set_size_out) *set_size_out = set_size;
     return put_text(text, stdout_buf, cap, need);
 }
 
-extern "C" int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
-                                double *set_size_out)
+extern "C" int mhx_screen_files_opts(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
+                                     size_t cap, size_t *need, double *set_size_out)
 {
     try {
-        return mhx_screen_files_impl(ref_msh, paths, n_paths, stdout_buf, cap, need, set_size_out);
+        return mhx_screen_files_impl(ref_msh, paths, n_paths, opts, stdout_buf, cap, need, set_size_out);
     } catch (const std::bad_alloc &) {
         return fail(MHX_E_INTERNAL, "mhx_screen_files: out of host memory");
     } catch (const std::exception &e) {
         return fail(MHX_E_INTERNAL, "mhx_screen_files: %s", e.what());
     }
+}
+
+extern "C" int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
+                                double *set_size_out)
+{
+    return mhx_screen_files_opts(ref_msh, paths, n_paths, nullptr, stdout_buf, cap, need, set_size_out);
 }
 
 extern "C" int mhx_msh_write(const char *path, int k, uint32_t s, uint32_t n_refs, const char *const *names,

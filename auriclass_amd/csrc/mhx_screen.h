@@ -1,7 +1,8 @@
 // mhx_screen.h -- the rules of the containment screen (`mash screen`) that are more than a line: geometry of the screen
 // table, the walk of a probe sequence, the build step that claims a slot, the counter that must not wrap and the selection
-// of a reference's median multiplicity.  Host+device functions: the kernels (mhx_kernels.hip) and the CPU emulator
-// (tests/emul/screen_emul.cpp) run these very functions.
+// of a reference's median multiplicity, and the winner-take-all form of the tally (`-w`: priority order, claim, "won").
+// Host+device functions: the kernels (mhx_kernels.hip) and the CPU emulators (tests/emul/screen_emul.cpp,
+// tests/emul/screen_winner_emul.cpp) run these very functions.
 //
 // The screen table is the candidate table's sibling: keys u64[2^n], vacant = 2^64-1 (kEmptyKey), cnts u32[2^n], slot =
 // hash & mask, linear probing.  It is built once from the reference rows (duplicates across references collapse into one
@@ -9,6 +10,9 @@
 // changes nothing.  The hash value 2^64-1 cannot be a key; its occurrences are counted in a word of their own.
 #pragma once
 #include <stdint.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "mhx_device_consts.h"
 #include "mhx_hd.h"
@@ -84,6 +88,64 @@ MHX_HD uint32_t screen_select_step(const uint32_t *hist, uint32_t &rank)
     uint32_t d = 0;
     while (d + 1 < (uint32_t)kScreenSelectBins && rank >= hist[d]) { rank -= hist[d]; ++d; }
     return d;
+}
+
+// Winner-take-all (`mash screen -w`): every hash found in the reads is credited to ONE of the references that hold it, the
+// best by (score, genome length, lowest index), score = the plain screen's shared / n.  The order of the scores is the
+// order of the exact ratios (pow(x, 1 / k) is monotone), so it is decided in integers: shared_a * n_b against shared_b *
+// n_a, both below 2^63 for lists of up to 2^31 entries.  A reference without entries holds no hash and is ranked last.
+// The order becomes one word per reference, the priority: unique, greater is better, kScreenNobody (0) is nobody's.
+// A winner word per table slot (win[nslots], and win[nslots] itself for the hash value 2^64-1, which is not a key) starts
+// at kScreenNobody; every entry whose key was seen raises the key's word to its reference's priority (claim); the tally
+// then keeps a count only where the word equals the reference's priority (won).
+constexpr uint32_t kScreenNobody = 0;
+
+// a ranks before b (strictly).  length: genome lengths, nullptr = all equal.
+inline bool screen_ranks_before(const uint32_t *shared0, const uint32_t *len, const uint64_t *length, uint32_t a, uint32_t b)
+{
+    if ((len[a] == 0) != (len[b] == 0)) return len[a] != 0;
+    const uint64_t sa = (uint64_t)shared0[a] * len[b], sb = (uint64_t)shared0[b] * len[a];
+    if (sa != sb) return sa > sb;
+    if (length && length[a] != length[b]) return length[a] > length[b];
+    return a < b;
+}
+
+// prio[nr]: nr for the best reference down to 1 for the last.  Host only (the plain tally's shared0 is on the host anyway).
+inline void screen_priorities(const uint32_t *shared0, const uint32_t *len, const uint64_t *length, uint32_t nr, uint32_t *prio)
+{
+    std::vector<uint32_t> order(nr);
+    for (uint32_t i = 0; i < nr; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return screen_ranks_before(shared0, len, length, a, b); });
+    for (uint32_t at = 0; at < nr; ++at) prio[order[at]] = nr - at;
+}
+
+// the winner word of hash h: a slot, mask + 1 for the hash value 2^64-1, kScreenAbsent when h is not a key
+MHX_HD uint64_t screen_winner_word(const uint64_t *keys, uint64_t mask, uint64_t h)
+{
+    return h == kEmptyKey ? mask + 1 : screen_find(keys, mask, h);
+}
+
+// Claim: the entry h of a reference with priority prio.  raise(word, prio) lifts win[word] to at least prio -- an
+// atomicMax on the device.
+template <class Raise>
+MHX_HD void screen_claim(const uint64_t *keys, const uint32_t *cnts, uint64_t mask, uint64_t h, uint64_t maxkey, uint32_t prio, Raise &raise)
+{
+    const uint64_t w = screen_winner_word(keys, mask, h);
+    if (w == kScreenAbsent) return;
+    if (w > mask ? maxkey != 0 : cnts[w] != 0u) raise(w, prio);
+}
+
+MHX_HD bool screen_won(uint32_t winner_word, uint32_t prio) { return winner_word == prio; }
+
+// count of hash h as the winner tally reads it for the reference with priority prio: screen_count_of where that
+// reference won h, 0 elsewhere
+MHX_HD uint32_t screen_count_won(const uint64_t *keys, const uint32_t *cnts, const uint32_t *win, uint64_t mask, uint64_t h,
+                                 uint64_t maxkey, uint32_t prio)
+{
+    const uint64_t w = screen_winner_word(keys, mask, h);
+    if (w == kScreenAbsent || !screen_won(win[w], prio)) return 0u;
+    if (w > mask) return maxkey < kScreenCountLimit ? (uint32_t)maxkey : kScreenCountLimit;
+    return cnts[w];
 }
 
 } // namespace mhx

@@ -143,6 +143,10 @@ def load() -> ctypes.CDLL:
         L.mhx_screen_identity.restype = c.c_double
         L.mhx_screen_p_value.argtypes = [c.c_uint64, c.c_uint64, c.c_double, c.c_int]
         L.mhx_screen_p_value.restype = c.c_double
+    if hasattr(L, "mhx_screener_finish_winner"):   # (or older than the winner-take-all form of the screen)
+        L.mhx_screener_finish_winner.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_double), c.c_void_p]
+        L.mhx_screen_files_opts.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ScreenOpts), c.c_char_p, c.c_size_t,
+                                            c.POINTER(c.c_size_t), c.POINTER(c.c_double)]
     _lib = L
     return L
 
@@ -229,15 +233,28 @@ def dist_files_multi(ref_msh, qry_paths: Sequence) -> str:
     return _text_call(load().mhx_dist_files_multi, os.fsencode(str(ref_msh)), arr, len(paths), guess=max(1, len(paths)) << 16)
 
 
-def screen_files(ref_msh, paths: Sequence) -> Tuple[str, float]:
-    """`mash screen REF.msh paths...` -> (stdout text, estimated set size of the read set): one row per reference,
-    "identity\\tshared/n\\tmedian\\tp\\tname\\tcomment".  All paths form one read set."""
+class ScreenOpts(ctypes.Structure):
+    """mhx_screen_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("winner", ctypes.c_int32), ("min_identity", ctypes.c_double),
+                ("max_p_value", ctypes.c_double)]
+
+
+def screen_files(ref_msh, paths: Sequence, winner: bool = False, min_identity: float = -1.0, max_p_value: float = 1.0) -> Tuple[str, float]:
+    """`mash screen [-w] [-i min_identity] [-v max_p_value] REF.msh paths...` -> (stdout text, estimated set size of the
+    read set): one row per reference, "identity\\tshared/n\\tmedian\\tp\\tname\\tcomment".  All paths form one read set.
+    winner: winner-take-all, every hash credited to the best reference that holds it (genome lengths from the reference
+    file).  The defaults print every row (mash's own -i default is 0: rows with identity > 0)."""
     init()
     files = [os.fsencode(str(p)) for p in paths]
     arr = (ctypes.c_char_p * len(files))(*files)
     size = ctypes.c_double(0.0)
-    text = _text_call(lambda buf, cap, need: load().mhx_screen_files(os.fsencode(str(ref_msh)), arr, len(files), buf, cap, need,
-                                                                     ctypes.byref(size)))
+    if not winner and min_identity == -1.0 and max_p_value == 1.0:
+        text = _text_call(lambda buf, cap, need: load().mhx_screen_files(os.fsencode(str(ref_msh)), arr, len(files), buf, cap, need,
+                                                                         ctypes.byref(size)))
+        return text, size.value
+    opts = ScreenOpts(ctypes.sizeof(ScreenOpts), int(bool(winner)), float(min_identity), float(max_p_value))
+    text = _text_call(lambda buf, cap, need: load().mhx_screen_files_opts(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts),
+                                                                          buf, cap, need, ctypes.byref(size)))
     return text, size.value
 
 
@@ -484,13 +501,24 @@ class Screener:
         _check(load().mhx_screener_sync(self._h))
         self._keep.clear()
 
-    def finish(self, with_counts: bool = False):
+    def finish(self, with_counts: bool = False, winner: bool = False, ref_length=None):
+        """winner: winner-take-all (`mash screen -w`, mhx_screener_finish_winner) -- every hash found is credited to the
+        best reference that holds it; ref_length: [nr] genome lengths that break ties of the score (None: all equal)."""
         shared = np.zeros(self.nr, dtype=np.uint32)
         median = np.zeros(self.nr, dtype=np.uint32)
         counts = np.zeros((self.nr, self.stride), dtype=np.uint32) if with_counts else None
         size = ctypes.c_double(0.0)
-        _check(load().mhx_screener_finish(self._h, shared.ctypes.data, median.ctypes.data, ctypes.byref(size),
-                                          counts.ctypes.data if with_counts else None))
+        if winner:
+            length = None
+            if ref_length is not None:
+                length = np.ascontiguousarray(ref_length, dtype=np.uint64)
+                assert length.shape == (self.nr,)
+            _check(load().mhx_screener_finish_winner(self._h, length.ctypes.data if length is not None else None, shared.ctypes.data,
+                                                     median.ctypes.data, ctypes.byref(size), counts.ctypes.data if with_counts else None))
+        else:
+            assert ref_length is None, "ref_length is read by the winner-take-all form only"
+            _check(load().mhx_screener_finish(self._h, shared.ctypes.data, median.ctypes.data, ctypes.byref(size),
+                                              counts.ctypes.data if with_counts else None))
         self._keep.clear()
         return shared, median, size.value, counts
 

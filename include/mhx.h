@@ -95,7 +95,7 @@ int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, s
 int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry,
                          char *stdout_buf, size_t cap, size_t *need);
 
-/* `mash screen REF.msh reads...` stdout (Mash 2.x defaults -i 0 -v 1, nucleotides, no -w): one row per reference of the
+/* `mash screen REF.msh reads...` stdout (Mash 2.x, nucleotides, every row printed; -w, -i and -v: mhx_screen_files_opts): one row per reference of the
  * sketch file, in its order, "identity\tshared/n\tmedian\tp\tname\tcomment\n".  All paths form ONE read set (FASTQ or
  * FASTA, plain or gzip / BGZF), read by the ingest of mhx_sketch_files(..., reads = 1, ...): every route, the record check
  * and the hand-over to the host record parser included (mhx_last_fastq_route reports this call's route too).
@@ -111,6 +111,24 @@ int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_
  * rule is Mash's CommandScreen restated, see DESIGN.md section 6. */
 int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
                      double *set_size_out);
+
+/* mhx_screen_files with `mash screen`'s -w, -i and -v.  opts == NULL, or {sizeof, 0, -1, 1}, is mhx_screen_files byte for
+ * byte.
+ *   winner != 0:   winner-take-all (-w, see mhx_screener_finish_winner); the genome lengths are the reference file's.
+ *   min_identity:  -i.  A row is printed when identity >= min_identity; 0 means identity > 0 only, -1 every row.  Mash's
+ *                  default is 0, ours stays -1.
+ *   max_p_value:   -v.  A row is printed when p <= max_p_value.
+ * Both filters compare the doubles of mhx_screen_identity / mhx_screen_p_value on the host; under -w they see the winner
+ * rows.  MHX_E_ARG: struct_size != sizeof(mhx_screen_opts), min_identity > 1 or max_p_value outside [0, 1] (or not a
+ * number). */
+typedef struct mhx_screen_opts {
+    uint32_t struct_size; /* sizeof(mhx_screen_opts) */
+    int32_t winner;
+    double min_identity;
+    double max_p_value;
+} mhx_screen_opts;
+int mhx_screen_files_opts(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
+                          size_t cap, size_t *need, double *set_size_out);
 
 /* `mash bounds -k K -p P` stdout. */
 int mhx_bounds(int k, double p, char *buf, size_t cap, size_t *need);
@@ -274,6 +292,18 @@ int mhx_screener_sync(mhx_screener *sc);
  * beyond ref_len[i] are 0).  MHX_E_CAPACITY when a multiplicity reached the counter's limit (0xF0000000).  May be called
  * again after further pushes. */
 int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts);
+/* mhx_screener_finish under winner-take-all (`mash screen -w`): every hash found in the reads is credited to ONE of the
+ * references that hold it.  With shared0[i] the plain shared of reference i and n[i] = ref_len[i], the winner of a hash is
+ * the holder with the greatest shared0 / n (compared exactly, as shared0[a] * n[b] against shared0[b] * n[a]: the order of
+ * the identities, since pow(x, 1 / k) is monotone); among equals the greatest ref_length (genome length; host pointer
+ * [nr], NULL = all equal); among equals again the LOWEST INDEX -- Mash walks an unordered_set there and leaves the choice
+ * open; this one is ours.  shared[i] = hashes reference i won, median[i] = element [shared / 2] of their ascending
+ * multiplicities, counts = the multiplicity where reference i won the entry, 0 elsewhere.  The sum of shared[] is the
+ * number of distinct reference hashes found in the reads.  Runs the plain tally, ranks on the host, then a winner pass and
+ * the winner tally on the device.  May be called again after further pushes and may alternate with mhx_screener_finish in
+ * any order: neither changes what the other reports. */
+int mhx_screener_finish_winner(mhx_screener *sc, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
+                               uint32_t *counts);
 /* scalar pieces of the screen row (host), Mash's estimateIdentity() and pValueWithin():
  * identity = 1 if shared == n, 0 if shared == 0, else pow(shared / n, 1 / k);
  * p = 1 if shared == 0, else P[Binomial(n, r) >= shared] with r = 1 / (1 + 4^k / floor(set_size)). */
