@@ -1,10 +1,9 @@
-// mhx_device.h -- shared between the HIP kernels (mhx_kernels.hip) and the host
-// engine (mhx_engine.cpp).  Internal; the public surface is include/mhx.h.
+// mhx_device.h -- argument structs and launchers shared between the HIP kernel files (mhx_*.hip) and the host
+// engine (mhx_engine*.cpp, mhx_files.cpp).  Internal; the public surface is include/mhx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mhx_device_consts.h"
-#include "mhx_dist.h"
 
 namespace mhx {
 
@@ -49,8 +48,9 @@ struct TableArgs {
     uint32_t verify_ntiles;    // ... and the number of tiles of that push
 };
 
-// launchers (mhx_kernels.hip)
+// the sketch tile kernel (mhx_sketch.hip)
 hipError_t launch_hash(int k, int fmt, const HashArgs &a, hipStream_t st);
+// passes over the candidate table (mhx_table.hip)
 hipError_t launch_tighten(const TableArgs &a, uint32_t cus, hipStream_t st); // cus: compute units of the device (bounds the grid)
 hipError_t launch_reset(const TableArgs &a, uint64_t t_init, uint32_t *tickets, uint32_t ntickets, uint32_t *out_n, hipStream_t st);
 hipError_t launch_cap_threshold(uint64_t *thresh, uint64_t cap, uint64_t *stats, hipStream_t st);
@@ -61,13 +61,14 @@ hipError_t launch_phase_verify(const uint8_t *rec, uint32_t ntiles, uint64_t *st
 // fastq_check_scratch_bytes(begin, end)
 size_t fastq_check_scratch_bytes(uint64_t begin, uint64_t end);
 hipError_t launch_fastq_check(const uint8_t *base, uint64_t begin, uint64_t end, void *scratch, uint64_t *stats, hipStream_t st);
+// (mhx_table.hip)
 hipError_t launch_extract(const TableArgs &a, uint64_t limit, uint32_t min_count, uint64_t *out_keys,
                           uint32_t *out_cnts, uint32_t cap, uint32_t *out_n, uint64_t *flags_out, const uint64_t *limit_dev,
                           uint64_t *limit_out, uint64_t *maxkey_out, hipStream_t st, uint32_t *order_cursor = nullptr, uint32_t order_log2 = 0,
                           uint64_t *hdr_dev = nullptr, uint64_t *hdr_host = nullptr, uint32_t *ticket = nullptr,
                           uint64_t *occ_out = nullptr, uint32_t nhdr = 4, uint64_t *hdr_copy = nullptr);
 
-// containment screen (mhx_screen.h): the screen table of a reference set, and what the reads left in it
+// containment screen (rules: mhx_screen.h, kernels: mhx_screen.hip): the screen table of a reference set, and what the reads left in it
 struct ScreenArgs {
     const uint64_t *rows;   // [nr][stride] reference hash lists (ascending, unique within a row)
     const uint32_t *len;    // [nr] valid entries per row
@@ -88,7 +89,7 @@ hipError_t launch_screen_tally(const ScreenArgs &a, hipStream_t st);
 hipError_t launch_screen_winner(const ScreenArgs &a, uint32_t *win, const uint32_t *prio, uint64_t maxkey, hipStream_t st);
 hipError_t launch_screen_tally_winner(const ScreenArgs &a, const uint32_t *win, const uint32_t *prio, hipStream_t st);
 
-// sharded path: the other ranks' gathered partial results go into this rank's candidate table (slab_insert_kernel)
+// sharded path: the other ranks' gathered partial results go into this rank's candidate table (slab_insert_kernel, mhx_merge.hip)
 constexpr uint32_t kMaxMergeRanks = 64; // ranks per launch (more: several launches)
 struct SlabMergeArgs {
     const uint64_t *slabs;  // device: nranks slabs of slab_words 8-byte words each: [hdr_words of header] hashes[cap] | counts u32[cap]
@@ -128,7 +129,7 @@ struct MergeArgs {
     uint32_t *sc_cnts;          // [nbins * region]
 };
 hipError_t launch_merge_bins(const MergeArgs &a, uint64_t max_n, uint64_t *out, uint32_t out_cap, hipStream_t st);
-bool hash_k_supported(int k);
+bool hash_k_supported(int k); // (mhx_sketch.hip)
 
 // FASTA on the device (mhx_fasta.hip): raw file bytes -> dense sequence stream + record separator positions.
 // ws: fasta_workspace_bytes(n) bytes; after the launch *(uint64_t *)(ws + o_off + 8 * ntiles) is the stream size,
@@ -148,10 +149,11 @@ struct DistArgs {
     double *dist;
     uint32_t out_stride, out_off;
 };
-hipError_t launch_dist_pairs(const DistArgs &a, hipStream_t st);
+hipError_t launch_dist_pairs(const DistArgs &a, hipStream_t st); // (mhx_dist.hip, like launch_dist_ranges below)
 
 // all-vs-refs fast path (nr <= 32): value-range partition + LDS hash probe.  kDistRanges, kDistTableSlots, kDistSegs and
-// the geometry rule (dist_windows) are in mhx_dist.h, with the logic the kernels share with the CPU emulator.
+// the geometry rule (dist_windows) are in mhx_dist.h, with the logic the kernels share with the CPU emulator; this header
+// does not include it (mhx_dist.hip and mhx_engine_dist.cpp do), so that a change there rebuilds those two alone.
 #ifndef MHX_DIST_QCHUNKS
 #define MHX_DIST_QCHUNKS 4
 #endif

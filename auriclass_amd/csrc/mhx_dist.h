@@ -1,7 +1,7 @@
 // mhx_dist.h -- the logic of the all-vs-refs distance path that does not depend on how a GPU runs it, as host+device
 // functions: the geometry rule (how many value ranges a call gets), the range index of a value, the offset rule of the
 // split pass, the range table's probe and the spread of a reference mask into byte counters, the window totals and the
-// finish walk (window totals -> cut window -> cut range -> two-pointer rule).  The kernels in mhx_kernels.hip call these
+// finish walk (window totals -> cut window -> cut range -> two-pointer rule).  The kernels in mhx_dist.hip call these
 // functions; tests/emul/dist_emul.cpp runs the same functions sequentially over whole batches on the CPU.
 #pragma once
 #include "mhx_hd.h"

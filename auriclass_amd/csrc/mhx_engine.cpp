@@ -1,7 +1,8 @@
 // mhx_engine.cpp -- host side of libmhx: device selection, the sketcher object that
-// schedules tile launches and threshold tightening, the multi-GPU partial export and the
-// batched distance entry point.  The file-level calls that replace AuriClass's
-// `mash sketch` / `mash dist` subprocesses live in mhx_files.cpp.
+// schedules tile launches and threshold tightening, and the multi-GPU partial export and
+// merge.  Batched distances are in mhx_engine_dist.cpp, the containment screen in
+// mhx_engine_screen.cpp; the file-level calls that replace AuriClass's `mash sketch` /
+// `mash dist` subprocesses live in mhx_files.cpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -21,7 +22,7 @@
 #include "mhx_device.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
-#include "mhx_screen.h"
+#include "mhx_sketcher.h"
 
 namespace mhx {
 
@@ -104,92 +105,7 @@ extern "C" int mhx_set_profiling(int on)
 // ---- sketcher -------------------------------------------------------------------------
 constexpr uint32_t kDeviceOrderMinSketch = 8192;
 
-struct SortScratch {
-    std::vector<uint32_t> start;
-    std::vector<uint64_t> keys;
-    std::vector<uint32_t> cnts;
-};
-
-struct mhx_sketcher {
-    SortScratch sorted;            // finish() / export(): the extracted entries in hash order
-    int k = 0;
-    uint32_t s = 0, m = 1;
-    bool hash32 = false;
-    uint64_t nslots = 0;
-    uint64_t hash_max = 0;   // largest representable hash (2^64-1 or 2^32-1)
-    uint64_t t_init = 0;     // initial admission threshold (everything admitted)
-    // device
-    DevArray<uint64_t> d_keys;
-    DevArray<uint32_t> d_cnts;
-    DevArray<uint64_t> d_thresh;
-    DevArray<uint32_t> d_hist;
-    DevArray<uint64_t> d_acc;
-    DevArray<uint64_t> d_stats;   // kStatReplicas x kStatCount
-    DevArray<uint32_t> d_tickets; // one per tile launch since the last reset (kTicketWords of them)
-    uint32_t tickets_used = 0;
-    DevArray<uint32_t> d_done;    // ticket of the tighten pass
-    DevArray<uint8_t> d_phase_rec; // FASTQ: phase_record() per tile of the span being pushed (chain check)
-    DevArray<uint32_t> d_need;    // FASTQ: some tile could not find its line phase by itself -> repair pass due
-    struct Span { const void *ptr; uint64_t n; };
-    std::vector<Span> unsettled;   // FASTQ pushes whose repair question is still open (their buffers are valid until the next sync)
-    DevArray<uint64_t> d_tile_state;
-    DevArray<uint8_t> d_stage;
-    DevArray<uint64_t> d_out_keys;
-    DevArray<uint32_t> d_out_cnts;
-    DevArray<uint32_t> d_out_n;
-    uint32_t out_cap() const { return (uint32_t)std::min(d_out_keys.cap(), d_out_cnts.cap()); }
-    // sharded path: header of the shard export [n, T, flags, #(2^64-1), occupied, 0, 0, 0], accumulated on the device and
-    // handed to the pinned mirror by the extract kernel itself (the entries stay in d_out_keys / d_out_cnts)
-    DevArray<uint64_t> d_exp_hdr;
-    PinnedArray<uint64_t> h_exp_hdr;
-    uint64_t exported = 0;     // entries of the last export_begin (valid until the next push / reset)
-    bool export_valid = false;
-    bool merged = false;       // merge_slabs has added other shards' entries to the table: reset before the next push
-    bool verify_fastq = false; // file-level callers: FASTQ4 pushes also run the record check (sketcher_verify_fastq)
-    DevArray<uint64_t> d_merge_in; // staging of gathered slabs that arrive in host memory (gloo)
-    // workspace of the binned merge (mhx_merge.hip): per-bin cursors / counts / flags (kept zero between merges by the
-    // kernels), bin regions
-    DevArray<uint32_t> d_mg_small;  // [kMergeMaxBins] cursor | [kMergeMaxBins] qn | [16] flags
-    DevArray<uint64_t> d_mg_keys;
-    DevArray<uint32_t> d_mg_cnts;
-    // finish(): one device block [n, T, flags, #(2^64-1) | hashes[fin_cap] | counts[fin_cap]] and its pinned host
-    // mirror, so the result comes back in ONE copy (five separate copies cost 20-60 us of idle gap each)
-    DevArray<uint64_t> d_fin;
-    PinnedArray<uint64_t> h_fin;
-    uint32_t fin_cap = 0;
-    // large sketches: a second block, the first in (almost) hash order (launch_order_block), and its bucket counters
-    DevArray<uint64_t> d_fin_ordered;
-    DevArray<uint32_t> d_order_buckets, d_order_starts, d_order_groups;
-    uint32_t order_log2 = 0;
-    bool table_dirty = true;   // tiles have been hashed since the last EXACT tighten pass
-    bool table_sampled = false; // ... but a sampled pass has run after the last of them: T is valid and ~s' solid hashes lie below it
-    // host
-    uint64_t next_chunk_bytes = 0; // geometric schedule of the tightening phase
-    uint64_t bytes_pushed = 0;
-    uint64_t repair_next_chunk_bytes = 0; // the same two for the FASTQ repair passes: the schedule the left-out tiles would
-    uint64_t repair_bytes = 0;            // have had on their own (T is at least as low as that schedule assumes)
-    uint64_t expected_bytes = 0;
-    uint64_t admit_scale = 1;      // multiplies the initial admission budget (retries after MHX_E_CAPACITY)
-    double hash_ms = 0.0;
-    uint64_t launches = 0;
-    uint64_t last_T = 0;
-    // m > 1 only: until s hashes with count >= m exist below T the table is protected by a bound that
-    // follows the input seen so far (see push_device)
-    bool bounded = false;      // as of the last finish(): the byte-count cap has limited T at least once (m > 1)
-    bool established = false;  // as of the last finish(): a tighten pass has lowered T from solid (count >= m) entries
-    uint64_t occupied = 0;     // table occupancy reported by the last tighten pass
-    uint64_t solid = 0;        // entries <= T with count >= m reported by the last tighten pass
-    // containment screen (mhx_screener below): d_keys / d_cnts are a screen table built from reference sketches and
-    // d_thresh holds T_screen, which never moves -- a push is ONE launch of the probing kernels, no tighten pass, no stages
-    bool screen = false;
-    uint64_t screen_T = 0;     // T_screen as the host knows it (chooses the kernel form)
-    // file-level screen: the prober of a screener rides along with the sketcher the ingest feeds -- every span pushed here is
-    // pushed there too, and whatever settles this sketcher's pushes settles the follower's (sketcher_set_follower)
-    mhx_sketcher *follower = nullptr;
-};
-
 static constexpr int kMaxLaunchesPerPush = 64;
-static constexpr uint32_t kTicketWords = 4096; // tile launches between two clears of the ticket words
 #ifndef MHX_CHUNK_GROWTH
 #define MHX_CHUNK_GROWTH 16
 #endif
@@ -348,7 +264,7 @@ static int read_threshold(mhx_sketcher *sk, uint64_t *T)
     return MHX_OK;
 }
 
-// FASTQ runs in two kernel forms (mhx_kernels.hip): kernel format 2, every tile finds its line phase by itself -- no
+// FASTQ runs in two kernel forms (mhx_sketch.hip): kernel format 2, every tile finds its line phase by itself -- no
 // ticket, no wait between workgroups --, and format 1, ticket + decoupled look-back.  A push goes through format 2; tiles
 // whose lines are too long to self-synchronise (reads beyond ~2.7 kb) leave themselves out and raise a word that
 // settle() reads at the next synchronisation point; the repair pass then runs format 1 over the same span with only
@@ -369,7 +285,7 @@ static int repair_unsettled(mhx_sketcher *sk)
 }
 
 // at a synchronisation point that is not finish(): is a repair pass due for the pushes since the last one?
-static int settle(mhx_sketcher *sk)
+int mhx::settle(mhx_sketcher *sk)
 {
     if (sk->follower) {
         const int rc = settle(sk->follower);
@@ -670,7 +586,7 @@ extern "C" int mhx_sketcher_sync(mhx_sketcher *sk)
     return MHX_OK;
 }
 
-static int fetch_stats(mhx_sketcher *sk, uint64_t *sum)
+int mhx::fetch_stats(mhx_sketcher *sk, uint64_t *sum)
 {
     std::vector<uint64_t> h(kStatReplicas * kStatCount);
     HIPCHK(hipMemcpyAsync(h.data(), sk->d_stats, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
@@ -756,7 +672,7 @@ extern "C" int mhx_sketcher_threshold(mhx_sketcher *sk, uint64_t *threshold)
     return read_threshold(sk, threshold);
 }
 
-static int check_flags(uint64_t flags)
+int mhx::check_flags(uint64_t flags)
 {
     if (flags & kFlagSpinTimeout) return fail(MHX_E_INTERNAL, "device look-back timed out");
     if (flags & kFlagTableFull) return fail(MHX_E_CAPACITY, "device candidate table overflowed; recreate the sketcher with a larger expected_bytes");
@@ -1329,474 +1245,9 @@ extern "C" int mhx_merge_shard_partials(const uint64_t *hashes, const uint32_t *
     return MHX_OK;
 }
 
-// ---- batched distance ------------------------------------------------------------------
-extern "C" double mhx_last_dist_kernel_ms(void) { return g.last_dist_ms; }
-extern "C" int mhx_last_dist_fallback_blocks(void) { return g.last_dist_fallbacks; }
-extern "C" int mhx_last_dist_ranges(void) { return g.last_dist_ranges; }
-
-// Persistent device staging of the host-pointer form (one buffer, grown on demand): six hipMalloc / hipFree pairs per
-// call cost more than the kernels of an AuriClass-sized comparison (1 query x 24 references).
-static int dist_stage(size_t bytes, uint8_t **out)
-{
-    if (g.dist_in.cap() < bytes) {
-        const size_t cap = (bytes + bytes / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-        if (g.dist_in.grow(cap, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed in dist_batch (%zu bytes)", cap);
-    }
-    *out = g.dist_in;
-    return MHX_OK;
-}
-
-// q_rows / r_rows (host form only): the rows where they lie, one pointer each (q / r are then unused) -- mhx_dist_files
-// hands over the hash lists inside its pinned image of the reference sketch file instead of building padded matrices
-static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len,
-                           uint32_t nr, uint32_t stride, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist,
-                           int device_ptrs, const uint64_t *const *q_rows, const uint64_t *const *r_rows)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (nq == 0 || nr == 0) return MHX_OK;
-    if ((!q && !q_rows) || !q_len || (!r && !r_rows) || !r_len || !common || !denom) return fail(MHX_E_ARG, "null argument");
-    if (device_ptrs && (q_rows || r_rows)) return fail(MHX_E_ARG, "row pointers are a host form");
-    if (k < 1 || k > 32 || s == 0 || stride == 0) return fail(MHX_E_ARG, "bad k / s / stride");
-    const uint64_t pairs = (uint64_t)nq * nr;
-    if (pairs > 0x7FFFFFFFull) return fail(MHX_E_ARG, "too many pairs for one call");
-    DistArgs a;
-    a.nq = nq; a.nr = nr; a.stride = stride; a.s = s; a.k = k; a.out_stride = nr; a.out_off = 0;
-    uint32_t *dc = nullptr, *dd = nullptr;
-    if (device_ptrs) {
-        a.q = q; a.q_len = q_len; a.r = r; a.r_len = r_len; a.common = common; a.denom = denom; a.dist = dist;
-    } else {
-        for (uint32_t i = 0; i < nq; ++i) if (q_len[i] > stride) return fail(MHX_E_ARG, "q_len[%u] exceeds stride", i);
-        for (uint32_t i = 0; i < nr; ++i) if (r_len[i] > stride) return fail(MHX_E_ARG, "r_len[%u] exceeds stride", i);
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t bq = up((size_t)nq * stride * 8), br = up((size_t)nr * stride * 8), bql = up((size_t)nq * 4), brl = up((size_t)nr * 4), bo = up(pairs * 4);
-        uint8_t *base = nullptr;
-        rc = dist_stage(bq + br + bql + brl + 2 * bo, &base);
-        if (rc) return rc;
-        uint8_t *dq = base, *dr = dq + bq, *dql = dr + br, *drl = dql + bql;
-        dc = (uint32_t *)(drl + brl);
-        dd = (uint32_t *)(drl + brl + bo);
-        // rows that are mostly padding travel one by one (valid prefix only), full ones as one block
-        hipError_t ce = hipSuccess;
-        auto rows = [&](uint8_t *dst, const uint64_t *src, const uint32_t *len, uint32_t n, const uint64_t *const *ptrs) {
-            if (ptrs) { // every row from its own place
-                for (uint32_t i = 0; i < n && ce == hipSuccess; ++i)
-                    if (len[i]) ce = hipMemcpyAsync(dst + (size_t)i * stride * 8, ptrs[i], (size_t)len[i] * 8, hipMemcpyHostToDevice, g.stream);
-                return;
-            }
-            uint64_t valid = 0;
-            for (uint32_t i = 0; i < n; ++i) valid += len[i];
-            if (n > 64 || valid * 2 >= (uint64_t)n * stride) {
-                if (ce == hipSuccess) ce = hipMemcpyAsync(dst, src, (size_t)n * stride * 8, hipMemcpyHostToDevice, g.stream);
-                return;
-            }
-            for (uint32_t i = 0; i < n && ce == hipSuccess; ++i)
-                if (len[i]) ce = hipMemcpyAsync(dst + (size_t)i * stride * 8, src + (size_t)i * stride, (size_t)len[i] * 8, hipMemcpyHostToDevice, g.stream);
-        };
-        rows(dq, q, q_len, nq, q_rows);
-        rows(dr, r, r_len, nr, r_rows);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(dql, q_len, (size_t)nq * 4, hipMemcpyHostToDevice, g.stream);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(drl, r_len, (size_t)nr * 4, hipMemcpyHostToDevice, g.stream);
-        if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in dist_batch: %s", hipGetErrorString(ce));
-        a.q = (const uint64_t *)dq; a.q_len = (const uint32_t *)dql; a.r = (const uint64_t *)dr; a.r_len = (const uint32_t *)drl;
-        a.common = dc; a.denom = dd; a.dist = nullptr; // distances in host libm below
-    }
-    // all-vs-refs fast path: the references go through in slices of 32 (one bit each in the range kernel's masks), the
-    // queries in batches (MHX_DIST_QBATCH; default: all at once), every (batch, slice) filling its block of the [nq][nr]
-    // outputs; the generic pair-per-workgroup kernel serves tiny batches and is the fallback of a block whose value
-    // ranges are too uneven for the LDS table.  Nothing is read back between the blocks: every block has its own flag
-    // word, all of them come back with ONE copy behind the last launch.
-    // (few pairs of LONG lists take it too -- AuriClass's own call, 1 query x 24 references at s = 50 000: 0.48 ms in the
-    // generic kernel, whose 24 workgroups each walk 100 000 elements)
-    // The number of value ranges follows the longest list of the call (its length, never its values; the row stride where
-    // the lengths are on the device): 1024 x W, W = 1 up to 65 536 entries -- the kernels, grids and workspace of round 3 --
-    // up to 16 at 2^20 (mhx_dist.h: dist_windows), so that sketches of up to 1 000 000 hashes keep slices of at most 64
-    // entries and stay on this path; longer lists have no geometry and go to the generic kernel.
-    uint32_t longest = stride;
-    if (!device_ptrs) {
-        longest = 0;
-        for (uint32_t i = 0; i < nq; ++i) longest = std::max(longest, q_len[i]);
-        for (uint32_t i = 0; i < nr; ++i) longest = std::max(longest, r_len[i]);
-    }
-    const uint32_t windows = dist_windows(longest), ranges = (uint32_t)kDistRanges * windows;
-    const bool fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)s >= 400000)) && windows != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
-    uint32_t qbatch = nq;
-    if (const char *e = getenv("MHX_DIST_QBATCH")) { const long v = atol(e); if (v > 0 && (uint64_t)v < nq) qbatch = (uint32_t)v; }
-    if (windows > 1) qbatch = std::min(qbatch, dist_wide_max_queries(nr < 32 ? nr : 32, ranges)); // the workspace stays below kDistWideWorkLimit
-    const uint32_t nslices = (nr + 31) / 32, nbatches = (nq + qbatch - 1) / qbatch, nblocks = nslices * nbatches;
-    DistWork w{};
-    uint32_t *d_params = nullptr;
-    constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together (a reference set of 131 072 sketches per group)
-    if (fast) {
-        size_t oq, orr, oc, ow, op;
-        const size_t need = dist_work_bytes(qbatch, nr < 32 ? nr : 32, ranges, &oq, &orr, &oc, &ow, &op) + (size_t)std::min(nblocks, kBlockGroup) * 8;
-        if (g.dist_ws.grow(need, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the distance workspace");
-        w.offs_q = (uint32_t *)(g.dist_ws + oq); w.offs_r = (uint32_t *)(g.dist_ws + orr);
-        w.cpart = g.dist_ws + oc;
-        w.wtot = (uint32_t *)(g.dist_ws + ow);
-        w.ranges = ranges;
-        d_params = (uint32_t *)(g.dist_ws + op); // [block][2]: shift, overflow flag
-    }
-    auto block_args = [&](uint32_t b) {
-        const uint32_t q0 = (b / nslices) * qbatch, r0 = (b % nslices) * 32;
-        DistArgs x = a;
-        x.q = a.q + (uint64_t)q0 * stride;
-        x.q_len = a.q_len + q0;
-        x.nq = nq - q0 < qbatch ? nq - q0 : qbatch;
-        x.r = a.r + (uint64_t)r0 * stride;
-        x.r_len = a.r_len + r0;
-        x.nr = nr - r0 < 32 ? nr - r0 : 32;
-        x.common = a.common + (uint64_t)q0 * nr;
-        x.denom = a.denom + (uint64_t)q0 * nr;
-        x.dist = a.dist ? a.dist + (uint64_t)q0 * nr : nullptr;
-        x.out_off = r0;
-        return x;
-    };
-    hipEventRecord(g.ev0, g.stream);
-    hipError_t le = hipSuccess;
-    if (!fast) { le = launch_dist_pairs(a, g.stream); g.last_dist_fallbacks = -1; }
-    if (fast) g.last_dist_fallbacks = 0;
-    g.last_dist_ranges = 0;
-    for (uint32_t b0 = 0; fast && b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
-        const uint32_t b1 = std::min(nblocks, b0 + kBlockGroup);
-        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b) {
-            w.params = d_params + 2 * (b - b0);
-            le = launch_dist_ranges(block_args(b), w, g.stream);
-        }
-        if (le != hipSuccess) break;
-        std::vector<uint32_t> flags((size_t)(b1 - b0) * 2);
-        if (hipMemcpyAsync(flags.data(), d_params, flags.size() * 4, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
-            hipStreamSynchronize(g.stream) != hipSuccess)
-            return fail(MHX_E_HIP, "dist kernel failed");
-        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b)
-            if (flags[2 * (b - b0) + 1]) { le = launch_dist_pairs(block_args(b), g.stream); ++g.last_dist_fallbacks; } // a value range overflowed the LDS table
-    }
-    hipEventRecord(g.ev1, g.stream);
-    if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges; // (0: the generic kernel did all the work)
-    if (le != hipSuccess) return fail(MHX_E_HIP, "dist kernel launch failed: %s", hipGetErrorString(le));
-    hipError_t se = hipSuccess;
-    if (!device_ptrs) {
-        se = hipMemcpyAsync(common, dc, pairs * 4, hipMemcpyDeviceToHost, g.stream);
-        if (se == hipSuccess) se = hipMemcpyAsync(denom, dd, pairs * 4, hipMemcpyDeviceToHost, g.stream);
-    }
-    if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, g.ev0, g.ev1);
-    g.last_dist_ms = ms;
-    if (se != hipSuccess) return fail(MHX_E_HIP, "dist kernel failed: %s", hipGetErrorString(se));
-    if (!device_ptrs && dist) {
-        for (uint64_t i = 0; i < pairs; ++i) {
-            double d;
-            if (common[i] == denom[i]) d = 0.0;
-            else if (common[i] == 0) d = 1.0;
-            else {
-                const double j = (double)common[i] / (double)denom[i];
-                d = -log(2.0 * j / (1.0 + j)) / (double)k;
-                if (d > 1.0) d = 1.0;
-            }
-            dist[i] = d;
-        }
-    }
-    return MHX_OK;
-}
-
-extern "C" int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len,
-                              uint32_t nr, uint32_t stride, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist,
-                              int device_ptrs)
-{
-    try {
-        return dist_batch_core(q, q_len, nq, r, r_len, nr, stride, k, s, common, denom, dist, device_ptrs, nullptr, nullptr);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_batch: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_batch: %s", e.what());
-    }
-}
-
-namespace mhx {
-int dist_batch_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const uint64_t *const *r_rows, const uint32_t *r_len,
-                    uint32_t nr, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist)
-{
-    uint32_t stride = 16;
-    for (uint32_t i = 0; i < nq; ++i) stride = q_len[i] > stride ? q_len[i] : stride;
-    for (uint32_t i = 0; i < nr; ++i) stride = r_len[i] > stride ? r_len[i] : stride;
-    stride = (stride + 15u) & ~15u; // rows of whole 128-byte lines on the device
-    return dist_batch_core(nullptr, q_len, nq, nullptr, r_len, nr, stride, k, s, common, denom, dist, 0, q_rows, r_rows);
-}
-} // namespace mhx
-
-// ---- containment screen ----------------------------------------------------------------
-// `mash screen`: which share of every REFERENCE sketch occurs in a read set, and how often.  A screener is the sketcher's
-// push machinery with another table behind it (mhx_screen.h): its prober is an mhx_sketcher in screen mode, so the FASTQ
-// line phase, the repair pass for long reads, the chain check, the device flags and the sync contract are the sketcher's
-// own code.  For the set size of the mixture it owns an ordinary sketcher (k, s_ref, m = 1) that sees every span too.
-struct mhx_screener {
-    SketcherPtr probe, setsk;
-    int k = 0;
-    uint32_t nr = 0, stride = 0, s_ref = 0;
-    DevArray<uint64_t> d_rows;
-    DevArray<uint32_t> d_len, d_counts, d_res; // d_res: shared[nr] | median[nr]
-    DevArray<uint32_t> d_win, d_prio;          // winner-take-all (mhx_screen.h): win[nslots + 1], prio[nr]; allocated by the first winner finish
-};
-
-static ScreenArgs screen_args(mhx_screener *sc)
-{
-    mhx_sketcher *p = sc->probe.get();
-    ScreenArgs a;
-    a.rows = sc->d_rows; a.len = sc->d_len; a.nr = sc->nr; a.stride = sc->stride;
-    a.keys = p->d_keys; a.cnts = p->d_cnts; a.nslots = p->nslots; a.thresh = p->d_thresh; a.stats = p->d_stats;
-    a.counts = sc->d_counts; a.shared = sc->d_res; a.median = sc->d_res + sc->nr;
-    return a;
-}
-
-// counts, counters, tickets and the "repair due" word of the prober to zero; the keys stay
-static int screener_clear(mhx_screener *sc)
-{
-    mhx_sketcher *p = sc->probe.get();
-    HIPCHK(launch_screen_clear(screen_args(sc), p->d_tickets, kTicketWords, p->d_need, g.stream));
-    p->tickets_used = 0;
-    p->unsettled.clear();
-    p->bytes_pushed = 0;
-    p->hash_ms = 0.0;
-    p->launches = 0;
-    return MHX_OK;
-}
-
-static int screener_create_impl(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
-                                int with_set_size, int device_ptrs, mhx_screener **out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!out) return fail(MHX_E_ARG, "null out pointer");
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    if (nr && (!ref_rows || !ref_len || stride == 0)) return fail(MHX_E_ARG, "null reference rows");
-    if (s_ref == 0) return fail(MHX_E_ARG, "sketch size must be positive");
-    const uint64_t entries = (uint64_t)nr * stride;
-    if (entries > (1ull << 31)) return fail(MHX_E_ARG, "reference set too large for one screen table (%llu entries)", (unsigned long long)entries);
-    std::unique_ptr<mhx_screener> sc(new mhx_screener());
-    sc->k = k; sc->nr = nr; sc->stride = stride ? stride : 1; sc->s_ref = s_ref;
-    std::unique_ptr<mhx_sketcher> p(new mhx_sketcher());
-    p->k = k; p->s = s_ref; p->m = 1;
-    p->hash32 = k <= 16;
-    p->hash_max = p->hash32 ? 0xFFFFFFFFull : ~0ull;
-    p->screen = true;
-    p->nslots = screen_table_slots(entries);
-    hipError_t e = hipSuccess;
-    auto A = [&](auto &arr, size_t n) { if (e == hipSuccess) e = arr.grow(n); };
-    A(p->d_keys, p->nslots);
-    A(p->d_cnts, p->nslots);
-    A(p->d_thresh, 1);
-    A(p->d_stats, kStatReplicas * kStatCount);
-    A(p->d_tickets, kTicketWords);
-    A(p->d_need, 1);
-    A(p->h_fin, 8); // the pinned landing word of settle()
-    A(sc->d_rows, std::max<uint64_t>(entries, 1));
-    A(sc->d_len, std::max<uint32_t>(nr, 1));
-    A(sc->d_counts, std::max<uint64_t>(entries, 1));
-    A(sc->d_res, 2 * (size_t)std::max<uint32_t>(nr, 1));
-    if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed while creating the screener: %s", hipGetErrorString(e));
-    sc->probe.reset(p.release());
-    if (!device_ptrs)
-        for (uint32_t i = 0; i < nr; ++i)
-            if (ref_len[i] > stride) return fail(MHX_E_ARG, "ref_len[%u] exceeds stride", i);
-    const hipMemcpyKind kind = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (entries) HIPCHK(hipMemcpyAsync(sc->d_rows, ref_rows, entries * sizeof(uint64_t), kind, g.stream));
-    if (nr) HIPCHK(hipMemcpyAsync(sc->d_len, ref_len, (size_t)nr * sizeof(uint32_t), kind, g.stream));
-    HIPCHK(hipMemsetAsync(sc->d_counts, 0, std::max<uint64_t>(entries, 1) * sizeof(uint32_t), g.stream));
-    HIPCHK(hipMemsetAsync(sc->probe->d_stats, 0, kStatReplicas * kStatCount * sizeof(uint64_t), g.stream));
-    HIPCHK(launch_screen_build(screen_args(sc.get()), g.stream));
-    uint64_t T = 0, flags = 0;
-    HIPCHK(hipMemcpyAsync(&T, sc->probe->d_thresh, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(&flags, sc->probe->d_stats + kStatFlags, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); // (the caller's rows are free again)
-    if (flags & kFlagTableFull) return fail(MHX_E_INTERNAL, "screen table overflowed while it was built");
-    sc->probe->screen_T = T;
-    sc->probe->last_T = T;
-    rc = screener_clear(sc.get());
-    if (rc) return rc;
-    if (with_set_size) {
-        mhx_sketcher *ss = nullptr;
-        rc = create_sketcher(k, s_ref, 1, 0, 1, &ss);
-        if (rc) return rc;
-        sc->setsk.reset(ss);
-    }
-    *out = sc.release();
-    return MHX_OK;
-}
-
-extern "C" int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
-                                   int with_set_size, int device_ptrs, mhx_screener **out)
-{
-    try {
-        return screener_create_impl(k, ref_rows, ref_len, nr, stride, s_ref, with_set_size, device_ptrs, out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_create: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_create: %s", e.what());
-    }
-}
-
-extern "C" void mhx_screener_destroy(mhx_screener *sc)
-{
-    if (g.ready) hipStreamSynchronize(g.stream);
-    delete sc;
-}
-
-extern "C" int mhx_screener_reset(mhx_screener *sc)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null screener");
-    rc = screener_clear(sc);
-    if (rc) return rc;
-    return sc->setsk ? mhx_sketcher_reset(sc->setsk.get()) : MHX_OK;
-}
-
-extern "C" int mhx_screener_push_device(mhx_screener *sc, const void *d_bytes, uint64_t n, int fmt)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null argument");
-    rc = mhx_sketcher_push_device(sc->probe.get(), d_bytes, n, fmt);
-    if (rc || !sc->setsk) return rc;
-    return mhx_sketcher_push_device(sc->setsk.get(), d_bytes, n, fmt); // a second launch over the same resident bytes
-}
-
-extern "C" int mhx_screener_push_host(mhx_screener *sc, const void *h_bytes, uint64_t n, int fmt)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc || (!h_bytes && n)) return fail(MHX_E_ARG, "null argument");
-    if (n == 0) return MHX_OK;
-    mhx_sketcher *p = sc->probe.get();
-    // one staging buffer (the prober's) for both: earlier pushes of either that may still read it come first
-    rc = settle(p);
-    if (!rc && sc->setsk) rc = settle(sc->setsk.get());
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    if (p->d_stage.cap() < n + 64) HIPCHK(p->d_stage.grow((size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1))));
-    HIPCHK(hipMemcpyAsync(p->d_stage, h_bytes, n, hipMemcpyHostToDevice, g.stream));
-    return mhx_screener_push_device(sc, p->d_stage, n, fmt);
-}
-
-extern "C" int mhx_screener_sync(mhx_screener *sc)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null argument");
-    rc = mhx_sketcher_sync(sc->probe.get());
-    if (rc || !sc->setsk) return rc;
-    return mhx_sketcher_sync(sc->setsk.get());
-}
-
-namespace mhx {
-double set_size_estimate(int k, const uint64_t *hashes, size_t n)
-{
-    return n ? pow(2.0, k > 16 ? 64.0 : 32.0) * (double)n / (double)hashes[n - 1] : 0.0;
-}
-mhx_sketcher *screener_prober(mhx_screener *sc) { return sc ? sc->probe.get() : nullptr; }
-} // namespace mhx
-
 void sketcher_set_follower(mhx_sketcher *sk, mhx_sketcher *follower)
 {
     if (sk) sk->follower = follower;
-}
-
-// Winner-take-all behind the plain tally, which has just been launched: its shared[] comes to the host and becomes the
-// priority order, the winner words go back to "nobody" (the counts have changed since the last call), every entry claims
-// its key, and the tally runs again in its winner form into the same result buffers.
-static int screener_winner_passes(mhx_screener *sc, const uint64_t *ref_length, uint64_t maxkey)
-{
-    mhx_sketcher *p = sc->probe.get();
-    const uint32_t nr = sc->nr;
-    std::vector<uint32_t> shared0(nr), len(nr), prio(nr);
-    HIPCHK(hipMemcpyAsync(shared0.data(), sc->d_res, (size_t)nr * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(len.data(), sc->d_len, (size_t)nr * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream));
-    screen_priorities(shared0.data(), len.data(), ref_length, nr, prio.data());
-    if (!sc->d_win.cap()) {
-        hipError_t e = sc->d_win.grow(p->nslots + 1);
-        if (e == hipSuccess) e = sc->d_prio.grow(nr);
-        if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the winner words of the screener: %s", hipGetErrorString(e));
-    }
-    HIPCHK(hipMemcpyAsync(sc->d_prio, prio.data(), (size_t)nr * sizeof(uint32_t), hipMemcpyHostToDevice, g.stream));
-    static_assert(kScreenNobody == 0, "the winner words are vacated by a memset");
-    HIPCHK(hipMemsetAsync(sc->d_win, 0, (size_t)(p->nslots + 1) * sizeof(uint32_t), g.stream));
-    const ScreenArgs a = screen_args(sc);
-    HIPCHK(launch_screen_winner(a, sc->d_win, sc->d_prio, maxkey, g.stream));
-    HIPCHK(launch_screen_tally_winner(a, sc->d_win, sc->d_prio, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); // (prio is free again)
-    return MHX_OK;
-}
-
-static int screener_finish_impl(mhx_screener *sc, bool winner, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
-                                uint32_t *counts)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc || (sc->nr && (!shared || !median))) return fail(MHX_E_ARG, "null argument");
-    mhx_sketcher *p = sc->probe.get();
-    rc = settle(p); // the repair pass of long reads, if one is due
-    if (rc) return rc;
-    uint64_t st[kStatCount];
-    rc = fetch_stats(p, st);
-    if (rc) return rc;
-    rc = check_flags(st[kStatFlags]);
-    if (rc) return rc;
-    if (st[kStatFlags] & kFlagCountWrap) return fail(MHX_E_CAPACITY, "a multiplicity counter of the screen table reached its limit");
-    if (sc->nr) {
-        HIPCHK(launch_screen_tally(screen_args(sc), g.stream));
-        if (winner) {
-            rc = screener_winner_passes(sc, ref_length, st[kStatMaxKey]);
-            if (rc) return rc;
-        }
-        std::vector<uint32_t> res(2 * (size_t)sc->nr);
-        HIPCHK(hipMemcpyAsync(res.data(), sc->d_res, res.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-        if (counts) HIPCHK(hipMemcpyAsync(counts, sc->d_counts, (size_t)sc->nr * sc->stride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-        memcpy(shared, res.data(), (size_t)sc->nr * sizeof(uint32_t));
-        memcpy(median, res.data() + sc->nr, (size_t)sc->nr * sizeof(uint32_t));
-    }
-    double size = 0.0;
-    if (sc->setsk) {
-        std::vector<uint64_t> h(sc->s_ref);
-        uint32_t n = 0;
-        rc = mhx_sketcher_finish(sc->setsk.get(), h.data(), nullptr, &n);
-        if (rc) return rc;
-        size = set_size_estimate(sc->k, h.data(), n);
-    }
-    if (set_size) *set_size = size;
-    return MHX_OK;
-}
-
-extern "C" int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
-{
-    try {
-        return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish: %s", e.what());
-    }
-}
-
-extern "C" int mhx_screener_finish_winner(mhx_screener *sc, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
-                                          uint32_t *counts)
-{
-    try {
-        return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: %s", e.what());
-    }
 }
 
 extern "C" int mhx_sketcher_finish(mhx_sketcher *sk, uint64_t *hashes, uint32_t *counts, uint32_t *n_out)

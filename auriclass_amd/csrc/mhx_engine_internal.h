@@ -1,5 +1,5 @@
-// mhx_engine_internal.h -- what mhx_engine.cpp (engine state, sketcher, distances) and mhx_files.cpp (file
-// ingest and the file-level calls) share.  Internal; the public surface is include/mhx.h.
+// mhx_engine_internal.h -- what the engine files (mhx_engine.cpp: engine state and sketcher, mhx_engine_dist.cpp,
+// mhx_engine_screen.cpp) and mhx_files.cpp (file ingest and the file-level calls) share.  Internal; the public surface is include/mhx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

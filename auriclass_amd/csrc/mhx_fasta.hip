@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mhx_block.h"
 #include "mhx_device.h"
 #include "mhx_tile.h"
 
@@ -100,7 +101,7 @@ __device__ __forceinline__ uint32_t chunk_state(const ChunkMasks &c)
     return ((c.gt >> q) & 1ull) ? kHdr : kSeq;
 }
 
-// exclusive scan of per-thread states with `combine`, and of two counters; one barrier each
+// exclusive scan of per-thread states with `combine`; one barrier (the counters go through block_scan_excl, mhx_block.h)
 __device__ __forceinline__ uint32_t block_scan_state(uint32_t s, uint32_t *tmp, uint32_t &total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -121,25 +122,6 @@ __device__ __forceinline__ uint32_t block_scan_state(uint32_t s, uint32_t *tmp, 
     }
     total = all;
     return combine(before, excl);
-}
-__device__ __forceinline__ uint32_t block_scan_add(uint32_t v, uint32_t *tmp, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) tmp[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < kFaThreads / 64; ++w) {
-        if (w < wave) before += tmp[w];
-        all += tmp[w];
-    }
-    total = all;
-    return before + incl - v;
 }
 
 // bytes of the chunk that go to the output for a given start state: the sequence-line bytes that are not blank, and the
@@ -172,11 +154,11 @@ __global__ __launch_bounds__(kFaThreads) void fasta_scan_kernel(const uint8_t *b
     }
     __syncthreads();
     uint32_t t_known, t_seq, t_hdr;
-    block_scan_add(known, tmp, t_known);
+    block_scan_excl<kFaThreads>(known, tmp, t_known);
     __syncthreads();
-    block_scan_add(if_seq, tmp, t_seq);
+    block_scan_excl<kFaThreads>(if_seq, tmp, t_seq);
     __syncthreads();
-    block_scan_add(if_hdr, tmp, t_hdr);
+    block_scan_excl<kFaThreads>(if_hdr, tmp, t_hdr);
     if (threadIdx.x == 0) {
         summary[3 * blockIdx.x] = tile_state;
         summary[3 * blockIdx.x + 1] = t_known + t_seq;
@@ -236,7 +218,7 @@ __global__ __launch_bounds__(kFaThreads) void fasta_compact_kernel(const uint8_t
     uint64_t keep = (~hdr & c.keepc) | (hdr & c.nl);
     __syncthreads();
     uint32_t total;
-    const uint32_t before = block_scan_add((uint32_t)__builtin_popcountll(keep), tmp, total);
+    const uint32_t before = block_scan_excl<kFaThreads>((uint32_t)__builtin_popcountll(keep), tmp, total);
     uint64_t pos = tile_off[blockIdx.x] + before;
     const uint64_t sepbits = hdr & c.nl;
     while (keep) {

@@ -14,7 +14,8 @@
 //   merge_compact_kernel  prefix over the bins' counts -> the qualifying entries, globally ascending, into the
 //                         pinned result block of the sketcher, header last
 // No pass over the 200 MB candidate table, no atomics on it, nothing sorted on the host.  A bin region or table that
-// overflows (non-uniform input) raises a flag and the caller falls back to the table path (slab_insert_kernel).
+// overflows (non-uniform input) raises a flag and the caller falls back to the table path (slab_insert_kernel, at the end
+// of this file).
 #include "mhx_device.h"
 
 namespace mhx {
@@ -171,7 +172,8 @@ __global__ __launch_bounds__(kCompactThreads) void merge_compact_kernel(const Me
         block_base = x;
         grand_total = y;
     }
-    // exclusive scan of the 256 bins' counts (threads 0 .. 255, one bin each)
+    // exclusive scan of the 256 bins' counts (threads 0 .. 255, one bin each; block_scan_excl of mhx_block.h scans a whole
+    // workgroup and returns a total: here four of the sixteen waves take part, hence `wave < 4`, and nobody wants the total)
     const uint32_t b = first + threadIdx.x;
     const uint32_t mine = threadIdx.x < 256 && b < a.nbins ? a.qn[b] : 0u;
     uint32_t v = mine;
@@ -243,6 +245,57 @@ hipError_t launch_merge_bins(const MergeArgs &a_in, uint64_t max_n, uint64_t *ou
     if (chunks) hipLaunchKernelGGL(merge_scatter_kernel, dim3(chunks, a.nranks), dim3(kScatterThreads), scatter_lds, st, a);
     hipLaunchKernelGGL(merge_bin_kernel, dim3(a.nbins), dim3(256), bin_lds, st, a);
     hipLaunchKernelGGL(merge_compact_kernel, dim3(a.nbins / 256), dim3(kCompactThreads), 0, st, a, out, out_cap);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// The table path, what a merge falls back to when the bins above overflow (mhx_sketcher_merge_slabs): after the all-gather
+// every rank holds all ranks' partial results in HBM.  Its own entries already sit in its candidate table with exact
+// counts; the other ranks' entries <= T_min are added to that table -- a key is claimed by CAS (or found), its count
+// added atomically -- and the ordinary extraction (count >= m, hash <= T_min) then yields the union's sketch.
+// One thread per entry, ranks along grid.y; the gathered buffer is `nranks` slabs of `slab_words` 8-byte words:
+// hashes[cap], then the u32 counts.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void slab_insert_kernel(const SlabMergeArgs a)
+{
+    const uint32_t r = blockIdx.y;
+    if (blockIdx.x == 0 && r == 0 && threadIdx.x == 0) {
+        *a.thresh = a.t_min; // what the extraction behind this kernel reads as its limit
+        if (a.maxkey_others) atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + kStatMaxKey, (unsigned long long)a.maxkey_others);
+    }
+    if (r == a.own_rank) return;
+    const uint64_t n = a.n[r];
+    const uint64_t *hashes = a.slabs + (uint64_t)r * a.slab_words + a.hdr_words;
+    const uint32_t *counts = reinterpret_cast<const uint32_t *>(hashes + a.cap);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(a.keys);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t h = hashes[i];
+        if (h > a.t_min || h == kEmptyKey) continue; // above T_min a shard's list is incomplete: not part of the union's evidence
+        const uint32_t c = counts[i];
+        uint64_t slot = h & a.slot_mask;
+        bool placed = false;
+        for (int probe = 0; probe < 8192; ++probe) {
+            // a slot only ever goes from vacant to a key: a plain load that shows this hash (or another one) is final,
+            // one that shows a vacant slot is settled by the CAS
+            unsigned long long cur = keys[slot];
+            if (cur == kEmptyKey) cur = atomicCAS(&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)h);
+            if (cur == kEmptyKey || cur == h) {
+                atomicAdd(&a.cnts[slot], c);
+                placed = true;
+                break;
+            }
+            slot = (slot + 1) & a.slot_mask;
+        }
+        if (!placed) atomicOr(reinterpret_cast<unsigned long long *>(a.stats) + kStatFlags, (unsigned long long)kFlagTableFull);
+    }
+}
+
+hipError_t launch_slab_insert(const SlabMergeArgs &a, uint64_t max_n, hipStream_t st)
+{
+    uint64_t blocks = (max_n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(slab_insert_kernel, dim3((unsigned)blocks, a.nranks), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // mhx_screen.h -- the rules of the containment screen (`mash screen`) that are more than a line: geometry of the screen
 // table, the walk of a probe sequence, the build step that claims a slot, the counter that must not wrap and the selection
 // of a reference's median multiplicity, and the winner-take-all form of the tally (`-w`: priority order, claim, "won").
-// Host+device functions: the kernels (mhx_kernels.hip) and the CPU emulators (tests/emul/screen_emul.cpp,
+// Host+device functions: the kernels (mhx_screen.hip, mhx_sketch.hip) and the CPU emulators (tests/emul/screen_emul.cpp,
 // tests/emul/screen_winner_emul.cpp) run these very functions.
 //
 // The screen table is the candidate table's sibling: keys u64[2^n], vacant = 2^64-1 (kEmptyKey), cnts u32[2^n], slot =

@@ -1,5 +1,5 @@
 // mhx_tile.h -- per-tile logic of the sketch kernel, written as host+device inline
-// functions: mhx_kernels.hip strings the phases together with __syncthreads(); the CPU
+// functions: mhx_sketch.hip strings the phases together with __syncthreads(); the CPU
 // phase emulator (tests/emul/tile_emul.cpp) runs the very same functions thread by
 // thread so that indexing and bit logic are checked without a GPU.
 //

@@ -1,4 +1,4 @@
-// tests/emul/dist_emul.cpp -- CPU emulator of the all-vs-refs distance path (mhx_kernels.hip: dist_shift / split / range /
+// tests/emul/dist_emul.cpp -- CPU emulator of the all-vs-refs distance path (mhx_dist.hip: dist_shift / split / range /
 // window / finish kernels, test tool).  Runs the host+device functions of auriclass_amd/csrc/mhx_dist.h in the kernels'
 // order, one work item after the other: the shift from the largest value, the split pass work item by work item (two
 // elements each), the range pass range by range in the workgroups' order (table build, probe, byte counters), the window

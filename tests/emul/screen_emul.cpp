@@ -1,4 +1,4 @@
-// tests/emul/screen_emul.cpp -- CPU emulator of the containment screen's table (mhx_kernels.hip: screen_build_kernel,
+// tests/emul/screen_emul.cpp -- CPU emulator of the containment screen's table (mhx_screen.hip: screen_build_kernel,
 // ScreenProber, screen_tally_kernel; test tool).  Runs the host+device functions of auriclass_amd/csrc/mhx_screen.h
 // sequentially, in the kernels' order: vacate and build (claim = a compare-and-swap done by one agent), one probe per
 // input hash, then per reference the look-up of every entry and the four selection passes over the counts.  Not part of

@@ -1,4 +1,4 @@
-// tests/emul/screen_winner_emul.cpp -- CPU emulator of the winner-take-all form of the containment screen (mhx_kernels.hip:
+// tests/emul/screen_winner_emul.cpp -- CPU emulator of the winner-take-all form of the containment screen (mhx_screen.hip:
 // screen_winner_kernel, screen_tally_winner_kernel; mhx_engine.cpp: screener_winner_passes; test tool).  Runs the host+device
 // functions of auriclass_amd/csrc/mhx_screen.h sequentially, in the engine's order: build, one probe per input hash, the plain
 // tally's shared, the priority order, the claim of every entry (raise = a maximum taken by one agent), then per reference the

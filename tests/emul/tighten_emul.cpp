@@ -1,4 +1,4 @@
-// tests/emul/tighten_emul.cpp -- CPU emulator of the tighten pass's last workgroup (mhx_kernels.hip: table_tighten_kernel;
+// tests/emul/tighten_emul.cpp -- CPU emulator of the tighten pass's last workgroup (mhx_table.hip: table_tighten_kernel;
 // test tool).  emul_tighten runs the host+device functions of auriclass_amd/csrc/mhx_tighten.h in the kernel's order:
 // 256 threads of eight bins each, a prefix over the threads, the search inside the one thread that holds the cut, then
 // thread 0's decision.  emul_tighten_former is the arithmetic the kernel carried inline before that header existed, kept

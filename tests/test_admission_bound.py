@@ -5,15 +5,12 @@ pass do the two products.  That test must never reject a hash <= T, whatever the
 and of their shift-xored low words) are, and it must not pass more than the three high words around hi(T) it gives away.
 The tails are built backwards from chosen products: ka = a * C2^-1."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "admission_bound_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_admission_bound_emul.so"
+from tests import emul_build
+
 C2 = 0xC4CEB9FE1A85EC53
 EDGE_HIGH = np.array([0, 1, 2, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFD, 0xFFFFFFFE, 0xFFFFFFFF], dtype=np.uint64)
 EDGE_LOW = np.array([0, 1, 0x80000000, 0xFFFFFFFF], dtype=np.uint64)
@@ -25,11 +22,7 @@ SATURATED = 0xFFFFFFFD  # from this high word of T on the bound says nothing
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    newest = max(p.stat().st_mtime for p in (SRC, csrc / "mhx_tile.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"))
-    if not SO.exists() or SO.stat().st_mtime < newest:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("admission_bound_emul")
     L.emul_fmix_c2_inverse.restype = ctypes.c_uint64
     L.emul_tails.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     L.emul_tails.restype = None

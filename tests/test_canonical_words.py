@@ -4,17 +4,13 @@ min(forward, reverse complement) of the upper-cased window, zero-padded, and mur
 The function selects only the source dwords a strand's kept bytes come from, by a rule that depends on K and J, so no
 (K, J) is left out; the bytes of the chunk around the window are arbitrary and must not show."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from oracle import mash_oracle as mo
+from tests import emul_build
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "canonical_words_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_canonical_words_emul.so"
 GROUP = 8
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 COMP = bytes.maketrans(b"ACGT", b"TGCA")
@@ -22,11 +18,7 @@ COMP = bytes.maketrans(b"ACGT", b"TGCA")
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    newest = max(p.stat().st_mtime for p in (SRC, csrc / "mhx_tile.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"))
-    if not SO.exists() or SO.stat().st_mtime < newest:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("canonical_words_emul")
     L.emul_chunk_dwords.argtypes = [ctypes.c_int]
     L.emul_canonical_words.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     return L

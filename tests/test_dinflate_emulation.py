@@ -2,26 +2,18 @@
 HIP kernels run) against Python's zlib: search, symbolic decode, chain check and redo, resolution and CRC-32, lane by lane."""
 import ctypes
 import gzip
-import subprocess
 import zlib
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from auriclass_amd import synth
-
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "dinflate_emul.cpp"
-HDR = [ROOT / "auriclass_amd" / "csrc" / h for h in ("mhx_dinflate.h", "mhx_deflate.h", "mhx_hd.h")]
-SO = ROOT / "tests" / "emul" / "_dinflate_emul.so"
+from tests import emul_build
 
 
 @pytest.fixture(scope="module")
 def emul():
-    if not SO.exists() or SO.stat().st_mtime < max(p.stat().st_mtime for p in [SRC, *HDR]):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC), "-lz"], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("dinflate_emul", libs=("-lz",))
     L.emul_gunzip.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
                               ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p]
     return L

@@ -1,29 +1,21 @@
 """CPU emulation of the all-vs-refs distance path (auriclass_amd/csrc/mhx_dist.h, the very functions the dist_* kernels of
-mhx_kernels.hip run): tests/emul/dist_emul.cpp runs them sequentially over whole batches -- shift, split pass, range
+mhx_dist.hip run): tests/emul/dist_emul.cpp runs them sequentially over whole batches -- shift, split pass, range
 pass, window totals, finish walk -- in the base form (1024 value ranges) and in the windowed form (1024 x W ranges for
 lists of more than 65 536 hashes); `common` and `denom` of every pair against the oracle's compareSketches."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from oracle import mash_oracle as mo
+from tests import emul_build
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "dist_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_dist_emul.so"
 WORST_HI = int(2 ** 63.01)   # the scale is rounded up to a power of two: values just above 2^63 leave half of the ranges in use
 
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    hdrs = [csrc / "mhx_dist.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"]
-    if not SO.exists() or SO.stat().st_mtime < max(p.stat().st_mtime for p in [SRC] + hdrs):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("dist_emul")
     L.emul_dist_windows.argtypes = [ctypes.c_uint64]
     L.emul_dist_windows.restype = ctypes.c_uint32
     L.emul_dist_max_windows.restype = ctypes.c_uint32

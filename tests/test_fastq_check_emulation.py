@@ -2,30 +2,22 @@
 runs): its verdict against a plain statement of the rule on seeded damaged files, and end to end with the sketch
 kernel's tile emulator: whatever the check and the layout check let through is sketched as the oracle sketches it."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from auriclass_amd import synth
 from oracle import mash_oracle as mo
+from tests import emul_build
 from tests.test_tile_emulation import MAXT, run_emul
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "fqcheck_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_fqcheck_emul.so"
 BLANKS = bytes(range(0x21)) + b"\x7f"   # what the kseq reader drops
 SPECIAL = np.frombuffer(b"\n\n\n@+>\r ANacgt" + b" \t\r\x7f\x00", np.uint8)
 
 
 @pytest.fixture(scope="module")
 def tile_emul():
-    src, so = ROOT / "tests" / "emul" / "tile_emul.cpp", ROOT / "tests" / "emul" / "_tile_emul.so"
-    hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_tile.h"
-    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(so), str(src)], check=True)
-    L = ctypes.CDLL(str(so))
+    L = emul_build.load("tile_emul")
     L.emul_sketch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     return L
@@ -33,10 +25,7 @@ def tile_emul():
 
 @pytest.fixture(scope="module")
 def fq():
-    hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_fqcheck.h"
-    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("fqcheck_emul")
     L.emul_fqcheck.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]
     L.emul_fqcheck.restype = ctypes.c_int
     return L

@@ -3,25 +3,18 @@ table build, probe and tally, run sequentially by tests/emul/screen_emul.cpp, ag
 count(h) = occurrences of h among the probes, per reference the number of entries with a non-zero count and element
 [len / 2] of their ascending counts."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "screen_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_screen_emul.so"
+from tests import emul_build
+
 MAXKEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    deps = [SRC, csrc / "mhx_screen.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"]
-    if not SO.exists() or SO.stat().st_mtime < max(d.stat().st_mtime for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("screen_emul")
     L.emul_screen.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
                               ctypes.c_uint64] + [ctypes.c_void_p] * 4
     L.emul_screen.restype = ctypes.c_int64

@@ -2,29 +2,21 @@
 the kernels and the engine run: priority order, claim, "won"), run sequentially by tests/emul/screen_winner_emul.cpp,
 against the plain statement of the rule (tests/screen_winner_rule.py)."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from tests import emul_build
 from tests import screen_winner_rule as wrule
 from tests.test_screen_emulation import pack, random_case
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "screen_winner_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_screen_winner_emul.so"
 MAXKEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 K = 21
 
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    deps = [SRC, csrc / "mhx_screen.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"]
-    if not SO.exists() or SO.stat().st_mtime < max(d.stat().st_mtime for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("screen_winner_emul")
     L.emul_screen_winner.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                      ctypes.c_uint64] + [ctypes.c_void_p] * 5
     L.emul_screen_winner.restype = ctypes.c_int64

@@ -2,26 +2,19 @@
 last workgroup runs) against the arithmetic the kernel carried inline before (tests/emul/tighten_emul.cpp), and against
 plain statements of what a pass must leave behind: T never rises, at least s qualifying entries lie at or below it."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "tighten_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_tighten_emul.so"
+from tests import emul_build
+
 BINS = 2048
 U64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    deps = [SRC, csrc / "mhx_tighten.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"]
-    if not SO.exists() or SO.stat().st_mtime < max(d.stat().st_mtime for d in deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("tighten_emul")
     for f in (L.emul_tighten, L.emul_tighten_former):
         f.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]

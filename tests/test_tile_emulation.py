@@ -1,26 +1,19 @@
 """CPU emulation of the sketch kernel's tile phases (auriclass_amd/csrc/mhx_tile.h, the very
 functions the HIP kernel runs) against the oracle's definition-level window hashes."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from oracle import mash_oracle as mo
+from tests import emul_build
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "tile_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_tile_emul.so"
 MAXT = 2 ** 64 - 1
 
 
 @pytest.fixture(scope="module")
 def emul():
-    hdr = ROOT / "auriclass_amd" / "csrc" / "mhx_tile.h"
-    if not SO.exists() or SO.stat().st_mtime < max(SRC.stat().st_mtime, hdr.stat().st_mtime, (hdr.parent / "mhx_hd.h").stat().st_mtime):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("tile_emul")
     L.emul_sketch.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
     return L

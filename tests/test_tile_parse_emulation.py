@@ -3,29 +3,21 @@ with its per-newline loops is the reference, phase_events + phase_good_events is
 newlines fit the event list.  Per tile: every word of the good map, the bad-format flag, the number of long records.
 Also: murmur3_h1<K> (seed folded into the first block's constant) against the oracle's hash for K = 1..32."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from auriclass_amd import synth
 from oracle import mash_oracle as mo
+from tests import emul_build
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "emul" / "tile_parse_emul.cpp"
-SO = ROOT / "tests" / "emul" / "_tile_parse_emul.so"
 TILE = 16384
 TILES, FALLBACK, GOOD_DIFF, BAD_DIFF, COUNT_DIFF, BAD_TILES, RECORDS, LINES = range(8)
 
 
 @pytest.fixture(scope="module")
 def emul():
-    csrc = ROOT / "auriclass_amd" / "csrc"
-    newest = max(p.stat().st_mtime for p in (SRC, csrc / "mhx_tile.h", csrc / "mhx_hd.h", csrc / "mhx_device_consts.h"))
-    if not SO.exists() or SO.stat().st_mtime < newest:
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", str(SO), str(SRC)], check=True)
-    L = ctypes.CDLL(str(SO))
+    L = emul_build.load("tile_parse_emul")
     L.emul_parse_compare.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
     L.emul_mask_compare.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
     L.emul_mask_compare.restype = ctypes.c_uint64

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Experiment builds of libmhx: tools/build_variants.sh name "DEFS" [name "DEFS" ...]
 #   -> auriclass_amd/lib_variants/<name>.so (git-ignored; travels to the GPU box), objects in csrc/_obj_<name>
-# Only mhx_kernels.hip is rebuilt per variant when MHX_ONLY_K is part of DEFS it compiles one k only (seconds).
+# Every object is built per variant (DEFS reaches all of them); with MHX_ONLY_K in DEFS mhx_sketch.hip, the one slow
+# file, compiles one k only (seconds).
 set -e
 cd "$(dirname "$0")/../auriclass_amd/csrc"
 mkdir -p ../lib_variants
