@@ -138,6 +138,13 @@ constexpr int kFastaTile = 16384;
 size_t fasta_workspace_bytes(uint64_t n, size_t *o_summary, size_t *o_in, size_t *o_off, size_t *o_flags);
 hipError_t launch_fasta_compact(const uint8_t *base, uint64_t n, uint8_t *ws, uint8_t *out, uint64_t *seps, uint32_t seps_cap, hipStream_t st);
 
+// segmented sketch (rules: mhx_segsketch.h, kernel: mhx_segsketch.hip): one workgroup per segment [seg_off[i], seg_off[i + 1])
+// of the MHX_FMT_SEQ stream `bytes`; segments of at most kSegCut windows get min(s, stride, distinct) ascending hashes in
+// rows[i][..] and their number in len[i], larger ones are left untouched (the host runs them through the sketcher).
+// The aligned dwords around every segment must be readable.
+hipError_t launch_segsketch(int k, const uint8_t *bytes, const uint64_t *seg_off, uint32_t n_seg, uint32_t s, uint64_t *rows,
+                            uint32_t *len, uint32_t stride, hipStream_t st);
+
 struct DistArgs {
     const uint64_t *q;
     const uint32_t *q_len;

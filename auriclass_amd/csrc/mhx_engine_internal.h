@@ -103,6 +103,18 @@ struct FastaCtx {
     uint64_t scale = 0;
 };
 
+// Segmented sketch (mhx_engine_segments.cpp), kept between calls: the staging of a host-pointer call (a round's bytes,
+// offsets, rows and lengths) and the sketcher that segments above the cut go through, one per (k, s), reset between them
+struct SegCtx {
+    DevArray<uint8_t> d_bytes;
+    DevArray<uint64_t> d_off, d_rows;
+    DevArray<uint32_t> d_len;
+    SketcherPtr sk;
+    int k = 0;
+    uint32_t s = 0;
+    uint64_t scale = 0;
+};
+
 // ---- engine state ---------------------------------------------------------------------
 // The streams come first: they are released last.  The one Engine (g) is never destroyed -- at exit the HIP runtime may
 // be gone already; mhx_shutdown releases everything while it is not.
@@ -125,6 +137,7 @@ struct Engine {
     PinnedArray<uint8_t> pinned[kPinnedSlots];
     HipEvent pinned_free[kPinnedSlots];
     FastaCtx fasta;
+    SegCtx seg;
     // chunked ingest (.gz FASTQ): pinned host buffers kept between calls, two device slots with their events, a pinned word
     static constexpr size_t kIngestPinnedKeep = 12;
     std::vector<PinnedArray<uint8_t>> ingest_pinned;
@@ -163,4 +176,10 @@ namespace mhx {
 mhx_sketcher *screener_prober(mhx_screener *sc);
 // "Estimated genome size" of a reads-mode sketch: 2^bits * n / largest hash (0 for an empty sketch)
 double set_size_estimate(int k, const uint64_t *hashes, size_t n);
+// Segmented sketch of a stream that lies on the device (the aligned dwords around it readable), offsets and results on the
+// host: segment i = [h_off[i], h_off[i + 1]) -- ascending and inside the stream, the caller has seen to that -- gets its
+// min(s, distinct) smallest hashes in h_rows[i][..] (stride >= min(s, the largest window count); zero behind h_len[i]).
+// (mhx_engine_segments.cpp; what mhx_sketch_segments and the file-level `mash sketch -i` share)
+int segments_resident(const uint8_t *d_bytes, const uint64_t *h_off, uint32_t n_seg, int k, uint32_t s, uint32_t stride, uint64_t *h_rows,
+                      uint32_t *h_len);
 } // namespace mhx

@@ -296,6 +296,55 @@ int parse_fastx(const uint8_t *buf, size_t n, int k, ParsedRecords &out)
     return MHX_OK;
 }
 
+// parse_fastx record by record (`mash sketch -i`): the same reading rules, but every record keeps its own header and its
+// place in the stream, short ones included; nothing stands between two records.
+int parse_fastx_records(const uint8_t *buf, size_t n, RecordList &out)
+{
+    size_t p = 0;
+    while (p < n && buf[p] != '>' && buf[p] != '@') ++p;
+    out.seq.reserve(out.seq.size() + (n - p) / 2 + 16);
+    if (out.off.empty()) out.off.push_back(out.seq.size());
+    while (p < n) {
+        size_t e = p + 1;
+        {
+            const uint8_t *nl = e < n ? (const uint8_t *)memchr(buf + e, '\n', n - e) : nullptr;
+            e = nl ? (size_t)(nl - buf) : n;
+        }
+        const size_t hdr_begin = p + 1;
+        size_t hdr_end = e;
+        if (hdr_end > hdr_begin && buf[hdr_end - 1] == '\r') --hdr_end;
+        p = e < n ? e + 1 : n;
+        const size_t seq_start = out.seq.size();
+        while (p < n && buf[p] != '>' && buf[p] != '@' && buf[p] != '+') {
+            const uint8_t *nl = (const uint8_t *)memchr(buf + p, '\n', n - p);
+            const size_t le = nl ? (size_t)(nl - buf) : n;
+            for (size_t q = p; q < le; ++q)
+                if (buf[q] > ' ' && buf[q] != 127) out.seq.push_back(buf[q]);
+            p = le < n ? le + 1 : n;
+        }
+        const size_t len = out.seq.size() - seq_start;
+        if (p < n && buf[p] == '+') {
+            while (p < n && buf[p] != '\n') ++p;
+            if (p < n) ++p;
+            size_t ql = 0;
+            while (p < n && ql < len) {
+                size_t le = p;
+                while (le < n && buf[le] != '\n') ++le;
+                for (size_t q = p; q < le; ++q) if (buf[q] > ' ' && buf[q] != 127) ++ql;
+                p = le < n ? le + 1 : n;
+            }
+            if (ql != len) return fail(MHX_E_FORMAT, "truncated quality string in FASTQ record %zu", out.name.size() + 1);
+            while (p < n && buf[p] != '>' && buf[p] != '@') ++p;
+        }
+        size_t sp = hdr_begin;
+        while (sp < hdr_end && buf[sp] != ' ' && buf[sp] != '\t') ++sp;
+        out.name.emplace_back(reinterpret_cast<const char *>(buf + hdr_begin), sp - hdr_begin);
+        out.comment.emplace_back(sp < hdr_end ? std::string(reinterpret_cast<const char *>(buf + sp + 1), hdr_end - sp - 1) : std::string());
+        out.off.push_back(out.seq.size());
+    }
+    return MHX_OK;
+}
+
 } // namespace mhx
 
 // ---- C ABI: sniffers and FASTA size (replace the pyfastx calls of the reference) ----------

@@ -970,7 +970,9 @@ static int ensure_fasta_buffers(uint64_t n)
 // Only for files that pass fasta_for_device, with ensure_fasta_buffers(n) done.  which: the raw buffer of this file
 // (d_raw[which]); on_device: the loader has already copied the bytes there on the copy stream (raw_ready[which] says when)
 static bool fasta_for_device(const uint8_t *raw, uint64_t n) { return n != 0 && raw[0] == '>' && n <= 0x7FFFFFFF00ull; }
-static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, int k, uint32_t s, std::vector<uint64_t> &hashes, FastaInfo &info)
+// the first half: raw bytes -> the dense stream in g.fasta.d_out (`total` bytes) and the sorted positions of the record
+// separators in it (separator i sits in front of record i)
+static int fasta_stream_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, std::vector<uint64_t> &seps, uint64_t &total)
 {
     FastaCtx &c = g.fasta;
     size_t os, oi, oo, of;
@@ -979,7 +981,7 @@ static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, boo
     uint8_t *d_raw = c.d_raw[which & 1];
     if (on_device) HIPCHK(hipStreamWaitEvent(g.stream, c.raw_ready[which & 1], 0));
     else HIPCHK(hipMemcpyAsync(d_raw, raw, n, hipMemcpyHostToDevice, g.stream));
-    uint64_t total = 0;
+    total = 0;
     uint32_t nsep = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         const uint32_t seps_cap = (uint32_t)c.d_seps.cap();
@@ -1000,13 +1002,23 @@ static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, boo
         if (c.d_seps.grow(want) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for %u FASTA record positions", want);
     }
     // records: separator i sits in front of record i; its length is the distance to the next separator (or the end)
-    std::vector<uint64_t> seps(nsep);
+    seps.assign(nsep, 0);
     if (nsep && nsep <= kFastaSepsInline) memcpy(seps.data(), &c.h_words[2], (size_t)nsep * 8);
     else if (nsep) {
         HIPCHK(hipMemcpyAsync(seps.data(), c.d_seps, seps.size() * 8, hipMemcpyDeviceToHost, g.stream));
         HIPCHK(hipStreamSynchronize(g.stream));
     }
     std::sort(seps.begin(), seps.end());
+    return MHX_OK;
+}
+
+static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, int k, uint32_t s, std::vector<uint64_t> &hashes, FastaInfo &info)
+{
+    FastaCtx &c = g.fasta;
+    std::vector<uint64_t> seps;
+    uint64_t total = 0;
+    const int src = fasta_stream_on_device(raw, n, which, on_device, seps, total);
+    if (src) return src;
     info = FastaInfo();
     uint64_t first_counted = ~0ull;
     for (size_t i = 0; i < seps.size(); ++i) {
@@ -1314,6 +1326,140 @@ static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, u
     rc = msh_write_file(out_msh, set);
     if (rc) return rc;
     return put_text(err, stderr_buf, stderr_cap, stderr_need);
+}
+
+// `mash sketch -i`: one reference per RECORD.  Either route lays a file out as a dense stream plus record offsets and ends
+// in the segmented sketch (mhx_engine_segments.cpp): plain FASTA through the device parser, whose separator positions are
+// the offsets (the separator byte in front of a record is a newline: part of the segment, never of a window); anything
+// else through the host record parser.  Records shorter than k are left out; a file from which none remains fails as it
+// does in the per-file mode.
+namespace {
+// every header line of a plain FASTA held in memory, in order (header i belongs to separator i of the device parser)
+void fasta_headers(const uint8_t *b, size_t n, std::vector<std::string> &names, std::vector<std::string> &comments)
+{
+    size_t p = 0;
+    while (p < n) {
+        const uint8_t *e = (const uint8_t *)memchr(b + p, '\n', n - p);
+        const size_t le = e ? (size_t)(e - b) : n;
+        if (b[p] == '>') {
+            names.emplace_back();
+            comments.emplace_back();
+            first_header(b + p, le - p, names.back(), comments.back());
+        }
+        p = le + 1;
+    }
+}
+
+constexpr uint64_t kIndividualRowsRound = 64ull << 20; // bytes of result rows on the host at a time
+
+// The records of one file -- record i = [off[i] + lead, off[i + 1]) of the stream, which lies on the device (d_stream) or on
+// the host (h_stream) -- sketched in rounds and appended to `set`; returns the number of references added in *added.
+int sketch_records(const uint8_t *d_stream, const uint8_t *h_stream, uint64_t stream_n, const std::vector<uint64_t> &off, uint64_t lead,
+                   const std::vector<std::string> &names, const std::vector<std::string> &comments, int k, uint32_t s, SketchSet &set,
+                   uint64_t *added)
+{
+    *added = 0;
+    const size_t nrec = off.empty() ? 0 : off.size() - 1;
+    if (nrec > 0x7FFFFFFFull) return fail(MHX_E_ARG, "too many records in one file (%zu)", nrec);
+    uint64_t max_w = 0;
+    for (size_t i = 0; i < nrec; ++i) max_w = std::max<uint64_t>(max_w, off[i + 1] - off[i] >= (uint64_t)k ? off[i + 1] - off[i] - (uint64_t)k + 1 : 0);
+    const uint32_t stride = (uint32_t)std::min<uint64_t>(s, max_w);
+    if (stride == 0) return MHX_OK; // no record of k bytes
+    const size_t per_round = (size_t)std::max<uint64_t>(1, kIndividualRowsRound / ((uint64_t)stride * sizeof(uint64_t)));
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> len;
+    for (size_t i0 = 0; i0 < nrec; i0 += per_round) {
+        const uint32_t cnt = (uint32_t)std::min(per_round, nrec - i0);
+        rows.resize((size_t)cnt * stride);
+        len.resize(cnt);
+        const int rc = d_stream ? segments_resident(d_stream, off.data() + i0, cnt, k, s, stride, rows.data(), len.data())
+                                : mhx_sketch_segments(h_stream, stream_n, off.data() + i0, cnt, k, s, rows.data(), len.data(), stride, 0);
+        if (rc) return rc;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const size_t i = i0 + j;
+            const uint64_t length = off[i + 1] - off[i] - lead;
+            if (off[i + 1] - off[i] < lead || length < (uint64_t)k) continue; // mash does not count a record shorter than k
+            RefSketch ref;
+            if (i < names.size()) { ref.name = names[i]; ref.comment = comments[i]; }
+            ref.length = length;
+            ref.hashes.assign(rows.data() + (size_t)j * stride, rows.data() + (size_t)j * stride + len[j]);
+            set.refs.push_back(std::move(ref));
+            ++*added;
+        }
+    }
+    return MHX_OK;
+}
+} // namespace
+
+static int mhx_sketch_files_individual_impl(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh, char *stderr_buf,
+                                            size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
+    for (int i = 0; i < n_paths; ++i)
+        if (!paths[i]) return fail(MHX_E_ARG, "sketch: input path %d is null", i);
+    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+    if (s == 0) return fail(MHX_E_ARG, "sketch: sketch size 0");
+    SketchSet set;
+    set.kmer_size = (uint32_t)k;
+    set.sketch_size = s;
+    std::string err;
+    std::vector<uint8_t> raw;
+    for (int i = 0; i < n_paths; ++i) {
+        err += std::string("Sketching ") + paths[i] + "...\n";
+        rc = read_all_maybe_gz(paths[i], raw);
+        if (rc) return rc;
+        uint64_t added = 0;
+        bool done = false;
+        if (!getenv("MHX_HOST_FASTA") && fasta_for_device(raw.data(), raw.size())) { // plain FASTA: parsed on the device
+            rc = ensure_fasta_buffers(raw.size());
+            if (rc) return rc;
+            std::vector<uint64_t> off;
+            uint64_t total = 0;
+            rc = fasta_stream_on_device(raw.data(), raw.size(), 0, false, off, total);
+            if (rc < 0) return rc;
+            if (rc == MHX_OK) {
+                off.push_back(total);
+                std::vector<std::string> names, comments;
+                fasta_headers(raw.data(), raw.size(), names, comments);
+                rc = sketch_records(g.fasta.d_out, nullptr, total, off, 1, names, comments, k, s, set, &added);
+                if (rc) return rc;
+                done = true;
+            }
+        }
+        if (!done) { // FASTQ, a file that does not start with '>', ...: the host record parser
+            RecordList rec;
+            rc = parse_fastx_records(raw.data(), raw.size(), rec);
+            if (rc) return rc;
+            if (rec.off.empty()) rec.off.push_back(0);
+            rc = sketch_records(nullptr, rec.seq.data(), rec.seq.size(), rec.off, 0, rec.name, rec.comment, k, s, set, &added);
+            if (rc) return rc;
+        }
+        if (added == 0) {
+            err += std::string("ERROR: Did not find fasta records in \"") + paths[i] + "\".\n";
+            put_text(err, stderr_buf, stderr_cap, stderr_need);
+            return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", paths[i]);
+        }
+    }
+    err += std::string("Writing to ") + out_msh + "...\n";
+    rc = msh_write_file(out_msh, set);
+    if (rc) return rc;
+    if (n_refs_out) *n_refs_out = set.refs.size();
+    return put_text(err, stderr_buf, stderr_cap, stderr_need);
+}
+
+extern "C" int mhx_sketch_files_individual(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh, char *stderr_buf,
+                                           size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out)
+{
+    try {
+        return mhx_sketch_files_individual_impl(paths, n_paths, k, s, out_msh, stderr_buf, stderr_cap, stderr_need, n_refs_out);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_sketch_files_individual: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_sketch_files_individual: %s", e.what());
+    }
 }
 
 // `mash dist REF QUERY [QUERY ...]`: mhx_dist_files is the n_qry == 1 case.  The reference file is read, parsed, checked and

@@ -64,6 +64,13 @@ struct ParsedRecords {
 };
 // kseq-compatible record reader over an inflated buffer (FASTA, FASTQ, multi-line either)
 int parse_fastx(const uint8_t *buf, size_t n, int k, ParsedRecords &out);
+// the same reader, record by record: every record of the buffer, shorter ones too, with its own header
+struct RecordList {
+    std::vector<uint8_t> seq;   // the bases of all records back to back (MHX_FMT_SEQ), nothing between two records
+    std::vector<uint64_t> off;  // record i is seq[off[i] .. off[i + 1]); one entry more than there are records
+    std::vector<std::string> name, comment;
+};
+int parse_fastx_records(const uint8_t *buf, size_t n, RecordList &out);
 bool looks_like_fastq4(const uint8_t *buf, size_t n);
 void first_header(const uint8_t *buf, size_t n, std::string &name, std::string &comment);
 

@@ -147,6 +147,13 @@ def load() -> ctypes.CDLL:
         L.mhx_screener_finish_winner.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(c.c_double), c.c_void_p]
         L.mhx_screen_files_opts.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ScreenOpts), c.c_char_p, c.c_size_t,
                                             c.POINTER(c.c_size_t), c.POINTER(c.c_double)]
+    if hasattr(L, "mhx_sketch_segments"):   # (or older than the segmented sketch, `mash sketch -i`)
+        L.mhx_sketch_segments.argtypes = [c.c_void_p, c.c_uint64, c.c_void_p, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p,
+                                          c.c_uint32, c.c_int]
+        L.mhx_sketch_segments_cut.argtypes = []
+        L.mhx_sketch_segments_cut.restype = c.c_uint32
+        L.mhx_sketch_files_individual.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.c_int, c.c_uint32, c.c_char_p, c.c_char_p,
+                                                  c.c_size_t, c.POINTER(c.c_size_t), u64p]
     _lib = L
     return L
 
@@ -199,8 +206,13 @@ def _text_call(fn, *args, guess: int = 1 << 16) -> str:
 
 
 # --------------------------------------------------------------------------- file level
-def sketch_files(paths: Sequence, k: int, s: int, out_msh, reads: bool = False, min_mult: int = 1) -> Tuple[str, float]:
-    """`mash sketch [-r -m M] -o OUT -k K -s S paths...` -> (stderr text, estimated genome size)."""
+def sketch_files(paths: Sequence, k: int, s: int, out_msh, reads: bool = False, min_mult: int = 1, individual: bool = False
+                 ) -> Tuple[str, float]:
+    """`mash sketch [-r -m M | -i] -o OUT -k K -s S paths...` -> (stderr text, estimated genome size).
+    individual: one reference per record of every file (`-i`, mhx_sketch_files_individual) instead of one per file; not
+    together with reads."""
+    if individual and reads:
+        raise ValueError("sketch_files: individual=True (-i) cannot be combined with reads=True (-r)")
     init()
     L = load()
     arr = (ctypes.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
@@ -208,8 +220,11 @@ def sketch_files(paths: Sequence, k: int, s: int, out_msh, reads: bool = False, 
     est = ctypes.c_double(0.0)
     cap = 4096 + sum(len(str(p)) for p in paths) * 2 + len(str(out_msh))
     buf = ctypes.create_string_buffer(cap)
-    rc = L.mhx_sketch_files(arr, len(paths), k, s, int(reads), min_mult, os.fsencode(str(out_msh)), buf, cap,
-                            ctypes.byref(need), ctypes.byref(est))
+    if individual:
+        rc = L.mhx_sketch_files_individual(arr, len(paths), k, s, os.fsencode(str(out_msh)), buf, cap, ctypes.byref(need), None)
+    else:
+        rc = L.mhx_sketch_files(arr, len(paths), k, s, int(reads), min_mult, os.fsencode(str(out_msh)), buf, cap,
+                                ctypes.byref(need), ctypes.byref(est))
     if rc == MHX_E_NO_RECORDS:
         raise NoRecordsError(rc, L.mhx_last_error().decode())
     _check(rc)
@@ -644,6 +659,40 @@ def dist_batch(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarra
     _check(load().mhx_dist_batch(q.ctypes.data, q_len.ctypes.data, nq, r.ctypes.data, r_len.ctypes.data, nr, stride,
                                  k, s, common.ctypes.data, denom.ctypes.data, dist.ctypes.data, 0))
     return common, denom, dist
+
+
+def sketch_segments_cut() -> int:
+    """L of sketch_segments: segments of up to L windows are sketched together by one launch, larger ones one by one."""
+    return int(load().mhx_sketch_segments_cut())
+
+
+def sketch_segments(data, seg_off, k: int, s: int, stride: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """One bottom-s list per segment of a dense sequence stream (`mash sketch -i` at buffer level, mhx_sketch_segments):
+    data is the MHX_FMT_SEQ stream (bytes or a uint8 array), seg_off the n_seg + 1 ascending byte offsets of the segments.
+    Returns (rows [n_seg, stride] uint64, len [n_seg] uint32): row i holds the len[i] = min(s, distinct) smallest hashes of
+    segment i, ascending, zero behind them -- as dist_batch and Screener take them.  stride: min(s, the largest window
+    count of a segment) unless given (a smaller one raises EngineError(MHX_E_ARG))."""
+    init()
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    off = np.ascontiguousarray(seg_off, dtype=np.uint64).reshape(-1)
+    n_seg = max(0, off.size - 1)
+    if stride is None:
+        span = np.diff(off.astype(np.int64)) if n_seg else np.zeros(0, np.int64)
+        stride = int(min(s, max(0, int(span.max()) - k + 1))) if n_seg else 0
+    rows = np.zeros((n_seg, stride), dtype=np.uint64)
+    lens = np.zeros(n_seg, dtype=np.uint32)
+    _check(load().mhx_sketch_segments(a.ctypes.data, a.size, off.ctypes.data, n_seg, k, s, rows.ctypes.data, lens.ctypes.data, stride, 0))
+    return rows, lens
+
+
+def sketch_segments_device(bytes_ptr: int, nbytes: int, seg_off_ptr: int, n_seg: int, k: int, s: int, rows_ptr: int, len_ptr: int,
+                           stride: int) -> None:
+    """Device pointers in and out (see mhx_sketch_segments for what must be readable around the stream); complete when it
+    returns.  rows_ptr / len_ptr can go straight into dist_batch_device or a screener built with device pointers."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_sketch_segments(v(bytes_ptr), nbytes, v(seg_off_ptr), n_seg, k, s, v(rows_ptr), v(len_ptr), stride, 1))
 
 
 def dist_batch_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_ptr: int, nr: int, stride: int, k: int, s: int,

@@ -2,7 +2,8 @@
 `mash` launcher (auriclass_amd/bin) first on PATH and the reference's five subprocess call sites
 (/root/reference/auriclass/general.py:198-205 `mash -h`; classes.py:576-596 and 696-706
 `mash sketch`; classes.py:92-97 `mash dist`; classes.py:305-312 `mash bounds`) run on the GPU
-engine.  `mash screen REF.msh reads...` (containment; AuriClass itself does not call it) is served too.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
+engine.  `mash screen REF.msh reads...` (containment) and `mash sketch -i` (one sketch per sequence of a file: how a
+reference set is made from one multi-FASTA) are served too; AuriClass itself calls neither.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
 codes follow mash (sketch: exit 1 with 'ERROR: Did not find fasta records in ...')."""
 from __future__ import annotations
 
@@ -53,6 +54,12 @@ def main(argv: List[str] = None) -> int:
             reads = "-r" in args
             if reads:
                 args.remove("-r")
+            individual = "-i" in args
+            if individual:
+                args.remove("-i")
+            if individual and reads:
+                sys.stderr.write("ERROR: mash sketch -i (one sketch per sequence) cannot be combined with -r in the mhx shim\n")
+                return 1
             m = _take(args, "-m", 1, int)
             out = _take(args, "-o", None)
             k = _take(args, "-k", 21, int)
@@ -63,7 +70,7 @@ def main(argv: List[str] = None) -> int:
             if not out.endswith(".msh"):
                 out += ".msh"
             try:
-                text, _ = engine.sketch_files(args, k, s, out, reads=reads, min_mult=m if reads else 1)
+                text, _ = engine.sketch_files(args, k, s, out, reads=reads, min_mult=m if reads else 1, individual=individual)
             except engine.NoRecordsError as exc:
                 sys.stderr.write("\n" + exc.message + "\n")
                 return 1

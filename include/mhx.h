@@ -7,6 +7,8 @@
  *
  *   mhx_sketch_files  <- `mash sketch [-r -m M] -o OUT -k K -s S files...`
  *                        auriclass/classes.py:576-596 (FASTQ) and :696-713 (FASTA)
+ *   mhx_sketch_files_individual <- `mash sketch -i -o OUT -k K -s S files...` (not called by AuriClass: how a reference
+ *                        set is made from one multi-FASTA, docs/faq.md "I want to build my own database")
  *   mhx_dist_files    <- `mash dist REF.msh QUERY.msh`      auriclass/classes.py:92-104
  *   mhx_dist_files_multi <- `mash dist REF.msh QUERY.msh [QUERY.msh ...]` (a run of samples, one call)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
@@ -79,6 +81,22 @@ int mhx_device_name(char *buf, size_t cap);
 int mhx_sketch_files(const char *const *paths, int n_paths, int k, uint32_t s, int reads,
                      uint32_t min_mult, const char *out_msh, char *stderr_buf, size_t stderr_cap,
                      size_t *stderr_need, double *est_genome_size);
+
+/* `mash sketch -i -k K -s S -o OUT files...`: one reference per RECORD, in file order and then record order -- what a
+ * reference set for mhx_dist_files / mhx_screen_files is built from when it ships as one multi-FASTA.  name = the record's
+ * header up to the first blank, comment = the rest of the header, length = the record's sequence length, hashes = the
+ * min(s, distinct) smallest hashes of the record's own windows.  stderr_buf receives the text of
+ * mhx_sketch_files(..., reads = 0, ...), *n_refs_out (may be NULL) the number of references written.
+ *   - A record shorter than k is left out (the per-file mode does not count it either).
+ *   - A record of at least k bytes without one valid window (all N) is kept, with an empty hash list (the per-file mode
+ *     keeps a file of such records too).
+ *   - A file from which no record remains fails with MHX_E_NO_RECORDS and mash's message.
+ * Plain FASTA is parsed on the device, everything else kseq reads (FASTQ, files that do not start with '>') by the host
+ * record parser; gzip and BGZF as everywhere.  Both routes end in mhx_sketch_segments.
+ * Not pinned by mash output (none is recorded for -i): the result is the oracle's sketch applied record by record; the
+ * two record rules above are ours where Mash's source leaves room.  DESIGN.md section 6. */
+int mhx_sketch_files_individual(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh,
+                                char *stderr_buf, size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out);
 
 /* `mash dist REF QUERY` stdout: rows "ref\tquery\tdist\tp\tcommon/denom\n", query-major. */
 int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need);
@@ -266,6 +284,27 @@ int mhx_last_dist_fallback_blocks(void);
  * from q_len / r_len, from `stride` when they are device pointers).  0 = the generic pair kernel did all the work: a tiny
  * batch, lists of more than 2^20 hashes, or every block gave up */
 int mhx_last_dist_ranges(void);
+
+/* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
+ * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is
+ * [seg_off[i], seg_off[i + 1]).  A window is k bytes that lie inside ONE segment and are all A/C/G/T (either case); it is
+ * hashed as an MHX_FMT_SEQ push hashes it (canonical strand, MurmurHash3_x64_128 seed 42, 32-bit values for k <= 16).
+ * Segments may touch: the cut is seg_off, no separator byte is needed between them.
+ * rows[n_seg][stride], len[n_seg]: row i receives the min(s, distinct) smallest distinct hashes of segment i, ascending,
+ * without multiplicities, len[i] their number -- the layout mhx_dist_batch and mhx_screener_create take, so a result can
+ * feed either without leaving the device.  Entries behind len[i] are zero with host pointers and left as they were with
+ * device pointers.  n_seg = 0 is MHX_OK; an empty segment or one shorter than k gives len[i] = 0.
+ * MHX_E_ARG: k outside 1..32, s = 0, offsets that descend or pass n, stride < min(s, the largest number of k-byte
+ * windows of any segment).
+ * device_ptrs != 0 => bytes, seg_off, rows and len are device pointers; the stream must be readable from the 4-byte boundary
+ * at or before bytes to the next 16-byte boundary past bytes + n (true for any hipMalloc / torch allocation).  Complete
+ * when it returns, either way.
+ * Segments of at most mhx_sketch_segments_cut() windows are sketched together by one kernel launch (a workgroup each, sort
+ * and selection in LDS: exact by construction, no admission threshold); larger ones go one by one through a sketcher on
+ * their slice.  With host pointers the stream and the rows are staged on the device in rounds of bounded size. */
+int mhx_sketch_segments(const void *bytes, uint64_t n, const uint64_t *seg_off, uint32_t n_seg, int k, uint32_t s,
+                        uint64_t *rows, uint32_t *len, uint32_t stride, int device_ptrs);
+uint32_t mhx_sketch_segments_cut(void); /* L: the most windows a segment of the one-launch route may hold */
 
 /* scalar pieces of the dist row (host): mash pValue() */
 double mhx_p_value(uint64_t common, uint64_t len_ref, uint64_t len_qry, int k, uint64_t denom);
