@@ -176,5 +176,31 @@ struct DistWork {
 // workspace of one (query batch, reference slice) block; with ranges == kDistRanges the layout of the base form (no wtot)
 size_t dist_work_bytes(uint32_t nq, uint32_t nr, uint32_t ranges, size_t *off_q, size_t *off_r, size_t *off_c, size_t *off_w, size_t *off_p);
 hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t st);
+// The passes of the windowed form one by one (R = w.ranges, any power of two >= 16), for a caller whose offs_q and offs_r
+// point into ONE [list][R + 1] table of a whole set: shift + split of the a.nq lists of a.q (a.nr = 0) into w.offs_q; the
+// range pass of one block; the finish pass of one block with R >= 1024 (below: launch_tri_finish_small).
+hipError_t launch_dist_offsets(const DistArgs &a, const DistWork &w, hipStream_t st);
+hipError_t launch_dist_range_pass(const DistArgs &a, const DistWork &w, hipStream_t st);
+hipError_t launch_dist_finish(const DistArgs &a, const DistWork &w, hipStream_t st);
+
+// all pairs within one set (rules: mhx_triangle.h, kernels: mhx_triangle.hip).  A block's results lie block-local in
+// loc_common / loc_denom [nq][32]; `flag` is the block's overflow word (non-zero: the results are not there, nothing is done).
+struct TriOut {
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;
+    uint32_t r0, nr, q0, nq; // the block (mhx_triangle.h: TriBlock)
+    int k;
+    // dense mode: packed outputs at tri_index(q, r)
+    uint32_t *common, *denom;
+    double *dist;            // may be null
+    // edge mode: pairs that count and pass tri_keep(., ., jmin) are appended through *count; beyond cap they are only counted
+    uint32_t *edge_i, *edge_j;
+    unsigned long long *count;
+    uint64_t cap;
+    double jmin;
+};
+hipError_t launch_tri_finish_small(const DistArgs &a, const DistWork &w, hipStream_t st); // 16 <= w.ranges < 1024
+hipError_t launch_tri_scatter(const TriOut &o, hipStream_t st);
+hipError_t launch_tri_edges(const TriOut &o, hipStream_t st);
 
 } // namespace mhx

@@ -744,4 +744,49 @@ hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t 
     return hipGetLastError();
 }
 
+// ---- the passes one by one, for a caller that keeps ONE offsets table for a whole set (mhx_triangle.hip) ------------------
+// The windowed kernels take R = w.ranges as a launch parameter and work for any power of two R >= 16 when offs_q and offs_r
+// point into the same [list][R + 1] table.  The entry points above do not come through here.
+hipError_t launch_dist_offsets(const DistArgs &a, const DistWork &w, hipStream_t st)
+{ // shift (w.params[0]; [1] = 0) and offsets of the a.nq lists of a.q into w.offs_q; a.nr must be 0
+    if (a.nq == 0) return hipSuccess;
+    hipLaunchKernelGGL(dist_shift_kernel<true>, dim3(1), dim3(256), 0, st, a, w);
+    const uint64_t per = (uint64_t)w.ranges + 1;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(a.nq, 0xFFFFFFFFull / per); // list * (R + 1) stays below 2^32 in the kernel
+    for (uint32_t c0 = 0; c0 < a.nq; c0 += chunk) {
+        DistArgs x = a;
+        DistWork y = w;
+        x.q = a.q + (uint64_t)c0 * a.stride;
+        x.q_len = a.q_len + c0;
+        x.nq = std::min(chunk, a.nq - c0);
+        y.offs_q = w.offs_q + (uint64_t)c0 * per;
+        hipLaunchKernelGGL(dist_split_kernel<true>, dim3(x.nq, (a.stride + 511) / 512), dim3(256), 0, st, x, y, 0u);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_range_pass(const DistArgs &a, const DistWork &w, hipStream_t st)
+{ // the range pass of one block (a.nr <= 32): byte counters into w.cpart, the overflow flag into w.params[1]
+    const uint32_t R = w.ranges;
+    if (a.nq >= 128 && getenv("MHX_DIST_NO_LANE") == nullptr)
+        hipLaunchKernelGGL(dist_range_lane_kernel<true>, dim3(R, (a.nq + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, a, w);
+    else {
+        const uint32_t chunks = std::min<uint32_t>(kDistQueryChunks, (a.nq + 31) / 32);
+        hipLaunchKernelGGL(dist_range_kernel<true>, dim3(R, chunks), dim3(256), 0, st, a, w);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_finish(const DistArgs &a, const DistWork &w, hipStream_t st)
+{ // the finish pass of one block with R >= 1024: the base kernel at 1024 (it does not read w.wtot), window totals + wide above
+    const uint32_t R = w.ranges, pairs = a.nq * a.nr;
+    if (R == (uint32_t)kDistRanges) hipLaunchKernelGGL(dist_finish_kernel, dim3((pairs + 15) / 16), dim3(256), 0, st, a, w);
+    else {
+        const uint32_t cells = a.nq * (R / kDistWindowRanges) * ((a.nr + 3) / 4);
+        hipLaunchKernelGGL(dist_window_kernel, dim3((cells + 255) / 256), dim3(256), 0, st, a, w);
+        hipLaunchKernelGGL(dist_finish_wide_kernel, dim3((pairs + 15) / 16), dim3(256), 0, st, a, w);
+    }
+    return hipGetLastError();
+}
+
 } // namespace mhx

@@ -23,15 +23,17 @@ extern "C" int mhx_last_dist_ranges(void) { return g.last_dist_ranges; }
 
 // Persistent device staging of the host-pointer form (one buffer, grown on demand): six hipMalloc / hipFree pairs per
 // call cost more than the kernels of an AuriClass-sized comparison (1 query x 24 references).
-static int dist_stage(size_t bytes, uint8_t **out)
+namespace mhx {
+int dist_stage(size_t bytes, uint8_t **out)
 {
     if (g.dist_in.cap() < bytes) {
         const size_t cap = (bytes + bytes / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-        if (g.dist_in.grow(cap, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed in dist_batch (%zu bytes)", cap);
+        if (g.dist_in.grow(cap, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the distance staging area (%zu bytes)", cap);
     }
     *out = g.dist_in;
     return MHX_OK;
 }
+} // namespace mhx
 
 // q_rows / r_rows (host form only): the rows where they lie, one pointer each (q / r are then unused) -- mhx_dist_files
 // hands over the hash lists inside its pinned image of the reference sketch file instead of building padded matrices

@@ -149,6 +149,8 @@ struct Engine {
 };
 extern Engine &g;
 int require_engine();
+// room for `bytes` in g.dist_in, the device staging of a host-pointer distance call (mhx_engine_dist.cpp; the triangle's too)
+int dist_stage(size_t bytes, uint8_t **out);
 
 } // namespace mhx
 

@@ -1,0 +1,299 @@
+// mhx_engine_triangle.cpp -- host side of the all-pairs distance within one sketch set (mhx_dist_triangle and
+// mhx_dist_triangle_edges): staging of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE
+// offsets table of the whole set, the fallback of a flagged block to the generic pair kernel, and the exact distance rule
+// and the order of the edge list on the host.  Rules: mhx_triangle.h; kernels: mhx_triangle.hip and mhx_dist.hip.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <exception>
+#include <new>
+#include <numeric>
+#include <vector>
+
+#include "mhx_device.h"
+#include "mhx_triangle.h"
+#include "mhx_engine_internal.h"
+#include "mhx_internal.h"
+
+using namespace mhx;
+
+namespace {
+
+struct TriCall { // everything on the device
+    const uint64_t *rows;
+    const uint32_t *len;
+    uint32_t n, stride, s, longest;
+    int k;
+    bool edges;
+    uint32_t *common, *denom; // dense: packed triangle; edges: [cap]
+    double *dist;             // may be null
+    uint32_t *edge_i, *edge_j;
+    uint64_t cap;
+    double jmin;
+    uint64_t found; // out, edge mode: pairs that passed the prefilter
+};
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Launches the whole call on the engine's stream and waits for it.  The set's lists are split into value ranges ONCE
+// (launch_dist_offsets over all n lists); every block then runs the range pass and a finish pass into its block-local
+// [queries][32] results, and the scatter or the edge pass takes the pairs that count from there.  Block flags come back
+// once per group of blocks; a flagged block is redone by the generic pair kernel into the same block-local arrays.
+int triangle_device(TriCall &c)
+{
+    const uint64_t pairs = (uint64_t)c.n * (c.n - 1) / 2;
+    const char *geo = getenv("MHX_TRI_GEOMETRY");
+    const uint32_t ranges = geo && strcmp(geo, "dist") == 0 ? tri_ranges_dist(c.longest) : tri_ranges(c.longest);
+    const bool fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)c.s >= 400000)) && ranges != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
+    uint32_t qbatch = tri_max_queries(fast ? ranges : kTriMinRanges);
+    if (const char *e = getenv("MHX_TRI_QBATCH")) { const long v = atol(e); if (v > 0 && (uint64_t)v < qbatch) qbatch = (uint32_t)v; }
+    qbatch = std::min(qbatch, c.n);
+    std::vector<TriBlock> blocks;
+    {
+        TriBlock b;
+        for (bool more = tri_first_block(c.n, qbatch, b); more; more = tri_next_block(c.n, qbatch, b)) blocks.push_back(b);
+    }
+    const uint32_t nblocks = (uint32_t)blocks.size();
+    constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together
+    const uint32_t group = std::min(nblocks, kBlockGroup);
+    // workspace: [offsets of the set][byte counters][window totals][block-local common, denom][words: shift, 0, the edge
+    // counter (two words), then two per block of a group]
+    const uint64_t per = (uint64_t)ranges + 1;
+    size_t o = 0;
+    const size_t o_offs = o; if (fast) o += up256((size_t)c.n * per * 4);
+    const size_t o_cpart = o; if (fast) o += up256((size_t)qbatch * ranges * kTriSlice);
+    const size_t o_wtot = o; if (fast && ranges > (uint32_t)kDistRanges) o += up256((size_t)qbatch * (ranges / kDistWindowRanges) * kTriSlice * 4);
+    const size_t o_lc = o; o += up256((size_t)qbatch * kTriSlice * 4);
+    const size_t o_ld = o; o += up256((size_t)qbatch * kTriSlice * 4);
+    const size_t o_words = o; o += up256((size_t)(4 + 2 * group) * 4);
+    if (g.dist_ws.grow(o, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the triangle workspace (%zu bytes)", o);
+    uint32_t *offs = (uint32_t *)(g.dist_ws + o_offs), *loc_c = (uint32_t *)(g.dist_ws + o_lc), *loc_d = (uint32_t *)(g.dist_ws + o_ld);
+    uint32_t *words = (uint32_t *)(g.dist_ws + o_words), *flags = words + 4;
+    unsigned long long *counter = (unsigned long long *)(words + 2);
+    DistWork w{};
+    w.cpart = g.dist_ws + o_cpart;
+    w.wtot = (uint32_t *)(g.dist_ws + o_wtot);
+    w.ranges = ranges;
+    DistArgs all{};
+    all.q = c.rows; all.q_len = c.len; all.nq = c.n; all.nr = 0; all.stride = c.stride; all.s = c.s; all.k = c.k;
+    auto block_args = [&](const TriBlock &b) {
+        DistArgs x = all;
+        x.q = c.rows + (uint64_t)b.q0 * c.stride; x.q_len = c.len + b.q0; x.nq = b.nq;
+        x.r = c.rows + (uint64_t)b.r0 * c.stride; x.r_len = c.len + b.r0; x.nr = b.nr;
+        x.common = loc_c; x.denom = loc_d; x.dist = nullptr; x.out_stride = kTriSlice; x.out_off = 0;
+        return x;
+    };
+    auto take_out = [&](const TriBlock &b, const uint32_t *flag) {
+        TriOut t{};
+        t.loc_common = loc_c; t.loc_denom = loc_d; t.flag = flag;
+        t.r0 = b.r0; t.nr = b.nr; t.q0 = b.q0; t.nq = b.nq; t.k = c.k;
+        t.common = c.common; t.denom = c.denom; t.dist = c.dist;
+        t.edge_i = c.edge_i; t.edge_j = c.edge_j; t.count = counter; t.cap = c.cap; t.jmin = c.jmin;
+        return c.edges ? launch_tri_edges(t, g.stream) : launch_tri_scatter(t, g.stream);
+    };
+    hipEventRecord(g.ev0, g.stream);
+    hipError_t le = hipMemsetAsync(words, 0, (size_t)(4 + 2 * group) * 4, g.stream);
+    g.last_dist_fallbacks = fast ? 0 : -1;
+    g.last_dist_ranges = 0;
+    if (fast && le == hipSuccess) {
+        DistWork wa = w;
+        wa.offs_q = offs; wa.offs_r = offs; wa.params = words; // words[0] the shift of the call, words[1] stays 0
+        le = launch_dist_offsets(all, wa, g.stream);
+    }
+    for (uint32_t b0 = 0; b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
+        const uint32_t b1 = std::min(nblocks, b0 + kBlockGroup);
+        if (b0 != 0) le = hipMemsetAsync(flags, 0, (size_t)2 * group * 4, g.stream);
+        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b) {
+            const TriBlock &blk = blocks[b];
+            const DistArgs x = block_args(blk);
+            if (!fast) {
+                le = launch_dist_pairs(x, g.stream);
+                if (le == hipSuccess) le = take_out(blk, words + 1);
+                continue;
+            }
+            w.offs_q = offs + (uint64_t)blk.q0 * per;
+            w.offs_r = offs + (uint64_t)blk.r0 * per;
+            w.params = flags + 2 * (b - b0);
+            le = launch_dist_range_pass(x, w, g.stream);
+            if (le == hipSuccess) le = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
+            if (le == hipSuccess) le = take_out(blk, w.params + 1);
+        }
+        if (!fast || le != hipSuccess) continue;
+        std::vector<uint32_t> back((size_t)(b1 - b0) * 2);
+        if (hipMemcpyAsync(back.data(), flags, back.size() * 4, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+            hipStreamSynchronize(g.stream) != hipSuccess)
+            return fail(MHX_E_HIP, "triangle kernel failed");
+        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b)
+            if (back[2 * (b - b0) + 1]) { // a value range overflowed the LDS table or the byte counters
+                le = launch_dist_pairs(block_args(blocks[b]), g.stream);
+                if (le == hipSuccess) le = take_out(blocks[b], words + 1);
+                ++g.last_dist_fallbacks;
+            }
+    }
+    hipEventRecord(g.ev1, g.stream);
+    if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
+    if (le != hipSuccess) return fail(MHX_E_HIP, "triangle kernel launch failed: %s", hipGetErrorString(le));
+    unsigned long long found = 0;
+    hipError_t se = hipSuccess;
+    if (c.edges) se = hipMemcpyAsync(&found, counter, 8, hipMemcpyDeviceToHost, g.stream);
+    if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, g.ev0, g.ev1);
+    g.last_dist_ms = ms;
+    if (se != hipSuccess) return fail(MHX_E_HIP, "triangle kernel failed: %s", hipGetErrorString(se));
+    c.found = found;
+    return MHX_OK;
+}
+
+// what both calls check first; *done: nothing to compute (n <= 1)
+int triangle_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, bool *done)
+{
+    clear_error();
+    *done = false;
+    const int rc = require_engine();
+    if (rc) return rc;
+    if (n <= 1) { *done = true; return MHX_OK; }
+    if (n > kTriMaxLists) return fail(MHX_E_ARG, "too many lists for one triangle (%u, at most %u)", n, kTriMaxLists);
+    if (!rows || !len) return fail(MHX_E_ARG, "null argument");
+    if (k < 1 || k > 32 || s == 0 || stride == 0) return fail(MHX_E_ARG, "bad k / s / stride");
+    if (!device_ptrs)
+        for (uint32_t i = 0; i < n; ++i) if (len[i] > stride) return fail(MHX_E_ARG, "len[%u] exceeds stride", i);
+    return MHX_OK;
+}
+
+// rows and lengths of a host-pointer call behind `extra` bytes of the staging area
+int stage_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, size_t extra, uint8_t **base, TriCall &c)
+{
+    const size_t br = up256((size_t)n * stride * 8), bl = up256((size_t)n * 4);
+    const int rc = dist_stage(up256(extra) + br + bl, base);
+    if (rc) return rc;
+    uint8_t *dr = *base + up256(extra), *dl = dr + br;
+    hipError_t ce = hipMemcpyAsync(dr, rows, (size_t)n * stride * 8, hipMemcpyHostToDevice, g.stream);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(dl, len, (size_t)n * 4, hipMemcpyHostToDevice, g.stream);
+    if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in dist_triangle: %s", hipGetErrorString(ce));
+    c.rows = (const uint64_t *)dr;
+    c.len = (const uint32_t *)dl;
+    c.longest = 0;
+    for (uint32_t i = 0; i < n; ++i) c.longest = std::max(c.longest, len[i]);
+    return MHX_OK;
+}
+
+int triangle_dense(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, uint32_t *common,
+                   uint32_t *denom, double *dist, int device_ptrs)
+{
+    bool done;
+    int rc = triangle_check(rows, len, n, stride, k, s, device_ptrs, &done);
+    if (rc || done) return rc;
+    if (!common || !denom) return fail(MHX_E_ARG, "null argument");
+    const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
+    TriCall c{};
+    c.n = n; c.stride = stride; c.s = s; c.k = k; c.edges = false;
+    if (device_ptrs) {
+        c.rows = rows; c.len = len; c.longest = stride; // the lengths are on the device: the row stride bounds them
+        c.common = common; c.denom = denom; c.dist = dist;
+        return triangle_device(c);
+    }
+    const size_t bo = up256(pairs * 4);
+    uint8_t *base = nullptr;
+    rc = stage_rows(rows, len, n, stride, 2 * bo, &base, c);
+    if (rc) return rc;
+    c.common = (uint32_t *)base; c.denom = (uint32_t *)(base + bo); c.dist = nullptr; // distances in host libm below
+    rc = triangle_device(c);
+    if (rc) return rc;
+    if (hipMemcpy(common, c.common, pairs * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(denom, c.denom, pairs * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(MHX_E_HIP, "D2H copy failed in dist_triangle");
+    if (dist)
+        for (uint64_t i = 0; i < pairs; ++i) dist[i] = tri_distance(common[i], denom[i], k);
+    return MHX_OK;
+}
+
+int triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, double max_dist,
+                   uint32_t *edge_i, uint32_t *edge_j, uint32_t *common, uint32_t *denom, double *dist, uint64_t cap, uint64_t *n_out,
+                   int device_ptrs)
+{
+    if (n_out) *n_out = 0;
+    bool done;
+    int rc = triangle_check(rows, len, n, stride, k, s, device_ptrs, &done);
+    if (rc || done) return rc;
+    if (!n_out || (cap && (!edge_i || !edge_j || !common || !denom))) return fail(MHX_E_ARG, "null argument");
+    if (!(max_dist == max_dist)) return fail(MHX_E_ARG, "max_dist is not a number");
+    const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
+    TriCall c{};
+    c.n = n; c.stride = stride; c.s = s; c.k = k; c.edges = true;
+    c.jmin = tri_jmin(max_dist, k);
+    if (device_ptrs) { // the list stays where it is: prefiltered only, in the order of arrival
+        c.rows = rows; c.len = len; c.longest = stride;
+        c.edge_i = edge_i; c.edge_j = edge_j; c.common = common; c.denom = denom; c.dist = dist; c.cap = cap;
+        rc = triangle_device(c);
+        if (rc) return rc;
+        *n_out = c.found;
+        if (c.found > cap) return fail(MHX_E_CAPACITY, "edge list too small (%llu needed)", (unsigned long long)c.found);
+        return MHX_OK;
+    }
+    // The device list holds what passes the prefilter; its size is not known before the run.  A first run with room for
+    // the caller's cap (at least 2^20 edges) counts them all; only when they did not fit does a second run follow.
+    uint64_t room = std::min<uint64_t>(pairs, std::max<uint64_t>(cap, 1u << 20));
+    std::vector<uint32_t> ei, ej, ec, ed;
+    for (int attempt = 0;; ++attempt) {
+        const size_t be = up256(room * 4);
+        uint8_t *base = nullptr;
+        rc = stage_rows(rows, len, n, stride, 4 * be, &base, c);
+        if (rc) return rc;
+        c.edge_i = (uint32_t *)base; c.edge_j = (uint32_t *)(base + be); c.common = (uint32_t *)(base + 2 * be); c.denom = (uint32_t *)(base + 3 * be);
+        c.dist = nullptr; c.cap = room;
+        rc = triangle_device(c);
+        if (rc) return rc;
+        if (c.found <= room) break;
+        if (attempt) return fail(MHX_E_INTERNAL, "edge count changed between two runs");
+        room = c.found;
+    }
+    const size_t m = (size_t)c.found;
+    ei.resize(m); ej.resize(m); ec.resize(m); ed.resize(m);
+    if (m && (hipMemcpy(ei.data(), c.edge_i, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ej.data(), c.edge_j, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(ec.data(), c.common, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ed.data(), c.denom, m * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(MHX_E_HIP, "D2H copy failed in dist_triangle_edges");
+    // the exact rule (the libm distance that is printed) on the survivors, then Mash's order: i ascending, j < i ascending
+    std::vector<size_t> keep;
+    keep.reserve(m);
+    for (size_t e = 0; e < m; ++e)
+        if (tri_distance(ec[e], ed[e], k) <= max_dist) keep.push_back(e);
+    std::sort(keep.begin(), keep.end(), [&](size_t a, size_t b) { return ei[a] != ei[b] ? ei[a] < ei[b] : ej[a] < ej[b]; });
+    *n_out = keep.size();
+    if (keep.size() > cap) return fail(MHX_E_CAPACITY, "edge list too small (%zu needed)", keep.size());
+    for (size_t t = 0; t < keep.size(); ++t) {
+        const size_t e = keep[t];
+        edge_i[t] = ei[e]; edge_j[t] = ej[e]; common[t] = ec[e]; denom[t] = ed[e];
+        if (dist) dist[t] = tri_distance(ec[e], ed[e], k);
+    }
+    return MHX_OK;
+}
+
+} // namespace
+
+extern "C" int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
+                                 uint32_t *common, uint32_t *denom, double *dist, int device_ptrs)
+{
+    try {
+        return triangle_dense(rows, len, n, stride, k, s, common, denom, dist, device_ptrs);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_triangle: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_triangle: %s", e.what());
+    }
+}
+
+extern "C" int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
+                                       double max_dist, uint32_t *edge_i, uint32_t *edge_j, uint32_t *common, uint32_t *denom,
+                                       double *dist, uint64_t cap, uint64_t *n_out, int device_ptrs)
+{
+    try {
+        return triangle_edges(rows, len, n, stride, k, s, max_dist, edge_i, edge_j, common, denom, dist, cap, n_out, device_ptrs);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_triangle_edges: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_triangle_edges: %s", e.what());
+    }
+}

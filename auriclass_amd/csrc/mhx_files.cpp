@@ -1721,3 +1721,94 @@ extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_
 {
     return dist_files_guarded("mhx_dist_files_multi", ref_msh, qry_msh, n_qry, stdout_buf, cap, need);
 }
+
+// `mash triangle a.msh [b.msh ...]`: the references of all files form one set (argument order, then file order), every
+// pair j < i of it is compared on the device (mhx_dist_triangle, or mhx_dist_triangle_edges when a distance bound can drop
+// pairs there), and the text is Mash's CommandTriangle: the lower-triangle matrix, or the edge list with its two filters.
+static int mhx_triangle_files_impl(const char *const *paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!paths || n_paths < 1) return fail(MHX_E_ARG, "triangle: at least one sketch path required");
+    for (int i = 0; i < n_paths; ++i)
+        if (!paths[i]) return fail(MHX_E_ARG, "triangle: sketch path %d is null", i);
+    mhx_triangle_opts o{(uint32_t)sizeof(mhx_triangle_opts), 0, 0, 1.0, 1.0};
+    if (opts) {
+        if (opts->struct_size != sizeof(mhx_triangle_opts)) return fail(MHX_E_ARG, "triangle: opts->struct_size is not sizeof(mhx_triangle_opts)");
+        o = *opts;
+    }
+    if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "triangle: max_dist / max_p_value is not a number");
+    const bool edge = o.edge != 0 || o.max_dist < 1.0 || o.max_p_value < 1.0; // -d and -v imply -E
+    std::vector<SketchSet> F((size_t)n_paths);
+    std::vector<const RefSketch *> refs;
+    for (int i = 0; i < n_paths; ++i) {
+        rc = msh_read_file(paths[i], F[i]); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        if (F[0].kmer_size != F[i].kmer_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", F[i].kmer_size, F[0].kmer_size);
+        if (F[0].hash_seed != F[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
+        if (F[i].sketch_size != F[0].sketch_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", paths[0], paths[i],
+                        F[0].sketch_size, F[i].sketch_size);
+        for (const RefSketch &r : F[i].refs) refs.push_back(&r);
+    }
+    if (refs.size() > 65536) return fail(MHX_E_ARG, "triangle: too many references for one call (%zu)", refs.size());
+    const uint32_t n = (uint32_t)refs.size(), s = F[0].sketch_size;
+    const int k = (int)F[0].kmer_size;
+    const uint64_t pairs = (uint64_t)n * (n ? n - 1 : 0) / 2;
+    uint32_t stride = 16;
+    for (const RefSketch *r : refs) stride = std::max<uint32_t>(stride, (uint32_t)r->hash_count());
+    stride = (stride + 15u) & ~15u; // rows of whole 128-byte lines on the device
+    std::vector<uint64_t> rows((size_t)n * stride, 0);
+    std::vector<uint32_t> len(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        len[i] = (uint32_t)refs[i]->hash_count();
+        if (len[i]) memcpy(&rows[(size_t)i * stride], refs[i]->hash_data(), (size_t)len[i] * 8);
+    }
+    std::string text;
+    if (!edge) {
+        std::vector<uint32_t> common(pairs), denom(pairs);
+        std::vector<double> dist(pairs);
+        rc = mhx_dist_triangle(rows.data(), len.data(), n, stride, k, s ? s : 1, common.data(), denom.data(), dist.data(), 0);
+        if (rc) return rc;
+        text = "\t" + std::to_string(n) + "\n";
+        for (uint32_t i = 0; i < n; ++i) {
+            text += o.comment ? refs[i]->comment : refs[i]->name;
+            for (uint32_t j = 0; j < i; ++j) text += "\t" + fmt_g(dist[(size_t)i * (i - 1) / 2 + j]);
+            text += "\n";
+        }
+        return put_text(text, stdout_buf, cap, need);
+    }
+    std::vector<uint32_t> ei, ej, common, denom;
+    std::vector<double> dist;
+    uint64_t found = 0, room = o.max_dist >= 1.0 ? pairs : std::min<uint64_t>(pairs, 1u << 16);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        ei.resize(room); ej.resize(room); common.resize(room); denom.resize(room); dist.resize(room);
+        rc = mhx_dist_triangle_edges(rows.data(), len.data(), n, stride, k, s ? s : 1, o.max_dist, ei.data(), ej.data(), common.data(), denom.data(),
+                                     dist.data(), room, &found, 0);
+        if (rc != MHX_E_CAPACITY) break;
+        room = found;
+    }
+    if (rc) return rc;
+    clear_error();
+    for (uint64_t e = 0; e < found; ++e) {
+        const RefSketch &a = *refs[ei[e]], &b = *refs[ej[e]];
+        const double pv = mhx_p_value(common[e], a.length, b.length, k, denom[e]);
+        if (!(pv <= o.max_p_value)) continue;
+        text += a.name + "\t" + b.name + "\t" + fmt_g(dist[e]) + "\t" + fmt_g(pv) + "\t" + std::to_string(common[e]) + "/" + std::to_string(denom[e]) + "\n";
+    }
+    return put_text(text, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_triangle_files(const char *const *msh_paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap,
+                                  size_t *need)
+{
+    try {
+        return mhx_triangle_files_impl(msh_paths, n_paths, opts, stdout_buf, cap, need);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_triangle_files: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_triangle_files: %s", e.what());
+    }
+}

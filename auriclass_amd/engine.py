@@ -154,6 +154,13 @@ def load() -> ctypes.CDLL:
         L.mhx_sketch_segments_cut.restype = c.c_uint32
         L.mhx_sketch_files_individual.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.c_int, c.c_uint32, c.c_char_p, c.c_char_p,
                                                   c.c_size_t, c.POINTER(c.c_size_t), u64p]
+    if hasattr(L, "mhx_dist_triangle"):   # (or older than the all-pairs call, `mash triangle`)
+        L.mhx_dist_triangle.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p,
+                                        c.c_void_p, c.c_int]
+        L.mhx_dist_triangle_edges.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_double, c.c_void_p,
+                                              c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, u64p, c.c_int]
+        L.mhx_triangle_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(TriangleOpts), c.c_char_p, c.c_size_t,
+                                         c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -271,6 +278,24 @@ def screen_files(ref_msh, paths: Sequence, winner: bool = False, min_identity: f
     text = _text_call(lambda buf, cap, need: load().mhx_screen_files_opts(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts),
                                                                           buf, cap, need, ctypes.byref(size)))
     return text, size.value
+
+
+class TriangleOpts(ctypes.Structure):
+    """mhx_triangle_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("edge", ctypes.c_int32), ("comment", ctypes.c_int32), ("max_dist", ctypes.c_double),
+                ("max_p_value", ctypes.c_double)]
+
+
+def triangle_files(paths: Sequence, edge: bool = False, comment: bool = False, max_dist: float = 1.0, max_p_value: float = 1.0) -> str:
+    """`mash triangle [-E] [-C] [-d max_dist] [-v max_p_value] paths...` stdout: the references of all sketch files are one
+    set; the lower-triangle distance matrix ("\\t<n>", then a line per reference: name, or comment under `comment`, and its
+    distances to the references before it), or with `edge` the list "name_i\\tname_j\\tdist\\tp\\tcommon/denom" of the pairs
+    j < i with distance <= max_dist and p <= max_p_value.  A bound below 1 implies the edge list, as in Mash."""
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = TriangleOpts(ctypes.sizeof(TriangleOpts), int(bool(edge)), int(bool(comment)), float(max_dist), float(max_p_value))
+    return _text_call(lambda buf, cap, need: load().mhx_triangle_files(arr, len(files), ctypes.byref(opts), buf, cap, need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -703,3 +728,70 @@ def dist_batch_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_ptr
     _check(load().mhx_dist_batch(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s,
                                  v(common_ptr), v(denom_ptr), v(dist_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
+
+
+def _triangle_rows(rows, lens):
+    rows = np.ascontiguousarray(rows, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    assert rows.ndim == 2 and lens.shape == (rows.shape[0],)
+    return rows, lens
+
+
+def dist_triangle(rows: np.ndarray, lens: np.ndarray, k: int, s: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """All pairs j < i of ONE set of hash lists (rows [n, stride], lens [n], as dist_batch takes a matrix): packed
+    (common, denom, dist) of n (n - 1) / 2 entries, pair (i, j) at i (i - 1) / 2 + j -- the lower triangle row by row."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    pairs = n * (n - 1) // 2 if n > 1 else 0
+    common = np.zeros(pairs, dtype=np.uint32)
+    denom = np.zeros(pairs, dtype=np.uint32)
+    dist = np.zeros(pairs, dtype=np.float64)
+    _check(load().mhx_dist_triangle(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, common.ctypes.data, denom.ctypes.data,
+                                    dist.ctypes.data, 0))
+    return common, denom, dist
+
+
+def dist_triangle_edges(rows: np.ndarray, lens: np.ndarray, k: int, s: int, max_dist: float, cap: Optional[int] = None):
+    """The pairs j < i with distance <= max_dist as (edge_i, edge_j, common, denom, dist), ascending by (i, j); nothing of
+    size n^2 is kept anywhere.  cap: room for that many edges (default 65 536); when it is too small the call is repeated
+    once with the size the library reported."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    cap = 1 << 16 if cap is None else int(cap)
+    found = ctypes.c_uint64(0)
+    for _ in range(2):
+        ei, ej = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        common, denom = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        dist = np.zeros(cap, dtype=np.float64)
+        rc = load().mhx_dist_triangle_edges(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, float(max_dist), ei.ctypes.data,
+                                            ej.ctypes.data, common.ctypes.data, denom.ctypes.data, dist.ctypes.data, cap, ctypes.byref(found), 0)
+        if rc != MHX_E_CAPACITY or found.value <= cap:
+            break
+        cap = found.value
+    _check(rc)
+    m = found.value
+    return ei[:m].copy(), ej[:m].copy(), common[:m].copy(), denom[:m].copy(), dist[:m].copy()
+
+
+def dist_triangle_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, common_ptr: int, denom_ptr: int,
+                         dist_ptr: int) -> float:
+    """Device pointers in and out (packed outputs as dist_triangle); returns the kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_triangle(v(rows_ptr), v(len_ptr), n, stride, k, s, v(common_ptr), v(denom_ptr), v(dist_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
+
+
+def dist_triangle_edges_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, max_dist: float, edge_i_ptr: int,
+                               edge_j_ptr: int, common_ptr: int, denom_ptr: int, dist_ptr: int, cap: int) -> int:
+    """Device pointers in and out: the edge list stays on the device, PREFILTERED ONLY (a pair within 1e-9 relative of the
+    bound may be in it although its distance rounds above max_dist) and in the order of arrival.  Returns the number of
+    edges; EngineError(MHX_E_CAPACITY) when it exceeds cap (the message names the number needed)."""
+    init()
+    v = ctypes.c_void_p
+    found = ctypes.c_uint64(0)
+    _check(load().mhx_dist_triangle_edges(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(edge_i_ptr), v(edge_j_ptr),
+                                          v(common_ptr), v(denom_ptr), v(dist_ptr), cap, ctypes.byref(found), 1))
+    return int(found.value)

@@ -3,7 +3,8 @@
 (/root/reference/auriclass/general.py:198-205 `mash -h`; classes.py:576-596 and 696-706
 `mash sketch`; classes.py:92-97 `mash dist`; classes.py:305-312 `mash bounds`) run on the GPU
 engine.  `mash screen REF.msh reads...` (containment) and `mash sketch -i` (one sketch per sequence of a file: how a
-reference set is made from one multi-FASTA) are served too; AuriClass itself calls neither.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
+reference set is made from one multi-FASTA) are served too, and `mash triangle SET.msh ...` (all pairs within a sketch
+set: matrix or, with -E / -d / -v, edge list); AuriClass itself calls none of them.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
 codes follow mash (sketch: exit 1 with 'ERROR: Did not find fasta records in ...')."""
 from __future__ import annotations
 
@@ -30,6 +31,8 @@ Commands:
   screen    Determine whether query sequences are within a larger pool of sequences.
 
   sketch    Create sketches (reduced representations for fast operations).
+
+  triangle  Estimate the distance of each sequence to every other sequence.
 
 """
 
@@ -93,6 +96,30 @@ def main(argv: List[str] = None) -> int:
                 return 1
             text, _ = engine.screen_files(args[0], args[1:])
             sys.stdout.write(text)
+            return 0
+        if cmd == "triangle":
+            for flag in ("-i", "-k", "-s", "-r", "-m", "-l", "-a", "-z", "-S", "-w", "-b", "-g", "-c", "-n", "-Z", "-M", "-I"):
+                if flag in args:
+                    sys.stderr.write(f"ERROR: mash triangle {flag} is not supported by the mhx shim (inputs are sketch files)\n")
+                    return 1
+            _take(args, "-p", 1, int)   # threads: the engine has its own
+            edge = "-E" in args
+            if edge:
+                args.remove("-E")
+            comment = "-C" in args
+            if comment:
+                args.remove("-C")
+            max_dist = _take(args, "-d", 1.0, float)
+            max_p = _take(args, "-v", 1.0, float)
+            if not args:
+                sys.stderr.write("ERROR: mash triangle <sketches.msh> [<sketches.msh> ...]\n")
+                return 1
+            for path in args:
+                if not str(path).endswith(".msh"):
+                    sys.stderr.write(f"ERROR: mash triangle in the mhx shim takes sketch files only; sketch {path} first "
+                                     "(mash sketch [-i] -o <out> ...) and pass the .msh\n")
+                    return 1
+            sys.stdout.write(engine.triangle_files(args, edge=edge, comment=comment, max_dist=max_dist, max_p_value=max_p))
             return 0
         if cmd == "bounds":
             k = _take(args, "-k", 21, int)

@@ -11,6 +11,8 @@
  *                        set is made from one multi-FASTA, docs/faq.md "I want to build my own database")
  *   mhx_dist_files    <- `mash dist REF.msh QUERY.msh`      auriclass/classes.py:92-104
  *   mhx_dist_files_multi <- `mash dist REF.msh QUERY.msh [QUERY.msh ...]` (a run of samples, one call)
+ *   mhx_triangle_files <- `mash triangle [-E] [-C] [-d D] [-v V] SET.msh [SET.msh ...]` (not called by AuriClass: all
+ *                        pairs within a reference set -- duplicates, the matrix a tree starts from, how far the clades are apart)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -148,6 +150,31 @@ typedef struct mhx_screen_opts {
 int mhx_screen_files_opts(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
                           size_t cap, size_t *need, double *set_size_out);
 
+/* `mash triangle [-E] [-C] [-d max_dist] [-v max_p_value] a.msh [b.msh ...]` stdout (Mash 2.x CommandTriangle restated).
+ * The references of all files form ONE set, in argument order and then file order; every pair j < i of it is compared by
+ * mhx_dist_triangle / mhx_dist_triangle_edges.
+ *   matrix (edge == 0): "\t<n>\n", then one line per reference i = 0 .. n - 1: its name (comment != 0: its comment),
+ *       "\t<distance>" for j = 0 .. i - 1, "\n".
+ *   edge list (edge != 0, or max_dist < 1, or max_p_value < 1, as Mash's -d / -v imply -E): no header; for i ascending and
+ *       j < i ascending every pair with distance <= max_dist and p <= max_p_value prints
+ *       "name_i\tname_j\tdist\tp\tcommon/denom\n" -- a `mash dist` row with reference i and query j,
+ *       p = mhx_p_value(common, length_i, length_j, k, denom).
+ * opts == NULL means {sizeof, 0, 0, 1, 1}.  All files must share k, hash seed and sketch size (MHX_E_MISMATCH otherwise);
+ * a hash list that is not ascending is MHX_E_FORMAT.  MHX_E_ARG: struct_size != sizeof(mhx_triangle_opts), a max_dist or
+ * max_p_value that is not a number, more than 65 536 references.
+ * Not pinned by mash output (none is recorded for `triangle`): like the screen, the mode is pinned by its restated rule,
+ * and its pairs by the mash-pinned distance path (the rows equal those mhx_dist_files prints for the same pairs).
+ * DESIGN.md section 6. */
+typedef struct mhx_triangle_opts {
+    uint32_t struct_size; /* sizeof(mhx_triangle_opts) */
+    int32_t edge;
+    int32_t comment;
+    double max_dist;
+    double max_p_value;
+} mhx_triangle_opts;
+int mhx_triangle_files(const char *const *msh_paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap,
+                       size_t *need);
+
 /* `mash bounds -k K -p P` stdout. */
 int mhx_bounds(int k, double p, char *buf, size_t cap, size_t *need);
 
@@ -276,7 +303,7 @@ int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const 
                    const uint32_t *r_len, uint32_t nr, uint32_t stride, int k, uint32_t s,
                    uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
 double mhx_last_dist_kernel_ms(void);
-/* diagnostics of the last mhx_dist_batch / mhx_dist_files call: -1 = the generic pair kernel did all the work (tiny batch),
+/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* call: -1 = the generic pair kernel did all the work (tiny batch),
  * else the number of (query batch, reference slice) blocks the all-vs-refs fast path gave up to it (0 for uniform hashes) */
 int mhx_last_dist_fallback_blocks(void);
 /* value ranges every (query batch, reference slice) block of that call was cut into: 1024 x W, W = the smallest power of two
@@ -284,6 +311,31 @@ int mhx_last_dist_fallback_blocks(void);
  * from q_len / r_len, from `stride` when they are device pointers).  0 = the generic pair kernel did all the work: a tiny
  * batch, lists of more than 2^20 hashes, or every block gave up */
 int mhx_last_dist_ranges(void);
+
+/* All pairs j < i of ONE set (`mash triangle` at buffer level): rows / len as mhx_dist_batch takes a list matrix,
+ * [n][stride] ascending unique hashes with len[i] valid entries.  Outputs are packed, [n (n - 1) / 2], pair (i, j) at
+ * i (i - 1) / 2 + j: the lower triangle row by row, Mash's print order.  dist may be NULL.  n <= 1 is MHX_OK with nothing
+ * written; n > 65 536 (more than 2^31 - 1 pairs) is MHX_E_ARG; k, s, stride and len[i] > stride are checked as in
+ * mhx_dist_batch.  device_ptrs != 0 => rows, len, common, denom, dist are device pointers and dist is the device's log;
+ * with host pointers the distances are libm doubles computed on the host, as in mhx_dist_batch.
+ * The set is split into value ranges once per call; slices of 32 lists are the references of a block, the lists behind
+ * a slice's first its queries.  The number of ranges follows the longest list (len, or stride
+ * when the lengths are on the device): the smallest power of two R with longest <= 16 R, between 16 and 16 384 -- 64 at
+ * s = 1000; MHX_TRI_GEOMETRY=dist takes mhx_dist_batch's geometry instead, MHX_TRI_QBATCH bounds the queries of a block.
+ * mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report this call too. */
+int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
+                      uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
+/* The pairs with distance <= max_dist only, as an edge list (i, j, common, denom, dist) of at most cap entries; nothing of
+ * size n^2 is materialised.  *n_out (a HOST pointer in both forms) receives the number of edges; when cap is too small
+ * the call returns MHX_E_CAPACITY, *n_out is the number needed and the buffers hold nothing of use.  dist may be NULL.
+ * Host pointers: the device prefilters by the Jaccard index of max_dist (lowered by 2^-30 relative), the host applies
+ * the exact rule -- the libm distance, the double that is printed, <= max_dist -- and sorts: ascending by (i, j).
+ * device_ptrs != 0: edge_i, edge_j, common, denom, dist are device buffers and the list STAYS on the device: prefiltered
+ * only (a pair within 1e-9 relative of the bound in the Jaccard index may be in it although its distance rounds above
+ * max_dist) and in the order of arrival, which changes from run to run; dist is the device's log. */
+int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
+                            double max_dist, uint32_t *edge_i, uint32_t *edge_j, uint32_t *common, uint32_t *denom,
+                            double *dist, uint64_t cap, uint64_t *n_out, int device_ptrs);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
  * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is
