@@ -180,6 +180,8 @@ hipError_t launch_dist_ranges(const DistArgs &a, const DistWork &w, hipStream_t 
 // point into ONE [list][R + 1] table of a whole set: shift + split of the a.nq lists of a.q (a.nr = 0) into w.offs_q; the
 // range pass of one block; the finish pass of one block with R >= 1024 (below: launch_tri_finish_small).
 hipError_t launch_dist_offsets(const DistArgs &a, const DistWork &w, hipStream_t st);
+// the same for two sets that share their ranges (the search): one shift over a.q and a.r, offsets into w.offs_q and w.offs_r
+hipError_t launch_dist_offsets_both(const DistArgs &a, const DistWork &w, hipStream_t st);
 hipError_t launch_dist_range_pass(const DistArgs &a, const DistWork &w, hipStream_t st);
 hipError_t launch_dist_finish(const DistArgs &a, const DistWork &w, hipStream_t st);
 
@@ -202,5 +204,23 @@ struct TriOut {
 hipError_t launch_tri_finish_small(const DistArgs &a, const DistWork &w, hipStream_t st); // 16 <= w.ranges < 1024
 hipError_t launch_tri_scatter(const TriOut &o, hipStream_t st);
 hipError_t launch_tri_edges(const TriOut &o, hipStream_t st);
+
+// reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
+// query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
+// with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.
+struct SearchOut {
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;
+    uint32_t r0, nr, q0, nq; // the block (mhx_search.h: SearchBlock); q0 counts from the call's first query
+    uint32_t top;
+    int k;
+    double jmin;             // candidates must pass tri_keep(., ., jmin)
+    uint32_t *hit_ref, *hit_common, *hit_denom;
+    uint32_t *n_hits;
+    double *hit_dist;        // launch_search_dist only
+};
+hipError_t launch_search_take(const SearchOut &o, hipStream_t st);
+// tri_distance of the o.nq lists from query o.q0 on into hit_dist (entries behind n_hits are left alone)
+hipError_t launch_search_dist(const SearchOut &o, hipStream_t st);
 
 } // namespace mhx

@@ -765,6 +765,29 @@ hipError_t launch_dist_offsets(const DistArgs &a, const DistWork &w, hipStream_t
     return hipGetLastError();
 }
 
+hipError_t launch_dist_offsets_both(const DistArgs &a, const DistWork &w, hipStream_t st)
+{ // ONE shift over the a.nq lists of a.q and the a.nr lists of a.r (w.params[0]; [1] = 0), then the offsets of the queries
+  // into w.offs_q and of the references into w.offs_r, [list][R + 1] each: the two sets of a search share their ranges
+    if (a.nq == 0 && a.nr == 0) return hipSuccess;
+    hipLaunchKernelGGL(dist_shift_kernel<true>, dim3(1), dim3(1024), 0, st, a, w); // a reference set is 10^5 lists: 1024 threads share them
+    const uint64_t per = (uint64_t)w.ranges + 1;
+    for (int side = 0; side < 2; ++side) {
+        const uint32_t n = side ? a.nr : a.nq;
+        const uint32_t chunk = (uint32_t)std::min<uint64_t>(n, 0xFFFFFFFFull / per); // list * (R + 1) stays below 2^32 in the kernel
+        for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+            DistArgs x = a;
+            DistWork y = w;
+            x.q = (side ? a.r : a.q) + (uint64_t)c0 * a.stride;
+            x.q_len = (side ? a.r_len : a.q_len) + c0;
+            x.nq = std::min(chunk, n - c0);
+            x.nr = 0;
+            y.offs_q = (side ? w.offs_r : w.offs_q) + (uint64_t)c0 * per;
+            hipLaunchKernelGGL(dist_split_kernel<true>, dim3(x.nq, (a.stride + 511) / 512), dim3(256), 0, st, x, y, 0u);
+        }
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_dist_range_pass(const DistArgs &a, const DistWork &w, hipStream_t st)
 { // the range pass of one block (a.nr <= 32): byte counters into w.cpart, the overflow flag into w.params[1]
     const uint32_t R = w.ranges;

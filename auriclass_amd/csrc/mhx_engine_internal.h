@@ -151,6 +151,12 @@ extern Engine &g;
 int require_engine();
 // room for `bytes` in g.dist_in, the device staging of a host-pointer distance call (mhx_engine_dist.cpp; the triangle's too)
 int dist_stage(size_t bytes, uint8_t **out);
+// Reference-set search (mhx_engine_search.cpp) of host queries, every row where it lies, against a reference set that the
+// caller has put on the device: rows [nr][stride] and len [nr] there, `longest` the largest len.  Outputs as the host form
+// of mhx_dist_search.  What mhx_search_files runs per batch of queries: the references are staged once per call.
+struct SearchRefs { const uint64_t *rows; const uint32_t *len; uint32_t nr, stride, longest; };
+int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
+                uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits);
 
 } // namespace mhx
 

@@ -1812,3 +1812,113 @@ extern "C" int mhx_triangle_files(const char *const *msh_paths, int n_paths, con
         return fail(MHX_E_INTERNAL, "mhx_triangle_files: %s", e.what());
     }
 }
+
+// Reference-set search at file level: the reference file is read, checked and staged on the device ONCE; the query files
+// are read one after the other and searched in batches of sketches (mhx_dist_search's host form against the resident
+// references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.
+static int mhx_search_files_impl(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf,
+                                 size_t cap, size_t *need)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "search: a reference sketch path and at least one query sketch path required");
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "search: query sketch path %d is null", i);
+    mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), 5, 1.0, 1.0};
+    if (opts) {
+        if (opts->struct_size != sizeof(mhx_search_opts)) return fail(MHX_E_ARG, "search: opts->struct_size is not sizeof(mhx_search_opts)");
+        o = *opts;
+    }
+    if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "search: top must be 1 .. 64");
+    if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "search: max_dist / max_p_value is not a number");
+    SketchSet R;
+    rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+    if (rc) return rc;
+    const int k = (int)R.kmer_size;
+    const uint32_t nr = (uint32_t)R.refs.size();
+    DevArray<uint64_t> d_rows;
+    DevArray<uint32_t> d_len;
+    SearchRefs refs{nullptr, nullptr, nr, 0, 0};
+    uint32_t q_sketch_size = 0, s = 0;
+    std::string text;
+    constexpr size_t kBatch = 4096; // query sketches per device call
+    std::vector<SketchSet> held;    // the files of the current batch
+    std::vector<const RefSketch *> qs;
+    auto stage_refs = [&]() -> int { // once, behind the first query file: rows of whole 128-byte lines that hold any list of the call
+        for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
+        refs.stride = (std::max<uint32_t>(16, std::max(refs.longest, q_sketch_size)) + 15u) & ~15u;
+        if (nr == 0) return MHX_OK;
+        std::vector<uint64_t> rows((size_t)nr * refs.stride, 0);
+        std::vector<uint32_t> len(nr);
+        for (uint32_t i = 0; i < nr; ++i) {
+            len[i] = (uint32_t)R.refs[i].hash_count();
+            if (len[i]) memcpy(&rows[(size_t)i * refs.stride], R.refs[i].hash_data(), (size_t)len[i] * 8);
+            std::vector<uint64_t>().swap(R.refs[i].hashes); // names and lengths stay for the text
+        }
+        if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
+        if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+        refs.rows = d_rows; refs.len = d_len;
+        return MHX_OK;
+    };
+    auto flush = [&]() -> int {
+        const uint32_t nq = (uint32_t)qs.size();
+        if (nq && nr) {
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq);
+            std::vector<double> hx((size_t)nq * o.top);
+            for (uint32_t i = 0; i < nq; ++i) {
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
+            }
+            const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data());
+            if (rc2) return rc2;
+            for (uint32_t qi = 0; qi < nq; ++qi)
+                for (uint32_t t = 0; t < nh[qi]; ++t) {
+                    const size_t p = (size_t)qi * o.top + t;
+                    const RefSketch &ref = R.refs[hr[p]];
+                    const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                    if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
+                    text += ref.name + "\t" + qs[qi]->name + "\t" + fmt_g(hx[p]) + "\t" + fmt_g(pv) + "\t" + std::to_string(hc[p]) + "/" + std::to_string(hd[p]) + "\n";
+                }
+        }
+        qs.clear();
+        held.clear();
+        return MHX_OK;
+    };
+    for (int i = 0; i < n_qry; ++i) {
+        held.emplace_back();
+        SketchSet &Q = held.back();
+        rc = msh_read_file(qry_msh[i], Q);
+        if (rc) return rc;
+        if (R.kmer_size != Q.kmer_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", Q.kmer_size, R.kmer_size);
+        if (R.hash_seed != Q.hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
+        if (i == 0) {
+            q_sketch_size = Q.sketch_size;
+            s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+            rc = stage_refs();
+            if (rc) return rc;
+        } else if (Q.sketch_size != q_sketch_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", qry_msh[0], qry_msh[i],
+                        q_sketch_size, Q.sketch_size);
+        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+    }
+    rc = flush();
+    if (rc) return rc;
+    return put_text(text, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf, size_t cap,
+                                size_t *need)
+{
+    try {
+        return mhx_search_files_impl(ref_msh, qry_msh, n_qry, opts, stdout_buf, cap, need);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_search_files: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_search_files: %s", e.what());
+    }
+}

@@ -161,6 +161,11 @@ def load() -> ctypes.CDLL:
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, u64p, c.c_int]
         L.mhx_triangle_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(TriangleOpts), c.c_char_p, c.c_size_t,
                                          c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
+        L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
+                                      c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_search_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(SearchOpts), c.c_char_p, c.c_size_t,
+                                       c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -296,6 +301,23 @@ def triangle_files(paths: Sequence, edge: bool = False, comment: bool = False, m
     arr = (ctypes.c_char_p * len(files))(*files)
     opts = TriangleOpts(ctypes.sizeof(TriangleOpts), int(bool(edge)), int(bool(comment)), float(max_dist), float(max_p_value))
     return _text_call(lambda buf, cap, need: load().mhx_triangle_files(arr, len(files), ctypes.byref(opts), buf, cap, need), guess=1 << 20)
+
+
+class SearchOpts(ctypes.Structure):
+    """mhx_search_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("top", ctypes.c_uint32), ("max_dist", ctypes.c_double), ("max_p_value", ctypes.c_double)]
+
+
+def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1.0, max_p_value: float = 1.0) -> str:
+    """For every query sketch of the files, in argument order and then file order, its `top` closest references of REF.msh
+    with distance <= max_dist, best first, as `mash dist` rows "ref\\tquery\\tdist\\tp\\tcommon/denom"; a query without hits
+    prints nothing.  max_p_value drops rows from the `top` already chosen and never promotes a lower-ranked pair."""
+    init()
+    files = [os.fsencode(str(p)) for p in qry_paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = SearchOpts(ctypes.sizeof(SearchOpts), int(top), float(max_dist), float(max_p_value))
+    return _text_call(lambda buf, cap, need: load().mhx_search_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
+                                                                     need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -795,3 +817,36 @@ def dist_triangle_edges_device(rows_ptr: int, len_ptr: int, n: int, stride: int,
     _check(load().mhx_dist_triangle_edges(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(edge_i_ptr), v(edge_j_ptr),
                                           v(common_ptr), v(denom_ptr), v(dist_ptr), cap, ctypes.byref(found), 1))
     return int(found.value)
+
+
+def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """For every query list its `top` (1 .. 64) closest references with distance <= max_dist, ranked on the device by the
+    exact Jaccard index (ties: the lower reference index): (ref, common, denom, dist) of shape [nq, top], best first and zero
+    behind n_hits [nq].  Rows and lengths as dist_batch takes them; no [nq, nr] array exists anywhere."""
+    init()
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    cells = (nq, max(int(top), 0))
+    ref, common, denom = np.zeros(cells, dtype=np.uint32), np.zeros(cells, dtype=np.uint32), np.zeros(cells, dtype=np.uint32)
+    dist = np.zeros(cells, dtype=np.float64)
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    _check(load().mhx_dist_search(q.ctypes.data, q_len.ctypes.data, nq, r.ctypes.data, r_len.ctypes.data, nr, stride, k, s, float(max_dist),
+                                  int(top), ref.ctypes.data, common.ctypes.data, denom.ctypes.data, dist.ctypes.data, n_hits.ctypes.data, 0))
+    return ref, common, denom, dist, n_hits
+
+
+def dist_search_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_ptr: int, nr: int, stride: int, k: int, s: int, top: int,
+                       max_dist: float, ref_ptr: int, common_ptr: int, denom_ptr: int, dist_ptr: int, n_hits_ptr: int) -> float:
+    """Device pointers in and out ([nq, top] lists and n_hits [nq]; a sketch_segments_device result goes straight in on either
+    side): the lists stay on the device, PREFILTERED ONLY (see dist_triangle_edges_device) but in rank order, dist (may be 0)
+    is the device's log, entries behind n_hits are unspecified.  Returns the kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_search(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s, float(max_dist), int(top), v(ref_ptr),
+                                  v(common_ptr), v(denom_ptr), v(dist_ptr or None), v(n_hits_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()

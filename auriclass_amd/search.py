@@ -1,0 +1,41 @@
+"""`python -m auriclass_amd.search [-n TOP] [-d MAX_DIST] [-v MAX_P] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: for every
+query sketch its TOP closest references of REF.msh within MAX_DIST, best first, as `mash dist` rows (engine.search_files).
+Ranking and filtering happen on the device, so REF.msh may hold a reference set far too large to print in full.  Inputs are
+sketch files: a sequence file is refused with the hint to sketch it first.  Exit status 1 with the engine's message when
+the call fails.  -p (threads) is accepted and ignored: the engine has its own."""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import List
+
+from auriclass_amd import engine
+
+
+def main(argv: List[str] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m auriclass_amd.search", description="closest references of a sketch set, per query sketch")
+    ap.add_argument("-n", dest="top", type=int, default=5, help="hits per query, 1 .. 64 [5]")
+    ap.add_argument("-d", dest="max_dist", type=float, default=1.0, help="maximum distance to report [1]")
+    ap.add_argument("-v", dest="max_p_value", type=float, default=1.0, help="maximum p-value to report (drops rows, promotes none) [1]")
+    ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
+    ap.add_argument("reference", metavar="REF.msh")
+    ap.add_argument("queries", metavar="QUERY.msh", nargs="+")
+    try:
+        args = ap.parse_args(argv)
+    except SystemExit as exc:
+        return 0 if exc.code == 0 else 1
+    for path in [args.reference] + args.queries:
+        if not str(path).endswith(".msh"):
+            sys.stderr.write(f"ERROR: the search takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
+            return 1
+    try:
+        text = engine.search_files(args.reference, args.queries, top=args.top, max_dist=args.max_dist, max_p_value=args.max_p_value)
+    except engine.EngineError as exc:
+        sys.stderr.write(exc.message + "\n")
+        return 1
+    sys.stdout.write(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

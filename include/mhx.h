@@ -13,6 +13,9 @@
  *   mhx_dist_files_multi <- `mash dist REF.msh QUERY.msh [QUERY.msh ...]` (a run of samples, one call)
  *   mhx_triangle_files <- `mash triangle [-E] [-C] [-d D] [-v V] SET.msh [SET.msh ...]` (not called by AuriClass: all
  *                        pairs within a reference set -- duplicates, the matrix a tree starts from, how far the clades are apart)
+ *   mhx_search_files  <- no mash command: `mash dist REF.msh QUERY.msh ...` followed by a sort per query, for a reference
+ *                        set too large to print in full -- per query sketch the `top` closest references within a
+ *                        distance bound, as dist rows (python -m auriclass_amd.search)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -303,7 +306,7 @@ int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const 
                    const uint32_t *r_len, uint32_t nr, uint32_t stride, int k, uint32_t s,
                    uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
 double mhx_last_dist_kernel_ms(void);
-/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* call: -1 = the generic pair kernel did all the work (tiny batch),
+/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* / mhx_dist_search call: -1 = the generic pair kernel did all the work (tiny batch),
  * else the number of (query batch, reference slice) blocks the all-vs-refs fast path gave up to it (0 for uniform hashes) */
 int mhx_last_dist_fallback_blocks(void);
 /* value ranges every (query batch, reference slice) block of that call was cut into: 1024 x W, W = the smallest power of two
@@ -336,6 +339,47 @@ int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint32_t n, uin
 int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
                             double max_dist, uint32_t *edge_i, uint32_t *edge_j, uint32_t *common, uint32_t *denom,
                             double *dist, uint64_t cap, uint64_t *n_out, int device_ptrs);
+
+/* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
+ * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
+ * mhx_dist_batch takes them, (common, denom) of a pair are mhx_dist_batch's.
+ * Rank: by the Jaccard index common / denom compared exactly -- a before b iff a.common * b.denom > b.common * a.denom in
+ * 64-bit integers, common == denom counting as 1/1 (which includes 0/0, two empty lists: distance 0) -- and pairs of equal
+ * index by the lower reference index: a total order.  Not by the distance, which is clamped to 1.
+ * Filter: a pair is a hit when the distance mhx_dist_batch computes on the host (libm) is <= max_dist; max_dist >= 1 keeps all.
+ * Outputs: hit_ref / hit_common / hit_denom / hit_dist are [nq][top] row-major, best first, n_hits[nq] the hits of each
+ * query (min(top, hits)); hit_dist may be NULL.
+ * Host pointers: exact by the rule above (the device prefilters by the Jaccard index of max_dist lowered by 2^-30 relative,
+ * as mhx_dist_triangle_edges does; the host applies the libm rule to the lists -- a pair it drops ranks behind all it keeps);
+ * distances are host libm doubles; entries behind n_hits[q] are zero.
+ * device_ptrs != 0: all pointers are device pointers, the lists stay on the device: prefiltered only (see
+ * mhx_dist_triangle_edges), still in rank order, hit_dist the device's log, entries behind n_hits[q] unspecified.
+ * nq == 0 or nr == 0: MHX_OK, n_hits zeroed where there are queries.  MHX_E_ARG: top outside 1 .. 64, max_dist not a
+ * number, k outside 1 .. 32, s or stride zero, a len > stride (host form), a null required pointer.
+ * Both sets are split into value ranges once per call with one shift; reference slices of 32 lists and query batches form
+ * the blocks, a block's candidates are merged into the queries' best lists by one wave per query.
+ * Ranges as mhx_dist_triangle (64 at s = 1000); MHX_SEARCH_GEOMETRY=dist takes mhx_dist_batch's geometry, MHX_SEARCH_QBATCH
+ * bounds the queries of a block.  mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report
+ * this call too. */
+int mhx_dist_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr,
+                    uint32_t stride, int k, uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref, uint32_t *hit_common,
+                    uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits, int device_ptrs);
+/* The same at file level: for every query sketch, in argument order and then file order, its hits best first as `mash dist`
+ * rows "ref\tquery\tdist\tp\tcommon/denom\n" (p = mhx_p_value); a query without hits prints nothing.  opts == NULL means
+ * {sizeof, 5, 1, 1}.  max_p_value drops the rows with p > max_p_value from the `top` already chosen by rank and distance:
+ * fewer rows may be printed, a lower-ranked pair is never promoted into their place.  k / seed / sketch-size mismatches
+ * (MHX_E_MISMATCH) and damaged files as mhx_dist_files_multi; MHX_E_ARG: struct_size != sizeof(mhx_search_opts), top outside
+ * 1 .. 64, a bound that is not a number.  The reference file is read, checked and staged once; the queries are processed
+ * in batches, so host memory stays bounded whatever n_qry is.  Not pinned by mash output (mash has no such command): pinned
+ * by the restated rule (tests/search_rule.py), its pairs by the mash-pinned distance path. */
+typedef struct mhx_search_opts {
+    uint32_t struct_size; /* sizeof(mhx_search_opts) */
+    uint32_t top;         /* hits per query, 1 .. 64 */
+    double max_dist;      /* keep pairs with distance <= max_dist (1: all) */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+} mhx_search_opts;
+int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf,
+                     size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
  * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is

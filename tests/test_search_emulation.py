@@ -1,0 +1,132 @@
+"""CPU emulation of the reference-set search (auriclass_amd/csrc/mhx_search.h, mhx_triangle.h and mhx_dist.h, the very
+functions the kernels run): tests/emul/search_emul.cpp runs them sequentially -- one shift, the split of both sets, block
+by block the range pass, the finish walk and search_insert per candidate, then the host's exact rule.  The order on its
+own (antisymmetric, transitive), the insertion against every arrival order, and the whole search against the rule of
+tests/search_rule.py on the shared case set."""
+import ctypes
+import itertools
+
+import numpy as np
+import pytest
+
+from tests import emul_build
+from tests import search_cases as sc
+from tests import search_rule as rule
+from tests import triangle_cases as tc
+
+
+@pytest.fixture(scope="module")
+def emul():
+    L = emul_build.load("search_emul")
+    u32, u64, vp = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
+    L.emul_search_better.argtypes = [u32] * 6
+    L.emul_search_better.restype = ctypes.c_int
+    L.emul_search_insert_many.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp]
+    L.emul_search_insert_many.restype = u32
+    L.emul_search_blocks.argtypes = [u32, u32, u32, vp, u64, vp]
+    L.emul_search_blocks.restype = None
+    L.emul_search.argtypes = [vp, vp, u32, vp, vp, u32, u32, u32, ctypes.c_int, u32, u32, ctypes.c_int, ctypes.c_double, u32, vp, vp, vp, vp, vp, vp]
+    L.emul_search.restype = ctypes.c_int
+    return L
+
+
+def sweep():
+    """(ref, common, denom): equal indices with different counts (1/2, 2/4, 500/1000), 0/0 and n/n, products beyond 2^32"""
+    big = 2 ** 32 - 1
+    fr = [(0, 0), (1, 1), (7, 7), (big, big), (1, 2), (2, 4), (500, 1000), (0, 5), (0, big), (1, big), (big - 1, big), (big - 2, big - 1),
+          (2 ** 31, big), (2 ** 31 - 1, big - 2), (65536, 65537), (65535, 65536), (3, 1000), (999, 1000), (49_999, 50_000)]
+    return [(r, c, d) for r, (c, d) in zip(itertools.cycle([5, 2, 9, 2 ** 32 - 1, 0]), fr)] + [(4, 1, 2), (6, 2, 4), (1, 0, 0)]
+
+
+def test_better_is_a_strict_total_order(emul):
+    items = sweep()
+    b = lambda x, y: bool(emul.emul_search_better(*x, *y))
+    for x in items:
+        assert not b(x, x)
+        for y in items:
+            assert b(x, y) == rule.better(x, y)                 # the library's order is the rule's
+            if x != y:
+                assert b(x, y) != b(y, x), (x, y)               # antisymmetric, and total: distinct references never tie
+    for x, y, z in itertools.product(items, repeat=3):
+        if b(x, y) and b(y, z):
+            assert b(x, z), (x, y, z)                          # transitive
+
+
+def insert_all(L, ref, common, denom, order, top):
+    order = np.ascontiguousarray(order, np.uint32)
+    out = [np.zeros(top, np.uint32) for _ in range(3)]
+    m = L.emul_search_insert_many(ref.ctypes.data, common.ctypes.data, denom.ctypes.data, order.ctypes.data, order.size, top,
+                                  *[a.ctypes.data for a in out])
+    return [a[:m].tolist() for a in out]
+
+
+@pytest.mark.parametrize("top", [1, 5, 64])
+def test_insertion_does_not_depend_on_the_order_of_arrival(emul, top):
+    common, denom, dist = sc.matrix()
+    rng = np.random.default_rng(top)
+    ref = np.arange(200, dtype=np.uint32)
+    blocks = [np.arange(r0, min(200, r0 + 32)) for r0 in range(0, 200, 32)]
+    shuffled = [blocks[i] for i in rng.permutation(len(blocks))]
+    for q in (0, 2, 24, 25, 26, 27, 60):
+        c, d = np.ascontiguousarray(common[q]), np.ascontiguousarray(denom[q])
+        want = rule.select([(r, int(c[r]), int(d[r]), 0.0) for r in range(200)], top)
+        want = [[h[a] for h in want] for a in range(3)]
+        for order in (np.concatenate(blocks), np.concatenate(blocks[::-1]), np.concatenate(shuffled), rng.permutation(200)):
+            assert insert_all(emul, ref, c, d, order, top) == want, q
+
+
+def test_schedule_covers_every_pair_once(emul):
+    for nq, nr, qb in ((150, 200, 150), (150, 200, 48), (1, 1, 1), (40, 33, 7), (3, 31, 64)):
+        out = np.zeros(4 * 256, np.uint32)
+        count = ctypes.c_uint64(0)
+        emul.emul_search_blocks(nq, nr, min(qb, nq), out.ctypes.data, 256, ctypes.byref(count))
+        seen = np.zeros((nq, nr), np.int32)
+        for r0, bnr, q0, bnq in out[:4 * count.value].reshape(-1, 4).tolist():
+            assert r0 % 32 == 0 and 1 <= bnr <= 32 and 1 <= bnq <= qb
+            seen[q0:q0 + bnq, r0:r0 + bnr] += 1
+        assert (seen == 1).all()
+
+
+def run_emul(L, qs, rs, s, top, max_dist, ranges=0, qbatch=0, reverse=0, k=sc.K):
+    stride = (max(max(map(len, qs)), max(map(len, rs)), 1) + 15) // 16 * 16
+    Q, ql = tc.pad_rows(qs, stride)
+    R, rl = tc.pad_rows(rs, stride)
+    nq = len(qs)
+    out = [np.full((nq, top), 0xFFFFFFFF, np.uint32) for _ in range(3)] + [np.full((nq, top), -1.0), np.full(nq, 0xFFFFFFFF, np.uint32)]
+    stats = np.zeros(5, np.uint32)
+    rc = L.emul_search(Q.ctypes.data, ql.ctypes.data, nq, R.ctypes.data, rl.ctypes.data, len(rs), stride, s, k, ranges, qbatch, reverse,
+                       max_dist, top, *[a.ctypes.data for a in out], stats.ctypes.data)
+    return rc, out, stats
+
+
+def same(got, want):
+    for a, b in zip(got[:3], want[:3]):
+        assert np.array_equal(a, b)
+    assert np.array_equal(got[3].view(np.uint64), want[3].view(np.uint64)) and np.array_equal(got[4], want[4])
+
+
+@pytest.mark.parametrize("top", [1, 5, 64])
+@pytest.mark.parametrize("max_dist", [0.0, 0.05, 1.0])
+def test_emulated_search_equals_the_rule(emul, top, max_dist):
+    refs, s = sc.references()
+    rc, got, stats = run_emul(emul, sc.queries(), refs, s, top, max_dist)
+    print("ranges", stats[0], "blocks", stats[1], "passed the prefilter", stats[3], "dropped by the exact rule", stats[4])
+    assert rc == 0 and stats[0] == 64 and stats[1] == 7 and stats[2] == 0
+    same(got, sc.expected(top, max_dist))
+
+
+@pytest.mark.parametrize("ranges,qbatch,reverse", [(64, 13, 0), (64, 13, 1), (1024, 0, 1), (2048, 16, 0)])
+def test_batches_geometries_and_block_order(emul, ranges, qbatch, reverse):
+    """40 queries in small batches, so that a query's list is carried across batches and slices; the blocks last to first;
+    the base finish at 1024 ranges and the windowed one at 2048"""
+    refs, s = sc.references()
+    for top, max_dist in ((5, 0.05), (64, 1.0)):
+        rc, got, stats = run_emul(emul, sc.queries()[:40], refs, s, top, max_dist, ranges, qbatch, reverse)
+        assert rc == 0 and stats[0] == ranges and stats[1] == 7 * (-(-40 // qbatch) if qbatch else 1)
+        same(got, sc.expected(top, max_dist, 40))
+
+
+def test_crowded_values_raise_the_flag(emul):
+    lists, s = tc.crowded(40)
+    rc, got, stats = run_emul(emul, lists[:20], lists[20:], s, 5, 1.0)
+    assert rc == 1 and stats[2] == stats[1] == 1
