@@ -82,13 +82,23 @@ MHX_HD void dist_split_offsets(uint32_t *offs, uint32_t per, uint32_t i, uint32_
 // ---- range pass -------------------------------------------------------------------------------------------------------
 MHX_HD uint32_t dist_slot_of(uint64_t v) { return (uint32_t)((v * 0x9E3779B97F4A7C15ull) >> 40) & (kDistTableSlots - 1); }
 
-// bit mask of the references that hold v (0: none); the table always has vacant slots (kDistTableLimit)
+// The table of one range: kDistTableSlots keys and kDistMaskWords masks.  A hash may be any 64-bit value, kEmptyKey (2^64 - 1)
+// included -- the segmented sketch appends it behind a row's sorted values -- but a slot cannot hold the vacant-slot marker as
+// a key: a compare-and-swap of kEmptyKey against kEmptyKey claims nothing, the slot stays vacant with the reference's bit on
+// it, the next key to probe it inherits the bit, and a query that holds 2^64 - 1 reads the mask of whatever vacant slot ends
+// its probe.  So that one value stays OUT of the slots: its references are kept in the mask word behind the last slot
+// (kDistEmptyMask), insert and probe go there directly, and it does not count as a key of the table.
+constexpr int kDistEmptyMask = kDistTableSlots;    // masks[kDistEmptyMask]: the references that hold kEmptyKey
+constexpr int kDistMaskWords = kDistTableSlots + 1;
+
+// bit mask of the references that hold v (0: none); the table always has vacant slots (kDistTableLimit).  v == kEmptyKey
+// "matches" the first vacant slot of its probe and takes the word kept for it instead of that slot's.
 MHX_HD uint32_t dist_table_probe(const unsigned long long *keys, const uint32_t *masks, uint64_t v)
 {
     uint32_t sl = dist_slot_of(v), m = 0;
     for (;;) {
         const unsigned long long kx = keys[sl];
-        if (kx == v) { m = masks[sl]; break; }
+        if (kx == v) { m = masks[kx == kEmptyKey ? (uint32_t)kDistEmptyMask : sl]; break; }
         if (kx == kEmptyKey) break;
         sl = (sl + 1) & (kDistTableSlots - 1);
     }
@@ -97,9 +107,10 @@ MHX_HD uint32_t dist_table_probe(const unsigned long long *keys, const uint32_t 
 
 // One reference hash into the table, by ONE thread of control (the emulator's form; the kernels' dist_table_insert is this
 // with atomicCAS / atomicOr in place of the plain accesses).  Returns the number of keys added: 0, 1, or kDistTableSlots
-// when the table had no room at all.
+// when the table had no room at all.  kEmptyKey goes into its own mask word and adds no key.
 MHX_HD uint32_t dist_table_insert_plain(unsigned long long *keys, uint32_t *masks, uint64_t v, uint32_t r)
 {
+    if (v == kEmptyKey) { masks[kDistEmptyMask] |= 1u << r; return 0u; }
     uint32_t sl = dist_slot_of(v);
     for (int probe = 0; probe < kDistTableSlots; ++probe) {
         const unsigned long long prev = keys[sl];
@@ -107,6 +118,15 @@ MHX_HD uint32_t dist_table_insert_plain(unsigned long long *keys, uint32_t *mask
         sl = (sl + 1) & (kDistTableSlots - 1);
     }
     return (uint32_t)kDistTableSlots;
+}
+
+// a vacant table: every slot, and the word of kEmptyKey (work item `i` of `step` clears its share)
+MHX_HD void dist_table_clear(unsigned long long *keys, uint32_t *masks, int i, int step)
+{
+    for (; i < kDistMaskWords; i += step) {
+        if (i < kDistTableSlots) keys[i] = kEmptyKey;
+        masks[i] = 0;
+    }
 }
 
 // bits 4j .. 4j+3 of a reference mask -> the low bit of the four byte counters of word j

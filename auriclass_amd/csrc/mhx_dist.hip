@@ -200,9 +200,12 @@ __device__ __forceinline__ uint32_t wave_sum_bytes(uint32_t v)
 // bounded by the table size, so a table that does fill up (non-uniform values) ends the build instead of hanging it; the
 // caller checks `ndistinct` against kDistTableLimit behind the barrier and gives the range up.
 // returns the number of keys this call added (0 or 1; kDistTableSlots when the table had no room at all): the callers sum
-// it per thread and add the wave totals to the shared count once, behind the build (dist_table_count)
+// it per thread and add the wave totals to the shared count once, behind the build (dist_table_count).
+// kEmptyKey (2^64 - 1, a legitimate hash) cannot be a slot's key: its references go into the mask word kept for it behind
+// the slots (mhx_dist.h: kDistEmptyMask) and it adds no key.
 __device__ __forceinline__ uint32_t dist_table_insert(unsigned long long *keys, uint32_t *masks, uint64_t v, uint32_t r)
 {
+    if (v == kEmptyKey) { atomicOr(&masks[kDistEmptyMask], 1u << r); return 0u; }
     uint32_t sl = dist_slot_of(v);
 #pragma nounroll
     for (int probe = 0; probe < kDistTableSlots; ++probe) {
@@ -222,13 +225,13 @@ __device__ __forceinline__ void dist_table_count(uint32_t *ndistinct, uint32_t m
 template <bool kWide> __global__ __launch_bounds__(256) void dist_range_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long keys[kDistTableSlots];
-    __shared__ uint32_t masks[kDistTableSlots];
+    __shared__ uint32_t masks[kDistMaskWords];
     __shared__ uint32_t too_big;
     // neighbouring ranges share the cache lines their slices begin and end in: consecutive workgroups go round the eight
     // XCDs, so this order puts ranges p, p + 1, ... of one eighth of the value space on ONE XCD (its L2), close in time
     const uint32_t R = dist_ranges<kWide>(w), p = dist_range_of_block(blockIdx.x, R), per = R + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < kDistTableSlots; i += 256) { keys[i] = kEmptyKey; masks[i] = 0; }
+    dist_table_clear(keys, masks, tid, 256);
     if (tid == 0) too_big = 0; // number of distinct keys in the table
     __syncthreads();
     // build: wave w inserts references w, w+4, ...; a reference's slice of this range is a
@@ -334,7 +337,7 @@ constexpr int kLaneBlock = MHX_DIST_LANE_BLOCK; // queries (= threads) per workg
 template <bool kWide> __global__ __launch_bounds__(kLaneBlock) void dist_range_lane_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long keys[kDistTableSlots];
-    __shared__ uint32_t masks[kDistTableSlots];
+    __shared__ uint32_t masks[kDistMaskWords];
     __shared__ uint32_t ndistinct; // keys in the table
     const uint32_t R = dist_ranges<kWide>(w), p = dist_range_of_block(blockIdx.x, R), per = R + 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -343,7 +346,7 @@ template <bool kWide> __global__ __launch_bounds__(kLaneBlock) void dist_range_l
     // reference and wave
     uint32_t rb = 0, re = 0;
     if ((uint32_t)lane < a.nr) { rb = w.offs_r[lane * per + p]; re = w.offs_r[lane * per + p + 1]; }
-    for (int i = tid; i < kDistTableSlots; i += kLaneBlock) { keys[i] = kEmptyKey; masks[i] = 0; }
+    dist_table_clear(keys, masks, tid, kLaneBlock);
     if (tid == 0) ndistinct = 0;
     uint32_t added = 0;
     auto insert = [&](uint64_t v, uint32_t r) { added += dist_table_insert(keys, masks, v, r); };
@@ -485,7 +488,7 @@ __global__ __launch_bounds__(256) void dist_segstart_kernel(const DistArgs a, Di
 __global__ __launch_bounds__(256) void dist_walk_kernel(const DistArgs a, DistWork w)
 {
     __shared__ unsigned long long keys[kDistTableSlots];
-    __shared__ uint32_t masks[kDistTableSlots];
+    __shared__ uint32_t masks[kDistMaskWords];
     __shared__ uint32_t too_big;
     constexpr uint32_t G = kDistRanges / kDistWalk, per = kDistRanges + 1;
     // consecutive workgroups go round the eight XCDs: neighbouring segments of one eighth of the value space on one XCD
@@ -509,7 +512,7 @@ __global__ __launch_bounds__(256) void dist_walk_kernel(const DistArgs a, DistWo
 #pragma nounroll
     for (uint32_t r = 0; r < kDistWalk; ++r) {
         const uint32_t p = g * kDistWalk + r;
-        for (int s2 = tid; s2 < kDistTableSlots; s2 += 256) { keys[s2] = kEmptyKey; masks[s2] = 0; }
+        dist_table_clear(keys, masks, tid, 256);
         if (tid == 0) too_big = 0; // number of distinct keys in the table
         __syncthreads();
         uint32_t added = 0;
@@ -548,7 +551,7 @@ __global__ __launch_bounds__(256) void dist_walk_kernel(const DistArgs a, DistWo
                     uint32_t sl = slot_of(v), m = 0;
                     for (;;) {
                         const unsigned long long kx = keys[sl];
-                        if (kx == v) { m = masks[sl]; break; }
+                        if (kx == v) { m = masks[kx == kEmptyKey ? (uint32_t)kDistEmptyMask : sl]; break; } // (dist_table_probe)
                         if (kx == kEmptyKey) break;
                         sl = (sl + 1) & (kDistTableSlots - 1);
                     }

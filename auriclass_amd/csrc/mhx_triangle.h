@@ -102,10 +102,15 @@ MHX_HD void tri_finish_walk(const DistPair &x, const uint32_t *seg_uni, const ui
 // rounding is ~1e-16 -- passes, a few more may, and the host drops those.
 MHX_HD bool tri_keep(uint32_t common, uint32_t denom, double jmin) { return common == denom || (double)common >= jmin * (double)denom; }
 
-// host: the Jaccard index below which the device drops a pair (0: max_dist >= 1 keeps everything)
+// host: the Jaccard index below which the device drops a pair (0: max_dist >= 1 keeps everything).  No distance is
+// negative, so a bound below 0 is the bound 0 to the prefilter: it keeps the identical pairs (common == denom), which the
+// exact rule of the host forms then drops.  (Taken as it is, 2 exp(k max_dist) - 1 falls to 0 and below at max_dist <=
+// -ln 2 / k, and the index of the bound with it: the prefilter would keep every pair.)
 MHX_HD double tri_jmin(double max_dist, int k)
 {
-    return max_dist >= 1.0 ? 0.0 : (1.0 / (2.0 * exp((double)k * max_dist) - 1.0)) * (1.0 - 0x1p-30);
+    if (max_dist >= 1.0) return 0.0;
+    const double d = max_dist < 0.0 ? 0.0 : max_dist;
+    return (1.0 / (2.0 * exp((double)k * d) - 1.0)) * (1.0 - 0x1p-30);
 }
 
 // the Mash distance of a pair (the arithmetic of dist_store and of the host forms)

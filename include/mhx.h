@@ -354,6 +354,8 @@ int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t 
  * distances are host libm doubles; entries behind n_hits[q] are zero.
  * device_ptrs != 0: all pointers are device pointers, the lists stay on the device: prefiltered only (see
  * mhx_dist_triangle_edges), still in rank order, hit_dist the device's log, entries behind n_hits[q] unspecified.
+ * max_dist < 0: no distance is negative, so the host form returns no hit at all; the prefilter takes such a bound for 0, so
+ * the device form's lists are those of max_dist = 0 -- the pairs with common == denom, distance 0.
  * nq == 0 or nr == 0: MHX_OK, n_hits zeroed where there are queries.  MHX_E_ARG: top outside 1 .. 64, max_dist not a
  * number, k outside 1 .. 32, s or stride zero, a len > stride (host form), a null required pointer.
  * Both sets are split into value ranges once per call with one shift; reference slices of 32 lists and query batches form

@@ -57,14 +57,14 @@ extern "C" int emul_dist(const uint64_t *q, const uint32_t *q_len, uint32_t nq, 
     const uint32_t nwords = (nr + 3) / 4, cstride = 4 * nwords;
     std::vector<uint32_t> cpart((size_t)nq * R * nwords, 0xA5A5A5A5u);
     std::vector<unsigned long long> keys(kDistTableSlots);
-    std::vector<uint32_t> masks(kDistTableSlots);
+    std::vector<uint32_t> masks(kDistMaskWords);
     uint32_t flag = 0, longest_slice = 0, most_keys = 0;
     std::vector<uint8_t> seen(R, 0);
     for (uint32_t block = 0; block < R; ++block) {
         const uint32_t p = dist_range_of_block(block, R);
         if (p >= R || seen[p]) return -3; // the order must be a permutation of the ranges
         seen[p] = 1;
-        for (int i = 0; i < kDistTableSlots; ++i) { keys[i] = kEmptyKey; masks[i] = 0; }
+        dist_table_clear(keys.data(), masks.data(), 0, 1);
         uint32_t ndistinct = 0;
         for (uint32_t ri = 0; ri < nr; ++ri) {
             const uint32_t b = offs_r[(size_t)ri * per + p], e = offs_r[(size_t)ri * per + p + 1];

@@ -125,7 +125,7 @@ extern "C" int emul_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     std::vector<SearchHit> lists((size_t)nq * top);
     std::vector<uint32_t> n(nq, 0);
     std::vector<unsigned long long> keys(kDistTableSlots);
-    std::vector<uint32_t> masks(kDistTableSlots);
+    std::vector<uint32_t> masks(kDistMaskWords);
     const uint64_t nblocks = search_blocks(nq, nr, qbatch);
     uint32_t nflagged = 0, passed = 0, dropped = 0;
     for (uint64_t bi = 0; bi < nblocks; ++bi) {
@@ -138,7 +138,7 @@ extern "C" int emul_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq
         uint32_t flag = 0;
         for (uint32_t block = 0; block < R; ++block) {
             const uint32_t p = dist_range_of_block(block, R);
-            for (int i = 0; i < kDistTableSlots; ++i) { keys[i] = kEmptyKey; masks[i] = 0; }
+            dist_table_clear(keys.data(), masks.data(), 0, 1);
             uint32_t ndistinct = 0;
             for (uint32_t ri = 0; ri < b.nr; ++ri) {
                 const uint32_t lo = offs_r[(size_t)ri * per + p], hi = offs_r[(size_t)ri * per + p + 1];

@@ -75,7 +75,7 @@ extern "C" int emul_triangle(const uint64_t *rows, const uint32_t *len, uint32_t
     const uint64_t npairs = (uint64_t)n * (n - 1) / 2;
     std::vector<uint8_t> written(npairs, 0);
     std::vector<unsigned long long> keys(kDistTableSlots);
-    std::vector<uint32_t> masks(kDistTableSlots);
+    std::vector<uint32_t> masks(kDistMaskWords);
     uint32_t longest_slice = 0, most_keys = 0, nblocks = 0, nflagged = 0, wasted = 0;
     TriBlock b;
     for (bool more = tri_first_block(n, qbatch, b); more; more = tri_next_block(n, qbatch, b)) {
@@ -89,7 +89,7 @@ extern "C" int emul_triangle(const uint64_t *rows, const uint32_t *len, uint32_t
         for (uint32_t block = 0; block < R; ++block) {
             const uint32_t p = dist_range_of_block(block, R);
             if (p >= R) return -3;
-            for (int i = 0; i < kDistTableSlots; ++i) { keys[i] = kEmptyKey; masks[i] = 0; }
+            dist_table_clear(keys.data(), masks.data(), 0, 1);
             uint32_t ndistinct = 0;
             for (uint32_t ri = 0; ri < nr; ++ri) {
                 const uint32_t lo = offs_r[(size_t)ri * per + p], hi = offs_r[(size_t)ri * per + p + 1];

@@ -7,7 +7,9 @@ fmt_g.  No mash output is recorded for it (mash has no such command).  Shared by
                  a.common * b.denom > b.common * a.denom in integers; common == denom counts as 1/1 (that includes 0/0, two
                  empty lists, whose distance is 0); pairs of equal index go by the lower reference index.  A total order.
                  Not by the distance: it is clamped to 1, so for small k many indices print as 1.
-    hit        = a pair whose distance is <= max_dist (max_dist >= 1 keeps everything)
+    hit        = a pair whose distance is <= max_dist (max_dist >= 1 keeps everything; max_dist < 0 keeps nothing: no
+                 distance is negative).  The device-pointer form of mhx_dist_search only prefilters, and its prefilter
+                 takes a negative bound for 0: there its lists are the rule's at max_dist = 0, the pairs of distance 0
     result     = per query the first min(top, hits) hits in rank order
     text       = for every query sketch, in argument order and then file order, its result as `mash dist` rows
                  "ref\\tquery\\tdistance\\tp\\tcommon/denom\\n"; rows with p > max_p_value are dropped from the result

@@ -9,6 +9,7 @@ import pytest
 
 from oracle import mash_oracle as mo
 from tests import emul_build
+from tests import extreme_cases as xc
 
 WORST_HI = int(2 ** 63.01)   # the scale is rounded up to a power of two: values just above 2^63 leave half of the ranges in use
 
@@ -182,3 +183,43 @@ def test_batches_of_the_windowed_form_keep_32_bit_indices(emul):
             work = 4 * (ranges + 1) * (n + nr) + ranges * n * cell + (ranges // 64) * n * cell * 4 + 4 * 256
             assert n >= 1 and work <= 256 << 20
             assert n * (ranges + 1) < 2 ** 32 and n * ranges * cell < 2 ** 32
+
+
+def run_slices(L, qrys, refs, s, windows=0):
+    """the references in slices of 32, as the host cuts them: one emulated block each"""
+    out = [run_emul(L, list(qrys), list(refs[r0:r0 + 32]), s, windows) for r0 in range(0, len(refs), 32)]
+    return [o[0] for o in out], np.hstack([o[1] for o in out]), np.hstack([o[2] for o in out]), [o[3] for o in out]
+
+
+def assert_matrix(common, denom, want, what):
+    bad = np.argwhere((common != want[0]) | (denom != want[1]))
+    assert bad.size == 0, (what, [(int(q), int(r), int(common[q, r]), int(want[0][q, r]), int(denom[q, r]), int(want[1][q, r])) for q, r in bad[:6]])
+
+
+@pytest.mark.parametrize("windows", [0, 2])
+@pytest.mark.parametrize("mirrored", [False, True])
+def test_the_vacant_slot_marker_as_a_hash(emul, mirrored, windows):
+    """2^64 - 1 (kEmptyKey) in lists that reach the range table, next to values of the same home slot: the planted batch of
+    tests/extreme_cases.py, references inserted in index order, in the base form and with W forced to 2.  Every pair is the
+    oracle's, and the block stays on the fast path.
+    Observed before the range table kept 2^64 - 1 out of its slots (dist_table_insert_plain took it for a key, the slot
+    stayed vacant with the reference's bit on it), in both geometries, as common/denom against the oracle's --
+    plain: (query 0, reference 0) 424/476 for 423/477, one too high; (query 1, reference 0) 0/897 for 1/896 and (query 6,
+    reference 0: the same list twice) 449/451 for 450/450, one too low;
+    mirrored: (query 0, reference 8) 1/897 for 0/898; (query 1, reference 8) 0/894 for 1/893; (query 6, reference 8) 446/448
+    for 447/447; every other pair right."""
+    qrys, refs, s = xc.batch(40, mirrored)
+    rc, common, denom, stats = run_slices(emul, qrys, refs, s, windows)
+    assert rc == [0, 0] and all(st[0] == (1024 if not windows else 2048) and st[3] == (54 if not windows else 53) for st in stats)
+    assert_matrix(common, denom, xc.batch_expected(40, mirrored), "mirrored" if mirrored else "plain")
+
+
+@pytest.mark.parametrize("case,args,shift", [("with_zero", (), 54), ("below_the_ranges", (1024, 300, 1000), 0), ("below_the_ranges", (16, 10, 16), 0),
+                                             ("power_of_two_top", (40, False), 30), ("power_of_two_top", (40, True), 31)])
+def test_values_uniform_draws_never_produce(emul, case, args, shift):
+    """hash 0 in zero-padded rows; every value below the number of ranges (shift 0); the largest value exactly 2^40 - 1 and
+    exactly 2^40"""
+    qrys, refs, s = getattr(xc, case)(*args)
+    rc, common, denom, stats = run_slices(emul, qrys, refs, s)
+    assert rc == [0, 0] and all(st[0] == 1024 and st[3] == shift for st in stats)
+    assert_matrix(common, denom, xc.oracle_matrix(qrys, refs, s), case)

@@ -195,3 +195,101 @@ def test_device_pointers_from_the_segmented_sketch(lib):
         assert np.array_equal(a.cpu().numpy().view(np.uint32)[live], b[live])
     x, wx = dist.cpu().numpy()[live], want[3][live]
     assert np.all(np.abs(x - wx) <= 2e-16 * np.maximum(1.0, np.abs(wx)) + 1e-300)   # device log(): <= 1 ulp (as tests/test_gpu_triangle.py)
+
+
+def all_pairs(qs, rs, s):
+    """(common, denom) [nq, nr] of every pair by sorting the two lists together, in numpy: the second copy of a shared hash
+    directly follows the first, its place in the union is its position less the copies before it, and it counts when
+    that place is below s; denom = min(s, size of the union).  No list may hold 2^64 - 1 or 2^64 - 2 (the paddings)."""
+    L = max(max(map(len, qs)), max(map(len, rs)))
+    pad_r, pad_q = np.uint64(2 ** 64 - 1), np.uint64(2 ** 64 - 2)
+    assert all(len(v) == 0 or v[-1] < pad_q for v in list(qs) + list(rs))
+    R = np.full((len(rs), L), pad_r, np.uint64)
+    for j, v in enumerate(rs):
+        R[j, :len(v)] = v
+    rl = np.array([len(v) for v in rs], np.int64)
+    common = np.zeros((len(qs), len(rs)), np.uint32)
+    denom = np.zeros_like(common)
+    at = np.arange(2 * L, dtype=np.int64)[None, :]
+    for i, q in enumerate(qs):
+        row = np.full(L, pad_q, np.uint64)
+        row[:len(q)] = q
+        both = np.sort(np.concatenate([R, np.broadcast_to(row, R.shape)], axis=1), axis=1)   # the paddings behind every hash
+        second = np.zeros(both.shape, bool)
+        second[:, 1:] = both[:, 1:] == both[:, :-1]
+        second &= at < (rl + len(q))[:, None]
+        place = at - np.cumsum(second, axis=1)
+        common[i] = (second & (place < s)).sum(axis=1)
+        denom[i] = np.minimum(s, rl + len(q) - second.sum(axis=1))
+    return common, denom
+
+
+def oracle_distances(common, denom, k):
+    """the oracle's distance for every (common, denom) of the matrices: compareSketches on two lists that produce them"""
+    dist = np.zeros(common.shape, np.float64)
+    for c, d in {(int(c), int(d)) for c, d in zip(common.ravel(), denom.ravel())}:
+        wc, wd, x = mo.compare(np.arange(d, dtype=np.uint64), np.arange(c, dtype=np.uint64), d, k)
+        assert (wc, wd) == (c, d) and d > 0
+        dist[(common == c) & (denom == d)] = x
+    return dist
+
+
+def test_more_blocks_than_one_group_of_flag_words(lib, monkeypatch):
+    """The flag words of the blocks come back per group of 4096 blocks.  One query per block, 150 queries against 900
+    references (29 slices) at s = 64 (16 ranges): 4350 blocks, the last 254 in a second group -- its flag words are cleared
+    and used again, and one of its blocks per query falls back: slice 27 holds 32 lists crowded into one value range (2048 keys
+    for a table of 1536).  Queries 145 and 147 of the second group derive from references of that slice, so their lists hold
+    what the generic kernel computed there.  The expected lists are the rule over all pairs computed in numpy, that matrix
+    cross-checked against the oracle's compareSketches on 400 pairs."""
+    monkeypatch.setenv("MHX_SEARCH_QBATCH", "1")
+    rng = np.random.default_rng(4350)
+    s, nq, nr = 64, 150, 900
+    bases = [tc.sketch_like(rng, s) for _ in range(30)]
+    refs = [tc.mutate(rng, bases[j % 30], 0.02 * (j % 11)) if j % 3 else tc.sketch_like(rng, s) for j in range(nr)]
+    lo = 1 << 62
+    for j in range(27 * 32, 28 * 32):
+        refs[j] = np.uint64(lo) + tc.sketch_like(rng, s, hi=2 ** 20)
+    qrys = [tc.mutate(rng, refs[(7 * i) % nr], 0.03 * (i % 9)) for i in range(nq)]
+    qrys[145], qrys[147], qrys[3] = refs[870].copy(), refs[880][5:].copy(), refs[866][::2].copy()
+    nblocks = nq * ((nr + 31) // 32)
+    assert nblocks > 4096 and 145 * 29 + 27 >= 4096   # query 145's block with slice 27 lies in the second group
+    assert len(np.unique(np.concatenate(refs[27 * 32:28 * 32]))) > 1536
+    common, denom = all_pairs(qrys, refs, s)
+    sample = set(zip(rng.integers(0, nq, 380).tolist(), rng.integers(0, nr, 380).tolist())) | {(q, r) for q in (3, 145, 147) for r in (866, 870, 880, 895)}
+    for q, r in sample:
+        assert (int(common[q, r]), int(denom[q, r])) == mo.compare(refs[r], qrys[q], s, K)[:2], (q, r)
+    dist = oracle_distances(common, denom, K)
+    for top, max_dist in ((5, 1.0), (3, 0.1)):
+        got = run(qrys, refs, s, top, max_dist)
+        assert lib.mhx_last_dist_ranges() == 16 and lib.mhx_last_dist_fallback_blocks() == nq   # slice 27 once per query
+        want = sc.lists_from(common, denom, dist, top, max_dist)
+        assert want[0][145, 0] == 870 and want[0][147, 0] == 880
+        check(got, want)
+
+
+def test_a_negative_bound(lib):
+    """No distance is negative.  The host form returns no hit.  The device form only prefilters, and the prefilter takes a
+    negative bound for 0: its lists are the rule's at max_dist = 0 -- the pairs of distance 0 -- however negative the bound."""
+    refs, s = sc.references()
+    qs, top = sc.queries()[:40], 5
+    for max_dist in (-0.001, -1.0):
+        got = run(qs, refs, s, top, max_dist)
+        assert not got[4].any() and not got[0].any() and not got[1].any()
+    want = sc.expected(top, 0.0, 40)
+    assert want[4].any()
+    stride = 1008
+    Q, ql = tc.pad_rows(qs, stride)
+    R, rl = tc.pad_rows(refs, stride)
+    dev = f"cuda:{torch.cuda.current_device()}"
+    d = [torch.from_numpy(a.view(np.int64 if a.dtype == np.uint64 else np.int32)).to(dev) for a in (Q, ql, R, rl)]
+    for max_dist in (-0.001, -1.0):
+        out = [torch.full((40, top), 7, dtype=torch.int32, device=dev) for _ in range(3)]
+        n_hits = torch.full((40,), 7, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        engine.dist_search_device(d[0].data_ptr(), d[1].data_ptr(), 40, d[2].data_ptr(), d[3].data_ptr(), len(refs), stride, K, s, top, max_dist,
+                                  out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), 0, n_hits.data_ptr())
+        n = n_hits.cpu().numpy().view(np.uint32)
+        assert np.array_equal(n, want[4])
+        live = np.arange(top)[None, :] < n[:, None]
+        for a, b in zip(out, want[:3]):
+            assert np.array_equal(a.cpu().numpy().view(np.uint32)[live], b[live])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import emul_build
+from tests import extreme_cases as xc
 from tests import search_cases as sc
 from tests import search_rule as rule
 from tests import triangle_cases as tc
@@ -130,3 +131,27 @@ def test_crowded_values_raise_the_flag(emul):
     lists, s = tc.crowded(40)
     rc, got, stats = run_emul(emul, lists[:20], lists[20:], s, 5, 1.0)
     assert rc == 1 and stats[2] == stats[1] == 1
+
+
+@pytest.mark.parametrize("ranges,qbatch", [(0, 0), (1024, 13), (2048, 0)])
+@pytest.mark.parametrize("mirrored", [False, True])
+def test_the_vacant_slot_marker_as_a_hash(emul, mirrored, ranges, qbatch):
+    """2^64 - 1 (kEmptyKey) and values of its home slot in both sets (the planted batch of tests/extreme_cases.py): the lists
+    are the rule's over the oracle's pairs.  top = 33 and max_dist = 1 put every pair into a list, so a count that is one off
+    shows whatever its rank."""
+    qrys, refs, s = xc.batch(40, mirrored)
+    want = xc.batch_expected(40, mirrored)
+    for top, max_dist in ((33, 1.0), (5, 0.05)):
+        rc, got, stats = run_emul(emul, qrys, refs, s, top, max_dist, ranges, qbatch, k=xc.K)
+        assert rc == 0 and stats[0] == (ranges or 64) and stats[2] == 0
+        same(got, sc.lists_from(*want, top, max_dist))
+
+
+@pytest.mark.parametrize("max_dist", [-0.001, -1.0])
+def test_a_negative_bound_keeps_nothing(emul, max_dist):
+    """the host form: the prefilter passes the identical pairs (it takes the bound for 0), the exact rule drops them all"""
+    refs, s = sc.references()
+    rc, got, stats = run_emul(emul, sc.queries()[:40], refs, s, 5, max_dist)
+    identical = int((sc.matrix()[0][:40] == sc.matrix()[1][:40]).sum())
+    assert rc == 0 and identical > 0 and stats[3] == identical   # fewer than `top` per query: all of them reach the host
+    assert stats[4] == identical and (got[4] == 0).all() and not got[0].any()

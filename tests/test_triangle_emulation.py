@@ -10,6 +10,7 @@ import pytest
 
 from oracle import mash_oracle as mo
 from tests import emul_build
+from tests import extreme_cases as xc
 from tests import triangle_cases as tc
 
 SENTINEL = 0xFFFFFFFF
@@ -196,3 +197,31 @@ def test_prefilter_keeps_what_the_exact_rule_keeps(emul):
                 extra += int((keep.astype(bool) & ~must).sum())
     print("pairs kept beyond the exact rule:", extra, "of", total)
     assert extra < 0.01 * total
+
+
+@pytest.mark.parametrize("ranges", [0, 16, 1024, 2048])
+@pytest.mark.parametrize("mirrored", [False, True])
+def test_the_vacant_slot_marker_as_a_hash(emul, mirrored, ranges):
+    """2^64 - 1 (kEmptyKey) and values of its home slot in one set (the planted batch of tests/extreme_cases.py, references
+    then queries: 73 lists, three slices), through every finish form.  Before the range table kept 2^64 - 1 out of its slots
+    the pairs of its holders with the holders of the colliding value were one off (the figures: tests/test_dist_emulation.py)."""
+    lists, s, (want_c, want_d, _) = xc.batch_as_one_set(40, mirrored)
+    rc, common, denom, stats = run_emul(emul, lists, s, ranges)
+    assert rc == 0 and stats[0] == (ranges or 64) and stats[4] == 0
+    bad = np.flatnonzero((common != want_c) | (denom != want_d))
+    assert bad.size == 0, (bad[:6], common[bad[:6]], want_c[bad[:6]], denom[bad[:6]], want_d[bad[:6]])
+
+
+def test_prefilter_takes_a_negative_bound_for_zero(emul):
+    """no distance is negative: below 0 the prefilter keeps what it keeps at 0, the identical pairs, however far below -- as it
+    stood, 2 exp(k D) - 1 reached 0 at D = -ln 2 / k and the index of the bound went to infinity and then negative, which
+    keeps every pair"""
+    for k in (11, 21, 32):
+        at_zero = emul.emul_tri_jmin(0.0, k)
+        assert at_zero == 1.0 - 2.0 ** -30
+        for D in (-1e-300, -0.001, -0.03, -0.0331, -0.1, -1.0, -1e9, float("-inf")):
+            assert emul.emul_tri_jmin(D, k) == at_zero, (k, D)
+    commons, denoms = np.array([0, 5, 999, 1000, 0], np.uint32), np.array([1000, 1000, 1000, 1000, 0], np.uint32)
+    keep = np.zeros(5, np.uint8)
+    emul.emul_tri_keep_many(commons.ctypes.data, denoms.ctypes.data, 5, emul.emul_tri_jmin(-1.0, 21), keep.ctypes.data)
+    assert keep.tolist() == [0, 0, 0, 1, 1]
