@@ -205,6 +205,23 @@ hipError_t launch_tri_finish_small(const DistArgs &a, const DistWork &w, hipStre
 hipError_t launch_tri_scatter(const TriOut &o, hipStream_t st);
 hipError_t launch_tri_edges(const TriOut &o, hipStream_t st);
 
+// single-linkage clustering of one set (rules: mhx_cluster.h, kernels: mhx_cluster.hip): a block's results, block-local as
+// above, feed a union-find over parent[n] instead of an output of pairs
+struct ClusterOut {
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;
+    uint32_t r0, nr, q0, nq; // the block (mhx_triangle.h: TriBlock)
+    const uint32_t *cmin;    // [s + 1] the bound as integers: a pair is an edge iff common >= cmin[denom]
+    uint32_t s;
+    uint32_t *parent;        // [n] set up by launch_cluster_init; the labels after the last launch_cluster_flatten
+    uint32_t *degree;        // [n] neighbours of every list, may be null
+    unsigned long long *n_edges;
+};
+hipError_t launch_cluster_init(uint32_t *parent, uint32_t *degree, uint32_t n, hipStream_t st);
+hipError_t launch_tri_cluster(const ClusterOut &o, hipStream_t st);
+// parent[i] = the root of i, in a launch of its own; count (may be null) receives the number of roots on top of what it holds
+hipError_t launch_cluster_flatten(uint32_t *parent, uint32_t n, unsigned long long *count, hipStream_t st);
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

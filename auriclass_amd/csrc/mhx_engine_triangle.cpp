@@ -1,7 +1,8 @@
-// mhx_engine_triangle.cpp -- host side of the all-pairs distance within one sketch set (mhx_dist_triangle and
-// mhx_dist_triangle_edges): staging of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE
-// offsets table of the whole set, the fallback of a flagged block to the generic pair kernel, and the exact distance rule
-// and the order of the edge list on the host.  Rules: mhx_triangle.h; kernels: mhx_triangle.hip and mhx_dist.hip.
+// mhx_engine_triangle.cpp -- host side of the all-pairs distance within one sketch set (mhx_dist_triangle,
+// mhx_dist_triangle_edges and mhx_dist_cluster): staging of a host-pointer call, the schedule of (query batch, reference
+// slice) blocks over ONE offsets table of the whole set, the fallback of a flagged block to the generic pair kernel, the
+// exact distance rule and the order of the edge list on the host, and the bound of the clustering as a table of integers.
+// Rules: mhx_triangle.h, mhx_cluster.h; kernels: mhx_triangle.hip, mhx_cluster.hip and mhx_dist.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "mhx_device.h"
+#include "mhx_cluster.h"
 #include "mhx_triangle.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
@@ -33,7 +35,12 @@ struct TriCall { // everything on the device
     uint32_t *edge_i, *edge_j;
     uint64_t cap;
     double jmin;
-    uint64_t found; // out, edge mode: pairs that passed the prefilter
+    uint64_t found; // out, edge mode: pairs that passed the prefilter; cluster mode: the edges
+    // cluster mode (mhx_cluster.h): the pairs feed a union-find over parent [n] instead of an output of pairs
+    bool cluster;
+    const uint32_t *h_cmin; // host, [s + 1]: copied into the workspace
+    uint32_t *parent, *degree; // degree may be null
+    uint32_t clusters;      // out
 };
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -60,7 +67,7 @@ int triangle_device(TriCall &c)
     constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together
     const uint32_t group = std::min(nblocks, kBlockGroup);
     // workspace: [offsets of the set][byte counters][window totals][block-local common, denom][words: shift, 0, the edge
-    // counter (two words), then two per block of a group]
+    // counter (two words), then two per block of a group][cluster mode: the root counter, the cmin table]
     const uint64_t per = (uint64_t)ranges + 1;
     size_t o = 0;
     const size_t o_offs = o; if (fast) o += up256((size_t)c.n * per * 4);
@@ -69,10 +76,13 @@ int triangle_device(TriCall &c)
     const size_t o_lc = o; o += up256((size_t)qbatch * kTriSlice * 4);
     const size_t o_ld = o; o += up256((size_t)qbatch * kTriSlice * 4);
     const size_t o_words = o; o += up256((size_t)(4 + 2 * group) * 4);
+    const size_t o_roots = o; if (c.cluster) o += 256;
+    const size_t o_cmin = o; if (c.cluster) o += up256(((size_t)c.s + 1) * 4);
     if (g.dist_ws.grow(o, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the triangle workspace (%zu bytes)", o);
     uint32_t *offs = (uint32_t *)(g.dist_ws + o_offs), *loc_c = (uint32_t *)(g.dist_ws + o_lc), *loc_d = (uint32_t *)(g.dist_ws + o_ld);
     uint32_t *words = (uint32_t *)(g.dist_ws + o_words), *flags = words + 4;
-    unsigned long long *counter = (unsigned long long *)(words + 2);
+    unsigned long long *counter = (unsigned long long *)(words + 2), *roots = (unsigned long long *)(g.dist_ws + o_roots);
+    uint32_t *cmin = (uint32_t *)(g.dist_ws + o_cmin);
     DistWork w{};
     w.cpart = g.dist_ws + o_cpart;
     w.wtot = (uint32_t *)(g.dist_ws + o_wtot);
@@ -87,6 +97,13 @@ int triangle_device(TriCall &c)
         return x;
     };
     auto take_out = [&](const TriBlock &b, const uint32_t *flag) {
+        if (c.cluster) {
+            ClusterOut t{};
+            t.loc_common = loc_c; t.loc_denom = loc_d; t.flag = flag;
+            t.r0 = b.r0; t.nr = b.nr; t.q0 = b.q0; t.nq = b.nq;
+            t.cmin = cmin; t.s = c.s; t.parent = c.parent; t.degree = c.degree; t.n_edges = counter;
+            return launch_tri_cluster(t, g.stream);
+        }
         TriOut t{};
         t.loc_common = loc_c; t.loc_denom = loc_d; t.flag = flag;
         t.r0 = b.r0; t.nr = b.nr; t.q0 = b.q0; t.nq = b.nq; t.k = c.k;
@@ -98,6 +115,9 @@ int triangle_device(TriCall &c)
     hipError_t le = hipMemsetAsync(words, 0, (size_t)(4 + 2 * group) * 4, g.stream);
     g.last_dist_fallbacks = fast ? 0 : -1;
     g.last_dist_ranges = 0;
+    if (c.cluster && le == hipSuccess) le = hipMemsetAsync(roots, 0, 8, g.stream);
+    if (c.cluster && le == hipSuccess) le = hipMemcpyAsync(cmin, c.h_cmin, ((size_t)c.s + 1) * 4, hipMemcpyHostToDevice, g.stream);
+    if (c.cluster && le == hipSuccess) le = launch_cluster_init(c.parent, c.degree, c.n, g.stream);
     if (fast && le == hipSuccess) {
         DistWork wa = w;
         wa.offs_q = offs; wa.offs_r = offs; wa.params = words; // words[0] the shift of the call, words[1] stays 0
@@ -120,6 +140,8 @@ int triangle_device(TriCall &c)
             le = launch_dist_range_pass(x, w, g.stream);
             if (le == hipSuccess) le = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
             if (le == hipSuccess) le = take_out(blk, w.params + 1);
+            // cluster mode: the trees stay shallow when every reference slice ends with a flatten pass
+            if (c.cluster && le == hipSuccess && (b + 1 == b1 || blocks[b + 1].r0 != blk.r0)) le = launch_cluster_flatten(c.parent, c.n, nullptr, g.stream);
         }
         if (!fast || le != hipSuccess) continue;
         std::vector<uint32_t> back((size_t)(b1 - b0) * 2);
@@ -133,22 +155,25 @@ int triangle_device(TriCall &c)
                 ++g.last_dist_fallbacks;
             }
     }
+    if (c.cluster && le == hipSuccess) le = launch_cluster_flatten(c.parent, c.n, roots, g.stream); // behind the last block: the labels
     hipEventRecord(g.ev1, g.stream);
     if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
     if (le != hipSuccess) return fail(MHX_E_HIP, "triangle kernel launch failed: %s", hipGetErrorString(le));
-    unsigned long long found = 0;
+    unsigned long long found = 0, nroots = 0;
     hipError_t se = hipSuccess;
-    if (c.edges) se = hipMemcpyAsync(&found, counter, 8, hipMemcpyDeviceToHost, g.stream);
+    if (c.edges || c.cluster) se = hipMemcpyAsync(&found, counter, 8, hipMemcpyDeviceToHost, g.stream);
+    if (c.cluster && se == hipSuccess) se = hipMemcpyAsync(&nroots, roots, 8, hipMemcpyDeviceToHost, g.stream);
     if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
     float ms = 0.f;
     hipEventElapsedTime(&ms, g.ev0, g.ev1);
     g.last_dist_ms = ms;
     if (se != hipSuccess) return fail(MHX_E_HIP, "triangle kernel failed: %s", hipGetErrorString(se));
     c.found = found;
+    c.clusters = (uint32_t)nroots;
     return MHX_OK;
 }
 
-// what both calls check first; *done: nothing to compute (n <= 1)
+// what all calls check first; *done: nothing to compute (n <= 1)
 int triangle_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, bool *done)
 {
     clear_error();
@@ -271,7 +296,65 @@ int triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32
     return MHX_OK;
 }
 
+// Single-linkage clustering: the triangle's blocks feed the union-find of mhx_cluster.h.  The bound goes to the device as the
+// cmin table, built here with host libm, so both forms are exact; nothing of the size of the pair count exists anywhere.
+int triangle_cluster(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, double max_dist,
+                     uint32_t *label, uint32_t *degree, uint32_t *n_clusters, uint64_t *n_edges, int device_ptrs)
+{
+    if (n_clusters) *n_clusters = 0;
+    if (n_edges) *n_edges = 0;
+    bool done;
+    int rc = triangle_check(rows, len, n, stride, k, s, device_ptrs, &done);
+    if (rc) return rc;
+    if (!(max_dist == max_dist)) return fail(MHX_E_ARG, "max_dist is not a number");
+    if (!n_clusters || !n_edges || (n && !label)) return fail(MHX_E_ARG, "null argument");
+    if (done) { // no pair: a list on its own is a cluster
+        if (n == 0) return MHX_OK;
+        if (!device_ptrs) { label[0] = 0; if (degree) degree[0] = 0; }
+        else if (hipMemset(label, 0, 4) != hipSuccess || (degree && hipMemset(degree, 0, 4) != hipSuccess))
+            return fail(MHX_E_HIP, "hipMemset failed in dist_cluster");
+        *n_clusters = 1;
+        return MHX_OK;
+    }
+    std::vector<uint32_t> cmin((size_t)s + 1);
+    cluster_cmin_build(s, k, max_dist, cmin.data());
+    TriCall c{};
+    c.n = n; c.stride = stride; c.s = s; c.k = k; c.edges = false; c.cluster = true; c.h_cmin = cmin.data();
+    if (device_ptrs) {
+        c.rows = rows; c.len = len; c.longest = stride;
+        c.parent = label; c.degree = degree;
+        rc = triangle_device(c);
+        if (rc) return rc;
+    } else {
+        const size_t bn = up256((size_t)n * 4);
+        uint8_t *base = nullptr;
+        rc = stage_rows(rows, len, n, stride, 2 * bn, &base, c);
+        if (rc) return rc;
+        c.parent = (uint32_t *)base; c.degree = degree ? (uint32_t *)(base + bn) : nullptr;
+        rc = triangle_device(c);
+        if (rc) return rc;
+        if (hipMemcpy(label, c.parent, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            (degree && hipMemcpy(degree, c.degree, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            return fail(MHX_E_HIP, "D2H copy failed in dist_cluster");
+    }
+    *n_clusters = c.clusters;
+    *n_edges = c.found;
+    return MHX_OK;
+}
+
 } // namespace
+
+extern "C" int mhx_dist_cluster(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, double max_dist,
+                                uint32_t *label, uint32_t *degree, uint32_t *n_clusters, uint64_t *n_edges, int device_ptrs)
+{
+    try {
+        return triangle_cluster(rows, len, n, stride, k, s, max_dist, label, degree, n_clusters, n_edges, device_ptrs);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_cluster: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_dist_cluster: %s", e.what());
+    }
+}
 
 extern "C" int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
                                  uint32_t *common, uint32_t *denom, double *dist, int device_ptrs)

@@ -1725,6 +1725,47 @@ extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_
 // `mash triangle a.msh [b.msh ...]`: the references of all files form one set (argument order, then file order), every
 // pair j < i of it is compared on the device (mhx_dist_triangle, or mhx_dist_triangle_edges when a distance bound can drop
 // pairs there), and the text is Mash's CommandTriangle: the lower-triangle matrix, or the edge list with its two filters.
+// The references of all files as ONE set (argument order, then file order), what `mash triangle` and the clustering start
+// from: every file read and checked, k / seed / sketch size the same in all, at most 65 536 references, and their hash
+// lists as the matrix mhx_dist_triangle takes.  `what` names the caller in the messages.
+struct SetOfFiles {
+    std::vector<SketchSet> F;
+    std::vector<const RefSketch *> refs;
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> len;
+    uint32_t stride = 16;
+};
+static int read_set_of_files(const char *what, const char *const *paths, int n_paths, SetOfFiles &S)
+{
+    if (!paths || n_paths < 1) return fail(MHX_E_ARG, "%s: at least one sketch path required", what);
+    for (int i = 0; i < n_paths; ++i)
+        if (!paths[i]) return fail(MHX_E_ARG, "%s: sketch path %d is null", what, i);
+    std::vector<SketchSet> &F = S.F;
+    F.resize((size_t)n_paths);
+    for (int i = 0; i < n_paths; ++i) {
+        const int rc = msh_read_file(paths[i], F[i]); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        if (F[0].kmer_size != F[i].kmer_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", F[i].kmer_size, F[0].kmer_size);
+        if (F[0].hash_seed != F[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
+        if (F[i].sketch_size != F[0].sketch_size)
+            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", paths[0], paths[i],
+                        F[0].sketch_size, F[i].sketch_size);
+        for (const RefSketch &r : F[i].refs) S.refs.push_back(&r);
+    }
+    if (S.refs.size() > 65536) return fail(MHX_E_ARG, "%s: too many references for one call (%zu)", what, S.refs.size());
+    const uint32_t n = (uint32_t)S.refs.size();
+    for (const RefSketch *r : S.refs) S.stride = std::max<uint32_t>(S.stride, (uint32_t)r->hash_count());
+    S.stride = (S.stride + 15u) & ~15u; // rows of whole 128-byte lines on the device
+    S.rows.assign((size_t)n * S.stride, 0);
+    S.len.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        S.len[i] = (uint32_t)S.refs[i]->hash_count();
+        if (S.len[i]) memcpy(&S.rows[(size_t)i * S.stride], S.refs[i]->hash_data(), (size_t)S.len[i] * 8);
+    }
+    return MHX_OK;
+}
+
 static int mhx_triangle_files_impl(const char *const *paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
     clear_error();
@@ -1740,32 +1781,16 @@ static int mhx_triangle_files_impl(const char *const *paths, int n_paths, const 
     }
     if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "triangle: max_dist / max_p_value is not a number");
     const bool edge = o.edge != 0 || o.max_dist < 1.0 || o.max_p_value < 1.0; // -d and -v imply -E
-    std::vector<SketchSet> F((size_t)n_paths);
-    std::vector<const RefSketch *> refs;
-    for (int i = 0; i < n_paths; ++i) {
-        rc = msh_read_file(paths[i], F[i]); // (checks that every hash list ascends: MHX_E_FORMAT)
-        if (rc) return rc;
-        if (F[0].kmer_size != F[i].kmer_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", F[i].kmer_size, F[0].kmer_size);
-        if (F[0].hash_seed != F[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
-        if (F[i].sketch_size != F[0].sketch_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", paths[0], paths[i],
-                        F[0].sketch_size, F[i].sketch_size);
-        for (const RefSketch &r : F[i].refs) refs.push_back(&r);
-    }
-    if (refs.size() > 65536) return fail(MHX_E_ARG, "triangle: too many references for one call (%zu)", refs.size());
-    const uint32_t n = (uint32_t)refs.size(), s = F[0].sketch_size;
+    SetOfFiles S;
+    rc = read_set_of_files("triangle", paths, n_paths, S);
+    if (rc) return rc;
+    const std::vector<SketchSet> &F = S.F;
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const std::vector<uint64_t> &rows = S.rows;
+    const std::vector<uint32_t> &len = S.len;
+    const uint32_t n = (uint32_t)refs.size(), s = F[0].sketch_size, stride = S.stride;
     const int k = (int)F[0].kmer_size;
     const uint64_t pairs = (uint64_t)n * (n ? n - 1 : 0) / 2;
-    uint32_t stride = 16;
-    for (const RefSketch *r : refs) stride = std::max<uint32_t>(stride, (uint32_t)r->hash_count());
-    stride = (stride + 15u) & ~15u; // rows of whole 128-byte lines on the device
-    std::vector<uint64_t> rows((size_t)n * stride, 0);
-    std::vector<uint32_t> len(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        len[i] = (uint32_t)refs[i]->hash_count();
-        if (len[i]) memcpy(&rows[(size_t)i * stride], refs[i]->hash_data(), (size_t)len[i] * 8);
-    }
     std::string text;
     if (!edge) {
         std::vector<uint32_t> common(pairs), denom(pairs);
@@ -1810,6 +1835,85 @@ extern "C" int mhx_triangle_files(const char *const *msh_paths, int n_paths, con
         return fail(MHX_E_INTERNAL, "mhx_triangle_files: out of host memory");
     } catch (const std::exception &e) {
         return fail(MHX_E_INTERNAL, "mhx_triangle_files: %s", e.what());
+    }
+}
+
+// Dereplication at file level: the references of all files form one set (as for the triangle), mhx_dist_cluster labels it on
+// the device, and the host numbers the clusters by their lowest member, picks a representative per cluster in one pass
+// and prints a row per reference; the representatives, unchanged, are written as a sketch file of their own on request.
+static int mhx_cluster_files_impl(const char *const *paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
+                                  size_t cap, size_t *need)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    mhx_cluster_opts o{(uint32_t)sizeof(mhx_cluster_opts), 0, 0, 1.0};
+    if (opts) {
+        if (opts->struct_size != sizeof(mhx_cluster_opts)) return fail(MHX_E_ARG, "cluster: opts->struct_size is not sizeof(mhx_cluster_opts)");
+        o = *opts;
+    }
+    if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "cluster: max_dist is not a number");
+    if (o.rep != 0 && o.rep != 1) return fail(MHX_E_ARG, "cluster: rep must be 0 (first) or 1 (longest)");
+    SetOfFiles S;
+    rc = read_set_of_files("cluster", paths, n_paths, S);
+    if (rc) return rc;
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const uint32_t n = (uint32_t)refs.size(), s = S.F[0].sketch_size;
+    const int k = (int)S.F[0].kmer_size;
+    if (out_msh)
+        for (const RefSketch *r : refs)
+            if (!r->counts.empty())
+                return fail(MHX_E_ARG, "cluster: %s carries multiplicity counts, which the output sketch file cannot store", r->name.c_str());
+    std::vector<uint32_t> label(n), degree(n);
+    uint32_t n_clusters = 0;
+    uint64_t n_edges = 0;
+    rc = mhx_dist_cluster(S.rows.data(), S.len.data(), n, S.stride, k, s ? s : 1, o.max_dist, label.data(), degree.data(), &n_clusters, &n_edges, 0);
+    if (rc) return rc;
+    // label[i] is the lowest member of i's cluster: a cluster's number, size and representative by its label, O(n)
+    std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = label[i];
+        if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "cluster: label %u of reference %u is not a cluster's lowest member", l, i);
+        if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
+        ++size[l];
+        if (o.rep == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
+    }
+    if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "cluster: %zu labels but %u clusters counted", order.size(), n_clusters);
+    auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
+    std::vector<std::vector<uint32_t>> members(order.size());
+    for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
+    std::string text;
+    for (size_t ci = 0; ci < order.size(); ++ci) {
+        const uint32_t l = order[ci];
+        for (uint32_t i : members[ci])
+            text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i) + "\t" + std::to_string(degree[i]) + "\n";
+    }
+    if (out_msh) {
+        const uint32_t m = (uint32_t)order.size();
+        std::vector<const char *> names(m), comments(m);
+        std::vector<uint64_t> lengths(m);
+        std::vector<const uint64_t *> hashes(m);
+        std::vector<uint32_t> n_hashes(m);
+        for (uint32_t ci = 0; ci < m; ++ci) {
+            const RefSketch &r = *refs[rep[order[ci]]];
+            names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
+            hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
+        }
+        rc = mhx_msh_write(out_msh, k, s, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
+        if (rc) return rc;
+    }
+    return put_text(text, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
+                                 size_t cap, size_t *need)
+{
+    try {
+        return mhx_cluster_files_impl(msh_paths, n_paths, opts, out_msh, stdout_buf, cap, need);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_cluster_files: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_cluster_files: %s", e.what());
     }
 }
 

@@ -161,6 +161,11 @@ def load() -> ctypes.CDLL:
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, u64p, c.c_int]
         L.mhx_triangle_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(TriangleOpts), c.c_char_p, c.c_size_t,
                                          c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_cluster"):   # (or older than the clustering)
+        L.mhx_dist_cluster.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_double, c.c_void_p, c.c_void_p,
+                                       u32p, u64p, c.c_int]
+        L.mhx_cluster_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(ClusterOpts), c.c_char_p, c.c_char_p, c.c_size_t,
+                                        c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
         L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -318,6 +323,29 @@ def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1
     opts = SearchOpts(ctypes.sizeof(SearchOpts), int(top), float(max_dist), float(max_p_value))
     return _text_call(lambda buf, cap, need: load().mhx_search_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
                                                                      need), guess=1 << 20)
+
+
+class ClusterOpts(ctypes.Structure):
+    """mhx_cluster_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("rep", ctypes.c_int32), ("max_dist", ctypes.c_double)]
+
+
+CLUSTER_REPS = {"first": 0, "longest": 1}
+
+
+def cluster_files(paths: Sequence, max_dist: float, comment: bool = False, rep: str = "first", out=None) -> str:
+    """Single-linkage clusters of the references of all sketch files (one set) at distance <= max_dist, a row per reference:
+    "cluster\\tsize\\trepresentative\\tmember\\tdegree", clusters numbered from 1 by their lowest member, members in index
+    order, names (comments under `comment`).  rep: "first" (the lowest index) or "longest" (the greatest genome length, ties
+    to the lower index).  out: a path that receives the representatives, unchanged, as a sketch file."""
+    if rep not in CLUSTER_REPS:
+        raise ValueError("cluster_files: rep must be 'first' or 'longest'")
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = ClusterOpts(ctypes.sizeof(ClusterOpts), int(bool(comment)), CLUSTER_REPS[rep], float(max_dist))
+    out_path = None if out is None else os.fsencode(str(out))
+    return _text_call(lambda buf, cap, need: load().mhx_cluster_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -817,6 +845,35 @@ def dist_triangle_edges_device(rows_ptr: int, len_ptr: int, n: int, stride: int,
     _check(load().mhx_dist_triangle_edges(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(edge_i_ptr), v(edge_j_ptr),
                                           v(common_ptr), v(denom_ptr), v(dist_ptr), cap, ctypes.byref(found), 1))
     return int(found.value)
+
+
+def dist_cluster(rows: np.ndarray, lens: np.ndarray, k: int, s: int, max_dist: float) -> Tuple[np.ndarray, np.ndarray, int, int]:
+    """Single-linkage clusters of ONE set of hash lists (rows [n, stride], lens [n], as dist_triangle takes them) at distance
+    <= max_dist (the host libm distance of dist_triangle): (label, degree, n_clusters, n_edges) with label[i] the lowest
+    index in i's cluster and degree[i] the neighbours of i.  The device joins the pairs as it computes them: no edge list and
+    nothing of size n^2 exists anywhere."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    label = np.zeros(n, dtype=np.uint32)
+    degree = np.zeros(n, dtype=np.uint32)
+    n_clusters, n_edges = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    _check(load().mhx_dist_cluster(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, float(max_dist), label.ctypes.data,
+                                   degree.ctypes.data, ctypes.byref(n_clusters), ctypes.byref(n_edges), 0))
+    return label, degree, int(n_clusters.value), int(n_edges.value)
+
+
+def dist_cluster_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, max_dist: float, label_ptr: int,
+                        degree_ptr: int = 0) -> Tuple[int, int]:
+    """Device pointers in and out (label [n] and degree [n] or 0; a sketch_segments_device result goes straight in): EXACT
+    like the host form -- the bound reaches the device as a table of integers -- and the same from call to call.  Returns
+    (n_clusters, n_edges); the kernel time is load().mhx_last_dist_kernel_ms()."""
+    init()
+    v = ctypes.c_void_p
+    n_clusters, n_edges = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    _check(load().mhx_dist_cluster(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(label_ptr), v(degree_ptr or None),
+                                   ctypes.byref(n_clusters), ctypes.byref(n_edges), 1))
+    return int(n_clusters.value), int(n_edges.value)
 
 
 def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0

@@ -16,6 +16,9 @@
  *   mhx_search_files  <- no mash command: `mash dist REF.msh QUERY.msh ...` followed by a sort per query, for a reference
  *                        set too large to print in full -- per query sketch the `top` closest references within a
  *                        distance bound, as dist rows (python -m auriclass_amd.search)
+ *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
+ *                        references of a set are the same thing within distance D, and one representative of each, as a
+ *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -306,7 +309,7 @@ int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const 
                    const uint32_t *r_len, uint32_t nr, uint32_t stride, int k, uint32_t s,
                    uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
 double mhx_last_dist_kernel_ms(void);
-/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* / mhx_dist_search call: -1 = the generic pair kernel did all the work (tiny batch),
+/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* / mhx_dist_cluster / mhx_dist_search call: -1 = the generic pair kernel did all the work (tiny batch),
  * else the number of (query batch, reference slice) blocks the all-vs-refs fast path gave up to it (0 for uniform hashes) */
 int mhx_last_dist_fallback_blocks(void);
 /* value ranges every (query batch, reference slice) block of that call was cut into: 1024 x W, W = the smallest power of two
@@ -339,6 +342,47 @@ int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint32_t n, uin
 int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s,
                             double max_dist, uint32_t *edge_i, uint32_t *edge_j, uint32_t *common, uint32_t *denom,
                             double *dist, uint64_t cap, uint64_t *n_out, int device_ptrs);
+
+/* Single-linkage clustering of ONE set (dereplication at buffer level): rows / len / n / stride / k / s as
+ * mhx_dist_triangle takes them, with its checks (n > 65 536, k, s, stride, len[i] > stride, null pointers: MHX_E_ARG; a
+ * max_dist that is not a number too), before anything is launched.
+ * Edge: lists i and j are neighbours iff the distance mhx_dist_triangle computes for the pair on the host (libm) is
+ * <= max_dist -- the rule of mhx_dist_triangle_edges' host form.  Two empty lists have distance 0: neighbours for any
+ * max_dist >= 0; max_dist < 0 gives no edge, max_dist >= 1 makes every pair one.
+ * Outputs: label[n], label[i] = the LOWEST index in the connected component of i, so the result does not depend on the
+ * order in which the device meets the pairs; degree[n] (may be NULL) the neighbours of i; *n_clusters the lists with
+ * label[i] == i; *n_edges the edges.  n_clusters and n_edges are HOST pointers in both forms.  n == 0: MHX_OK, 0 clusters;
+ * n == 1: label[0] = 0, 1 cluster.
+ * device_ptrs != 0 => rows, len, label and degree are device pointers, and the result is EXACT in this form as well --
+ * unlike the device form of mhx_dist_triangle_edges, whose list is prefiltered only: the host turns max_dist into a table
+ * cmin[0 .. s] with libm once per call (cmin[d] = the smallest common with distance(common, d) <= max_dist) and the
+ * device keeps a pair iff common >= cmin[denom], in integers.  Two calls on the same input give identical outputs.
+ * The triangle's blocks feed a lock-free union-find on the device: no edge list and nothing of
+ * size n^2 exists anywhere; the workspace is the triangle's plus 4 (s + 1) bytes.  Geometry, MHX_TRI_GEOMETRY and
+ * MHX_TRI_QBATCH are the triangle's; mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges
+ * report this call too.  Not lifted here: the limit of 65 536 lists; linkages other than single. */
+int mhx_dist_cluster(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, double max_dist,
+                     uint32_t *label, uint32_t *degree, uint32_t *n_clusters, uint64_t *n_edges, int device_ptrs);
+/* The same at file level: the references of all files form one set, read and checked as mhx_triangle_files does (k / seed /
+ * sketch-size mismatches MHX_E_MISMATCH, damaged files, at most 65 536 references).  Clusters are numbered from 1 in the
+ * order of their lowest member, members in index order; one row per reference, names (comments when `comment` is set):
+ *     cluster\tsize\trepresentative\tmember\tdegree\n
+ * The representative of a cluster is its lowest index (rep = 0, "first") or its member of greatest genome length, ties to
+ * the lower index (rep = 1, "longest").  out_msh (may be NULL): the representatives in cluster order, with their names,
+ * comments, lengths and hash lists unchanged, written as mhx_msh_write writes them -- a set that mhx_search_files,
+ * mhx_dist_files and mhx_screen_files read; when a reference of the set carries multiplicity counts, which that file
+ * cannot store, out_msh is refused with MHX_E_ARG (nothing is dropped silently).  opts == NULL means {sizeof, 0, 0, 1.0}.
+ * MHX_E_ARG: struct_size != sizeof(mhx_cluster_opts), rep outside 0 .. 1, a max_dist that is not a number.  Not pinned by
+ * mash output (mash has no such command): pinned by the restated rule (tests/cluster_rule.py), its pairs by the
+ * mash-pinned distance path.  No p-value filter and no distance-to-representative column. */
+typedef struct mhx_cluster_opts {
+    uint32_t struct_size; /* sizeof(mhx_cluster_opts) */
+    int32_t comment;      /* non-zero: print comments in place of names */
+    int32_t rep;          /* 0 first, 1 longest */
+    double max_dist;      /* neighbours: distance <= max_dist */
+} mhx_cluster_opts;
+int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
+                      size_t cap, size_t *need);
 
 /* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
  * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
