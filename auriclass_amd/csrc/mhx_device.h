@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mhx_device_consts.h"
+#include "mhx_merge.h"
 
 namespace mhx {
 
@@ -90,7 +91,7 @@ hipError_t launch_screen_winner(const ScreenArgs &a, uint32_t *win, const uint32
 hipError_t launch_screen_tally_winner(const ScreenArgs &a, const uint32_t *win, const uint32_t *prio, hipStream_t st);
 
 // sharded path: the other ranks' gathered partial results go into this rank's candidate table (slab_insert_kernel, mhx_merge.hip)
-constexpr uint32_t kMaxMergeRanks = 64; // ranks per launch (more: several launches)
+// (kMaxMergeRanks ranks per launch, mhx_merge.h; more: several launches)
 struct SlabMergeArgs {
     const uint64_t *slabs;  // device: nranks slabs of slab_words 8-byte words each: [hdr_words of header] hashes[cap] | counts u32[cap]
     uint64_t slab_words, cap;
@@ -108,7 +109,6 @@ struct SlabMergeArgs {
 hipError_t launch_slab_insert(const SlabMergeArgs &a, uint64_t max_n, hipStream_t st);
 
 // sharded path, the usual case: the gathered slabs are binned by value and merged bin by bin in LDS (mhx_merge.hip)
-constexpr uint32_t kMergeMaxBins = 16384, kMergeMaxSlots = 4096; // LDS: 2 x 4 bytes per bin in the scatter pass, 12 per slot in the bin pass
 struct MergeArgs {
     const uint64_t *slabs;      // device: nranks slabs of slab_words 8-byte words each: [hdr_words of header] hashes[cap] | counts u32[cap]
     uint64_t slab_words, cap;
@@ -124,7 +124,7 @@ struct MergeArgs {
     uint32_t chunk;             // slab entries per workgroup of the scatter pass (set by launch_merge_bins)
     uint32_t *cursor;           // [nbins] entries placed per bin; zero between merges (merge_bin_kernel clears it)
     uint32_t *qn;               // [nbins] qualifying entries per bin
-    uint32_t *flags;            // [0]: 1 a region overflowed, 2 a table overflowed, 4 too many qualifying entries in a bin; zero between merges
+    uint32_t *flags;            // [0]: kMergeFlag* of mhx_merge.h (a region or table overflowed, too many qualify in a bin, a count wrapped); zero between merges
     uint64_t *sc_keys;          // [nbins * region]
     uint32_t *sc_cnts;          // [nbins * region]
 };

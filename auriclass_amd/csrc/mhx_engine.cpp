@@ -979,6 +979,7 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
     clear_error();
     int rc = require_engine();
     if (rc) return rc;
+    if (sk) sk->mg_info = {}; // (a call that ends in an argument error leaves "no path", not the previous merge's)
     if (!sk || !headers || !hashes || !n_out || n_ranks == 0) return fail(MHX_E_ARG, "null argument");
     if (own_rank >= n_ranks) return fail(MHX_E_ARG, "own_rank %u out of range (%u ranks)", own_rank, n_ranks);
     if (cap_entries & 1) return fail(MHX_E_ARG, "merge_slabs: odd slab capacity");
@@ -1012,57 +1013,54 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
     // entries take the table path below.
     static const bool force_table = getenv("MHX_MERGE_TABLE") != nullptr;
     const uint64_t total = others + headers[8 * (size_t)own_rank];
-    if (!force_table && n_ranks <= kMaxMergeRanks && total > 0 && total <= (uint64_t)kMergeMaxBins * 1024) {
-        uint32_t nbins = 256;
-        while ((uint64_t)nbins * 1024 < total) nbins <<= 1;
-        const uint32_t lg = (uint32_t)__builtin_ctz(nbins);
-        const uint32_t bits = 64u - (uint32_t)__builtin_clzll(t_min | 1ull);
+    MergeGeometry geo;
+    if (!force_table && merge_geometry(total, t_min, n_ranks, geo)) {
+        const uint32_t nbins = geo.nbins;
+        const uint64_t bins_used = geo.bins_used;
         MergeArgs a;
-        a.shift = bits > lg ? bits - lg : 0u;
-        const uint64_t bins_used = (t_min >> a.shift) + 1;
-        const double avg = (double)total / (double)bins_used;
-        a.region = (uint32_t)(avg + 6.0 * sqrt(avg) + 64.0);
-        a.table_slots = 256;
-        while ((uint64_t)a.table_slots * 3 / 4 < a.region) a.table_slots <<= 1;
-        if (a.table_slots <= kMergeMaxSlots) {
-            if (!sk->d_mg_small) {
-                HIPCHK(sk->d_mg_small.grow(2 * (size_t)kMergeMaxBins + 16));
-                HIPCHK(hipMemsetAsync(sk->d_mg_small, 0, (2 * (size_t)kMergeMaxBins + 16) * sizeof(uint32_t), g.stream));
-            }
-            const size_t need = (size_t)nbins * a.region;
-            if (std::min(sk->d_mg_keys.cap(), sk->d_mg_cnts.cap()) < need) {
-                HIPCHK(sk->d_mg_keys.grow(need + need / 4, g.stream));
-                HIPCHK(sk->d_mg_cnts.grow(need + need / 4));
-            }
-            a.slabs = d_slabs; a.slab_words = slab_words; a.cap = cap_entries; a.hdr_words = hdr_words; a.nranks = n_ranks; a.min_mult = sk->m; a.t_min = t_min; a.nbins = nbins;
-            uint64_t max_all = 0;
-            for (uint32_t r = 0; r < kMaxMergeRanks; ++r) { a.n[r] = r < n_ranks ? headers[8 * (size_t)r] : 0; max_all = a.n[r] > max_all ? a.n[r] : max_all; }
-            a.cursor = sk->d_mg_small; a.qn = sk->d_mg_small + kMergeMaxBins; a.flags = sk->d_mg_small + 2 * kMergeMaxBins;
-            a.sc_keys = sk->d_mg_keys; a.sc_cnts = sk->d_mg_cnts;
-            HIPCHK(launch_merge_bins(a, max_all, sk->h_fin, sk->fin_cap, g.stream));
-            HIPCHK(hipStreamSynchronize(g.stream));
-            const uint64_t *h = sk->h_fin;
-            const uint64_t n_q = h[0];
-            static const bool dbg = getenv("MHX_MERGE_DEBUG") != nullptr;
-            if (dbg) fprintf(stderr, "[mhx merge] %u ranks, %llu entries, %u bins (%llu used) of %u entries, table %u: %llu qualify, flags %llu\n", n_ranks,
-                             (unsigned long long)total, nbins, (unsigned long long)bins_used, a.region, a.table_slots, (unsigned long long)n_q, (unsigned long long)h[2]);
-            if (h[2] == 0) { // (more qualify than the block holds? the bins are in value order: its first s entries are the sketch)
-                const uint64_t maxkey_all = maxkey_others + headers[8 * (size_t)own_rank + 3];
-                const bool extra = t_min == ~0ull && maxkey_all >= sk->m; // the one hash value no table holds
-                const uint64_t n_src = n_q + (extra ? 1 : 0);
-                if (n_src < sk->s && t_min < sk->hash_max)
-                    return fail(MHX_E_CAPACITY, "sharded sketch not exact: %llu of %u entries with multiplicity >= %u below the smallest shard threshold; "
-                                "every rank must sketch its shard again with a larger budget_scale", (unsigned long long)n_src, sk->s, sk->m);
-                const uint32_t nn = n_src < sk->s ? (uint32_t)n_src : sk->s;
-                const uint32_t from_block = nn < n_q ? nn : (uint32_t)n_q; // <= s <= fin_cap: all of them are in the block
-                memcpy(hashes, h + 4, (size_t)from_block * sizeof(uint64_t));
-                if (counts) memcpy(counts, reinterpret_cast<const uint32_t *>(h + 4 + sk->fin_cap), (size_t)from_block * sizeof(uint32_t));
-                if (nn > from_block) { hashes[from_block] = ~0ull; if (counts) counts[from_block] = maxkey_all > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxkey_all; }
-                *n_out = nn;
-                return MHX_OK;
-            }
-            // (flags raised -- a bin's region or table overflowed on non-uniform data: the table path decides)
+        a.shift = geo.shift; a.region = geo.region; a.table_slots = geo.table_slots;
+        if (!sk->d_mg_small) {
+            HIPCHK(sk->d_mg_small.grow(2 * (size_t)kMergeMaxBins + 16));
+            HIPCHK(hipMemsetAsync(sk->d_mg_small, 0, (2 * (size_t)kMergeMaxBins + 16) * sizeof(uint32_t), g.stream));
         }
+        const size_t need = (size_t)nbins * a.region;
+        if (std::min(sk->d_mg_keys.cap(), sk->d_mg_cnts.cap()) < need) {
+            HIPCHK(sk->d_mg_keys.grow(need + need / 4, g.stream));
+            HIPCHK(sk->d_mg_cnts.grow(need + need / 4));
+        }
+        a.slabs = d_slabs; a.slab_words = slab_words; a.cap = cap_entries; a.hdr_words = hdr_words; a.nranks = n_ranks; a.min_mult = sk->m; a.t_min = t_min; a.nbins = nbins;
+        uint64_t max_all = 0;
+        for (uint32_t r = 0; r < kMaxMergeRanks; ++r) { a.n[r] = r < n_ranks ? headers[8 * (size_t)r] : 0; max_all = a.n[r] > max_all ? a.n[r] : max_all; }
+        a.cursor = sk->d_mg_small; a.qn = sk->d_mg_small + kMergeMaxBins; a.flags = sk->d_mg_small + 2 * kMergeMaxBins;
+        a.sc_keys = sk->d_mg_keys; a.sc_cnts = sk->d_mg_cnts;
+        HIPCHK(launch_merge_bins(a, max_all, sk->h_fin, sk->fin_cap, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream));
+        const uint64_t *h = sk->h_fin;
+        const uint64_t n_q = h[0];
+        sk->mg_info.attempted = 1; sk->mg_info.flags = (uint32_t)h[2];
+        sk->mg_info.nbins = nbins; sk->mg_info.region = a.region; sk->mg_info.table_slots = a.table_slots;
+        static const bool dbg = getenv("MHX_MERGE_DEBUG") != nullptr;
+        if (dbg) fprintf(stderr, "[mhx merge] %u ranks, %llu entries, %u bins (%llu used) of %u entries, table %u: %llu qualify, flags %llu\n", n_ranks,
+                         (unsigned long long)total, nbins, (unsigned long long)bins_used, a.region, a.table_slots, (unsigned long long)n_q, (unsigned long long)h[2]);
+        if (h[2] == 0) {
+            sk->mg_info.path = kMergePathBinned;
+            // (more qualify than the block holds? the bins are in value order: its first s entries are the sketch)
+            const uint64_t maxkey_all = maxkey_others + headers[8 * (size_t)own_rank + 3];
+            const bool extra = t_min == ~0ull && maxkey_all >= sk->m; // the one hash value no table holds
+            const uint64_t n_src = n_q + (extra ? 1 : 0);
+            if (n_src < sk->s && t_min < sk->hash_max)
+                return fail(MHX_E_CAPACITY, "sharded sketch not exact: %llu of %u entries with multiplicity >= %u below the smallest shard threshold; "
+                            "every rank must sketch its shard again with a larger budget_scale", (unsigned long long)n_src, sk->s, sk->m);
+            const uint32_t nn = n_src < sk->s ? (uint32_t)n_src : sk->s;
+            const uint32_t from_block = nn < n_q ? nn : (uint32_t)n_q; // <= s <= fin_cap: all of them are in the block
+            memcpy(hashes, h + 4, (size_t)from_block * sizeof(uint64_t));
+            if (counts) memcpy(counts, reinterpret_cast<const uint32_t *>(h + 4 + sk->fin_cap), (size_t)from_block * sizeof(uint32_t));
+            if (nn > from_block) { hashes[from_block] = ~0ull; if (counts) counts[from_block] = maxkey_all > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)maxkey_all; }
+            *n_out = nn;
+            return MHX_OK;
+        }
+        // (flags raised -- a bin's region or table overflowed on non-uniform data, or a count sum passed 2^32-1: the
+        // table path decides)
     }
     const uint64_t occupied = headers[8 * (size_t)own_rank + 4];
     if (occupied + others > sk->nslots / 2) {
@@ -1081,13 +1079,14 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
             const uint64_t n = headers[8 * (size_t)r], mk = headers[8 * (size_t)r + 3];
             const uint64_t *hp = hbuf.data() + (size_t)r * slab_words + hdr_words;
             const uint32_t *cp = reinterpret_cast<const uint32_t *>(hp + cap_entries);
-            ah.insert(ah.end(), hp, hp + n);
-            ac.insert(ac.end(), cp, cp + n);
-            an[r] = n;
+            an[r] = 0;
+            for (uint64_t i = 0; i < n; ++i) // (2^64-1 inside a slab is a vacant slot to the kernels: it travels in header word 3 alone)
+                if (hp[i] != kEmptyKey) { ah.push_back(hp[i]); ac.push_back(cp[i]); ++an[r]; }
             at[r] = headers[8 * (size_t)r + 1];
             if (mk && at[r] == ~0ull) { ah.push_back(~0ull); ac.push_back(mk > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)mk); ++an[r]; } // the one value the table cannot hold
         }
         sk->merged = true;
+        sk->mg_info.path = kMergePathHost;
         return mhx_merge_shard_partials(ah.data(), ac.data(), an.data(), at.data(), n_ranks, sk->k, sk->s, sk->m, hashes, counts, n_out);
     }
     for (uint32_t r0 = 0; r0 < n_ranks; r0 += kMaxMergeRanks) { // (one launch for up to 64 ranks)
@@ -1096,9 +1095,9 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
         a.slab_words = slab_words;
         a.cap = cap_entries;
         a.hdr_words = hdr_words;
-        a.nranks = n_ranks - r0 < kMaxMergeRanks ? n_ranks - r0 : kMaxMergeRanks;
+        a.nranks = merge_launch_ranks(n_ranks, r0);
         for (uint32_t r = 0; r < kMaxMergeRanks; ++r) a.n[r] = r < a.nranks ? headers[8 * (size_t)(r0 + r)] : 0;
-        a.own_rank = own_rank >= r0 && own_rank - r0 < a.nranks ? own_rank - r0 : kMaxMergeRanks;
+        a.own_rank = merge_launch_own(own_rank, r0, a.nranks);
         a.t_min = t_min;
         a.maxkey_others = r0 == 0 ? maxkey_others : 0;
         a.keys = sk->d_keys; a.cnts = sk->d_cnts; a.slot_mask = sk->nslots - 1; a.thresh = sk->d_thresh; a.stats = sk->d_stats;
@@ -1109,7 +1108,18 @@ static int merge_slabs_impl(mhx_sketcher *sk, const void *slabs, int slabs_on_de
     sk->table_dirty = false;
     sk->table_sampled = false;
     sk->unsettled.clear();
+    sk->mg_info.path = kMergePathTable;
     return mhx_sketcher_finish(sk, hashes, counts, n_out);
+}
+
+extern "C" int mhx_sketcher_merge_info(mhx_sketcher *sk, uint64_t *info8)
+{
+    clear_error();
+    if (!sk || !info8) return fail(MHX_E_ARG, "null argument");
+    const MergeInfo &i = sk->mg_info;
+    info8[0] = i.path; info8[1] = i.attempted; info8[2] = i.flags; info8[3] = i.nbins; info8[4] = i.region; info8[5] = i.table_slots;
+    info8[6] = info8[7] = 0;
+    return MHX_OK;
 }
 
 extern "C" int mhx_sketcher_merge_slabs(mhx_sketcher *sk, const void *slabs, int slabs_on_device, uint32_t n_ranks, uint64_t cap_entries,
@@ -1157,6 +1167,7 @@ extern "C" int mhx_sketcher_merge_gathered(mhx_sketcher *sk, const void *d_slabs
     clear_error();
     int rc = require_engine();
     if (rc) return rc;
+    if (sk) sk->mg_info = {};
     if (!sk || !d_slabs || !hashes || !n_out || !need_cap || n_ranks == 0 || (cap_entries & 1)) return fail(MHX_E_ARG, "merge_gathered: null argument or odd capacity");
     *need_cap = 0;
     try {

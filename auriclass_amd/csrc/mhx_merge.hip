@@ -17,6 +17,7 @@
 // overflows (non-uniform input) raises a flag and the caller falls back to the table path (slab_insert_kernel, at the end
 // of this file).
 #include "mhx_device.h"
+#include "mhx_merge.h"
 
 namespace mhx {
 
@@ -24,7 +25,6 @@ namespace mhx {
 // the first choice, gave 8 x 704 k entries 88 workgroups on 256 CUs: 0.31 ms), large enough that the one global atomic
 // per (workgroup, bin) is shared by a few entries
 constexpr uint32_t kMergeChunkDefault = 8192;
-constexpr uint32_t kMergeMaxQual = 1024; // qualifying entries a bin can rank in LDS
 
 constexpr int kScatterThreads = 1024, kScatterBatch = 4; // loads in flight per thread: the passes are chains of HBM round trips otherwise
 
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kScatterThreads) void merge_scatter_kernel(const Me
         }
 #pragma unroll
         for (int u = 0; u < kScatterBatch; ++u)
-            if (h[u] <= a.t_min && h[u] != kEmptyKey) atomicAdd(&cnt[(uint32_t)(h[u] >> a.shift)], 1u);
+            if (merge_takes(h[u], a.t_min)) atomicAdd(&cnt[merge_bin(h[u], a.shift)], 1u);
     }
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < a.nbins; b += blockDim.x) {
@@ -72,8 +72,8 @@ __global__ __launch_bounds__(kScatterThreads) void merge_scatter_kernel(const Me
         }
 #pragma unroll
         for (int u = 0; u < kScatterBatch; ++u) {
-            if (h[u] > a.t_min || h[u] == kEmptyKey) continue;
-            const uint32_t b = (uint32_t)(h[u] >> a.shift);
+            if (!merge_takes(h[u], a.t_min)) continue;
+            const uint32_t b = merge_bin(h[u], a.shift);
             const uint32_t pos = base[b] + atomicAdd(&cnt[b], 1u);
             if (pos < a.region) {
                 a.sc_keys[(uint64_t)b * a.region + pos] = h[u];
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kScatterThreads) void merge_scatter_kernel(const Me
             }
         }
     }
-    if (over) atomicOr(a.flags, 1u);
+    if (over) atomicOr(a.flags, kMergeFlagRegion);
 }
 
 __global__ __launch_bounds__(256) void merge_bin_kernel(const MergeArgs a)
@@ -100,45 +100,31 @@ __global__ __launch_bounds__(256) void merge_bin_kernel(const MergeArgs a)
     for (uint32_t i = threadIdx.x; i < a.table_slots; i += blockDim.x) { keys[i] = kEmptyKey; cnts[i] = 0; }
     if (threadIdx.x == 0) nq = 0;
     __syncthreads();
-    if (n > (a.table_slots * 3u) / 4u) { // cannot happen with region <= 3/4 of the table; kept as a guard
-        if (threadIdx.x == 0) { atomicOr(a.flags, 2u); a.qn[b] = 0; a.cursor[b] = 0; }
+    if (merge_table_guard(n, a.table_slots)) { // cannot happen with region <= 3/4 of the table; kept as a guard
+        if (threadIdx.x == 0) { atomicOr(a.flags, kMergeFlagTable); a.qn[b] = 0; a.cursor[b] = 0; }
         return;
     }
     const uint64_t *rk = a.sc_keys + (uint64_t)b * a.region;
     const uint32_t *rc = a.sc_cnts + (uint64_t)b * a.region;
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        const uint64_t h = rk[i];
-        const uint32_t c = rc[i];
-        // the bits below the bin index tell the entries of one bin apart
-        uint32_t sl = (uint32_t)((h * 0x9E3779B97F4A7C15ull) >> 40) & mask;
-        for (;;) {
-            unsigned long long cur = keys[sl];
-            if (cur == kEmptyKey) cur = atomicCAS(&keys[sl], (unsigned long long)kEmptyKey, (unsigned long long)h);
-            if (cur == kEmptyKey || cur == h) { atomicAdd(&cnts[sl], c); break; }
-            sl = (sl + 1) & mask;
-        }
-    }
+    bool wrapped = false; // a sum past 2^32-1: the table path clamps it as the host rule does
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) wrapped |= merge_lds_insert(keys, cnts, mask, rk[i], rc[i]);
+    if (wrapped) atomicOr(a.flags, kMergeFlagWrap);
     __syncthreads();
     bool over = false;
     for (uint32_t i = threadIdx.x; i < a.table_slots; i += blockDim.x) {
-        if (keys[i] != kEmptyKey && cnts[i] >= a.min_mult) {
+        if (merge_qualifies(keys[i], cnts[i], a.min_mult)) {
             const uint32_t p = atomicAdd(&nq, 1u);
             if (p < kMergeMaxQual) { qk[p] = keys[i]; qc[p] = cnts[i]; }
             else over = true;
         }
     }
-    if (over) atomicOr(a.flags, 4u);
+    if (over) atomicOr(a.flags, kMergeFlagQual);
     __syncthreads();
     const uint32_t q = nq < kMergeMaxQual ? nq : kMergeMaxQual;
     // in order, back to the head of the bin's own region (its inputs are all in LDS by now)
     uint64_t *ok = a.sc_keys + (uint64_t)b * a.region;
     uint32_t *oc = a.sc_cnts + (uint64_t)b * a.region;
-    for (uint32_t t = threadIdx.x; t < q; t += blockDim.x) {
-        const unsigned long long mine = qk[t];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < q; ++j) rank += qk[j] < mine ? 1u : 0u; // the keys of a table are distinct
-        if (rank < a.region) { ok[rank] = mine; oc[rank] = qc[t]; }
-    }
+    for (uint32_t t = threadIdx.x; t < q; t += blockDim.x) merge_rank_write(qk, qc, q, t, a.region, ok, oc);
     if (threadIdx.x == 0) {
         a.qn[b] = q < a.region ? q : a.region;
         a.cursor[b] = 0; // zero again for the next merge
@@ -197,14 +183,7 @@ __global__ __launch_bounds__(kCompactThreads) void merge_compact_kernel(const Me
     // one dependent load after the other took 0.14 ms at 8 x 704 k entries, 256 threads with one entry in flight 0.12.
     uint32_t *oc = reinterpret_cast<uint32_t *>(out + 4 + out_cap);
     const uint32_t lo = s_off[0], hi = s_off[256] < out_cap ? s_off[256] : out_cap;
-    auto source = [&](uint32_t e) { // the bin of entry e: the last i with s_off[i] <= e (empty bins share an offset with their successor)
-        uint32_t x = 0, y = 256;
-        while (y - x > 1) {
-            const uint32_t mid = (x + y) >> 1;
-            if (s_off[mid] <= e) x = mid; else y = mid;
-        }
-        return (uint64_t)(first + x) * a.region + (e - s_off[x]);
-    };
+    auto source = [&](uint32_t e) { return merge_source(s_off, e, first, a.region); }; // (empty bins share an offset with their successor)
     for (uint32_t e = lo + threadIdx.x; e < hi; e += 2 * kCompactThreads) {
         const uint32_t e2 = e + kCompactThreads;
         const bool two = e2 < hi;
@@ -233,12 +212,11 @@ hipError_t launch_merge_bins(const MergeArgs &a_in, uint64_t max_n, uint64_t *ou
     static const uint32_t chunk_knob = getenv("MHX_MERGE_CHUNK") ? (uint32_t)atol(getenv("MHX_MERGE_CHUNK")) : 0u; // experiment knob
     a.chunk = chunk_knob >= 1024 ? chunk_knob : kMergeChunkDefault;
     const unsigned chunks = (unsigned)((max_n + a.chunk - 1) / a.chunk);
-    const size_t scatter_lds = 2 * (size_t)a.nbins * sizeof(uint32_t);
-    const size_t bin_lds = (size_t)a.table_slots * 12 + (size_t)kMergeMaxQual * 12;
+    const size_t scatter_lds = merge_scatter_lds_bytes(a.nbins), bin_lds = merge_bin_lds_bytes(a.table_slots);
     static bool attr_set = false; // dynamic LDS beyond 64 KB has to be asked for once per kernel
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(merge_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kMergeMaxBins * 4);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(merge_bin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMergeMaxSlots * 12 + kMergeMaxQual * 12);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(merge_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_scatter_lds_bytes(kMergeMaxBins));
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(merge_bin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)merge_bin_lds_bytes(kMergeMaxSlots));
         if (e != hipSuccess) return e;
         attr_set = true;
     }
@@ -270,23 +248,8 @@ __global__ __launch_bounds__(256) void slab_insert_kernel(const SlabMergeArgs a)
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(a.keys);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t h = hashes[i];
-        if (h > a.t_min || h == kEmptyKey) continue; // above T_min a shard's list is incomplete: not part of the union's evidence
-        const uint32_t c = counts[i];
-        uint64_t slot = h & a.slot_mask;
-        bool placed = false;
-        for (int probe = 0; probe < 8192; ++probe) {
-            // a slot only ever goes from vacant to a key: a plain load that shows this hash (or another one) is final,
-            // one that shows a vacant slot is settled by the CAS
-            unsigned long long cur = keys[slot];
-            if (cur == kEmptyKey) cur = atomicCAS(&keys[slot], (unsigned long long)kEmptyKey, (unsigned long long)h);
-            if (cur == kEmptyKey || cur == h) {
-                atomicAdd(&a.cnts[slot], c);
-                placed = true;
-                break;
-            }
-            slot = (slot + 1) & a.slot_mask;
-        }
-        if (!placed) atomicOr(reinterpret_cast<unsigned long long *>(a.stats) + kStatFlags, (unsigned long long)kFlagTableFull);
+        if (!merge_takes(h, a.t_min)) continue; // above T_min a shard's list is incomplete: not part of the union's evidence
+        if (!merge_table_insert(keys, a.cnts, a.slot_mask, h, counts[i])) atomicOr(reinterpret_cast<unsigned long long *>(a.stats) + kStatFlags, (unsigned long long)kFlagTableFull);
     }
 }
 

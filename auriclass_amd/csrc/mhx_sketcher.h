@@ -16,6 +16,13 @@ struct SortScratch {
     std::vector<uint32_t> cnts;
 };
 
+struct MergeInfo {
+    uint32_t path = 0;        // kMergePath* (mhx_merge.h): what produced the answer; 0: no merge yet, or the last call ended in an error before any path ran (cleared at the entry of every merge call)
+    uint32_t attempted = 0;   // 1: the binned merge ran; flags / nbins / region / table_slots are its
+    uint32_t flags = 0;       // kMergeFlag* the binned attempt returned
+    uint32_t nbins = 0, region = 0, table_slots = 0;
+};
+
 struct mhx_sketcher {
     SortScratch sorted;            // finish() / export(): the extracted entries in hash order
     int k = 0;
@@ -58,6 +65,7 @@ struct mhx_sketcher {
     DevArray<uint32_t> d_mg_small;  // [kMergeMaxBins] cursor | [kMergeMaxBins] qn | [16] flags
     DevArray<uint64_t> d_mg_keys;
     DevArray<uint32_t> d_mg_cnts;
+    MergeInfo mg_info;             // the last merge on this sketcher (mhx_sketcher_merge_info)
     // finish(): one device block [n, T, flags, #(2^64-1) | hashes[fin_cap] | counts[fin_cap]] and its pinned host
     // mirror, so the result comes back in ONE copy (five separate copies cost 20-60 us of idle gap each)
     DevArray<uint64_t> d_fin;

@@ -29,6 +29,7 @@ MHX_E_HIP = -6
 MHX_E_CAPACITY = -7
 MHX_E_MISMATCH = -8
 MHX_E_INTERNAL = -9
+MERGE_BINNED, MERGE_TABLE, MERGE_HOST = 1, 2, 3   # Sketcher.merge_info()["path"]
 
 FMT_SEQ = 0
 FMT_FASTQ4 = 1
@@ -119,6 +120,8 @@ def load() -> ctypes.CDLL:
     L.mhx_sketcher_export_pack.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64]
     L.mhx_sketcher_export_into.argtypes = [c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p]
     L.mhx_sketcher_merge_gathered.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint64, c.c_uint32, c.c_void_p, c.c_void_p, u32p, u64p]
+    if hasattr(L, "mhx_sketcher_merge_info"):   # (MHX_LIB may name an experiment build older than the accessor: tools/merge_time.py A/B)
+        L.mhx_sketcher_merge_info.argtypes = [c.c_void_p, c.c_void_p]
     L.mhx_sketcher_merge_slabs.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_uint32, c.c_uint64, c.c_void_p, c.c_uint32,
                                            c.c_void_p, c.c_void_p, u32p]
     L.mhx_gunzip_buffer.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
@@ -506,6 +509,17 @@ class Sketcher:
         _check(load().mhx_sketcher_merge_slabs(self._h, ctypes.c_void_p(slabs_ptr), int(on_device), n_ranks, cap_entries,
                                                headers.ctypes.data, own_rank, hashes.ctypes.data, counts.ctypes.data, ctypes.byref(n)))
         return hashes[:n.value].copy(), counts[:n.value].copy()
+
+    def merge_info(self) -> dict:
+        """The last merge on this sketcher: `path` that produced the answer (MERGE_BINNED, MERGE_TABLE, MERGE_HOST; 0: none),
+        `flags` the binned attempt returned (None when it did not run) and its `nbins`, `region`, `table_slots`."""
+        raw = np.zeros(8, dtype=np.uint64)
+        if not hasattr(load(), "mhx_sketcher_merge_info"):
+            raise EngineError(MHX_E_ARG, f"{LIB_PATH} is older than mhx_sketcher_merge_info")
+        _check(load().mhx_sketcher_merge_info(self._h, raw.ctypes.data))
+        ran = bool(raw[1])
+        return {"path": int(raw[0]), "flags": int(raw[2]) if ran else None, "nbins": int(raw[3]), "region": int(raw[4]),
+                "table_slots": int(raw[5])}
 
     def export_into(self, device_ptr: int, cap_entries: int) -> np.ndarray:
         """One-collective form of the exchange (device buffers): the partial result straight into the send slab

@@ -284,6 +284,17 @@ int mhx_sketcher_export_into(mhx_sketcher *sk, void *d_slab, uint64_t cap_entrie
 int mhx_sketcher_merge_gathered(mhx_sketcher *sk, const void *d_slabs, uint32_t n_ranks, uint64_t cap_entries,
                                 uint32_t own_rank, uint64_t *hashes, uint32_t *counts, uint32_t *n_out,
                                 uint64_t *need_cap);
+/* The last merge on this sketcher (read-only): info8[0] the path that produced the answer -- MHX_MERGE_BINNED (value bins
+ * merged in LDS), MHX_MERGE_TABLE (the other ranks' entries added to the candidate table) or MHX_MERGE_HOST (the host
+ * merge on the gathered data); 0 before the first merge, and when the last merge call was rejected before any path ran (the info is
+ * cleared at the entry of every merge call; mhx_sketcher_reset() keeps it) --, [1] 1 if the binned
+ * merge ran, and then [2] the flags word it returned (1 a bin's region overflowed, 2 a bin's table guard, 4 too many
+ * entries qualify in one bin, 8 a summed count passed 2^32-1; any of them sends the call on to the table path),
+ * [3] its bins, [4] entries per bin region, [5] slots of a bin's table; [6..7] 0. */
+#define MHX_MERGE_BINNED 1
+#define MHX_MERGE_TABLE 2
+#define MHX_MERGE_HOST 3
+int mhx_sketcher_merge_info(mhx_sketcher *sk, uint64_t *info8);
 int mhx_merge_partials(const uint64_t *hashes, const uint32_t *counts, uint64_t n, uint32_t s,
                        uint32_t min_mult, uint64_t *out_hashes, uint32_t *out_counts, uint32_t *n_out);
 /* bits a shard adds to word [2] of its slab besides the device flags (diagnostics of the m > 1 phase) */

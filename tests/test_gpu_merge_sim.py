@@ -66,7 +66,9 @@ def test_simulated_ranks_merge_to_the_oracle_sketch(seed):
             assert e.code == engine.MHX_E_CAPACITY
             assert inexact in (None, True)
             inexact = True
+            assert sks[r].merge_info()["path"] in (engine.MERGE_BINNED, engine.MERGE_TABLE, engine.MERGE_HOST)
             continue
+        assert sks[r].merge_info()["path"] in (engine.MERGE_BINNED, engine.MERGE_TABLE, engine.MERGE_HOST)   # a path was recorded
         assert inexact in (None, False)
         inexact = False
         assert np.array_equal(h, want_h), (seed, k, s, m, R, r)
