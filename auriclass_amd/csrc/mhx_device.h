@@ -222,6 +222,39 @@ hipError_t launch_tri_cluster(const ClusterOut &o, hipStream_t st);
 // parent[i] = the root of i, in a launch of its own; count (may be null) receives the number of roots on top of what it holds
 hipError_t launch_cluster_flatten(uint32_t *parent, uint32_t n, unsigned long long *count, hipStream_t st);
 
+// single-linkage tree of one set (rules: mhx_mst.h, kernels: mhx_mst.hip): the passes of one Boruvka round.  best [n] holds
+// the best outgoing edge of every list (mst_pack), winner [n] the list that stands for a component, comp [n] the flattened
+// parent of the round before (read-only within a round), parent [n] the union-find the hooks write.
+struct MstOut { // propose, recomputed source: a block's results, block-local as above
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;
+    uint32_t r0, nr, q0, nq; // the block (mhx_triangle.h: TriBlock)
+    const uint32_t *comp;
+    uint64_t *best;
+};
+struct MstScan { // propose, stored source: the packed triangle of mhx_dist_triangle's dense mode
+    const uint32_t *common, *denom;
+    uint32_t n;
+    const uint32_t *comp;
+    uint64_t *best;
+};
+struct MstHookArgs {
+    const uint32_t *comp, *winner;
+    const uint64_t *best;
+    uint32_t *parent;
+    uint32_t n;
+    int k;
+    uint32_t *edge_i, *edge_j, *common, *denom; // [cap] the result, appended through *n_edges
+    double *dist;                               // may be null
+    unsigned long long *n_edges;
+    uint64_t cap;
+};
+hipError_t launch_mst_reset(uint64_t *best, uint32_t *winner, uint32_t n, hipStream_t st);
+hipError_t launch_tri_mst(const MstOut &o, hipStream_t st);
+hipError_t launch_mst_scan(const MstScan &o, hipStream_t st);
+hipError_t launch_mst_choose(const uint64_t *best, const uint32_t *comp, uint32_t *winner, uint32_t n, hipStream_t st);
+hipError_t launch_mst_hook(const MstHookArgs &o, hipStream_t st);
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

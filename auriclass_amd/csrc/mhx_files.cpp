@@ -1917,6 +1917,97 @@ extern "C" int mhx_cluster_files(const char *const *msh_paths, int n_paths, cons
     }
 }
 
+// The single-linkage tree at file level: the references of all files form one set (as for the triangle), mhx_dist_mst gives
+// its n - 1 merges in merge order, and the host prints them as a table or as a Newick dendrogram.
+// Newick: a name is single-quoted when it holds any of ( ) [ ] ' : ; , or a blank, an inner quote doubled
+static std::string newick_name(const std::string &name)
+{
+    bool quote = false;
+    for (const char ch : name) quote = quote || strchr("()[]':;,", ch) != nullptr || isspace((unsigned char)ch);
+    if (!quote) return name;
+    std::string out = "'";
+    for (const char ch : name) { out += ch; if (ch == '\'') out += ch; }
+    return out + "'";
+}
+
+static int mhx_tree_files_impl(const char *const *paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    mhx_tree_opts o{(uint32_t)sizeof(mhx_tree_opts), 0, 0};
+    if (opts) {
+        if (opts->struct_size != sizeof(mhx_tree_opts)) return fail(MHX_E_ARG, "tree: opts->struct_size is not sizeof(mhx_tree_opts)");
+        o = *opts;
+    }
+    SetOfFiles S;
+    rc = read_set_of_files("tree", paths, n_paths, S);
+    if (rc) return rc;
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const uint32_t n = (uint32_t)refs.size(), s = S.F[0].sketch_size;
+    const int k = (int)S.F[0].kmer_size;
+    const uint32_t m = n ? n - 1 : 0;
+    std::vector<uint32_t> ei(m), ej(m), common(m), denom(m);
+    std::vector<double> dist(m);
+    rc = mhx_dist_mst(S.rows.data(), S.len.data(), n, S.stride, k, s ? s : 1, ei.data(), ej.data(), common.data(), denom.data(), dist.data(), 0);
+    if (rc) return rc;
+    auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
+    std::string text;
+    if (!o.newick) { // one row per merge: the triangle's edge-list row and the clusters left after it
+        for (uint32_t e = 0; e < m; ++e) {
+            const RefSketch &a = *refs[ei[e]], &b = *refs[ej[e]];
+            const double pv = mhx_p_value(common[e], a.length, b.length, k, denom[e]);
+            text += shown(ei[e]) + "\t" + shown(ej[e]) + "\t" + fmt_g(dist[e]) + "\t" + fmt_g(pv) + "\t" + std::to_string(common[e]) + "/" +
+                    std::to_string(denom[e]) + "\t" + std::to_string(n - 1 - e) + "\n";
+        }
+        return put_text(text, stdout_buf, cap, need);
+    }
+    if (n == 0) return put_text(text, stdout_buf, cap, need);
+    // nodes 0 .. n - 1 are the leaves, node n + e the merge e; a node's height is its merge distance (leaves: 0), a branch
+    // is as long as the parent is higher, never negative; the child whose lowest index is lower comes first
+    std::vector<uint32_t> top(n), left(m), right(m), lowest((size_t)n + m), find(n);
+    std::vector<double> height((size_t)n + m, 0.0);
+    for (uint32_t i = 0; i < n; ++i) { top[i] = i; lowest[i] = i; find[i] = i; }
+    auto root = [&](uint32_t x) { while (find[x] != x) { find[x] = find[find[x]]; x = find[x]; } return x; };
+    for (uint32_t e = 0; e < m; ++e) {
+        const uint32_t ra = root(ei[e]), rb = root(ej[e]);
+        if (ra == rb) return fail(MHX_E_INTERNAL, "tree: merge %u joins one component with itself", e);
+        uint32_t a = top[ra], b = top[rb];
+        if (lowest[b] < lowest[a]) std::swap(a, b);
+        left[e] = a; right[e] = b;
+        lowest[n + e] = lowest[a];
+        height[n + e] = dist[e];
+        find[rb] = ra;
+        top[ra] = n + e;
+    }
+    // written without recursion: a chain of 65 535 merges is a tree of that depth
+    struct Item { uint32_t node; int stage; };
+    std::vector<Item> todo{{m ? n + m - 1 : 0u, 0}};
+    auto branch = [&](uint32_t child, uint32_t parent) { const double d = height[parent] - height[child]; return ":" + fmt_g(d > 0.0 ? d : 0.0); };
+    while (!todo.empty()) {
+        const Item it = todo.back();
+        todo.pop_back();
+        if (it.node < n) { text += newick_name(shown(it.node)); continue; }
+        const uint32_t e = it.node - n;
+        if (it.stage == 0) { text += "("; todo.push_back({it.node, 1}); todo.push_back({left[e], 0}); }
+        else if (it.stage == 1) { text += branch(left[e], it.node) + ","; todo.push_back({it.node, 2}); todo.push_back({right[e], 0}); }
+        else text += branch(right[e], it.node) + ")";
+    }
+    text += ";\n";
+    return put_text(text, stdout_buf, cap, need);
+}
+
+extern "C" int mhx_tree_files(const char *const *msh_paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    try {
+        return mhx_tree_files_impl(msh_paths, n_paths, opts, stdout_buf, cap, need);
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "mhx_tree_files: out of host memory");
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "mhx_tree_files: %s", e.what());
+    }
+}
+
 // Reference-set search at file level: the reference file is read, checked and staged on the device ONCE; the query files
 // are read one after the other and searched in batches of sketches (mhx_dist_search's host form against the resident
 // references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.

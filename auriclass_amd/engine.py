@@ -169,6 +169,11 @@ def load() -> ctypes.CDLL:
                                        u32p, u64p, c.c_int]
         L.mhx_cluster_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(ClusterOpts), c.c_char_p, c.c_char_p, c.c_size_t,
                                         c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_mst"):   # (or older than the single-linkage tree)
+        L.mhx_dist_mst.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p,
+                                   c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_mst_labels.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint32, c.c_int, c.c_double, c.c_void_p, u32p]
+        L.mhx_tree_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(TreeOpts), c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
         L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -349,6 +354,23 @@ def cluster_files(paths: Sequence, max_dist: float, comment: bool = False, rep: 
     opts = ClusterOpts(ctypes.sizeof(ClusterOpts), int(bool(comment)), CLUSTER_REPS[rep], float(max_dist))
     out_path = None if out is None else os.fsencode(str(out))
     return _text_call(lambda buf, cap, need: load().mhx_cluster_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
+
+
+class TreeOpts(ctypes.Structure):
+    """mhx_tree_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("newick", ctypes.c_int32)]
+
+
+def tree_files(paths: Sequence, comment: bool = False, newick: bool = False) -> str:
+    """The single-linkage tree of the references of all sketch files (one set), a row per merge in merge order:
+    "name_i\\tname_j\\tdist\\tp\\tcommon/denom\\tclusters" -- the triangle's edge-list row of the pair and the clusters left
+    after the merge; names, or comments under `comment`.  newick: the dendrogram in Newick format instead (node height = merge
+    distance)."""
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = TreeOpts(ctypes.sizeof(TreeOpts), int(bool(comment)), int(bool(newick)))
+    return _text_call(lambda buf, cap, need: load().mhx_tree_files(arr, len(files), ctypes.byref(opts), buf, cap, need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -888,6 +910,46 @@ def dist_cluster_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int
     _check(load().mhx_dist_cluster(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(label_ptr), v(degree_ptr or None),
                                    ctypes.byref(n_clusters), ctypes.byref(n_edges), 1))
     return int(n_clusters.value), int(n_edges.value)
+
+
+def dist_mst(rows: np.ndarray, lens: np.ndarray, k: int, s: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The single-linkage tree of ONE set of hash lists (rows [n, stride], lens [n], as dist_triangle takes them): the n - 1
+    edges (edge_i, edge_j, common, denom, dist) of the minimum spanning tree of all pairs, edge_i > edge_j, in edge order --
+    the greater Jaccard index first, compared exactly, ties by the lower min(i, j), then the lower max(i, j) -- which is the
+    merge order of the dendrogram; dist is the host libm distance of dist_triangle.  mst_labels cuts it at any distance."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    m = max(n - 1, 0)
+    edge_i, edge_j, common, denom = (np.zeros(m, dtype=np.uint32) for _ in range(4))
+    dist = np.zeros(m, dtype=np.float64)
+    _check(load().mhx_dist_mst(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, edge_i.ctypes.data, edge_j.ctypes.data,
+                               common.ctypes.data, denom.ctypes.data, dist.ctypes.data, 0))
+    return edge_i, edge_j, common, denom, dist
+
+
+def dist_mst_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, edge_i_ptr: int, edge_j_ptr: int, common_ptr: int,
+                    denom_ptr: int, dist_ptr: int = 0) -> int:
+    """Device pointers in and out (four uint32 [n - 1] and dist, double [n - 1] or 0; a sketch_segments_device result goes
+    straight in): the edge SET is exact and the same from call to call, its order is that of arrival, dist is the device's
+    log.  Returns the number of edges, n - 1 (0 for n <= 1); the rounds taken are load().mhx_last_mst_rounds()."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_mst(v(rows_ptr), v(len_ptr), n, stride, k, s, v(edge_i_ptr), v(edge_j_ptr), v(common_ptr), v(denom_ptr),
+                               v(dist_ptr or None), 1))
+    return max(n - 1, 0)
+
+
+def mst_labels(edge_i, edge_j, common, denom, n: int, k: int, max_dist: float) -> Tuple[np.ndarray, int]:
+    """The clusters of dist_cluster at max_dist from the tree of dist_mst alone, on the host (mhx_mst_labels: no device needed):
+    a union-find over the tree edges whose libm distance (the double dist_triangle gives) is <= max_dist; (label, n_clusters),
+    label[i] = the lowest index of i's cluster."""
+    cols = [np.ascontiguousarray(a, dtype=np.uint32) for a in (edge_i, edge_j, common, denom)]
+    assert all(a.shape == (max(n - 1, 0),) for a in cols)
+    label = np.zeros(n, dtype=np.uint32)
+    n_clusters = ctypes.c_uint32(0)
+    _check(load().mhx_mst_labels(*(a.ctypes.data for a in cols), n, k, float(max_dist), label.ctypes.data, ctypes.byref(n_clusters)))
+    return label, int(n_clusters.value)
 
 
 def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0

@@ -1,0 +1,41 @@
+"""`python -m auriclass_amd.tree [-C] [--newick] [-p N] SET.msh [SET.msh ...]`: the references of all sketch files are one set;
+its single-linkage tree -- the minimum spanning tree of all pairwise distances, computed on the device -- is printed as one
+row per merge in merge order, "name_i\\tname_j\\tdist\\tp\\tcommon/denom\\tclusters" (engine.tree_files): the gaps in the dist
+column are the distances at which `python -m auriclass_amd.cluster -d D` changes its answer.  --newick prints the dendrogram
+instead (node height = merge distance).  Inputs are sketch files: a sequence file is refused with the hint to sketch it
+first.  Exit status 1 with the engine's message when the call fails.  -p (threads) is accepted and ignored: the engine has
+its own."""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import List
+
+from auriclass_amd import engine
+
+
+def main(argv: List[str] = None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m auriclass_amd.tree", description="single-linkage tree of a sketch set: its merges, or a Newick dendrogram")
+    ap.add_argument("-C", dest="comment", action="store_true", help="print comments in place of names")
+    ap.add_argument("--newick", action="store_true", help="print the dendrogram in Newick format in place of the merge table")
+    ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
+    ap.add_argument("sets", metavar="SET.msh", nargs="+")
+    try:
+        args = ap.parse_args(argv)
+    except SystemExit as exc:
+        return 0 if exc.code == 0 else 1
+    for path in args.sets:
+        if not str(path).endswith(".msh"):
+            sys.stderr.write(f"ERROR: the tree takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
+            return 1
+    try:
+        text = engine.tree_files(args.sets, comment=args.comment, newick=args.newick)
+    except engine.EngineError as exc:
+        sys.stderr.write(exc.message + "\n")
+        return 1
+    sys.stdout.write(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

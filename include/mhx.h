@@ -19,6 +19,10 @@
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
+ *   mhx_dist_mst      <- no mash command: `mash triangle` followed by a sort of all pairs and a union-find -- the single-
+ *                        linkage tree of a set, every cut of mhx_dist_cluster at once (buffer level; engine.dist_mst)
+ *   mhx_tree_files    <- no mash command: the same for sketch files, as a table of merges or a Newick dendrogram
+ *                        (python -m auriclass_amd.tree)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -394,6 +398,63 @@ typedef struct mhx_cluster_opts {
 } mhx_cluster_opts;
 int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
                       size_t cap, size_t *need);
+
+/* Single-linkage TREE of ONE set: the minimum spanning tree of the graph of all pairs, which is the single-linkage
+ * dendrogram -- its n - 1 edges, sorted, are the merges, and cutting them at any D gives the clusters of mhx_dist_cluster at
+ * D (mhx_mst.h: mst_labels; engine.mst_labels in Python).  rows / len / n / stride / k / s as mhx_dist_triangle takes them,
+ * with its checks (n > 65 536, k, s, stride, len[i] > stride, null pointers: MHX_E_ARG); in addition s >= 2^20 is MHX_E_ARG.
+ * All before anything is launched.  n == 0 and n == 1: MHX_OK, no edge.
+ * Pairs: every pair j < i is an edge with the (common, denom) of mhx_dist_triangle; no distance bound applies.
+ * Edge order: edge a precedes edge b iff its Jaccard index common / denom is greater, compared exactly (a.common * b.denom >
+ * b.common * a.denom in 64 bits; common == denom counts as 1/1, 0/0 included); equal indices go by the lower min(i, j), then
+ * by the lower max(i, j).  The order is total and strict, so the tree is unique: Kruskal over the edges in this order.
+ * Outputs, [n - 1] each: edge_i > edge_j the ends, common / denom of the pair, dist (may be NULL) its distance.
+ * Host pointers: the edges come out in edge order -- the merge order of the dendrogram -- and dist is host libm, the double
+ * mhx_dist_triangle gives.  device_ptrs != 0 => rows, len and the five outputs are device pointers; the edge SET is exact and
+ * the same from run to run, the order is that of arrival and unspecified, dist is the device's log.
+ * Boruvka on the device: every round each component picks its best outgoing edge in the edge
+ * order -- pairs propose to a 64-bit word per list with a compare-and-swap loop, lists to a 32-bit word per component --, the
+ * picks join the lock-free union-find of the clustering, one small readback per round tells the host how many components
+ * are left.  At most ceil(log2 n) + 1 rounds (more: MHX_E_INTERNAL); mhx_last_mst_rounds() reports the rounds of the last
+ * call.  The pairs of a round come from the packed triangle, computed once, when its 8 n (n - 1) / 2 bytes fit
+ * MHX_MST_STORE_MB (default 4096: n <= 32 768) -- the only thing of size n^2 this call ever holds, released on return -- and
+ * from the triangle's blocks run again every round otherwise (workspace O(n)); MHX_MST_STORE=0|1 forces either form.
+ * mhx_last_mst_stored() reports the form that ran: 1 stored, 0 recomputed, -1 when the last call launched nothing.
+ * Geometry, MHX_TRI_GEOMETRY and MHX_TRI_QBATCH are the triangle's, and its three diagnostics report this call too, with
+ * these meanings: mhx_last_dist_kernel_ms is stream time, the readbacks between rounds included -- stored: the triangle's own
+ * figure plus the time from the first launch of the rounds to the last; recomputed: from the first launch of the triangle's
+ * passes (behind the set-up of parent and comp, which is not in it) to the last of the last round.
+ * mhx_last_dist_fallback_blocks counts the blocks the generic kernel redid ONCE: those of the triangle (stored), those of the
+ * FIRST round (recomputed, where every later round redoes the same blocks again without counting them).
+ * mhx_last_dist_ranges is the triangle's.  Not built: average and complete linkage, a sorted device form, more than 65 536 lists. */
+int mhx_dist_mst(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, uint32_t *edge_i,
+                 uint32_t *edge_j, uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
+int mhx_last_mst_rounds(void);
+int mhx_last_mst_stored(void);
+/* The cut of that tree at max_dist, on the host (no device needed): a union-find over the n - 1 tree edges whose host libm
+ * distance -- the double mhx_dist_triangle gives -- is <= max_dist; label[n], label[i] = the lowest index of i's cluster,
+ * *n_clusters their number.  Equal to mhx_dist_cluster's labels at max_dist.  The edges may come in any order (a device-form
+ * result copied back as it is).  MHX_E_ARG: null pointers, k outside 1 .. 32, a max_dist that is not a number, an edge end
+ * >= n.  n == 0: MHX_OK, 0 clusters. */
+int mhx_mst_labels(const uint32_t *edge_i, const uint32_t *edge_j, const uint32_t *common, const uint32_t *denom, uint32_t n, int k,
+                   double max_dist, uint32_t *label, uint32_t *n_clusters);
+/* The same at file level: the references of all files form one set, read and checked as mhx_triangle_files does (k / seed /
+ * sketch-size mismatches MHX_E_MISMATCH, damaged files, at most 65 536 references; sketch sizes from 2^20: MHX_E_ARG).
+ * Default output, one row per merge in merge order (names; comments when `comment` is set):
+ *     name_i\tname_j\tdist\tp\tcommon/denom\tclusters\n
+ * the first five fields are the edge-list row of mhx_triangle_files for the pair, `clusters` the number of clusters left after
+ * this merge (n - 1 down to 1).  newick != 0 prints the dendrogram instead: the height of a node is its merge distance, a
+ * branch is as long as the parent is higher than the child (leaves at 0), floored at 0 and printed %g; of two children the
+ * one whose lowest reference index is lower comes first; a name is single-quoted when it holds any of ( ) [ ] ' : ; , or a
+ * blank, an inner quote doubled; one reference prints "name;", the output ends ";\n".  opts == NULL means {sizeof, 0, 0}.
+ * MHX_E_ARG: struct_size != sizeof(mhx_tree_opts).  Not pinned by mash output (mash has no such command): pinned by the
+ * restated rules (tests/mst_rule.py, tests/tree_rule.py), its pairs by the mash-pinned distance path. */
+typedef struct mhx_tree_opts {
+    uint32_t struct_size; /* sizeof(mhx_tree_opts) */
+    int32_t comment;      /* non-zero: print comments in place of names */
+    int32_t newick;       /* non-zero: the dendrogram in Newick format in place of the merge table */
+} mhx_tree_opts;
+int mhx_tree_files(const char *const *msh_paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need);
 
 /* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
  * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
