@@ -1,5 +1,5 @@
 // mhx_device.h -- argument structs and launchers shared between the HIP kernel files (mhx_*.hip) and the host
-// engine (mhx_engine*.cpp, mhx_files.cpp).  Internal; the public surface is include/mhx.h.
+// engine (mhx_engine*.cpp, mhx_files*.cpp).  Internal; the public surface is include/mhx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,10 +2,9 @@
 // schedules tile launches and threshold tightening, and the multi-GPU partial export and
 // merge.  Batched distances are in mhx_engine_dist.cpp, the containment screen in
 // mhx_engine_screen.cpp; the file-level calls that replace AuriClass's `mash sketch` /
-// `mash dist` subprocesses live in mhx_files.cpp.
+// `mash dist` subprocesses live in mhx_files.cpp and mhx_files_sets.cpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,20 +25,6 @@
 
 namespace mhx {
 
-// ---- errors ---------------------------------------------------------------------------
-static thread_local std::string g_err;
-int fail(int code, const char *fmt, ...)
-{
-    char b[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    g_err = b;
-    return code;
-}
-void clear_error() { g_err.clear(); }
-
 Engine &g = *new Engine; // never deleted: see Engine
 
 int require_engine()
@@ -52,7 +37,6 @@ int require_engine()
 
 using namespace mhx;
 
-extern "C" const char *mhx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *mhx_version(void) { return "mhx 0.1.0 (gfx950)"; }
 extern "C" void *mhx_stream(void) { return g.stream; }
 
@@ -745,143 +729,6 @@ static void sort_pairs(const uint64_t *keys, const uint32_t *cnts, size_t n, Sor
     insertion_pass(k2, c2, n);
 }
 
-static int mhx_sketcher_finish_impl(mhx_sketcher *sk, uint64_t *hashes, uint32_t *counts, uint32_t *n_out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sk || !hashes || !n_out) return fail(MHX_E_ARG, "null argument");
-    if (sk->screen) return fail(MHX_E_ARG, "a screener's prober has no sketch");
-    if (sk->follower) { // its spans are the ones pushed here: settled while they are still in place
-        rc = settle(sk->follower);
-        if (rc) return rc;
-    }
-    // One batch on the stream, one copy, one synchronisation: final (exact) tighten unless the last pass already was
-    // one, extract with the threshold read on the device into the result block, the block to its pinned mirror.
-    const uint32_t cap = sk->fin_cap;
-    uint64_t *d = sk->d_fin;
-    const size_t fin_bytes = (4 + (size_t)cap + cap / 2) * sizeof(uint64_t);
-    static const bool dbg = getenv("MHX_FINISH_DEBUG") != nullptr; // stderr: where finish() spends its time
-    const auto t_begin = std::chrono::steady_clock::now();
-    bool want_exact = false;
-  again:
-    // big tables: the sampled pass behind the last launch left T at about the (s + 8 sqrt(s))-th solid hash, the block holds
-    // twice that, and the host keeps the first s -- a second pass over the table only if that turns out not to be so
-    if (sk->table_dirty && (want_exact || !sk->table_sampled)) {
-        HIPCHK(launch_tighten(table_args(sk), (uint32_t)g.cu_count, g.stream));
-        sk->table_dirty = false;
-        sk->table_sampled = false;
-    }
-    const bool ordered = sk->d_fin_ordered != nullptr;
-    if (ordered) { // large sketches: the kernels put the block in hash order and store it into the pinned block themselves
-        HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(uint64_t), g.stream));
-        HIPCHK(launch_extract(table_args(sk), 0, sk->m, d + 4, (uint32_t *)(d + 4 + cap), cap, (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3, g.stream,
-                              sk->d_order_buckets, sk->order_log2));
-        HIPCHK(launch_order_block(d, cap, sk->order_log2, sk->d_order_buckets, sk->d_order_starts, sk->d_order_groups, sk->d_fin_ordered, sk->h_fin, g.stream));
-    } else { // one kernel, nothing else: the entries go straight into the pinned block, the workgroup that finishes last
-             // adds the header words (kept on the device while they are being accumulated) and clears them for the next call
-        HIPCHK(launch_extract(table_args(sk), 0, sk->m, sk->h_fin + 4, (uint32_t *)(sk->h_fin + 4 + cap), cap, (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3,
-                              g.stream, nullptr, 0, d, sk->h_fin, sk->d_done));
-    }
-    HIPCHK(hipStreamSynchronize(g.stream));
-    const auto t_device = std::chrono::steady_clock::now();
-    const uint64_t *h = sk->h_fin;
-    const uint32_t n = (uint32_t)h[0];
-    const uint64_t T = h[1], flags = h[2], maxkey = h[3];
-    if ((flags & kFlagNeedLookback) && !sk->unsettled.empty()) { // FASTQ tiles left out by the self-synchronising pass
-        rc = repair_unsettled(sk);
-        if (rc) return rc;
-        goto again;
-    }
-    sk->unsettled.clear();
-    if (n > cap && sk->table_dirty && !want_exact) { // the sampled threshold was not the expected one: count exactly
-        want_exact = true;
-        goto again;
-    }
-    sk->last_T = T;
-    sk->bounded = (flags & kFlagStateBounded) != 0;
-    sk->established = (flags & kFlagStateEstablished) != 0;
-    rc = check_flags(flags);
-    if (rc) return rc;
-    std::vector<uint64_t> keys;
-    std::vector<uint32_t> cnts;
-    const uint64_t *src_keys = h + 4; // the common case: sorted straight out of the pinned block
-    const uint32_t *src_cnts = reinterpret_cast<const uint32_t *>(h + 4 + cap);
-    size_t n_src = n;
-    const bool extra = T == ~0ull && maxkey >= sk->m; // the one hash value the table cannot hold
-    if (n > cap || extra) {
-        if (n > cap) { // more entries below T than the result block holds: the general path
-            rc = extract(sk, T, sk->m, keys, cnts);
-            if (rc) return rc;
-        } else {
-            keys.assign(src_keys, src_keys + n);
-            cnts.assign(src_cnts, src_cnts + n);
-        }
-        if (extra) {
-            keys.push_back(~0ull);
-            cnts.push_back((uint32_t)maxkey);
-        }
-        src_keys = keys.data();
-        src_cnts = cnts.data();
-        n_src = keys.size();
-    }
-    // exactness: either nothing was ever rejected (T still at its initial value), or at least s qualifying
-    // hashes lie below T.  Fewer than s below a lowered T means the bound was too tight: a host-imposed cap
-    // of the m > 1 phase (sk->bounded), or -- never seen, ~1e-9 per pass -- a sampled tighten pass that overshot.
-    if (n_src < sk->s && T < sk->hash_max)
-        return fail(MHX_E_CAPACITY, "admission threshold was too tight for this input (%zu of %u sketch entries%s); recreate the sketcher with a larger table",
-                    n_src, sk->s, sk->bounded ? ", capped threshold" : "");
-    const auto t_copy = std::chrono::steady_clock::now();
-    const uint32_t nn = n_src < sk->s ? (uint32_t)n_src : sk->s;
-    bool in_order = ordered && src_keys == h + 4; // what the ordering kernels promise, checked
-    for (size_t i = 1; in_order && i < n_src; ++i) in_order = src_keys[i - 1] < src_keys[i];
-    if (in_order) {
-        memcpy(hashes, src_keys, (size_t)nn * sizeof(uint64_t));
-        if (counts) memcpy(counts, src_cnts, (size_t)nn * sizeof(uint32_t));
-    } else {
-        sort_pairs(src_keys, src_cnts, n_src, sk->sorted);
-        memcpy(hashes, sk->sorted.keys.data(), (size_t)nn * sizeof(uint64_t));
-        if (counts) memcpy(counts, sk->sorted.cnts.data(), (size_t)nn * sizeof(uint32_t));
-    }
-    *n_out = nn;
-    if (dbg) {
-        const auto t_end = std::chrono::steady_clock::now();
-        auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-        fprintf(stderr, "[mhx finish] device+copy %.0f us (block %zu bytes, %u entries), unpack %.0f us, sort+out %.0f us\n",
-                us(t_begin, t_device), fin_bytes, n, us(t_device, t_copy), us(t_copy, t_end));
-    }
-    return MHX_OK;
-}
-
-static int mhx_sketcher_export_impl(mhx_sketcher *sk, uint64_t limit, uint64_t *hashes, uint32_t *counts, uint32_t cap, uint32_t *n_out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sk || !n_out) return fail(MHX_E_ARG, "null argument");
-    rc = settle(sk);
-    if (rc) return rc;
-    uint64_t st[kStatCount];
-    rc = fetch_stats(sk, st);
-    if (rc) return rc;
-    rc = check_flags(st[kStatFlags]);
-    if (rc) return rc;
-    std::vector<uint64_t> keys;
-    std::vector<uint32_t> cnts;
-    rc = extract(sk, limit, 1, keys, cnts);
-    if (rc) return rc;
-    if (limit == ~0ull && st[kStatMaxKey]) { keys.push_back(~0ull); cnts.push_back((uint32_t)st[kStatMaxKey]); }
-    *n_out = (uint32_t)keys.size();
-    if (keys.size() > cap) return fail(MHX_E_CAPACITY, "export: %zu entries, buffer holds %u", keys.size(), cap);
-    if (!keys.empty()) {
-        if (!hashes || !counts) return fail(MHX_E_ARG, "null output buffer");
-        sort_pairs(keys.data(), cnts.data(), keys.size(), sk->sorted);
-        memcpy(hashes, sk->sorted.keys.data(), keys.size() * sizeof(uint64_t));
-        memcpy(counts, sk->sorted.cnts.data(), cnts.size() * sizeof(uint32_t));
-    }
-    return MHX_OK;
-}
-
 // Multi-GPU fast path: the shard's partial result as ONE device-resident slab of int64 words
 //   [0] n entries (may exceed cap: then only cap are present)   [1] admission threshold T
 //   [2] device flags   [3 .. 3+cap) hashes   [3+cap ..) counts, two u32 per word
@@ -1125,13 +972,7 @@ extern "C" int mhx_sketcher_merge_info(mhx_sketcher *sk, uint64_t *info8)
 extern "C" int mhx_sketcher_merge_slabs(mhx_sketcher *sk, const void *slabs, int slabs_on_device, uint32_t n_ranks, uint64_t cap_entries,
                                         const uint64_t *headers, uint32_t own_rank, uint64_t *hashes, uint32_t *counts, uint32_t *n_out)
 {
-    try {
-        return merge_slabs_impl(sk, slabs, slabs_on_device, n_ranks, cap_entries, headers, own_rank, hashes, counts, n_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_merge_slabs: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_merge_slabs: %s", e.what());
-    }
+    return guarded("mhx_sketcher_merge_slabs", [&] { return merge_slabs_impl(sk, slabs, slabs_on_device, n_ranks, cap_entries, headers, own_rank, hashes, counts, n_out); });
 }
 
 // ---- the same exchange in ONE collective when the slabs live on the device (RCCL) -----------------------------------
@@ -1170,7 +1011,7 @@ extern "C" int mhx_sketcher_merge_gathered(mhx_sketcher *sk, const void *d_slabs
     if (sk) sk->mg_info = {};
     if (!sk || !d_slabs || !hashes || !n_out || !need_cap || n_ranks == 0 || (cap_entries & 1)) return fail(MHX_E_ARG, "merge_gathered: null argument or odd capacity");
     *need_cap = 0;
-    try {
+    return guarded("mhx_sketcher_merge_gathered", [&]() -> int {
         const uint64_t slab_words = 8 + cap_entries + cap_entries / 2;
         std::vector<uint64_t> headers((size_t)n_ranks * 8);
         // the gathered headers: 64 bytes at the front of every slab
@@ -1183,11 +1024,7 @@ extern "C" int mhx_sketcher_merge_gathered(mhx_sketcher *sk, const void *d_slabs
             return fail(MHX_E_CAPACITY, "merge_gathered: a shard holds %llu entries, the slabs %llu", (unsigned long long)max_n, (unsigned long long)cap_entries);
         }
         return merge_slabs_impl(sk, d_slabs, 1, n_ranks, cap_entries, headers.data(), own_rank, hashes, counts, n_out, 8);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_merge_gathered: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_merge_gathered: %s", e.what());
-    }
+    });
 }
 
 // Union of shard partials: sum the counts of equal hashes, keep count >= m, first s.
@@ -1238,18 +1075,16 @@ extern "C" int mhx_merge_shard_partials(const uint64_t *hashes, const uint32_t *
         total += shard_n[r];
     }
     if ((!hashes || !counts) && total) return fail(MHX_E_ARG, "null input");
-    try {
+    const int rc = guarded("mhx_merge_shard_partials", [&] {
         std::vector<uint64_t> h;
         std::vector<uint32_t> c;
         h.reserve(total);
         c.reserve(total);
         for (uint64_t i = 0; i < total; ++i)
             if (hashes[i] <= t_min) { h.push_back(hashes[i]); c.push_back(counts[i]); }
-        int rc = mhx_merge_partials(h.data(), c.data(), h.size(), s, min_mult, out_hashes, out_counts, n_out);
-        if (rc) return rc;
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_merge_shard_partials: out of host memory");
-    }
+        return mhx_merge_partials(h.data(), c.data(), h.size(), s, min_mult, out_hashes, out_counts, n_out);
+    });
+    if (rc) return rc;
     if (*n_out < s && t_min < hash_max)
         return fail(MHX_E_CAPACITY, "sharded sketch not exact: %u of %u entries with multiplicity >= %u below the smallest shard threshold; "
                     "every rank must sketch its shard again with a larger budget_scale", *n_out, s, min_mult ? min_mult : 1);
@@ -1263,22 +1098,141 @@ void sketcher_set_follower(mhx_sketcher *sk, mhx_sketcher *follower)
 
 extern "C" int mhx_sketcher_finish(mhx_sketcher *sk, uint64_t *hashes, uint32_t *counts, uint32_t *n_out)
 {
-    try {
-        return mhx_sketcher_finish_impl(sk, hashes, counts, n_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_finish: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_finish: %s", e.what());
-    }
+    return guarded("mhx_sketcher_finish", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!sk || !hashes || !n_out) return fail(MHX_E_ARG, "null argument");
+        if (sk->screen) return fail(MHX_E_ARG, "a screener's prober has no sketch");
+        if (sk->follower) { // its spans are the ones pushed here: settled while they are still in place
+            rc = settle(sk->follower);
+            if (rc) return rc;
+        }
+        // One batch on the stream, one copy, one synchronisation: final (exact) tighten unless the last pass already was
+        // one, extract with the threshold read on the device into the result block, the block to its pinned mirror.
+        const uint32_t cap = sk->fin_cap;
+        uint64_t *d = sk->d_fin;
+        const size_t fin_bytes = (4 + (size_t)cap + cap / 2) * sizeof(uint64_t);
+        static const bool dbg = getenv("MHX_FINISH_DEBUG") != nullptr; // stderr: where finish() spends its time
+        const auto t_begin = std::chrono::steady_clock::now();
+        bool want_exact = false;
+      again:
+        // big tables: the sampled pass behind the last launch left T at about the (s + 8 sqrt(s))-th solid hash, the block holds
+        // twice that, and the host keeps the first s -- a second pass over the table only if that turns out not to be so
+        if (sk->table_dirty && (want_exact || !sk->table_sampled)) {
+            HIPCHK(launch_tighten(table_args(sk), (uint32_t)g.cu_count, g.stream));
+            sk->table_dirty = false;
+            sk->table_sampled = false;
+        }
+        const bool ordered = sk->d_fin_ordered != nullptr;
+        if (ordered) { // large sketches: the kernels put the block in hash order and store it into the pinned block themselves
+            HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(uint64_t), g.stream));
+            HIPCHK(launch_extract(table_args(sk), 0, sk->m, d + 4, (uint32_t *)(d + 4 + cap), cap, (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3, g.stream,
+                                  sk->d_order_buckets, sk->order_log2));
+            HIPCHK(launch_order_block(d, cap, sk->order_log2, sk->d_order_buckets, sk->d_order_starts, sk->d_order_groups, sk->d_fin_ordered, sk->h_fin, g.stream));
+        } else { // one kernel, nothing else: the entries go straight into the pinned block, the workgroup that finishes last
+                 // adds the header words (kept on the device while they are being accumulated) and clears them for the next call
+            HIPCHK(launch_extract(table_args(sk), 0, sk->m, sk->h_fin + 4, (uint32_t *)(sk->h_fin + 4 + cap), cap, (uint32_t *)d, d + 2, sk->d_thresh, d + 1, d + 3,
+                                  g.stream, nullptr, 0, d, sk->h_fin, sk->d_done));
+        }
+        HIPCHK(hipStreamSynchronize(g.stream));
+        const auto t_device = std::chrono::steady_clock::now();
+        const uint64_t *h = sk->h_fin;
+        const uint32_t n = (uint32_t)h[0];
+        const uint64_t T = h[1], flags = h[2], maxkey = h[3];
+        if ((flags & kFlagNeedLookback) && !sk->unsettled.empty()) { // FASTQ tiles left out by the self-synchronising pass
+            rc = repair_unsettled(sk);
+            if (rc) return rc;
+            goto again;
+        }
+        sk->unsettled.clear();
+        if (n > cap && sk->table_dirty && !want_exact) { // the sampled threshold was not the expected one: count exactly
+            want_exact = true;
+            goto again;
+        }
+        sk->last_T = T;
+        sk->bounded = (flags & kFlagStateBounded) != 0;
+        sk->established = (flags & kFlagStateEstablished) != 0;
+        rc = check_flags(flags);
+        if (rc) return rc;
+        std::vector<uint64_t> keys;
+        std::vector<uint32_t> cnts;
+        const uint64_t *src_keys = h + 4; // the common case: sorted straight out of the pinned block
+        const uint32_t *src_cnts = reinterpret_cast<const uint32_t *>(h + 4 + cap);
+        size_t n_src = n;
+        const bool extra = T == ~0ull && maxkey >= sk->m; // the one hash value the table cannot hold
+        if (n > cap || extra) {
+            if (n > cap) { // more entries below T than the result block holds: the general path
+                rc = extract(sk, T, sk->m, keys, cnts);
+                if (rc) return rc;
+            } else {
+                keys.assign(src_keys, src_keys + n);
+                cnts.assign(src_cnts, src_cnts + n);
+            }
+            if (extra) {
+                keys.push_back(~0ull);
+                cnts.push_back((uint32_t)maxkey);
+            }
+            src_keys = keys.data();
+            src_cnts = cnts.data();
+            n_src = keys.size();
+        }
+        // exactness: either nothing was ever rejected (T still at its initial value), or at least s qualifying
+        // hashes lie below T.  Fewer than s below a lowered T means the bound was too tight: a host-imposed cap
+        // of the m > 1 phase (sk->bounded), or -- never seen, ~1e-9 per pass -- a sampled tighten pass that overshot.
+        if (n_src < sk->s && T < sk->hash_max)
+            return fail(MHX_E_CAPACITY, "admission threshold was too tight for this input (%zu of %u sketch entries%s); recreate the sketcher with a larger table",
+                        n_src, sk->s, sk->bounded ? ", capped threshold" : "");
+        const auto t_copy = std::chrono::steady_clock::now();
+        const uint32_t nn = n_src < sk->s ? (uint32_t)n_src : sk->s;
+        bool in_order = ordered && src_keys == h + 4; // what the ordering kernels promise, checked
+        for (size_t i = 1; in_order && i < n_src; ++i) in_order = src_keys[i - 1] < src_keys[i];
+        if (in_order) {
+            memcpy(hashes, src_keys, (size_t)nn * sizeof(uint64_t));
+            if (counts) memcpy(counts, src_cnts, (size_t)nn * sizeof(uint32_t));
+        } else {
+            sort_pairs(src_keys, src_cnts, n_src, sk->sorted);
+            memcpy(hashes, sk->sorted.keys.data(), (size_t)nn * sizeof(uint64_t));
+            if (counts) memcpy(counts, sk->sorted.cnts.data(), (size_t)nn * sizeof(uint32_t));
+        }
+        *n_out = nn;
+        if (dbg) {
+            const auto t_end = std::chrono::steady_clock::now();
+            auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+            fprintf(stderr, "[mhx finish] device+copy %.0f us (block %zu bytes, %u entries), unpack %.0f us, sort+out %.0f us\n",
+                    us(t_begin, t_device), fin_bytes, n, us(t_device, t_copy), us(t_copy, t_end));
+        }
+        return MHX_OK;
+    });
 }
 
 extern "C" int mhx_sketcher_export(mhx_sketcher *sk, uint64_t limit, uint64_t *hashes, uint32_t *counts, uint32_t cap, uint32_t *n_out)
 {
-    try {
-        return mhx_sketcher_export_impl(sk, limit, hashes, counts, cap, n_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_export: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketcher_export: %s", e.what());
-    }
+    return guarded("mhx_sketcher_export", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!sk || !n_out) return fail(MHX_E_ARG, "null argument");
+        rc = settle(sk);
+        if (rc) return rc;
+        uint64_t st[kStatCount];
+        rc = fetch_stats(sk, st);
+        if (rc) return rc;
+        rc = check_flags(st[kStatFlags]);
+        if (rc) return rc;
+        std::vector<uint64_t> keys;
+        std::vector<uint32_t> cnts;
+        rc = extract(sk, limit, 1, keys, cnts);
+        if (rc) return rc;
+        if (limit == ~0ull && st[kStatMaxKey]) { keys.push_back(~0ull); cnts.push_back((uint32_t)st[kStatMaxKey]); }
+        *n_out = (uint32_t)keys.size();
+        if (keys.size() > cap) return fail(MHX_E_CAPACITY, "export: %zu entries, buffer holds %u", keys.size(), cap);
+        if (!keys.empty()) {
+            if (!hashes || !counts) return fail(MHX_E_ARG, "null output buffer");
+            sort_pairs(keys.data(), cnts.data(), keys.size(), sk->sorted);
+            memcpy(hashes, sk->sorted.keys.data(), keys.size() * sizeof(uint64_t));
+            memcpy(counts, sk->sorted.cnts.data(), cnts.size() * sizeof(uint32_t));
+        }
+        return MHX_OK;
+    });
 }

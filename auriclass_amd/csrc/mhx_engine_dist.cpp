@@ -194,13 +194,7 @@ extern "C" int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t
                               uint32_t nr, uint32_t stride, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist,
                               int device_ptrs)
 {
-    try {
-        return dist_batch_core(q, q_len, nq, r, r_len, nr, stride, k, s, common, denom, dist, device_ptrs, nullptr, nullptr);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_batch: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_batch: %s", e.what());
-    }
+    return guarded("mhx_dist_batch", [&] { return dist_batch_core(q, q_len, nq, r, r_len, nr, stride, k, s, common, denom, dist, device_ptrs, nullptr, nullptr); });
 }
 
 namespace mhx {

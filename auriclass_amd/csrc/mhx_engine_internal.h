@@ -1,5 +1,6 @@
 // mhx_engine_internal.h -- what the engine files (mhx_engine.cpp: engine state and sketcher, mhx_engine_dist.cpp,
-// mhx_engine_screen.cpp) and mhx_files.cpp (file ingest and the file-level calls) share.  Internal; the public surface is include/mhx.h.
+// mhx_engine_screen.cpp), mhx_files.cpp (file ingest and the calls that read sequence files) and mhx_files_sets.cpp (the
+// file-level commands over sketch sets) share.  Internal; the public surface is include/mhx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -153,6 +154,10 @@ extern Engine &g;
 int require_engine();
 // room for `bytes` in g.dist_in, the device staging of a host-pointer distance call (mhx_engine_dist.cpp; the triangle's too)
 int dist_stage(size_t bytes, uint8_t **out);
+// what the two file-level files share (mhx_files.cpp): the text of a call into the caller's buffer (*need: its size with the
+// terminator; cap == 0 only asks), and [off, off + len) of fd read into dst by `nthreads` parallel preads (false: short read)
+int put_text(const std::string &t, char *buf, size_t cap, size_t *need);
+bool parallel_pread(int fd, uint8_t *dst, uint64_t off, size_t len, int nthreads);
 // Reference-set search (mhx_engine_search.cpp) of host queries, every row where it lies, against a reference set that the
 // caller has put on the device: rows [nr][stride] and len [nr] there, `longest` the largest len.  Outputs as the host form
 // of mhx_dist_search.  What mhx_search_files runs per batch of queries: the references are staged once per call.

@@ -53,79 +53,69 @@ static int screener_clear(mhx_screener *sc)
     return MHX_OK;
 }
 
-static int screener_create_impl(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
-                                int with_set_size, int device_ptrs, mhx_screener **out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!out) return fail(MHX_E_ARG, "null out pointer");
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    if (nr && (!ref_rows || !ref_len || stride == 0)) return fail(MHX_E_ARG, "null reference rows");
-    if (s_ref == 0) return fail(MHX_E_ARG, "sketch size must be positive");
-    const uint64_t entries = (uint64_t)nr * stride;
-    if (entries > (1ull << 31)) return fail(MHX_E_ARG, "reference set too large for one screen table (%llu entries)", (unsigned long long)entries);
-    std::unique_ptr<mhx_screener> sc(new mhx_screener());
-    sc->k = k; sc->nr = nr; sc->stride = stride ? stride : 1; sc->s_ref = s_ref;
-    std::unique_ptr<mhx_sketcher> p(new mhx_sketcher());
-    p->k = k; p->s = s_ref; p->m = 1;
-    p->hash32 = k <= 16;
-    p->hash_max = p->hash32 ? 0xFFFFFFFFull : ~0ull;
-    p->screen = true;
-    p->nslots = screen_table_slots(entries);
-    hipError_t e = hipSuccess;
-    auto A = [&](auto &arr, size_t n) { if (e == hipSuccess) e = arr.grow(n); };
-    A(p->d_keys, p->nslots);
-    A(p->d_cnts, p->nslots);
-    A(p->d_thresh, 1);
-    A(p->d_stats, kStatReplicas * kStatCount);
-    A(p->d_tickets, kTicketWords);
-    A(p->d_need, 1);
-    A(p->h_fin, 8); // the pinned landing word of settle()
-    A(sc->d_rows, std::max<uint64_t>(entries, 1));
-    A(sc->d_len, std::max<uint32_t>(nr, 1));
-    A(sc->d_counts, std::max<uint64_t>(entries, 1));
-    A(sc->d_res, 2 * (size_t)std::max<uint32_t>(nr, 1));
-    if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed while creating the screener: %s", hipGetErrorString(e));
-    sc->probe.reset(p.release());
-    if (!device_ptrs)
-        for (uint32_t i = 0; i < nr; ++i)
-            if (ref_len[i] > stride) return fail(MHX_E_ARG, "ref_len[%u] exceeds stride", i);
-    const hipMemcpyKind kind = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (entries) HIPCHK(hipMemcpyAsync(sc->d_rows, ref_rows, entries * sizeof(uint64_t), kind, g.stream));
-    if (nr) HIPCHK(hipMemcpyAsync(sc->d_len, ref_len, (size_t)nr * sizeof(uint32_t), kind, g.stream));
-    HIPCHK(hipMemsetAsync(sc->d_counts, 0, std::max<uint64_t>(entries, 1) * sizeof(uint32_t), g.stream));
-    HIPCHK(hipMemsetAsync(sc->probe->d_stats, 0, kStatReplicas * kStatCount * sizeof(uint64_t), g.stream));
-    HIPCHK(launch_screen_build(screen_args(sc.get()), g.stream));
-    uint64_t T = 0, flags = 0;
-    HIPCHK(hipMemcpyAsync(&T, sc->probe->d_thresh, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipMemcpyAsync(&flags, sc->probe->d_stats + kStatFlags, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
-    HIPCHK(hipStreamSynchronize(g.stream)); // (the caller's rows are free again)
-    if (flags & kFlagTableFull) return fail(MHX_E_INTERNAL, "screen table overflowed while it was built");
-    sc->probe->screen_T = T;
-    sc->probe->last_T = T;
-    rc = screener_clear(sc.get());
-    if (rc) return rc;
-    if (with_set_size) {
-        mhx_sketcher *ss = nullptr;
-        rc = create_sketcher(k, s_ref, 1, 0, 1, &ss);
-        if (rc) return rc;
-        sc->setsk.reset(ss);
-    }
-    *out = sc.release();
-    return MHX_OK;
-}
-
 extern "C" int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
                                    int with_set_size, int device_ptrs, mhx_screener **out)
 {
-    try {
-        return screener_create_impl(k, ref_rows, ref_len, nr, stride, s_ref, with_set_size, device_ptrs, out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_create: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_create: %s", e.what());
-    }
+    return guarded("mhx_screener_create", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!out) return fail(MHX_E_ARG, "null out pointer");
+        if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+        if (nr && (!ref_rows || !ref_len || stride == 0)) return fail(MHX_E_ARG, "null reference rows");
+        if (s_ref == 0) return fail(MHX_E_ARG, "sketch size must be positive");
+        const uint64_t entries = (uint64_t)nr * stride;
+        if (entries > (1ull << 31)) return fail(MHX_E_ARG, "reference set too large for one screen table (%llu entries)", (unsigned long long)entries);
+        std::unique_ptr<mhx_screener> sc(new mhx_screener());
+        sc->k = k; sc->nr = nr; sc->stride = stride ? stride : 1; sc->s_ref = s_ref;
+        std::unique_ptr<mhx_sketcher> p(new mhx_sketcher());
+        p->k = k; p->s = s_ref; p->m = 1;
+        p->hash32 = k <= 16;
+        p->hash_max = p->hash32 ? 0xFFFFFFFFull : ~0ull;
+        p->screen = true;
+        p->nslots = screen_table_slots(entries);
+        hipError_t e = hipSuccess;
+        auto A = [&](auto &arr, size_t n) { if (e == hipSuccess) e = arr.grow(n); };
+        A(p->d_keys, p->nslots);
+        A(p->d_cnts, p->nslots);
+        A(p->d_thresh, 1);
+        A(p->d_stats, kStatReplicas * kStatCount);
+        A(p->d_tickets, kTicketWords);
+        A(p->d_need, 1);
+        A(p->h_fin, 8); // the pinned landing word of settle()
+        A(sc->d_rows, std::max<uint64_t>(entries, 1));
+        A(sc->d_len, std::max<uint32_t>(nr, 1));
+        A(sc->d_counts, std::max<uint64_t>(entries, 1));
+        A(sc->d_res, 2 * (size_t)std::max<uint32_t>(nr, 1));
+        if (e != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed while creating the screener: %s", hipGetErrorString(e));
+        sc->probe.reset(p.release());
+        if (!device_ptrs)
+            for (uint32_t i = 0; i < nr; ++i)
+                if (ref_len[i] > stride) return fail(MHX_E_ARG, "ref_len[%u] exceeds stride", i);
+        const hipMemcpyKind kind = device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        if (entries) HIPCHK(hipMemcpyAsync(sc->d_rows, ref_rows, entries * sizeof(uint64_t), kind, g.stream));
+        if (nr) HIPCHK(hipMemcpyAsync(sc->d_len, ref_len, (size_t)nr * sizeof(uint32_t), kind, g.stream));
+        HIPCHK(hipMemsetAsync(sc->d_counts, 0, std::max<uint64_t>(entries, 1) * sizeof(uint32_t), g.stream));
+        HIPCHK(hipMemsetAsync(sc->probe->d_stats, 0, kStatReplicas * kStatCount * sizeof(uint64_t), g.stream));
+        HIPCHK(launch_screen_build(screen_args(sc.get()), g.stream));
+        uint64_t T = 0, flags = 0;
+        HIPCHK(hipMemcpyAsync(&T, sc->probe->d_thresh, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipMemcpyAsync(&flags, sc->probe->d_stats + kStatFlags, sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
+        HIPCHK(hipStreamSynchronize(g.stream)); // (the caller's rows are free again)
+        if (flags & kFlagTableFull) return fail(MHX_E_INTERNAL, "screen table overflowed while it was built");
+        sc->probe->screen_T = T;
+        sc->probe->last_T = T;
+        rc = screener_clear(sc.get());
+        if (rc) return rc;
+        if (with_set_size) {
+            mhx_sketcher *ss = nullptr;
+            rc = create_sketcher(k, s_ref, 1, 0, 1, &ss);
+            if (rc) return rc;
+            sc->setsk.reset(ss);
+        }
+        *out = sc.release();
+        return MHX_OK;
+    });
 }
 
 extern "C" void mhx_screener_destroy(mhx_screener *sc)
@@ -263,23 +253,11 @@ static int screener_finish_impl(mhx_screener *sc, bool winner, const uint64_t *r
 
 extern "C" int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
 {
-    try {
-        return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish: %s", e.what());
-    }
+    return guarded("mhx_screener_finish", [&] { return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts); });
 }
 
 extern "C" int mhx_screener_finish_winner(mhx_screener *sc, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
                                           uint32_t *counts)
 {
-    try {
-        return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screener_finish_winner: %s", e.what());
-    }
+    return guarded("mhx_screener_finish_winner", [&] { return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts); });
 }

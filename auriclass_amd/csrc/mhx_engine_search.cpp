@@ -213,32 +213,6 @@ int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
     return MHX_OK;
 }
 
-int dist_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t stride, int k,
-                uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist,
-                uint32_t *n_hits, int device_ptrs)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    rc = search_check(nq, nr, stride, k, s, max_dist, top);
-    if (rc) return rc;
-    if (nq == 0) return MHX_OK;
-    if (!n_hits) return fail(MHX_E_ARG, "null argument");
-    if (nr == 0) {
-        if (device_ptrs) { if (hipMemset(n_hits, 0, (size_t)nq * 4) != hipSuccess) return fail(MHX_E_HIP, "hipMemset failed in dist_search"); }
-        else memset(n_hits, 0, (size_t)nq * 4);
-        return MHX_OK;
-    }
-    if (!q || !q_len || !r || !r_len || !hit_ref || !hit_common || !hit_denom) return fail(MHX_E_ARG, "null argument");
-    if (!device_ptrs) return search_host(q, nullptr, q_len, nq, r, r_len, nullptr, nr, stride, k, s, max_dist, top, hit_ref, hit_common, hit_denom, hit_dist, n_hits);
-    SearchCall c{}; // the lists stay where they are: prefiltered only, in rank order
-    c.q = q; c.q_len = q_len; c.r = r; c.r_len = r_len; c.nq = nq; c.nr = nr; c.stride = stride; c.s = s; c.k = k; c.top = top;
-    c.longest = stride; // the lengths are on the device: the row stride bounds them
-    c.jmin = tri_jmin(max_dist, k);
-    c.hit_ref = hit_ref; c.hit_common = hit_common; c.hit_denom = hit_denom; c.n_hits = n_hits; c.hit_dist = hit_dist;
-    return search_device(c);
-}
-
 } // namespace
 
 namespace mhx {
@@ -253,15 +227,30 @@ int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t n
 }
 } // namespace mhx
 
-extern "C" int mhx_dist_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr,
-                               uint32_t stride, int k, uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref, uint32_t *hit_common,
-                               uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits, int device_ptrs)
+extern "C" int mhx_dist_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t stride, int k,
+                               uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist,
+                               uint32_t *n_hits, int device_ptrs)
 {
-    try {
-        return dist_search(q, q_len, nq, r, r_len, nr, stride, k, s, max_dist, top, hit_ref, hit_common, hit_denom, hit_dist, n_hits, device_ptrs);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_search: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_dist_search: %s", e.what());
-    }
+    return guarded("mhx_dist_search", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        rc = search_check(nq, nr, stride, k, s, max_dist, top);
+        if (rc) return rc;
+        if (nq == 0) return MHX_OK;
+        if (!n_hits) return fail(MHX_E_ARG, "null argument");
+        if (nr == 0) {
+            if (device_ptrs) { if (hipMemset(n_hits, 0, (size_t)nq * 4) != hipSuccess) return fail(MHX_E_HIP, "hipMemset failed in dist_search"); }
+            else memset(n_hits, 0, (size_t)nq * 4);
+            return MHX_OK;
+        }
+        if (!q || !q_len || !r || !r_len || !hit_ref || !hit_common || !hit_denom) return fail(MHX_E_ARG, "null argument");
+        if (!device_ptrs) return search_host(q, nullptr, q_len, nq, r, r_len, nullptr, nr, stride, k, s, max_dist, top, hit_ref, hit_common, hit_denom, hit_dist, n_hits);
+        SearchCall c{}; // the lists stay where they are: prefiltered only, in rank order
+        c.q = q; c.q_len = q_len; c.r = r; c.r_len = r_len; c.nq = nq; c.nr = nr; c.stride = stride; c.s = s; c.k = k; c.top = top;
+        c.longest = stride; // the lengths are on the device: the row stride bounds them
+        c.jmin = tri_jmin(max_dist, k);
+        c.hit_ref = hit_ref; c.hit_common = hit_common; c.hit_denom = hit_denom; c.n_hits = n_hits; c.hit_dist = hit_dist;
+        return search_device(c);
+    });
 }

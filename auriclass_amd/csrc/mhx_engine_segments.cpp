@@ -115,71 +115,61 @@ int segments_resident(const uint8_t *d_bytes, const uint64_t *h_off, uint32_t n_
 }
 } // namespace mhx
 
-static int sketch_segments_impl(const void *bytes, uint64_t n, const uint64_t *seg_off, uint32_t n_seg, int k, uint32_t s, uint64_t *rows,
-                                uint32_t *len, uint32_t stride, int device_ptrs)
+extern "C" int mhx_sketch_segments(const void *bytes, uint64_t n, const uint64_t *seg_off, uint32_t n_seg, int k, uint32_t s, uint64_t *rows,
+                                   uint32_t *len, uint32_t stride, int device_ptrs)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    if (s == 0) return fail(MHX_E_ARG, "sketch_segments: sketch size 0");
-    if (n_seg == 0) return MHX_OK;
-    if (n_seg > 0x7FFFFFFFu) return fail(MHX_E_ARG, "sketch_segments: too many segments for one call (%u)", n_seg);
-    if (!seg_off || !len || (!bytes && n)) return fail(MHX_E_ARG, "sketch_segments: null argument");
-    std::vector<uint64_t> off_copy;
-    const uint64_t *h_off = seg_off;
-    if (device_ptrs) {
-        off_copy.resize((size_t)n_seg + 1);
-        HIPCHK(hipMemcpyAsync(off_copy.data(), seg_off, off_copy.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
-        HIPCHK(hipStreamSynchronize(g.stream));
-        h_off = off_copy.data();
-    }
-    uint32_t need = 0;
-    rc = check_offsets(h_off, n_seg, n, k, s, &need);
-    if (rc) return rc;
-    if (stride < need) return fail(MHX_E_ARG, "sketch_segments: stride %u, but a segment may fill %u entries", stride, need);
-    if (need && !rows) return fail(MHX_E_ARG, "sketch_segments: null argument");
-    const uint8_t *stream = (const uint8_t *)bytes;
-    if (device_ptrs) return segments_on_device(stream, h_off, seg_off, n_seg, k, s, rows, len, stride);
-
-    // host pointers: runs of whole segments whose bytes fit a round are staged and sketched where they lie; a segment larger
-    // than a round (far above the cut) is pushed from the host, the sketcher stages it by itself
-    SegCtx &c = g.seg;
-    std::vector<uint64_t> rebased, hashes;
-    for (uint32_t i0 = 0; i0 < n_seg;) {
-        uint32_t i1 = i0 + 1;
-        while (i1 < n_seg && h_off[i1 + 1] - h_off[i0] <= kSegBytesRound) ++i1;
-        const uint64_t span = h_off[i1] - h_off[i0];
-        if (span > kSegBytesRound) { // one segment
-            rc = sketch_large_segment(stream + h_off[i0], span, false, k, s, hashes);
-            if (rc) return rc;
-            if (stride) memset(rows + (size_t)i0 * stride, 0, (size_t)stride * sizeof(uint64_t));
-            if (!hashes.empty()) memcpy(rows + (size_t)i0 * stride, hashes.data(), hashes.size() * sizeof(uint64_t));
-            len[i0] = (uint32_t)hashes.size();
-        } else {
-            HIPCHK(c.d_bytes.grow((size_t)span + 64, g.stream));
-            if (span) HIPCHK(hipMemcpyAsync(c.d_bytes, stream + h_off[i0], (size_t)span, hipMemcpyHostToDevice, g.stream));
-            HIPCHK(hipMemsetAsync(c.d_bytes + span, 0, 64, g.stream));
-            rebased.resize((size_t)(i1 - i0) + 1);
-            for (uint32_t i = i0; i <= i1; ++i) rebased[i - i0] = h_off[i] - h_off[i0];
-            rc = segments_resident(c.d_bytes, rebased.data(), i1 - i0, k, s, stride, rows + (size_t)i0 * stride, len + i0);
-            if (rc) return rc;
+    return guarded("mhx_sketch_segments", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+        if (s == 0) return fail(MHX_E_ARG, "sketch_segments: sketch size 0");
+        if (n_seg == 0) return MHX_OK;
+        if (n_seg > 0x7FFFFFFFu) return fail(MHX_E_ARG, "sketch_segments: too many segments for one call (%u)", n_seg);
+        if (!seg_off || !len || (!bytes && n)) return fail(MHX_E_ARG, "sketch_segments: null argument");
+        std::vector<uint64_t> off_copy;
+        const uint64_t *h_off = seg_off;
+        if (device_ptrs) {
+            off_copy.resize((size_t)n_seg + 1);
+            HIPCHK(hipMemcpyAsync(off_copy.data(), seg_off, off_copy.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g.stream));
+            HIPCHK(hipStreamSynchronize(g.stream));
+            h_off = off_copy.data();
         }
-        i0 = i1;
-    }
-    return MHX_OK;
-}
+        uint32_t need = 0;
+        rc = check_offsets(h_off, n_seg, n, k, s, &need);
+        if (rc) return rc;
+        if (stride < need) return fail(MHX_E_ARG, "sketch_segments: stride %u, but a segment may fill %u entries", stride, need);
+        if (need && !rows) return fail(MHX_E_ARG, "sketch_segments: null argument");
+        const uint8_t *stream = (const uint8_t *)bytes;
+        if (device_ptrs) return segments_on_device(stream, h_off, seg_off, n_seg, k, s, rows, len, stride);
 
-extern "C" int mhx_sketch_segments(const void *bytes, uint64_t n, const uint64_t *seg_off, uint32_t n_seg, int k, uint32_t s,
-                                   uint64_t *rows, uint32_t *len, uint32_t stride, int device_ptrs)
-{
-    try {
-        return sketch_segments_impl(bytes, n, seg_off, n_seg, k, s, rows, len, stride, device_ptrs);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_segments: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_segments: %s", e.what());
-    }
+        // host pointers: runs of whole segments whose bytes fit a round are staged and sketched where they lie; a segment larger
+        // than a round (far above the cut) is pushed from the host, the sketcher stages it by itself
+        SegCtx &c = g.seg;
+        std::vector<uint64_t> rebased, hashes;
+        for (uint32_t i0 = 0; i0 < n_seg;) {
+            uint32_t i1 = i0 + 1;
+            while (i1 < n_seg && h_off[i1 + 1] - h_off[i0] <= kSegBytesRound) ++i1;
+            const uint64_t span = h_off[i1] - h_off[i0];
+            if (span > kSegBytesRound) { // one segment
+                rc = sketch_large_segment(stream + h_off[i0], span, false, k, s, hashes);
+                if (rc) return rc;
+                if (stride) memset(rows + (size_t)i0 * stride, 0, (size_t)stride * sizeof(uint64_t));
+                if (!hashes.empty()) memcpy(rows + (size_t)i0 * stride, hashes.data(), hashes.size() * sizeof(uint64_t));
+                len[i0] = (uint32_t)hashes.size();
+            } else {
+                HIPCHK(c.d_bytes.grow((size_t)span + 64, g.stream));
+                if (span) HIPCHK(hipMemcpyAsync(c.d_bytes, stream + h_off[i0], (size_t)span, hipMemcpyHostToDevice, g.stream));
+                HIPCHK(hipMemsetAsync(c.d_bytes + span, 0, 64, g.stream));
+                rebased.resize((size_t)(i1 - i0) + 1);
+                for (uint32_t i = i0; i <= i1; ++i) rebased[i - i0] = h_off[i] - h_off[i0];
+                rc = segments_resident(c.d_bytes, rebased.data(), i1 - i0, k, s, stride, rows + (size_t)i0 * stride, len + i0);
+                if (rc) return rc;
+            }
+            i0 = i1;
+        }
+        return MHX_OK;
+    });
 }
 
 extern "C" uint32_t mhx_sketch_segments_cut(void) { return kSegCut; }

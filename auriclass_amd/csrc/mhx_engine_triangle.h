@@ -1,0 +1,66 @@
+// mhx_engine_triangle.h -- what the host side of the tree (mhx_engine_mst.cpp) takes from the triangle's
+// (mhx_engine_triangle.cpp): the inputs of a call and their staging, the dense mode as the stored pair source, and the
+// blocks run once per round as the recomputed one.  Internal.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mhx_mst.h"
+#include "mhx_internal.h"
+
+namespace mhx {
+
+struct TriCall { // the inputs of a call, everything on the device
+    const uint64_t *rows;
+    const uint32_t *len;
+    uint32_t n, stride, s, longest;
+    int k;
+};
+
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// what all calls check first; *done: nothing to compute (n <= 1)
+int triangle_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, bool *done);
+// the inputs of a call and `extra` bytes of the staging area at *base for the caller, see there
+int stage_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, size_t extra, uint8_t **base,
+               TriCall &c);
+// the dense mode: every pair into the packed triangle [n (n - 1) / 2]; dist may be null
+int run_dense(const TriCall &c, uint32_t *common, uint32_t *denom, double *dist);
+
+// The state of a single-linkage tree call (mhx_mst.h) between its rounds, everything on the device: what the five steps of
+// a round read and write, and the counters that come back once per round.
+struct MstRun {
+    uint64_t *best; // [n]
+    uint32_t *winner, *parent, *comp; // [n] each
+    unsigned long long *counters; // [0] edges appended so far, [1] roots of the last flatten pass
+    uint32_t *edge_i, *edge_j, *common, *denom; // [n - 1] the result
+    double *dist;             // may be null
+    uint32_t n;
+    int k;
+    uint32_t components, rounds; // host: after the last round closed
+    uint64_t appended;
+};
+
+hipError_t mst_round_open(MstRun &m); // step 1; the proposals of step 2 follow, from either pair source
+int mst_round_close(MstRun &m);       // steps 3 to 5 and the one small readback of a round
+
+// The rounds of a tree until one component is left (mst_max_rounds bounds them): a round opens, `propose(round)` runs step 2
+// from its pair source, the round closes.  Nothing synchronises between the rounds but mst_round_close.  le: the first
+// launch error, the caller's to report; nothing is launched after it.
+template <class Propose> int mst_rounds(MstRun &m, hipError_t &le, Propose propose)
+{
+    for (uint32_t round = 0; le == hipSuccess && m.components > 1; ++round) {
+        if (round == mst_max_rounds(m.n)) return fail(MHX_E_INTERNAL, "the tree is not finished after %u rounds (%u components)", round, m.components);
+        le = mst_round_open(m);
+        int rc = le == hipSuccess ? propose(round) : MHX_OK;
+        if (rc == MHX_OK && le == hipSuccess) rc = mst_round_close(m);
+        if (rc) return rc;
+    }
+    return MHX_OK;
+}
+
+// the tree from the recomputed pair source: every round's proposals from the triangle's blocks.  The caller has run mst_begin.
+int run_mst_recomputed(const TriCall &c, MstRun &m);
+
+} // namespace mhx

@@ -389,28 +389,19 @@ extern "C" int mhx_sniff_fastq(const char *path) { return sniff_guarded(path, '@
 extern "C" int mhx_sniff_fasta(const char *path) { return sniff_guarded(path, '>'); }
 extern "C" int mhx_fastq_tail_complete(const void *tail, size_t n) { return tail || n == 0 ? (fastq_tail_complete((const uint8_t *)tail, n) ? 1 : 0) : 1; }
 
-static int fasta_total_bases_impl(const char *path, uint64_t *total)
-{
-    clear_error();
-    if (!path || !total) return fail(MHX_E_ARG, "null argument");
-    std::vector<uint8_t> raw;
-    int rc = read_all_maybe_gz(path, raw);
-    if (rc) return rc;
-    ParsedRecords pr;
-    rc = parse_fastx(raw.data(), raw.size(), 0, pr);
-    if (rc) return rc;
-    *total = pr.total_length;
-    return MHX_OK;
-}
-
 // no exception may cross the C boundary (ctypes would abort the process): a crafted .gz can ask for gigabytes
 extern "C" int mhx_fasta_total_bases(const char *path, uint64_t *total)
 {
-    try {
-        return fasta_total_bases_impl(path, total);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_fasta_total_bases: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_fasta_total_bases: %s", e.what());
-    }
+    return guarded("mhx_fasta_total_bases", [&]() -> int {
+        clear_error();
+        if (!path || !total) return fail(MHX_E_ARG, "null argument");
+        std::vector<uint8_t> raw;
+        int rc = read_all_maybe_gz(path, raw);
+        if (rc) return rc;
+        ParsedRecords pr;
+        rc = parse_fastx(raw.data(), raw.size(), 0, pr);
+        if (rc) return rc;
+        *total = pr.total_length;
+        return MHX_OK;
+    });
 }

@@ -1,6 +1,7 @@
 // mhx_files.cpp -- the file-level half of libmhx: FASTQ / FASTA ingest (bulk path for uncompressed
-// files, inflate threads for .gz, whole-file record parser as the last resort) and the two calls that
-// replace AuriClass's `mash sketch` / `mash dist` subprocesses
+// files, inflate threads for .gz, whole-file record parser as the last resort) and the calls that read
+// sequence files (mhx_sketch_files*, mhx_screen_files*).  The commands over sketch sets, `mash dist` first, are in
+// mhx_files_sets.cpp; together they replace AuriClass's `mash sketch` / `mash dist` subprocesses
 // (/root/reference/auriclass/classes.py:576-596, 696-713, 92-104).
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
@@ -36,7 +37,8 @@
 using namespace mhx;
 
 // ---- file level -------------------------------------------------------------------------
-static int put_text(const std::string &t, char *buf, size_t cap, size_t *need)
+namespace mhx {
+int put_text(const std::string &t, char *buf, size_t cap, size_t *need)
 {
     if (need) *need = t.size() + 1;
     if (cap == 0) return MHX_OK;
@@ -44,6 +46,7 @@ static int put_text(const std::string &t, char *buf, size_t cap, size_t *need)
     memcpy(buf, t.c_str(), t.size() + 1);
     return MHX_OK;
 }
+} // namespace mhx
 
 static std::string make_comment(const std::string &name, const std::string &comment, uint64_t count)
 { // mash sketchFile(): "<name> <comment>", wrapped when several records were counted
@@ -623,28 +626,9 @@ uint64_t guess_inflated_bytes(const char *path)
 // ranges of a 64 MiB block into a pinned staging slot, the block is copied to its place in the
 // device buffer on a copy stream while the next block is being read, and the device parser
 // finds the records itself (line phase by look-back), so the host never scans the bytes.
-namespace {
-constexpr size_t kBulkBlock = 64u << 20;
-
-struct BulkFile {
-    DevArray<uint8_t> d_buf;
-    uint64_t size = 0;
-    std::vector<uint8_t> head; // first bytes of the file (record name / comment)
-    std::vector<uint8_t> tail; // its last bytes (is the last record complete?)
-};
-
-static int ensure_pinned_ring()
-{
-    if (!g.copy_stream) HIPCHK(hipStreamCreateWithFlags(g.copy_stream.out(), hipStreamNonBlocking));
-    for (int i = 0; i < Engine::kPinnedSlots; ++i) {
-        HIPCHK(g.pinned[i].grow(kBulkBlock));
-        if (!g.pinned_free[i]) HIPCHK(hipEventCreateWithFlags(g.pinned_free[i].out(), hipEventDisableTiming));
-    }
-    return MHX_OK;
-}
-
+namespace mhx {
 // reads [off, off + len) of fd into dst with `nthreads` parallel preads; false on a short read
-static bool parallel_pread(int fd, uint8_t *dst, uint64_t off, size_t len, int nthreads)
+bool parallel_pread(int fd, uint8_t *dst, uint64_t off, size_t len, int nthreads)
 {
     JoinedThreads th;
     if (nthreads < 1) nthreads = 1;
@@ -668,6 +652,27 @@ static bool parallel_pread(int fd, uint8_t *dst, uint64_t off, size_t len, int n
     th.join();
     for (int v : ok) if (!v) return false;
     return true;
+}
+} // namespace mhx
+
+namespace {
+constexpr size_t kBulkBlock = 64u << 20;
+
+struct BulkFile {
+    DevArray<uint8_t> d_buf;
+    uint64_t size = 0;
+    std::vector<uint8_t> head; // first bytes of the file (record name / comment)
+    std::vector<uint8_t> tail; // its last bytes (is the last record complete?)
+};
+
+static int ensure_pinned_ring()
+{
+    if (!g.copy_stream) HIPCHK(hipStreamCreateWithFlags(g.copy_stream.out(), hipStreamNonBlocking));
+    for (int i = 0; i < Engine::kPinnedSlots; ++i) {
+        HIPCHK(g.pinned[i].grow(kBulkBlock));
+        if (!g.pinned_free[i]) HIPCHK(hipEventCreateWithFlags(g.pinned_free[i].out(), hipEventDisableTiming));
+    }
+    return MHX_OK;
 }
 
 // MHX_OK and f->d_buf set, or MHX_OK with d_buf == nullptr when the file should take another path
@@ -1203,131 +1208,6 @@ static int sketch_read_set(const char *const *paths, int n_paths, int k, uint32_
     return MHX_OK;
 }
 
-static int mhx_sketch_files_impl(const char *const *paths, int n_paths, int k, uint32_t s, int reads, uint32_t min_mult,
-                                const char *out_msh, char *stderr_buf, size_t stderr_cap, size_t *stderr_need,
-                                double *est_genome_size)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    SketchSet set;
-    set.kmer_size = (uint32_t)k;
-    set.sketch_size = s;
-    std::string err;
-    std::vector<Loaded> loaded(n_paths);
-    auto no_records = [&](const char *p) {
-        err += std::string("ERROR: Did not find fasta records in \"") + p + "\".\n";
-        put_text(err, stderr_buf, stderr_cap, stderr_need);
-        return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", p);
-    };
-    if (reads) {
-        RefSketch ref;
-        uint64_t kmers = 0, count = 0;
-        std::string fname, fcomment;
-        rc = sketch_read_set(paths, n_paths, k, s, min_mult ? min_mult : 1, nullptr, ref, kmers, count, fname, fcomment);
-        if (rc) return rc;
-        // mash stops when no record holds k bases.  (`kmers` is not that question: the device counts every window of k BYTES
-        // inside one line, and a CRLF file of reads one base shorter than k has such windows -- 31 bases and the '\r' --
-        // although none of them is a k-mer.)
-        if (count == 0) return no_records(paths[0]);
-        double set_size = 0.0, mult = 0.0;
-        if (!ref.hashes.empty()) {
-            set_size = pow(2.0, k > 16 ? 64.0 : 32.0) * (double)ref.hashes.size() / (double)ref.hashes.back();
-            uint64_t sum = 0;
-            for (uint32_t c : ref.counts) sum += c;
-            mult = (double)sum / (double)ref.hashes.size();
-        }
-        ref.name = paths[0];
-        ref.comment = make_comment(fname, fcomment, count);
-        ref.length = (uint64_t)set_size;
-        ref.counts.clear(); // mash stores counts only with -M
-        set.refs.push_back(std::move(ref));
-        err += "Estimated genome size: " + fmt_g(set_size) + "\n";
-        err += "Estimated coverage:    " + fmt_g(mult) + "\n";
-        if (est_genome_size) *est_genome_size = set_size;
-    } else {
-        // one reference per file; file i + 1 is read (and inflated) on a helper thread while file i is on the GPU
-        const bool pinned_ok = !getenv("MHX_HOST_FASTA") && ensure_pinned_ring() == MHX_OK;
-        if (!pinned_ok) { clear_error(); (void)hipGetLastError(); }
-        std::vector<FastaInput> inputs(n_paths);
-        // the device buffers are sized for the largest uncompressed input up front, so that a loader can copy file i + 1
-        // into its raw buffer while file i is still on the GPU
-        uint64_t largest = 0;
-        for (int i = 0; i < n_paths; ++i) {
-            struct stat sb;
-            if (stat(paths[i], &sb) == 0 && S_ISREG(sb.st_mode) && !is_gzip_file(paths[i])) largest = std::max<uint64_t>(largest, (uint64_t)sb.st_size);
-        }
-        bool stream_ok = pinned_ok && largest > 0 && largest + 64 <= kBulkBlock && ensure_fasta_buffers(largest) == MHX_OK;
-        if (!stream_ok) clear_error();
-        auto raw_of = [&](int i) { return stream_ok ? g.fasta.d_raw[i & 1] : (uint8_t *)nullptr; };
-        std::thread loader;
-        struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{loader};
-        auto start_loader = [&](int j) { // file j on its way while file j - 1 is on the GPU; without a thread to be had: loaded here and now
-            try {
-                loader = std::thread(load_fasta_input, paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), (hipEvent_t)g.fasta.raw_ready[j & 1]);
-            } catch (const std::system_error &) {
-                load_fasta_input(paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), g.fasta.raw_ready[j & 1]);
-            }
-        };
-        load_fasta_input(paths[0], 0, pinned_ok, &inputs[0], raw_of(0), g.fasta.d_raw[0].cap(), g.fasta.raw_ready[0]);
-        for (int i = 0; i < n_paths; ++i) {
-            if (loader.joinable()) loader.join();
-            FastaInput &in = inputs[i];
-            err += std::string("Sketching ") + paths[i] + "...\n";
-            if (in.rc) return fail(in.rc, "%s", in.error.c_str());
-            // The FASTA device buffers regrow only while no loader holds one of them: file i's are sized here, before file
-            // i + 1's loader is handed its raw buffer.  Bytes that went to a buffer that has since been regrown are copied
-            // again from the host.
-            const bool device_parser = !getenv("MHX_HOST_FASTA") && fasta_for_device(in.data, in.n);
-            if (device_parser) {
-                const size_t raw_cap = g.fasta.d_raw[i & 1].cap();
-                rc = ensure_fasta_buffers(in.n);
-                if (rc) return rc;
-                if (g.fasta.d_raw[i & 1].cap() != raw_cap) in.on_device = false;
-            }
-            if (i + 1 < n_paths) start_loader(i + 1);
-            if (device_parser) { // plain FASTA: parsed on the device
-                RefSketch ref;
-                FastaInfo info;
-                rc = sketch_fasta_on_device(in.data, in.n, i, in.on_device, k, s, ref.hashes, info);
-                if (rc < 0) return rc;
-                if (rc == MHX_OK) {
-                    if (info.records == 0) return no_records(paths[i]);
-                    ref.name = paths[i];
-                    ref.comment = make_comment(info.first_name, info.first_comment, info.records);
-                    ref.length = info.total_length;
-                    set.refs.push_back(std::move(ref));
-                    in = FastaInput();
-                    continue;
-                }
-            }
-            if (in.slot >= 0) in.owned.assign(in.data, in.data + in.n); // the record parser path keeps the bytes beyond this slot's turn
-            loaded[i].raw.swap(in.owned);
-            in = FastaInput();
-            rc = parse_fastx(loaded[i].raw.data(), loaded[i].raw.size(), k, loaded[i].rec);
-            if (rc) return rc;
-            if (loaded[i].rec.records == 0) return no_records(paths[i]);
-            RefSketch ref;
-            std::vector<Loaded *> in2{&loaded[i]};
-            rc = sketch_reference(in2, k, s, 1, false, ref.hashes, ref.counts, nullptr);
-            if (rc) return rc;
-            ref.counts.clear();
-            ref.name = paths[i];
-            ref.comment = make_comment(loaded[i].rec.first_name, loaded[i].rec.first_comment, loaded[i].rec.records);
-            ref.length = loaded[i].rec.total_length;
-            set.refs.push_back(std::move(ref));
-            loaded[i] = Loaded();
-        }
-        if (est_genome_size) *est_genome_size = 0.0;
-    }
-    err += std::string("Writing to ") + out_msh + "...\n";
-    rc = msh_write_file(out_msh, set);
-    if (rc) return rc;
-    return put_text(err, stderr_buf, stderr_cap, stderr_need);
-}
-
 // `mash sketch -i`: one reference per RECORD.  Either route lays a file out as a dense stream plus record offsets and ends
 // in the segmented sketch (mhx_engine_segments.cpp): plain FASTA through the device parser, whose separator positions are
 // the offsets (the separator byte in front of a record is a newline: part of the segment, never of a window); anything
@@ -1391,181 +1271,65 @@ int sketch_records(const uint8_t *d_stream, const uint8_t *h_stream, uint64_t st
 }
 } // namespace
 
-static int mhx_sketch_files_individual_impl(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh, char *stderr_buf,
-                                            size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
-    for (int i = 0; i < n_paths; ++i)
-        if (!paths[i]) return fail(MHX_E_ARG, "sketch: input path %d is null", i);
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    if (s == 0) return fail(MHX_E_ARG, "sketch: sketch size 0");
-    SketchSet set;
-    set.kmer_size = (uint32_t)k;
-    set.sketch_size = s;
-    std::string err;
-    std::vector<uint8_t> raw;
-    for (int i = 0; i < n_paths; ++i) {
-        err += std::string("Sketching ") + paths[i] + "...\n";
-        rc = read_all_maybe_gz(paths[i], raw);
-        if (rc) return rc;
-        uint64_t added = 0;
-        bool done = false;
-        if (!getenv("MHX_HOST_FASTA") && fasta_for_device(raw.data(), raw.size())) { // plain FASTA: parsed on the device
-            rc = ensure_fasta_buffers(raw.size());
-            if (rc) return rc;
-            std::vector<uint64_t> off;
-            uint64_t total = 0;
-            rc = fasta_stream_on_device(raw.data(), raw.size(), 0, false, off, total);
-            if (rc < 0) return rc;
-            if (rc == MHX_OK) {
-                off.push_back(total);
-                std::vector<std::string> names, comments;
-                fasta_headers(raw.data(), raw.size(), names, comments);
-                rc = sketch_records(g.fasta.d_out, nullptr, total, off, 1, names, comments, k, s, set, &added);
-                if (rc) return rc;
-                done = true;
-            }
-        }
-        if (!done) { // FASTQ, a file that does not start with '>', ...: the host record parser
-            RecordList rec;
-            rc = parse_fastx_records(raw.data(), raw.size(), rec);
-            if (rc) return rc;
-            if (rec.off.empty()) rec.off.push_back(0);
-            rc = sketch_records(nullptr, rec.seq.data(), rec.seq.size(), rec.off, 0, rec.name, rec.comment, k, s, set, &added);
-            if (rc) return rc;
-        }
-        if (added == 0) {
-            err += std::string("ERROR: Did not find fasta records in \"") + paths[i] + "\".\n";
-            put_text(err, stderr_buf, stderr_cap, stderr_need);
-            return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", paths[i]);
-        }
-    }
-    err += std::string("Writing to ") + out_msh + "...\n";
-    rc = msh_write_file(out_msh, set);
-    if (rc) return rc;
-    if (n_refs_out) *n_refs_out = set.refs.size();
-    return put_text(err, stderr_buf, stderr_cap, stderr_need);
-}
-
 extern "C" int mhx_sketch_files_individual(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh, char *stderr_buf,
                                            size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out)
 {
-    try {
-        return mhx_sketch_files_individual_impl(paths, n_paths, k, s, out_msh, stderr_buf, stderr_cap, stderr_need, n_refs_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_files_individual: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_files_individual: %s", e.what());
-    }
-}
-
-// `mash dist REF QUERY [QUERY ...]`: mhx_dist_files is the n_qry == 1 case.  The reference file is read, parsed, checked and
-// staged once per call, and the sketches of ALL query files go to the device together, so that a run of samples reaches
-// the all-vs-refs kernels in the shape they were made for (many queries x few references) instead of 1 x nr per sample.
-static int mhx_dist_files_impl(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (n_qry == 1 && (!ref_msh || !qry_msh || !qry_msh[0])) return fail(MHX_E_ARG, "dist: two sketch paths required");
-    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "dist: a reference sketch path and at least one query sketch path required");
-    for (int i = 0; i < n_qry; ++i)
-        if (!qry_msh[i]) return fail(MHX_E_ARG, "dist: query sketch path %d is null", i);
-    // The reference sketch file (9.6 MB at AuriClass's defaults: 24 x 50 000 hashes) is read ONCE, into a pinned block,
-    // parsed where it is (64-bit hash lists stay views into the image), checked for order on a few threads and copied
-    // row by row from the pinned image into the device staging area: one pass over the bytes on the host instead of
-    // five (file buffer, segment copies, hash vectors, padded matrix, pageable H2D staging): 5.6 -> 2 ms per call.
-    SketchSet R;
-    std::vector<SketchSet> Q((size_t)n_qry);
-    std::vector<uint8_t> ref_heap;
-    static const bool timing = getenv("MHX_DIST_TIMING") != nullptr; // phase times of a call on stderr
-    const auto t_start = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[mhx dist_files] %s at %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-    };
-    {
-        struct stat sb;
-        const int fd = open(ref_msh, O_RDONLY);
-        if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { if (fd >= 0) close(fd); return fail(MHX_E_IO, "cannot open sketch %s", ref_msh); }
-        const size_t len = (size_t)sb.st_size;
-        uint8_t *img = nullptr;
-        if (len >= (1u << 20) && len <= (256u << 20)) { // a pinned block of its own, kept between calls (larger files, or MHX_DIST_PAGEABLE=1: the heap)
-            if (g.dist_img.cap() < len && !getenv("MHX_DIST_PAGEABLE") &&
-                g.dist_img.grow((len + len / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1)) != hipSuccess)
-                (void)hipGetLastError();
-            if (g.dist_img.cap() >= len) img = g.dist_img;
-        }
-        if (!img) { ref_heap.resize(len); img = ref_heap.data(); }
-        const bool ok = len == 0 || parallel_pread(fd, img, 0, len, len >= (4u << 20) ? std::min(8, ingest_thread_budget()) : 1);
-        close(fd);
-        if (!ok) return fail(MHX_E_IO, "cannot read %s", ref_msh);
-        lap("reference file read");
-        rc = msh_parse_image(img, len, ref_msh, R, true);
+    return guarded("mhx_sketch_files_individual", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
         if (rc) return rc;
-        lap("parsed");
-        // the distance kernels merge ascending duplicate-free lists (what mash writes); anything else is a damaged file
-        std::vector<int> bad(R.refs.size(), 0);
-        {
-            JoinedThreads th;
-            const size_t nthreads = len >= (4u << 20) ? (size_t)std::min(8, ingest_thread_budget()) : 1;
-            for (size_t t = 0; t < nthreads; ++t) {
-                auto part = [&, t]() {
-                    for (size_t i = t; i < R.refs.size(); i += nthreads)
-                        if (R.refs[i].view && !check_ascending(R.refs[i].view, R.refs[i].view_n)) bad[i] = 1;
-                };
-                if (t + 1 == nthreads || !th.spawn(part)) part();
+        if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
+        for (int i = 0; i < n_paths; ++i)
+            if (!paths[i]) return fail(MHX_E_ARG, "sketch: input path %d is null", i);
+        if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+        if (s == 0) return fail(MHX_E_ARG, "sketch: sketch size 0");
+        SketchSet set;
+        set.kmer_size = (uint32_t)k;
+        set.sketch_size = s;
+        std::string err;
+        std::vector<uint8_t> raw;
+        for (int i = 0; i < n_paths; ++i) {
+            err += std::string("Sketching ") + paths[i] + "...\n";
+            rc = read_all_maybe_gz(paths[i], raw);
+            if (rc) return rc;
+            uint64_t added = 0;
+            bool done = false;
+            if (!getenv("MHX_HOST_FASTA") && fasta_for_device(raw.data(), raw.size())) { // plain FASTA: parsed on the device
+                rc = ensure_fasta_buffers(raw.size());
+                if (rc) return rc;
+                std::vector<uint64_t> off;
+                uint64_t total = 0;
+                rc = fasta_stream_on_device(raw.data(), raw.size(), 0, false, off, total);
+                if (rc < 0) return rc;
+                if (rc == MHX_OK) {
+                    off.push_back(total);
+                    std::vector<std::string> names, comments;
+                    fasta_headers(raw.data(), raw.size(), names, comments);
+                    rc = sketch_records(g.fasta.d_out, nullptr, total, off, 1, names, comments, k, s, set, &added);
+                    if (rc) return rc;
+                    done = true;
+                }
+            }
+            if (!done) { // FASTQ, a file that does not start with '>', ...: the host record parser
+                RecordList rec;
+                rc = parse_fastx_records(raw.data(), raw.size(), rec);
+                if (rc) return rc;
+                if (rec.off.empty()) rec.off.push_back(0);
+                rc = sketch_records(nullptr, rec.seq.data(), rec.seq.size(), rec.off, 0, rec.name, rec.comment, k, s, set, &added);
+                if (rc) return rc;
+            }
+            if (added == 0) {
+                err += std::string("ERROR: Did not find fasta records in \"") + paths[i] + "\".\n";
+                put_text(err, stderr_buf, stderr_cap, stderr_need);
+                return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", paths[i]);
             }
         }
-        for (size_t i = 0; i < bad.size(); ++i)
-            if (bad[i]) return fail(MHX_E_FORMAT, "%s: hash list of reference %zu is not ascending", ref_msh, i);
-        lap("order checked");
-    }
-    uint64_t nq_all = 0;
-    for (int i = 0; i < n_qry; ++i) {
-        rc = msh_read_file(qry_msh[i], Q[i]);
+        err += std::string("Writing to ") + out_msh + "...\n";
+        rc = msh_write_file(out_msh, set);
         if (rc) return rc;
-        if (R.kmer_size != Q[i].kmer_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", Q[i].kmer_size, R.kmer_size);
-        if (R.hash_seed != Q[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
-        if (Q[i].sketch_size != Q[0].sketch_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", qry_msh[0], qry_msh[i],
-                        Q[0].sketch_size, Q[i].sketch_size);
-        nq_all += Q[i].refs.size();
-    }
-    lap("query read");
-    const int k = (int)R.kmer_size;
-    const uint32_t s = R.sketch_size < Q[0].sketch_size ? R.sketch_size : Q[0].sketch_size;
-    const uint32_t nr = (uint32_t)R.refs.size();
-    if (nq_all * (nr ? nr : 1) > 0x7FFFFFFFull) return fail(MHX_E_ARG, "too many pairs for one call");
-    const uint32_t nq = (uint32_t)nq_all;
-    std::string text;
-    if (nr && nq) {
-        std::vector<const RefSketch *> qs;
-        qs.reserve(nq);
-        for (const SketchSet &set : Q)
-            for (const RefSketch &q : set.refs) qs.push_back(&q);
-        std::vector<const uint64_t *> rrows(nr), qrows(nq);
-        std::vector<uint32_t> rl(nr), ql(nq);
-        for (uint32_t i = 0; i < nr; ++i) { rrows[i] = R.refs[i].hash_data(); rl[i] = (uint32_t)R.refs[i].hash_count(); }
-        for (uint32_t i = 0; i < nq; ++i) { qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count(); }
-        std::vector<uint32_t> common((size_t)nq * nr), denom((size_t)nq * nr);
-        std::vector<double> dist((size_t)nq * nr);
-        rc = dist_batch_rows(qrows.data(), ql.data(), nq, rrows.data(), rl.data(), nr, k, s, common.data(), denom.data(), dist.data());
-        if (rc) return rc;
-        lap("distances back");
-        for (uint32_t qi = 0; qi < nq; ++qi)
-            for (uint32_t ri = 0; ri < nr; ++ri) {
-                const size_t p = (size_t)qi * nr + ri;
-                const double pv = mhx_p_value(common[p], R.refs[ri].length, qs[qi]->length, k, denom[p]);
-                text += R.refs[ri].name + "\t" + qs[qi]->name + "\t" + fmt_g(dist[p]) + "\t" + fmt_g(pv) + "\t" +
-                        std::to_string(common[p]) + "/" + std::to_string(denom[p]) + "\n";
-            }
-        lap("text written");
-    }
-    return put_text(text, stdout_buf, cap, need);
+        if (n_refs_out) *n_refs_out = set.refs.size();
+        return put_text(err, stderr_buf, stderr_cap, stderr_need);
+    });
 }
 
 // `mash screen REF.msh reads...`: the reference sketches become a screen table on the device (mhx_screen.h), the read set
@@ -1646,13 +1410,7 @@ static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, 
 extern "C" int mhx_screen_files_opts(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
                                      size_t cap, size_t *need, double *set_size_out)
 {
-    try {
-        return mhx_screen_files_impl(ref_msh, paths, n_paths, opts, stdout_buf, cap, need, set_size_out);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_screen_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_screen_files: %s", e.what());
-    }
+    return guarded("mhx_screen_files", [&] { return mhx_screen_files_impl(ref_msh, paths, n_paths, opts, stdout_buf, cap, need, set_size_out); });
 }
 
 extern "C" int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
@@ -1667,453 +1425,146 @@ extern "C" int mhx_msh_write(const char *path, int k, uint32_t s, uint32_t n_ref
 {
     clear_error();
     if (!path || (n_refs && (!names || !comments || !lengths || !hashes || !n_hashes))) return fail(MHX_E_ARG, "null argument");
-    try {
-    SketchSet set;
-    set.kmer_size = (uint32_t)k;
-    set.sketch_size = s;
-    set.refs.resize(n_refs);
-    for (uint32_t i = 0; i < n_refs; ++i) {
-        set.refs[i].name = names[i] ? names[i] : "";
-        set.refs[i].comment = comments[i] ? comments[i] : "";
-        set.refs[i].length = lengths[i];
-        if (n_hashes[i]) set.refs[i].hashes.assign(hashes[i], hashes[i] + n_hashes[i]);
-    }
-    return msh_write_file(path, set);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_msh_write: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_msh_write: %s", e.what());
-    }
+    return guarded("mhx_msh_write", [&] {
+        SketchSet set;
+        set.kmer_size = (uint32_t)k;
+        set.sketch_size = s;
+        set.refs.resize(n_refs);
+        for (uint32_t i = 0; i < n_refs; ++i) {
+            set.refs[i].name = names[i] ? names[i] : "";
+            set.refs[i].comment = comments[i] ? comments[i] : "";
+            set.refs[i].length = lengths[i];
+            if (n_hashes[i]) set.refs[i].hashes.assign(hashes[i], hashes[i] + n_hashes[i]);
+        }
+        return msh_write_file(path, set);
+    });
 }
 
 extern "C" int mhx_sketch_files(const char *const *paths, int n_paths, int k, uint32_t s, int reads, uint32_t min_mult,
                                 const char *out_msh, char *stderr_buf, size_t stderr_cap, size_t *stderr_need,
                                 double *est_genome_size)
 {
-    try {
-        return mhx_sketch_files_impl(paths, n_paths, k, s, reads, min_mult, out_msh, stderr_buf, stderr_cap, stderr_need, est_genome_size);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_sketch_files: %s", e.what());
-    }
+    return guarded("mhx_sketch_files", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
+        if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+        SketchSet set;
+        set.kmer_size = (uint32_t)k;
+        set.sketch_size = s;
+        std::string err;
+        std::vector<Loaded> loaded(n_paths);
+        auto no_records = [&](const char *p) {
+            err += std::string("ERROR: Did not find fasta records in \"") + p + "\".\n";
+            put_text(err, stderr_buf, stderr_cap, stderr_need);
+            return fail(MHX_E_NO_RECORDS, "ERROR: Did not find fasta records in \"%s\".", p);
+        };
+        if (reads) {
+            RefSketch ref;
+            uint64_t kmers = 0, count = 0;
+            std::string fname, fcomment;
+            rc = sketch_read_set(paths, n_paths, k, s, min_mult ? min_mult : 1, nullptr, ref, kmers, count, fname, fcomment);
+            if (rc) return rc;
+            // mash stops when no record holds k bases.  (`kmers` is not that question: the device counts every window of k BYTES
+            // inside one line, and a CRLF file of reads one base shorter than k has such windows -- 31 bases and the '\r' --
+            // although none of them is a k-mer.)
+            if (count == 0) return no_records(paths[0]);
+            double set_size = 0.0, mult = 0.0;
+            if (!ref.hashes.empty()) {
+                set_size = pow(2.0, k > 16 ? 64.0 : 32.0) * (double)ref.hashes.size() / (double)ref.hashes.back();
+                uint64_t sum = 0;
+                for (uint32_t c : ref.counts) sum += c;
+                mult = (double)sum / (double)ref.hashes.size();
+            }
+            ref.name = paths[0];
+            ref.comment = make_comment(fname, fcomment, count);
+            ref.length = (uint64_t)set_size;
+            ref.counts.clear(); // mash stores counts only with -M
+            set.refs.push_back(std::move(ref));
+            err += "Estimated genome size: " + fmt_g(set_size) + "\n";
+            err += "Estimated coverage:    " + fmt_g(mult) + "\n";
+            if (est_genome_size) *est_genome_size = set_size;
+        } else {
+            // one reference per file; file i + 1 is read (and inflated) on a helper thread while file i is on the GPU
+            const bool pinned_ok = !getenv("MHX_HOST_FASTA") && ensure_pinned_ring() == MHX_OK;
+            if (!pinned_ok) { clear_error(); (void)hipGetLastError(); }
+            std::vector<FastaInput> inputs(n_paths);
+            // the device buffers are sized for the largest uncompressed input up front, so that a loader can copy file i + 1
+            // into its raw buffer while file i is still on the GPU
+            uint64_t largest = 0;
+            for (int i = 0; i < n_paths; ++i) {
+                struct stat sb;
+                if (stat(paths[i], &sb) == 0 && S_ISREG(sb.st_mode) && !is_gzip_file(paths[i])) largest = std::max<uint64_t>(largest, (uint64_t)sb.st_size);
+            }
+            bool stream_ok = pinned_ok && largest > 0 && largest + 64 <= kBulkBlock && ensure_fasta_buffers(largest) == MHX_OK;
+            if (!stream_ok) clear_error();
+            auto raw_of = [&](int i) { return stream_ok ? g.fasta.d_raw[i & 1] : (uint8_t *)nullptr; };
+            std::thread loader;
+            struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{loader};
+            auto start_loader = [&](int j) { // file j on its way while file j - 1 is on the GPU; without a thread to be had: loaded here and now
+                try {
+                    loader = std::thread(load_fasta_input, paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), (hipEvent_t)g.fasta.raw_ready[j & 1]);
+                } catch (const std::system_error &) {
+                    load_fasta_input(paths[j], j % Engine::kPinnedSlots, pinned_ok, &inputs[j], raw_of(j), g.fasta.d_raw[j & 1].cap(), g.fasta.raw_ready[j & 1]);
+                }
+            };
+            load_fasta_input(paths[0], 0, pinned_ok, &inputs[0], raw_of(0), g.fasta.d_raw[0].cap(), g.fasta.raw_ready[0]);
+            for (int i = 0; i < n_paths; ++i) {
+                if (loader.joinable()) loader.join();
+                FastaInput &in = inputs[i];
+                err += std::string("Sketching ") + paths[i] + "...\n";
+                if (in.rc) return fail(in.rc, "%s", in.error.c_str());
+                // The FASTA device buffers regrow only while no loader holds one of them: file i's are sized here, before file
+                // i + 1's loader is handed its raw buffer.  Bytes that went to a buffer that has since been regrown are copied
+                // again from the host.
+                const bool device_parser = !getenv("MHX_HOST_FASTA") && fasta_for_device(in.data, in.n);
+                if (device_parser) {
+                    const size_t raw_cap = g.fasta.d_raw[i & 1].cap();
+                    rc = ensure_fasta_buffers(in.n);
+                    if (rc) return rc;
+                    if (g.fasta.d_raw[i & 1].cap() != raw_cap) in.on_device = false;
+                }
+                if (i + 1 < n_paths) start_loader(i + 1);
+                if (device_parser) { // plain FASTA: parsed on the device
+                    RefSketch ref;
+                    FastaInfo info;
+                    rc = sketch_fasta_on_device(in.data, in.n, i, in.on_device, k, s, ref.hashes, info);
+                    if (rc < 0) return rc;
+                    if (rc == MHX_OK) {
+                        if (info.records == 0) return no_records(paths[i]);
+                        ref.name = paths[i];
+                        ref.comment = make_comment(info.first_name, info.first_comment, info.records);
+                        ref.length = info.total_length;
+                        set.refs.push_back(std::move(ref));
+                        in = FastaInput();
+                        continue;
+                    }
+                }
+                if (in.slot >= 0) in.owned.assign(in.data, in.data + in.n); // the record parser path keeps the bytes beyond this slot's turn
+                loaded[i].raw.swap(in.owned);
+                in = FastaInput();
+                rc = parse_fastx(loaded[i].raw.data(), loaded[i].raw.size(), k, loaded[i].rec);
+                if (rc) return rc;
+                if (loaded[i].rec.records == 0) return no_records(paths[i]);
+                RefSketch ref;
+                std::vector<Loaded *> in2{&loaded[i]};
+                rc = sketch_reference(in2, k, s, 1, false, ref.hashes, ref.counts, nullptr);
+                if (rc) return rc;
+                ref.counts.clear();
+                ref.name = paths[i];
+                ref.comment = make_comment(loaded[i].rec.first_name, loaded[i].rec.first_comment, loaded[i].rec.records);
+                ref.length = loaded[i].rec.total_length;
+                set.refs.push_back(std::move(ref));
+                loaded[i] = Loaded();
+            }
+            if (est_genome_size) *est_genome_size = 0.0;
+        }
+        err += std::string("Writing to ") + out_msh + "...\n";
+        rc = msh_write_file(out_msh, set);
+        if (rc) return rc;
+        return put_text(err, stderr_buf, stderr_cap, stderr_need);
+    });
 }
 
 extern "C" int mhx_last_fastq_route(void) { return g.last_fastq_route; }
-
-static int dist_files_guarded(const char *what, const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
-{
-    try {
-        return mhx_dist_files_impl(ref_msh, qry_msh, n_qry, stdout_buf, cap, need);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "%s: out of host memory", what);
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "%s: %s", what, e.what());
-    }
-}
-
-extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
-{
-    return dist_files_guarded("mhx_dist_files", ref_msh, &qry_msh, 1, stdout_buf, cap, need);
-}
-
-extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
-{
-    return dist_files_guarded("mhx_dist_files_multi", ref_msh, qry_msh, n_qry, stdout_buf, cap, need);
-}
-
-// `mash triangle a.msh [b.msh ...]`: the references of all files form one set (argument order, then file order), every
-// pair j < i of it is compared on the device (mhx_dist_triangle, or mhx_dist_triangle_edges when a distance bound can drop
-// pairs there), and the text is Mash's CommandTriangle: the lower-triangle matrix, or the edge list with its two filters.
-// The references of all files as ONE set (argument order, then file order), what `mash triangle` and the clustering start
-// from: every file read and checked, k / seed / sketch size the same in all, at most 65 536 references, and their hash
-// lists as the matrix mhx_dist_triangle takes.  `what` names the caller in the messages.
-struct SetOfFiles {
-    std::vector<SketchSet> F;
-    std::vector<const RefSketch *> refs;
-    std::vector<uint64_t> rows;
-    std::vector<uint32_t> len;
-    uint32_t stride = 16;
-};
-static int read_set_of_files(const char *what, const char *const *paths, int n_paths, SetOfFiles &S)
-{
-    if (!paths || n_paths < 1) return fail(MHX_E_ARG, "%s: at least one sketch path required", what);
-    for (int i = 0; i < n_paths; ++i)
-        if (!paths[i]) return fail(MHX_E_ARG, "%s: sketch path %d is null", what, i);
-    std::vector<SketchSet> &F = S.F;
-    F.resize((size_t)n_paths);
-    for (int i = 0; i < n_paths; ++i) {
-        const int rc = msh_read_file(paths[i], F[i]); // (checks that every hash list ascends: MHX_E_FORMAT)
-        if (rc) return rc;
-        if (F[0].kmer_size != F[i].kmer_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", F[i].kmer_size, F[0].kmer_size);
-        if (F[0].hash_seed != F[i].hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
-        if (F[i].sketch_size != F[0].sketch_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", paths[0], paths[i],
-                        F[0].sketch_size, F[i].sketch_size);
-        for (const RefSketch &r : F[i].refs) S.refs.push_back(&r);
-    }
-    if (S.refs.size() > 65536) return fail(MHX_E_ARG, "%s: too many references for one call (%zu)", what, S.refs.size());
-    const uint32_t n = (uint32_t)S.refs.size();
-    for (const RefSketch *r : S.refs) S.stride = std::max<uint32_t>(S.stride, (uint32_t)r->hash_count());
-    S.stride = (S.stride + 15u) & ~15u; // rows of whole 128-byte lines on the device
-    S.rows.assign((size_t)n * S.stride, 0);
-    S.len.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        S.len[i] = (uint32_t)S.refs[i]->hash_count();
-        if (S.len[i]) memcpy(&S.rows[(size_t)i * S.stride], S.refs[i]->hash_data(), (size_t)S.len[i] * 8);
-    }
-    return MHX_OK;
-}
-
-static int mhx_triangle_files_impl(const char *const *paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap, size_t *need)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!paths || n_paths < 1) return fail(MHX_E_ARG, "triangle: at least one sketch path required");
-    for (int i = 0; i < n_paths; ++i)
-        if (!paths[i]) return fail(MHX_E_ARG, "triangle: sketch path %d is null", i);
-    mhx_triangle_opts o{(uint32_t)sizeof(mhx_triangle_opts), 0, 0, 1.0, 1.0};
-    if (opts) {
-        if (opts->struct_size != sizeof(mhx_triangle_opts)) return fail(MHX_E_ARG, "triangle: opts->struct_size is not sizeof(mhx_triangle_opts)");
-        o = *opts;
-    }
-    if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "triangle: max_dist / max_p_value is not a number");
-    const bool edge = o.edge != 0 || o.max_dist < 1.0 || o.max_p_value < 1.0; // -d and -v imply -E
-    SetOfFiles S;
-    rc = read_set_of_files("triangle", paths, n_paths, S);
-    if (rc) return rc;
-    const std::vector<SketchSet> &F = S.F;
-    const std::vector<const RefSketch *> &refs = S.refs;
-    const std::vector<uint64_t> &rows = S.rows;
-    const std::vector<uint32_t> &len = S.len;
-    const uint32_t n = (uint32_t)refs.size(), s = F[0].sketch_size, stride = S.stride;
-    const int k = (int)F[0].kmer_size;
-    const uint64_t pairs = (uint64_t)n * (n ? n - 1 : 0) / 2;
-    std::string text;
-    if (!edge) {
-        std::vector<uint32_t> common(pairs), denom(pairs);
-        std::vector<double> dist(pairs);
-        rc = mhx_dist_triangle(rows.data(), len.data(), n, stride, k, s ? s : 1, common.data(), denom.data(), dist.data(), 0);
-        if (rc) return rc;
-        text = "\t" + std::to_string(n) + "\n";
-        for (uint32_t i = 0; i < n; ++i) {
-            text += o.comment ? refs[i]->comment : refs[i]->name;
-            for (uint32_t j = 0; j < i; ++j) text += "\t" + fmt_g(dist[(size_t)i * (i - 1) / 2 + j]);
-            text += "\n";
-        }
-        return put_text(text, stdout_buf, cap, need);
-    }
-    std::vector<uint32_t> ei, ej, common, denom;
-    std::vector<double> dist;
-    uint64_t found = 0, room = o.max_dist >= 1.0 ? pairs : std::min<uint64_t>(pairs, 1u << 16);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        ei.resize(room); ej.resize(room); common.resize(room); denom.resize(room); dist.resize(room);
-        rc = mhx_dist_triangle_edges(rows.data(), len.data(), n, stride, k, s ? s : 1, o.max_dist, ei.data(), ej.data(), common.data(), denom.data(),
-                                     dist.data(), room, &found, 0);
-        if (rc != MHX_E_CAPACITY) break;
-        room = found;
-    }
-    if (rc) return rc;
-    clear_error();
-    for (uint64_t e = 0; e < found; ++e) {
-        const RefSketch &a = *refs[ei[e]], &b = *refs[ej[e]];
-        const double pv = mhx_p_value(common[e], a.length, b.length, k, denom[e]);
-        if (!(pv <= o.max_p_value)) continue;
-        text += a.name + "\t" + b.name + "\t" + fmt_g(dist[e]) + "\t" + fmt_g(pv) + "\t" + std::to_string(common[e]) + "/" + std::to_string(denom[e]) + "\n";
-    }
-    return put_text(text, stdout_buf, cap, need);
-}
-
-extern "C" int mhx_triangle_files(const char *const *msh_paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap,
-                                  size_t *need)
-{
-    try {
-        return mhx_triangle_files_impl(msh_paths, n_paths, opts, stdout_buf, cap, need);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_triangle_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_triangle_files: %s", e.what());
-    }
-}
-
-// Dereplication at file level: the references of all files form one set (as for the triangle), mhx_dist_cluster labels it on
-// the device, and the host numbers the clusters by their lowest member, picks a representative per cluster in one pass
-// and prints a row per reference; the representatives, unchanged, are written as a sketch file of their own on request.
-static int mhx_cluster_files_impl(const char *const *paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
-                                  size_t cap, size_t *need)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    mhx_cluster_opts o{(uint32_t)sizeof(mhx_cluster_opts), 0, 0, 1.0};
-    if (opts) {
-        if (opts->struct_size != sizeof(mhx_cluster_opts)) return fail(MHX_E_ARG, "cluster: opts->struct_size is not sizeof(mhx_cluster_opts)");
-        o = *opts;
-    }
-    if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "cluster: max_dist is not a number");
-    if (o.rep != 0 && o.rep != 1) return fail(MHX_E_ARG, "cluster: rep must be 0 (first) or 1 (longest)");
-    SetOfFiles S;
-    rc = read_set_of_files("cluster", paths, n_paths, S);
-    if (rc) return rc;
-    const std::vector<const RefSketch *> &refs = S.refs;
-    const uint32_t n = (uint32_t)refs.size(), s = S.F[0].sketch_size;
-    const int k = (int)S.F[0].kmer_size;
-    if (out_msh)
-        for (const RefSketch *r : refs)
-            if (!r->counts.empty())
-                return fail(MHX_E_ARG, "cluster: %s carries multiplicity counts, which the output sketch file cannot store", r->name.c_str());
-    std::vector<uint32_t> label(n), degree(n);
-    uint32_t n_clusters = 0;
-    uint64_t n_edges = 0;
-    rc = mhx_dist_cluster(S.rows.data(), S.len.data(), n, S.stride, k, s ? s : 1, o.max_dist, label.data(), degree.data(), &n_clusters, &n_edges, 0);
-    if (rc) return rc;
-    // label[i] is the lowest member of i's cluster: a cluster's number, size and representative by its label, O(n)
-    std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t l = label[i];
-        if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "cluster: label %u of reference %u is not a cluster's lowest member", l, i);
-        if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
-        ++size[l];
-        if (o.rep == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
-    }
-    if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "cluster: %zu labels but %u clusters counted", order.size(), n_clusters);
-    auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
-    std::vector<std::vector<uint32_t>> members(order.size());
-    for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
-    std::string text;
-    for (size_t ci = 0; ci < order.size(); ++ci) {
-        const uint32_t l = order[ci];
-        for (uint32_t i : members[ci])
-            text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i) + "\t" + std::to_string(degree[i]) + "\n";
-    }
-    if (out_msh) {
-        const uint32_t m = (uint32_t)order.size();
-        std::vector<const char *> names(m), comments(m);
-        std::vector<uint64_t> lengths(m);
-        std::vector<const uint64_t *> hashes(m);
-        std::vector<uint32_t> n_hashes(m);
-        for (uint32_t ci = 0; ci < m; ++ci) {
-            const RefSketch &r = *refs[rep[order[ci]]];
-            names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
-            hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
-        }
-        rc = mhx_msh_write(out_msh, k, s, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
-        if (rc) return rc;
-    }
-    return put_text(text, stdout_buf, cap, need);
-}
-
-extern "C" int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
-                                 size_t cap, size_t *need)
-{
-    try {
-        return mhx_cluster_files_impl(msh_paths, n_paths, opts, out_msh, stdout_buf, cap, need);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_cluster_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_cluster_files: %s", e.what());
-    }
-}
-
-// The single-linkage tree at file level: the references of all files form one set (as for the triangle), mhx_dist_mst gives
-// its n - 1 merges in merge order, and the host prints them as a table or as a Newick dendrogram.
-// Newick: a name is single-quoted when it holds any of ( ) [ ] ' : ; , or a blank, an inner quote doubled
-static std::string newick_name(const std::string &name)
-{
-    bool quote = false;
-    for (const char ch : name) quote = quote || strchr("()[]':;,", ch) != nullptr || isspace((unsigned char)ch);
-    if (!quote) return name;
-    std::string out = "'";
-    for (const char ch : name) { out += ch; if (ch == '\'') out += ch; }
-    return out + "'";
-}
-
-static int mhx_tree_files_impl(const char *const *paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    mhx_tree_opts o{(uint32_t)sizeof(mhx_tree_opts), 0, 0};
-    if (opts) {
-        if (opts->struct_size != sizeof(mhx_tree_opts)) return fail(MHX_E_ARG, "tree: opts->struct_size is not sizeof(mhx_tree_opts)");
-        o = *opts;
-    }
-    SetOfFiles S;
-    rc = read_set_of_files("tree", paths, n_paths, S);
-    if (rc) return rc;
-    const std::vector<const RefSketch *> &refs = S.refs;
-    const uint32_t n = (uint32_t)refs.size(), s = S.F[0].sketch_size;
-    const int k = (int)S.F[0].kmer_size;
-    const uint32_t m = n ? n - 1 : 0;
-    std::vector<uint32_t> ei(m), ej(m), common(m), denom(m);
-    std::vector<double> dist(m);
-    rc = mhx_dist_mst(S.rows.data(), S.len.data(), n, S.stride, k, s ? s : 1, ei.data(), ej.data(), common.data(), denom.data(), dist.data(), 0);
-    if (rc) return rc;
-    auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
-    std::string text;
-    if (!o.newick) { // one row per merge: the triangle's edge-list row and the clusters left after it
-        for (uint32_t e = 0; e < m; ++e) {
-            const RefSketch &a = *refs[ei[e]], &b = *refs[ej[e]];
-            const double pv = mhx_p_value(common[e], a.length, b.length, k, denom[e]);
-            text += shown(ei[e]) + "\t" + shown(ej[e]) + "\t" + fmt_g(dist[e]) + "\t" + fmt_g(pv) + "\t" + std::to_string(common[e]) + "/" +
-                    std::to_string(denom[e]) + "\t" + std::to_string(n - 1 - e) + "\n";
-        }
-        return put_text(text, stdout_buf, cap, need);
-    }
-    if (n == 0) return put_text(text, stdout_buf, cap, need);
-    // nodes 0 .. n - 1 are the leaves, node n + e the merge e; a node's height is its merge distance (leaves: 0), a branch
-    // is as long as the parent is higher, never negative; the child whose lowest index is lower comes first
-    std::vector<uint32_t> top(n), left(m), right(m), lowest((size_t)n + m), find(n);
-    std::vector<double> height((size_t)n + m, 0.0);
-    for (uint32_t i = 0; i < n; ++i) { top[i] = i; lowest[i] = i; find[i] = i; }
-    auto root = [&](uint32_t x) { while (find[x] != x) { find[x] = find[find[x]]; x = find[x]; } return x; };
-    for (uint32_t e = 0; e < m; ++e) {
-        const uint32_t ra = root(ei[e]), rb = root(ej[e]);
-        if (ra == rb) return fail(MHX_E_INTERNAL, "tree: merge %u joins one component with itself", e);
-        uint32_t a = top[ra], b = top[rb];
-        if (lowest[b] < lowest[a]) std::swap(a, b);
-        left[e] = a; right[e] = b;
-        lowest[n + e] = lowest[a];
-        height[n + e] = dist[e];
-        find[rb] = ra;
-        top[ra] = n + e;
-    }
-    // written without recursion: a chain of 65 535 merges is a tree of that depth
-    struct Item { uint32_t node; int stage; };
-    std::vector<Item> todo{{m ? n + m - 1 : 0u, 0}};
-    auto branch = [&](uint32_t child, uint32_t parent) { const double d = height[parent] - height[child]; return ":" + fmt_g(d > 0.0 ? d : 0.0); };
-    while (!todo.empty()) {
-        const Item it = todo.back();
-        todo.pop_back();
-        if (it.node < n) { text += newick_name(shown(it.node)); continue; }
-        const uint32_t e = it.node - n;
-        if (it.stage == 0) { text += "("; todo.push_back({it.node, 1}); todo.push_back({left[e], 0}); }
-        else if (it.stage == 1) { text += branch(left[e], it.node) + ","; todo.push_back({it.node, 2}); todo.push_back({right[e], 0}); }
-        else text += branch(right[e], it.node) + ")";
-    }
-    text += ";\n";
-    return put_text(text, stdout_buf, cap, need);
-}
-
-extern "C" int mhx_tree_files(const char *const *msh_paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
-{
-    try {
-        return mhx_tree_files_impl(msh_paths, n_paths, opts, stdout_buf, cap, need);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_tree_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_tree_files: %s", e.what());
-    }
-}
-
-// Reference-set search at file level: the reference file is read, checked and staged on the device ONCE; the query files
-// are read one after the other and searched in batches of sketches (mhx_dist_search's host form against the resident
-// references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.
-static int mhx_search_files_impl(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf,
-                                 size_t cap, size_t *need)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "search: a reference sketch path and at least one query sketch path required");
-    for (int i = 0; i < n_qry; ++i)
-        if (!qry_msh[i]) return fail(MHX_E_ARG, "search: query sketch path %d is null", i);
-    mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), 5, 1.0, 1.0};
-    if (opts) {
-        if (opts->struct_size != sizeof(mhx_search_opts)) return fail(MHX_E_ARG, "search: opts->struct_size is not sizeof(mhx_search_opts)");
-        o = *opts;
-    }
-    if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "search: top must be 1 .. 64");
-    if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "search: max_dist / max_p_value is not a number");
-    SketchSet R;
-    rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
-    if (rc) return rc;
-    const int k = (int)R.kmer_size;
-    const uint32_t nr = (uint32_t)R.refs.size();
-    DevArray<uint64_t> d_rows;
-    DevArray<uint32_t> d_len;
-    SearchRefs refs{nullptr, nullptr, nr, 0, 0};
-    uint32_t q_sketch_size = 0, s = 0;
-    std::string text;
-    constexpr size_t kBatch = 4096; // query sketches per device call
-    std::vector<SketchSet> held;    // the files of the current batch
-    std::vector<const RefSketch *> qs;
-    auto stage_refs = [&]() -> int { // once, behind the first query file: rows of whole 128-byte lines that hold any list of the call
-        for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
-        refs.stride = (std::max<uint32_t>(16, std::max(refs.longest, q_sketch_size)) + 15u) & ~15u;
-        if (nr == 0) return MHX_OK;
-        std::vector<uint64_t> rows((size_t)nr * refs.stride, 0);
-        std::vector<uint32_t> len(nr);
-        for (uint32_t i = 0; i < nr; ++i) {
-            len[i] = (uint32_t)R.refs[i].hash_count();
-            if (len[i]) memcpy(&rows[(size_t)i * refs.stride], R.refs[i].hash_data(), (size_t)len[i] * 8);
-            std::vector<uint64_t>().swap(R.refs[i].hashes); // names and lengths stay for the text
-        }
-        if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
-        if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return fail(MHX_E_HIP, "H2D copy of the reference set failed");
-        refs.rows = d_rows; refs.len = d_len;
-        return MHX_OK;
-    };
-    auto flush = [&]() -> int {
-        const uint32_t nq = (uint32_t)qs.size();
-        if (nq && nr) {
-            std::vector<const uint64_t *> qrows(nq);
-            std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq);
-            std::vector<double> hx((size_t)nq * o.top);
-            for (uint32_t i = 0; i < nq; ++i) {
-                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
-            }
-            const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data());
-            if (rc2) return rc2;
-            for (uint32_t qi = 0; qi < nq; ++qi)
-                for (uint32_t t = 0; t < nh[qi]; ++t) {
-                    const size_t p = (size_t)qi * o.top + t;
-                    const RefSketch &ref = R.refs[hr[p]];
-                    const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
-                    if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
-                    text += ref.name + "\t" + qs[qi]->name + "\t" + fmt_g(hx[p]) + "\t" + fmt_g(pv) + "\t" + std::to_string(hc[p]) + "/" + std::to_string(hd[p]) + "\n";
-                }
-        }
-        qs.clear();
-        held.clear();
-        return MHX_OK;
-    };
-    for (int i = 0; i < n_qry; ++i) {
-        held.emplace_back();
-        SketchSet &Q = held.back();
-        rc = msh_read_file(qry_msh[i], Q);
-        if (rc) return rc;
-        if (R.kmer_size != Q.kmer_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", Q.kmer_size, R.kmer_size);
-        if (R.hash_seed != Q.hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
-        if (i == 0) {
-            q_sketch_size = Q.sketch_size;
-            s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
-            rc = stage_refs();
-            if (rc) return rc;
-        } else if (Q.sketch_size != q_sketch_size)
-            return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", qry_msh[0], qry_msh[i],
-                        q_sketch_size, Q.sketch_size);
-        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-    }
-    rc = flush();
-    if (rc) return rc;
-    return put_text(text, stdout_buf, cap, need);
-}
-
-extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf, size_t cap,
-                                size_t *need)
-{
-    try {
-        return mhx_search_files_impl(ref_msh, qry_msh, n_qry, opts, stdout_buf, cap, need);
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_search_files: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_search_files: %s", e.what());
-    }
-}

@@ -1,0 +1,507 @@
+// mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
+// triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files), the single-linkage tree (mhx_tree_files) and the
+// reference-set search (mhx_search_files).  They read sketch files, call the device paths of the engine files and write
+// Mash's text; the ingest of sequence files is in mhx_files.cpp.
+#include <hip/hip_runtime.h>
+#include <ctype.h>
+#include <fcntl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "mhx_engine_internal.h"
+#include "mhx_internal.h"
+
+using namespace mhx;
+
+namespace {
+
+// The options of a command: `o` holds the defaults and takes the caller's struct if there is one.  Its size is its version.
+template <class O> int take_opts(const char *cmd, const O *opts, O &o)
+{
+    if (!opts) return MHX_OK;
+    if (opts->struct_size != sizeof(O)) return fail(MHX_E_ARG, "%s: opts->struct_size is not sizeof(mhx_%s_opts)", cmd, cmd);
+    o = *opts;
+    return MHX_OK;
+}
+
+// one row of `mash dist` / `mash triangle -E`; `more`: a further column behind it
+void pair_row(std::string &text, const std::string &a, const std::string &b, double dist, double p, uint32_t common, uint32_t denom,
+              const std::string &more = std::string())
+{
+    text += a + "\t" + b + "\t" + fmt_g(dist) + "\t" + fmt_g(p) + "\t" + std::to_string(common) + "/" + std::to_string(denom);
+    if (!more.empty()) text += "\t" + more;
+    text += "\n";
+}
+
+// One more sketch file `x` of a call: k-mer size and hash seed as in `base`, sketch size as in the first file of its kind,
+// in Mash's words.
+int check_same_kind(const SketchSet &base, const SketchSet &x, uint32_t first_size, const char *first_path, const char *x_path)
+{
+    if (base.kmer_size != x.kmer_size)
+        return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different k-mer sizes (%u and %u)", x.kmer_size, base.kmer_size);
+    if (base.hash_seed != x.hash_seed) return fail(MHX_E_MISMATCH, "ERROR: The query and reference sketches have different hash seeds");
+    if (x.sketch_size != first_size)
+        return fail(MHX_E_MISMATCH, "ERROR: The query sketches %s and %s have different sketch sizes (%u and %u)", first_path, x_path, first_size,
+                    x.sketch_size);
+    return MHX_OK;
+}
+
+// rows of whole 128-byte lines on the device that hold a list of `longest` hashes
+uint32_t row_stride(uint32_t longest) { return (std::max<uint32_t>(16, longest) + 15u) & ~15u; }
+
+// the hash lists as the matrix the device calls take: rows [n][stride], zero behind a list's end, and the lengths
+void pack_rows(const std::vector<const RefSketch *> &refs, uint32_t stride, std::vector<uint64_t> &rows, std::vector<uint32_t> &len)
+{
+    const uint32_t n = (uint32_t)refs.size();
+    rows.assign((size_t)n * stride, 0);
+    len.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        len[i] = (uint32_t)refs[i]->hash_count();
+        if (len[i]) memcpy(&rows[(size_t)i * stride], refs[i]->hash_data(), (size_t)len[i] * 8);
+    }
+}
+
+// `mash dist REF QUERY [QUERY ...]`: mhx_dist_files is the n_qry == 1 case.  The reference file is read, parsed, checked and
+// staged once per call, and the sketches of ALL query files go to the device together, so that a run of samples reaches
+// the all-vs-refs kernels in the shape they were made for (many queries x few references) instead of 1 x nr per sample.
+int dist_files(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
+{
+    clear_error();
+    int rc = require_engine();
+    if (rc) return rc;
+    if (n_qry == 1 && (!ref_msh || !qry_msh || !qry_msh[0])) return fail(MHX_E_ARG, "dist: two sketch paths required");
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "dist: a reference sketch path and at least one query sketch path required");
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "dist: query sketch path %d is null", i);
+    // The reference sketch file (9.6 MB at AuriClass's defaults: 24 x 50 000 hashes) is read ONCE, into a pinned block,
+    // parsed where it is (64-bit hash lists stay views into the image), checked for order on a few threads and copied
+    // row by row from the pinned image into the device staging area: one pass over the bytes on the host instead of
+    // five (file buffer, segment copies, hash vectors, padded matrix, pageable H2D staging): 5.6 -> 2 ms per call.
+    SketchSet R;
+    std::vector<SketchSet> Q((size_t)n_qry);
+    std::vector<uint8_t> ref_heap;
+    static const bool timing = getenv("MHX_DIST_TIMING") != nullptr; // phase times of a call on stderr
+    const auto t_start = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (timing) fprintf(stderr, "[mhx dist_files] %s at %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+    };
+    {
+        struct stat sb;
+        const int fd = open(ref_msh, O_RDONLY);
+        if (fd < 0 || fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { if (fd >= 0) close(fd); return fail(MHX_E_IO, "cannot open sketch %s", ref_msh); }
+        const size_t len = (size_t)sb.st_size;
+        uint8_t *img = nullptr;
+        if (len >= (1u << 20) && len <= (256u << 20)) { // a pinned block of its own, kept between calls (larger files, or MHX_DIST_PAGEABLE=1: the heap)
+            if (g.dist_img.cap() < len && !getenv("MHX_DIST_PAGEABLE") &&
+                g.dist_img.grow((len + len / 4 + (1u << 20)) & ~(size_t)((1u << 20) - 1)) != hipSuccess)
+                (void)hipGetLastError();
+            if (g.dist_img.cap() >= len) img = g.dist_img;
+        }
+        if (!img) { ref_heap.resize(len); img = ref_heap.data(); }
+        const bool ok = len == 0 || parallel_pread(fd, img, 0, len, len >= (4u << 20) ? std::min(8, ingest_thread_budget()) : 1);
+        close(fd);
+        if (!ok) return fail(MHX_E_IO, "cannot read %s", ref_msh);
+        lap("reference file read");
+        rc = msh_parse_image(img, len, ref_msh, R, true);
+        if (rc) return rc;
+        lap("parsed");
+        // the distance kernels merge ascending duplicate-free lists (what mash writes); anything else is a damaged file
+        std::vector<int> bad(R.refs.size(), 0);
+        {
+            JoinedThreads th;
+            const size_t nthreads = len >= (4u << 20) ? (size_t)std::min(8, ingest_thread_budget()) : 1;
+            for (size_t t = 0; t < nthreads; ++t) {
+                auto part = [&, t]() {
+                    for (size_t i = t; i < R.refs.size(); i += nthreads)
+                        if (R.refs[i].view && !check_ascending(R.refs[i].view, R.refs[i].view_n)) bad[i] = 1;
+                };
+                if (t + 1 == nthreads || !th.spawn(part)) part();
+            }
+        }
+        for (size_t i = 0; i < bad.size(); ++i)
+            if (bad[i]) return fail(MHX_E_FORMAT, "%s: hash list of reference %zu is not ascending", ref_msh, i);
+        lap("order checked");
+    }
+    uint64_t nq_all = 0;
+    for (int i = 0; i < n_qry; ++i) {
+        rc = msh_read_file(qry_msh[i], Q[i]);
+        if (rc == MHX_OK) rc = check_same_kind(R, Q[i], Q[0].sketch_size, qry_msh[0], qry_msh[i]);
+        if (rc) return rc;
+        nq_all += Q[i].refs.size();
+    }
+    lap("query read");
+    const int k = (int)R.kmer_size;
+    const uint32_t s = R.sketch_size < Q[0].sketch_size ? R.sketch_size : Q[0].sketch_size;
+    const uint32_t nr = (uint32_t)R.refs.size();
+    if (nq_all * (nr ? nr : 1) > 0x7FFFFFFFull) return fail(MHX_E_ARG, "too many pairs for one call");
+    const uint32_t nq = (uint32_t)nq_all;
+    std::string text;
+    if (nr && nq) {
+        std::vector<const RefSketch *> qs;
+        qs.reserve(nq);
+        for (const SketchSet &set : Q)
+            for (const RefSketch &q : set.refs) qs.push_back(&q);
+        std::vector<const uint64_t *> rrows(nr), qrows(nq);
+        std::vector<uint32_t> rl(nr), ql(nq);
+        for (uint32_t i = 0; i < nr; ++i) { rrows[i] = R.refs[i].hash_data(); rl[i] = (uint32_t)R.refs[i].hash_count(); }
+        for (uint32_t i = 0; i < nq; ++i) { qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count(); }
+        std::vector<uint32_t> common((size_t)nq * nr), denom((size_t)nq * nr);
+        std::vector<double> dist((size_t)nq * nr);
+        rc = dist_batch_rows(qrows.data(), ql.data(), nq, rrows.data(), rl.data(), nr, k, s, common.data(), denom.data(), dist.data());
+        if (rc) return rc;
+        lap("distances back");
+        for (uint32_t qi = 0; qi < nq; ++qi)
+            for (uint32_t ri = 0; ri < nr; ++ri) {
+                const size_t p = (size_t)qi * nr + ri;
+                const double pv = mhx_p_value(common[p], R.refs[ri].length, qs[qi]->length, k, denom[p]);
+                pair_row(text, R.refs[ri].name, qs[qi]->name, dist[p], pv, common[p], denom[p]);
+            }
+        lap("text written");
+    }
+    return put_text(text, stdout_buf, cap, need);
+}
+
+// The references of all files as ONE set (argument order, then file order), what `mash triangle`, the clustering and the
+// tree start from: every file read and checked, k / seed / sketch size the same in all, at most 65 536 references, and
+// their hash lists as the matrix mhx_dist_triangle takes.  `what` names the caller in the messages.
+struct SetOfFiles {
+    std::vector<SketchSet> F;
+    std::vector<const RefSketch *> refs;
+    std::vector<uint64_t> rows;
+    std::vector<uint32_t> len;
+    uint32_t stride = 16;
+    uint32_t n() const { return (uint32_t)refs.size(); }
+    uint32_t s() const { return F[0].sketch_size ? F[0].sketch_size : 1; } // for the device calls
+    int k() const { return (int)F[0].kmer_size; }
+};
+int read_set_of_files(const char *what, const char *const *paths, int n_paths, SetOfFiles &S)
+{
+    if (!paths || n_paths < 1) return fail(MHX_E_ARG, "%s: at least one sketch path required", what);
+    for (int i = 0; i < n_paths; ++i)
+        if (!paths[i]) return fail(MHX_E_ARG, "%s: sketch path %d is null", what, i);
+    std::vector<SketchSet> &F = S.F;
+    F.resize((size_t)n_paths);
+    for (int i = 0; i < n_paths; ++i) {
+        int rc = msh_read_file(paths[i], F[i]); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc == MHX_OK) rc = check_same_kind(F[0], F[i], F[0].sketch_size, paths[0], paths[i]);
+        if (rc) return rc;
+        for (const RefSketch &r : F[i].refs) S.refs.push_back(&r);
+    }
+    if (S.refs.size() > 65536) return fail(MHX_E_ARG, "%s: too many references for one call (%zu)", what, S.refs.size());
+    uint32_t longest = 0;
+    for (const RefSketch *r : S.refs) longest = std::max<uint32_t>(longest, (uint32_t)r->hash_count());
+    S.stride = row_stride(longest);
+    pack_rows(S.refs, S.stride, S.rows, S.len);
+    return MHX_OK;
+}
+
+// Newick: a name is single-quoted when it holds any of ( ) [ ] ' : ; , or a blank, an inner quote doubled
+std::string newick_name(const std::string &name)
+{
+    bool quote = false;
+    for (const char ch : name) quote = quote || strchr("()[]':;,", ch) != nullptr || isspace((unsigned char)ch);
+    if (!quote) return name;
+    std::string out = "'";
+    for (const char ch : name) { out += ch; if (ch == '\'') out += ch; }
+    return out + "'";
+}
+
+} // namespace
+
+extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_dist_files", [&] { return dist_files(ref_msh, &qry_msh, 1, stdout_buf, cap, need); });
+}
+
+extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_dist_files_multi", [&] { return dist_files(ref_msh, qry_msh, n_qry, stdout_buf, cap, need); });
+}
+
+// `mash triangle a.msh [b.msh ...]`: every pair j < i of the set is compared on the device (mhx_dist_triangle, or
+// mhx_dist_triangle_edges when a distance bound can drop pairs there), and the text is Mash's CommandTriangle: the
+// lower-triangle matrix, or the edge list with its two filters.
+extern "C" int mhx_triangle_files(const char *const *paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_triangle_files", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        mhx_triangle_opts o{(uint32_t)sizeof(mhx_triangle_opts), 0, 0, 1.0, 1.0};
+        rc = take_opts("triangle", opts, o);
+        if (rc) return rc;
+        if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "triangle: max_dist / max_p_value is not a number");
+        const bool edge = o.edge != 0 || o.max_dist < 1.0 || o.max_p_value < 1.0; // -d and -v imply -E
+        SetOfFiles S;
+        rc = read_set_of_files("triangle", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        const int k = S.k();
+        const uint64_t pairs = (uint64_t)n * (n ? n - 1 : 0) / 2;
+        std::string text;
+        if (!edge) {
+            std::vector<uint32_t> common(pairs), denom(pairs);
+            std::vector<double> dist(pairs);
+            rc = mhx_dist_triangle(S.rows.data(), S.len.data(), n, S.stride, k, S.s(), common.data(), denom.data(), dist.data(), 0);
+            if (rc) return rc;
+            text = "\t" + std::to_string(n) + "\n";
+            for (uint32_t i = 0; i < n; ++i) {
+                text += o.comment ? refs[i]->comment : refs[i]->name;
+                for (uint32_t j = 0; j < i; ++j) text += "\t" + fmt_g(dist[(size_t)i * (i - 1) / 2 + j]);
+                text += "\n";
+            }
+            return put_text(text, stdout_buf, cap, need);
+        }
+        std::vector<uint32_t> ei, ej, common, denom;
+        std::vector<double> dist;
+        uint64_t found = 0, room = o.max_dist >= 1.0 ? pairs : std::min<uint64_t>(pairs, 1u << 16);
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            ei.resize(room); ej.resize(room); common.resize(room); denom.resize(room); dist.resize(room);
+            rc = mhx_dist_triangle_edges(S.rows.data(), S.len.data(), n, S.stride, k, S.s(), o.max_dist, ei.data(), ej.data(), common.data(), denom.data(),
+                                         dist.data(), room, &found, 0);
+            if (rc != MHX_E_CAPACITY) break;
+            room = found;
+        }
+        if (rc) return rc;
+        clear_error();
+        for (uint64_t e = 0; e < found; ++e) {
+            const RefSketch &a = *refs[ei[e]], &b = *refs[ej[e]];
+            const double pv = mhx_p_value(common[e], a.length, b.length, k, denom[e]);
+            if (pv <= o.max_p_value) pair_row(text, a.name, b.name, dist[e], pv, common[e], denom[e]);
+        }
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// Dereplication at file level: the references of all files form one set (as for the triangle), mhx_dist_cluster labels it on
+// the device, and the host numbers the clusters by their lowest member, picks a representative per cluster in one pass
+// and prints a row per reference; the representatives, unchanged, are written as a sketch file of their own on request.
+extern "C" int mhx_cluster_files(const char *const *paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_cluster_files", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        mhx_cluster_opts o{(uint32_t)sizeof(mhx_cluster_opts), 0, 0, 1.0};
+        rc = take_opts("cluster", opts, o);
+        if (rc) return rc;
+        if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "cluster: max_dist is not a number");
+        if (o.rep != 0 && o.rep != 1) return fail(MHX_E_ARG, "cluster: rep must be 0 (first) or 1 (longest)");
+        SetOfFiles S;
+        rc = read_set_of_files("cluster", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        if (out_msh)
+            for (const RefSketch *r : refs)
+                if (!r->counts.empty())
+                    return fail(MHX_E_ARG, "cluster: %s carries multiplicity counts, which the output sketch file cannot store", r->name.c_str());
+        std::vector<uint32_t> label(n), degree(n);
+        uint32_t n_clusters = 0;
+        uint64_t n_edges = 0;
+        rc = mhx_dist_cluster(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), o.max_dist, label.data(), degree.data(), &n_clusters, &n_edges, 0);
+        if (rc) return rc;
+        // label[i] is the lowest member of i's cluster: a cluster's number, size and representative by its label, O(n)
+        std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t l = label[i];
+            if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "cluster: label %u of reference %u is not a cluster's lowest member", l, i);
+            if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
+            ++size[l];
+            if (o.rep == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
+        }
+        if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "cluster: %zu labels but %u clusters counted", order.size(), n_clusters);
+        auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
+        std::vector<std::vector<uint32_t>> members(order.size());
+        for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
+        std::string text;
+        for (size_t ci = 0; ci < order.size(); ++ci) {
+            const uint32_t l = order[ci];
+            for (uint32_t i : members[ci])
+                text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i) + "\t" + std::to_string(degree[i]) + "\n";
+        }
+        if (out_msh) {
+            const uint32_t m = (uint32_t)order.size();
+            std::vector<const char *> names(m), comments(m);
+            std::vector<uint64_t> lengths(m);
+            std::vector<const uint64_t *> hashes(m);
+            std::vector<uint32_t> n_hashes(m);
+            for (uint32_t ci = 0; ci < m; ++ci) {
+                const RefSketch &r = *refs[rep[order[ci]]];
+                names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
+                hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
+            }
+            rc = mhx_msh_write(out_msh, S.k(), S.F[0].sketch_size, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
+            if (rc) return rc;
+        }
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// The single-linkage tree at file level: the references of all files form one set (as for the triangle), mhx_dist_mst gives
+// its n - 1 merges in merge order, and the host prints them as a table or as a Newick dendrogram.
+extern "C" int mhx_tree_files(const char *const *paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_tree_files", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        mhx_tree_opts o{(uint32_t)sizeof(mhx_tree_opts), 0, 0};
+        rc = take_opts("tree", opts, o);
+        if (rc) return rc;
+        SetOfFiles S;
+        rc = read_set_of_files("tree", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        const int k = S.k();
+        const uint32_t m = n ? n - 1 : 0;
+        std::vector<uint32_t> ei(m), ej(m), common(m), denom(m);
+        std::vector<double> dist(m);
+        rc = mhx_dist_mst(S.rows.data(), S.len.data(), n, S.stride, k, S.s(), ei.data(), ej.data(), common.data(), denom.data(), dist.data(), 0);
+        if (rc) return rc;
+        auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
+        std::string text;
+        if (!o.newick) { // one row per merge: the triangle's edge-list row and the clusters left after it
+            for (uint32_t e = 0; e < m; ++e) {
+                const double pv = mhx_p_value(common[e], refs[ei[e]]->length, refs[ej[e]]->length, k, denom[e]);
+                pair_row(text, shown(ei[e]), shown(ej[e]), dist[e], pv, common[e], denom[e], std::to_string(n - 1 - e));
+            }
+            return put_text(text, stdout_buf, cap, need);
+        }
+        if (n == 0) return put_text(text, stdout_buf, cap, need);
+        // nodes 0 .. n - 1 are the leaves, node n + e the merge e; a node's height is its merge distance (leaves: 0), a branch
+        // is as long as the parent is higher, never negative; the child whose lowest index is lower comes first
+        std::vector<uint32_t> top(n), left(m), right(m), lowest((size_t)n + m), find(n);
+        std::vector<double> height((size_t)n + m, 0.0);
+        for (uint32_t i = 0; i < n; ++i) { top[i] = i; lowest[i] = i; find[i] = i; }
+        auto root = [&](uint32_t x) { while (find[x] != x) { find[x] = find[find[x]]; x = find[x]; } return x; };
+        for (uint32_t e = 0; e < m; ++e) {
+            const uint32_t ra = root(ei[e]), rb = root(ej[e]);
+            if (ra == rb) return fail(MHX_E_INTERNAL, "tree: merge %u joins one component with itself", e);
+            uint32_t a = top[ra], b = top[rb];
+            if (lowest[b] < lowest[a]) std::swap(a, b);
+            left[e] = a; right[e] = b;
+            lowest[n + e] = lowest[a];
+            height[n + e] = dist[e];
+            find[rb] = ra;
+            top[ra] = n + e;
+        }
+        // written without recursion: a chain of 65 535 merges is a tree of that depth
+        struct Item { uint32_t node; int stage; };
+        std::vector<Item> todo{{m ? n + m - 1 : 0u, 0}};
+        auto branch = [&](uint32_t child, uint32_t parent) { const double d = height[parent] - height[child]; return ":" + fmt_g(d > 0.0 ? d : 0.0); };
+        while (!todo.empty()) {
+            const Item it = todo.back();
+            todo.pop_back();
+            if (it.node < n) { text += newick_name(shown(it.node)); continue; }
+            const uint32_t e = it.node - n;
+            if (it.stage == 0) { text += "("; todo.push_back({it.node, 1}); todo.push_back({left[e], 0}); }
+            else if (it.stage == 1) { text += branch(left[e], it.node) + ","; todo.push_back({it.node, 2}); todo.push_back({right[e], 0}); }
+            else text += branch(right[e], it.node) + ")";
+        }
+        text += ";\n";
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// Reference-set search at file level: the reference file is read, checked and staged on the device ONCE; the query files
+// are read one after the other and searched in batches of sketches (mhx_dist_search's host form against the resident
+// references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.
+extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    return guarded("mhx_search_files", [&]() -> int {
+        clear_error();
+        int rc = require_engine();
+        if (rc) return rc;
+        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "search: a reference sketch path and at least one query sketch path required");
+        for (int i = 0; i < n_qry; ++i)
+            if (!qry_msh[i]) return fail(MHX_E_ARG, "search: query sketch path %d is null", i);
+        mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), 5, 1.0, 1.0};
+        rc = take_opts("search", opts, o);
+        if (rc) return rc;
+        if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "search: top must be 1 .. 64");
+        if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "search: max_dist / max_p_value is not a number");
+        SketchSet R;
+        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        const int k = (int)R.kmer_size;
+        const uint32_t nr = (uint32_t)R.refs.size();
+        DevArray<uint64_t> d_rows;
+        DevArray<uint32_t> d_len;
+        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
+        uint32_t q_sketch_size = 0, s = 0;
+        std::string text;
+        constexpr size_t kBatch = 4096; // query sketches per device call
+        std::vector<SketchSet> held;    // the files of the current batch
+        std::vector<const RefSketch *> qs;
+        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
+            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
+            refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
+            if (nr == 0) return MHX_OK;
+            std::vector<const RefSketch *> lists;
+            for (const RefSketch &r : R.refs) lists.push_back(&r);
+            std::vector<uint64_t> rows;
+            std::vector<uint32_t> len;
+            pack_rows(lists, refs.stride, rows, len);
+            for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
+            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
+            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+            refs.rows = d_rows; refs.len = d_len;
+            return MHX_OK;
+        };
+        auto flush = [&]() -> int {
+            const uint32_t nq = (uint32_t)qs.size();
+            if (nq && nr) {
+                std::vector<const uint64_t *> qrows(nq);
+                std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq);
+                std::vector<double> hx((size_t)nq * o.top);
+                for (uint32_t i = 0; i < nq; ++i) {
+                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                    if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
+                }
+                const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data());
+                if (rc2) return rc2;
+                for (uint32_t qi = 0; qi < nq; ++qi)
+                    for (uint32_t t = 0; t < nh[qi]; ++t) {
+                        const size_t p = (size_t)qi * o.top + t;
+                        const RefSketch &ref = R.refs[hr[p]];
+                        const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                        if (pv <= o.max_p_value) pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p]); // drops a row, never promotes a lower-ranked pair
+                    }
+            }
+            qs.clear();
+            held.clear();
+            return MHX_OK;
+        };
+        for (int i = 0; i < n_qry; ++i) {
+            held.emplace_back();
+            SketchSet &Q = held.back();
+            rc = msh_read_file(qry_msh[i], Q);
+            if (rc) return rc;
+            if (i == 0) q_sketch_size = Q.sketch_size;
+            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+            if (rc) return rc;
+            if (i == 0) {
+                s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+                rc = stage_refs();
+                if (rc) return rc;
+            }
+            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+        }
+        rc = flush();
+        if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
+    });
+}

@@ -1,6 +1,8 @@
 // mhx_internal.h -- host-side internals of libmhx (not part of the C ABI).
 #pragma once
 #include <stdint.h>
+#include <exception>
+#include <new>
 #include <string>
 #include <system_error>
 #include <thread>
@@ -11,9 +13,20 @@
 
 namespace mhx {
 
-// ---- errors ---------------------------------------------------------------------------
+// ---- errors (mhx_text.cpp) ------------------------------------------------------------
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void clear_error();
+// What an entry point of the C ABI runs its work in: no exception leaves the library, the message names the entry point.
+template <class F> int guarded(const char *name, F &&body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        return fail(MHX_E_INTERNAL, "%s: out of host memory", name);
+    } catch (const std::exception &e) {
+        return fail(MHX_E_INTERNAL, "%s: %s", name, e.what());
+    }
+}
 
 // ---- sketch container (mhx_msh.cpp) -----------------------------------------------------
 struct RefSketch {

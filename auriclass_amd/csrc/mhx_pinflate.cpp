@@ -780,7 +780,7 @@ extern "C" int mhx_gunzip_buffer_mt(const void *gz, size_t n, void *out, size_t 
 {
     clear_error();
     if (!gz || !out_n) return fail(MHX_E_ARG, "null argument");
-    try {
+    return guarded("mhx_gunzip_buffer_mt", [&]() -> int {
         std::vector<uint8_t> in(n + GzInflater::kInputPad, 0);
         memcpy(in.data(), gz, n);
         uint8_t *dst = (uint8_t *)out;
@@ -829,9 +829,5 @@ extern "C" int mhx_gunzip_buffer_mt(const void *gz, size_t n, void *out, size_t 
         *out_n = total;
         if (dst && total > cap) return fail(MHX_E_CAPACITY, "gunzip: output buffer too small (%zu needed)", total);
         return MHX_OK;
-    } catch (const std::bad_alloc &) {
-        return fail(MHX_E_INTERNAL, "mhx_gunzip_buffer_mt: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(MHX_E_INTERNAL, "mhx_gunzip_buffer_mt: %s", e.what());
-    }
+    });
 }

@@ -4,12 +4,28 @@
 // /root/reference/auriclass/classes.py:111-116 (dist TSV) and :352-375 (bounds table), so it
 // has to match `ostream << double` (== printf %g) character for character.
 #include <math.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
 #include "mhx_internal.h"
 
 namespace mhx {
+
+// ---- errors: the message of the calling thread's last failure (host code only, so that host tests can link it) --------
+static thread_local std::string g_err;
+int fail(int code, const char *fmt, ...)
+{
+    char b[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(b, sizeof(b), fmt, ap);
+    va_end(ap);
+    g_err = b;
+    return code;
+}
+void clear_error() { g_err.clear(); }
+extern "C" const char *mhx_last_error(void) { return g_err.c_str(); }
 
 std::string fmt_g(double v)
 {

@@ -84,6 +84,23 @@ def test_longer_lists_take_the_windowed_finish(lib, monkeypatch, store):
     check_source(lib, store)
 
 
+def test_the_generic_kernel_alone_feeds_the_recomputed_rounds(lib, monkeypatch):
+    """MHX_DIST_GENERIC=1 on set200, recomputed: no value ranges, the blocks go through the generic pair kernel alone (the
+    counters say 0 ranges and -1 fallbacks) and run again every round, from the second on over flag words that a round
+    before has used.  The tree is the rule's and, edge for edge, the one the stored source gives on the fast path."""
+    lists, s = mc.set200()
+    monkeypatch.setenv("MHX_MST_STORE", "1")
+    stored = run(lists, s)
+    check_source(lib, "1")
+    monkeypatch.setenv("MHX_MST_STORE", "0")
+    monkeypatch.setenv("MHX_DIST_GENERIC", "1")
+    got = run(lists, s)
+    assert lib.mhx_last_dist_ranges() == 0 and lib.mhx_last_dist_fallback_blocks() == -1
+    check(lib, got, mc.expected("set200"), len(lists))
+    check_source(lib, "0")
+    assert all(np.array_equal(a, b) for a, b in zip(got, stored))
+
+
 def test_the_budget_chooses_the_pair_source(lib, monkeypatch):
     """set200 holds 19 900 pairs, 159 200 bytes: a budget of 0 MB recomputes, 1 MB and the default store, and MHX_MST_STORE
     overrides the budget either way; mhx_last_mst_stored() tells which ran, and all give the rule's tree"""

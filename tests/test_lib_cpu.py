@@ -96,6 +96,16 @@ def test_compute_calls_fail_loudly_without_gpu(lib, tmp_path):
     with pytest.raises(engine.EngineError) as e:
         engine.dist_batch(q, [100], q, [100], 21, 100)
     assert e.value.code == engine.MHX_E_NO_DEVICE
+    # The wrappers above stop in mhx_init.  The file-level set calls and the triangle family at their C entry points, with
+    # nothing but null pointers and zeros: each is reached, refuses for want of an engine before it looks at an argument,
+    # and says so.
+    for name in ("mhx_dist_files", "mhx_dist_files_multi", "mhx_triangle_files", "mhx_cluster_files", "mhx_tree_files", "mhx_search_files",
+                 "mhx_dist_batch", "mhx_dist_search", "mhx_dist_triangle", "mhx_dist_triangle_edges", "mhx_dist_cluster", "mhx_dist_mst"):
+        fn = getattr(lib, name)
+        assert fn.argtypes, name
+        args = [None if t in (ctypes.c_char_p, ctypes.c_void_p) or hasattr(t, "contents") else t(0) for t in fn.argtypes]
+        assert fn(*args) == engine.MHX_E_NO_DEVICE, name
+        assert b"no GPU engine" in lib.mhx_last_error(), name
     # the host-only entry points keep working: bounds text, container writer, gunzip
     assert "Parameters (run with -h for details)" in engine.bounds(27, 0.99)
 
@@ -295,6 +305,27 @@ def test_inflate_under_address_sanitizer(tmp_path):
         if name == "dyn.gz":   # the parallel path really ran: the intact seed decoded to its full length, mutants were refused
             assert "(seed: %d)" % len(text) in r.stdout, r.stdout
             assert int(r.stdout.split("parallel: ok ")[1].split()[2]) > 50, r.stdout
+
+
+def test_exception_guard_under_address_sanitizer(tmp_path):
+    """CPU ASan/UBSan build of tests/emul/guard_emul.cpp with mhx_text.cpp (fail() and its message): the guard of the C entry
+    points turns std::bad_alloc and std::runtime_error("x") into MHX_E_INTERNAL with "NAME: out of host memory" and
+    "NAME: x", byte for byte, and hands a body's 7 through."""
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = Path(__file__).resolve().parent.parent
+    exe = tmp_path / "guard_emul"
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+           str(root / "tests" / "emul" / "guard_emul.cpp"), str(root / "auriclass_amd" / "csrc" / "mhx_text.cpp"), "-o", str(exe), "-lpthread"]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "sanitize" in b.stderr and "cannot find" in b.stderr:
+        pytest.skip("no sanitizer runtime on this host")
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="abort_on_error=0"), timeout=60)
+    assert r.returncode == 0 and r.stdout == "ok 3\n", (r.stdout[-500:], r.stderr[-3000:])
 
 
 def test_parallel_gunzip_equals_zlib(lib, monkeypatch):
