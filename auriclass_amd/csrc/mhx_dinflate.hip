@@ -236,96 +236,98 @@ using namespace mhx;
 
 extern "C" int mhx_gunzip_device(const void *gz, size_t n, void *d_out, size_t cap, size_t *out_n)
 {
-    clear_error();
-    if (!gz || !out_n) return fail(MHX_E_ARG, "null argument");
-    int rc = require_engine();
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    memset(g_stats, 0, sizeof(g_stats));
-    const uint8_t *in = (const uint8_t *)gz;
-    hipStream_t st = g.stream;
-    const size_t min_member = env_size("MHX_DINFLATE_MIN", 1u << 20);     // smaller members: the host decoder
-    const size_t seg_bytes = env_size("MHX_DINFLATE_SEGMENT", 64u << 10); // target compressed bytes per segment
-    // segments of the largest round; one resolution launch spans a round's segments in its grid's y dimension
-    const uint32_t round_segs = (uint32_t)std::min<size_t>(env_size("MHX_DINFLATE_ROUND", 1024), 65535);
-    const int host_threads = ingest_thread_budget();
-    size_t total = 0;
-    bool on_device = false;
-    rc = [&]() -> int {
-        DeviceBackend be;
-        be.st = st;
-        be.user_out = (uint8_t *)d_out;
-        be.user_cap = d_out ? cap : 0;
-        be.out = be.user_out;
-        DevArray<uint8_t> d_in;
-        size_t off = 0;
-        bool uploaded = false;
-        (void)on_device;
-        // Members go to the device while at least min_member compressed bytes remain and the last one it decoded was that
-        // large; a BGZF block (bgzip's many small members), a header the host refuses, the first small member decoded and
-        // everything behind them go to the host decoders (BgzfReader for a run of BGZF blocks).
-        while (off < n) {
-            const int64_t h = member_data_offset(in + off, n - off);
-            if (h == 0) break; // no further member: the host decoder ignores what is left, so does this
-            if (h < 0 || n - off < min_member || bgzf_block_size(in + off, n - off)) break;
-            if (!uploaded) {
-                if (!be.ok(d_in.grow(n + kInPad)) || !be.ok(hipMemsetAsync(d_in + n, 0, kInPad, st)) ||
-                    !be.ok(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, st)))
-                    return 1;
-                be.d_in = d_in;
-                be.n = n;
-                uploaded = true;
-            }
-            MemberOut mo;
-            MemberStats ms;
-            const int mrc = inflate_member(be, n, (uint64_t)(off + (size_t)h) * 8, (uint64_t)seg_bytes * 8, 16, round_segs, total,
-                                           combine_crc, &mo, &ms);
-            g_stats[1] += ms.segments;
-            g_stats[2] += ms.redone;
-            g_stats[3] += ms.hops;
-            if (mrc != kMemberOk) return 1;
-            const size_t tb = (size_t)((mo.end_bit + 7) / 8);
-            if (tb + 8 > n || le32(in + tb) != mo.crc || le32(in + tb + 4) != (uint32_t)mo.out_n) return 1;
-            total += mo.out_n;
-            be.out_len = total;
-            ++g_stats[0];
-            const bool small = tb + 8 - off < min_member;
-            off = tb + 8;
-            on_device = true;
-            if (small) break;
-        }
-        if (off < n && member_data_offset(in + off, n - off) != 0) { // the rest through the host decoders, appended
-            std::vector<uint8_t> tmp(std::max<size_t>(4 * (n - off), 1u << 20));
-            size_t rest = 0;
-            int hrc = mhx_gunzip_buffer_mt(in + off, n - off, tmp.data(), tmp.size(), &rest, host_threads);
-            if (hrc == MHX_E_CAPACITY) {
-                tmp.resize(rest);
-                hrc = mhx_gunzip_buffer_mt(in + off, n - off, tmp.data(), tmp.size(), &rest, host_threads);
-            }
-            if (hrc) return 1; // the sequential decoder on the whole input decides what the error is
-            if (rest) {
-                if (!be.out_room(total + rest)) return 1;
-                if (!be.ok(hipMemcpyAsync(be.out + total, tmp.data(), rest, hipMemcpyHostToDevice, st)) || !be.ok(hipStreamSynchronize(st)))
-                    return 1;
-            }
-            g_stats[4] += n - off;
-            total += rest;
-        }
-        return 0;
-    }();
-    g_stats[5] = 0;
-    if (rc != 0) { // the host has the last word
-        memset(g_stats, 0, sizeof(g_stats));
-        g_stats[4] = n;
+    return guarded("mhx_gunzip_device", [&]() -> int { // (the arguments are checked before the engine: the prologue stays as it was)
         clear_error();
-        rc = host_gunzip_into(in, n, (uint8_t *)d_out, cap, &total, st);
+        if (!gz || !out_n) return fail(MHX_E_ARG, "null argument");
+        int rc = require_engine();
         if (rc) return rc;
-    }
-    g_stats[5] = total;
-    if (g.profiling) g_stats[6] = (uint64_t)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *out_n = total;
-    if (d_out && total > cap) return fail(MHX_E_CAPACITY, "gunzip: output buffer too small (%zu needed)", total);
-    return MHX_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        memset(g_stats, 0, sizeof(g_stats));
+        const uint8_t *in = (const uint8_t *)gz;
+        hipStream_t st = g.stream;
+        const size_t min_member = env_size("MHX_DINFLATE_MIN", 1u << 20);     // smaller members: the host decoder
+        const size_t seg_bytes = env_size("MHX_DINFLATE_SEGMENT", 64u << 10); // target compressed bytes per segment
+        // segments of the largest round; one resolution launch spans a round's segments in its grid's y dimension
+        const uint32_t round_segs = (uint32_t)std::min<size_t>(env_size("MHX_DINFLATE_ROUND", 1024), 65535);
+        const int host_threads = ingest_thread_budget();
+        size_t total = 0;
+        bool on_device = false;
+        rc = [&]() -> int {
+            DeviceBackend be;
+            be.st = st;
+            be.user_out = (uint8_t *)d_out;
+            be.user_cap = d_out ? cap : 0;
+            be.out = be.user_out;
+            DevArray<uint8_t> d_in;
+            size_t off = 0;
+            bool uploaded = false;
+            (void)on_device;
+            // Members go to the device while at least min_member compressed bytes remain and the last one it decoded was that
+            // large; a BGZF block (bgzip's many small members), a header the host refuses, the first small member decoded and
+            // everything behind them go to the host decoders (BgzfReader for a run of BGZF blocks).
+            while (off < n) {
+                const int64_t h = member_data_offset(in + off, n - off);
+                if (h == 0) break; // no further member: the host decoder ignores what is left, so does this
+                if (h < 0 || n - off < min_member || bgzf_block_size(in + off, n - off)) break;
+                if (!uploaded) {
+                    if (!be.ok(d_in.grow(n + kInPad)) || !be.ok(hipMemsetAsync(d_in + n, 0, kInPad, st)) ||
+                        !be.ok(hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, st)))
+                        return 1;
+                    be.d_in = d_in;
+                    be.n = n;
+                    uploaded = true;
+                }
+                MemberOut mo;
+                MemberStats ms;
+                const int mrc = inflate_member(be, n, (uint64_t)(off + (size_t)h) * 8, (uint64_t)seg_bytes * 8, 16, round_segs, total,
+                                               combine_crc, &mo, &ms);
+                g_stats[1] += ms.segments;
+                g_stats[2] += ms.redone;
+                g_stats[3] += ms.hops;
+                if (mrc != kMemberOk) return 1;
+                const size_t tb = (size_t)((mo.end_bit + 7) / 8);
+                if (tb + 8 > n || le32(in + tb) != mo.crc || le32(in + tb + 4) != (uint32_t)mo.out_n) return 1;
+                total += mo.out_n;
+                be.out_len = total;
+                ++g_stats[0];
+                const bool small = tb + 8 - off < min_member;
+                off = tb + 8;
+                on_device = true;
+                if (small) break;
+            }
+            if (off < n && member_data_offset(in + off, n - off) != 0) { // the rest through the host decoders, appended
+                std::vector<uint8_t> tmp(std::max<size_t>(4 * (n - off), 1u << 20));
+                size_t rest = 0;
+                int hrc = mhx_gunzip_buffer_mt(in + off, n - off, tmp.data(), tmp.size(), &rest, host_threads);
+                if (hrc == MHX_E_CAPACITY) {
+                    tmp.resize(rest);
+                    hrc = mhx_gunzip_buffer_mt(in + off, n - off, tmp.data(), tmp.size(), &rest, host_threads);
+                }
+                if (hrc) return 1; // the sequential decoder on the whole input decides what the error is
+                if (rest) {
+                    if (!be.out_room(total + rest)) return 1;
+                    if (!be.ok(hipMemcpyAsync(be.out + total, tmp.data(), rest, hipMemcpyHostToDevice, st)) || !be.ok(hipStreamSynchronize(st)))
+                        return 1;
+                }
+                g_stats[4] += n - off;
+                total += rest;
+            }
+            return 0;
+        }();
+        g_stats[5] = 0;
+        if (rc != 0) { // the host has the last word
+            memset(g_stats, 0, sizeof(g_stats));
+            g_stats[4] = n;
+            clear_error();
+            rc = host_gunzip_into(in, n, (uint8_t *)d_out, cap, &total, st);
+            if (rc) return rc;
+        }
+        g_stats[5] = total;
+        if (g.profiling) g_stats[6] = (uint64_t)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *out_n = total;
+        if (d_out && total > cap) return fail(MHX_E_CAPACITY, "gunzip: output buffer too small (%zu needed)", total);
+        return MHX_OK;
+    });
 }
 
 extern "C" int mhx_last_inflate_stats(uint64_t *out8)

@@ -41,9 +41,6 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
                            uint32_t nr, uint32_t stride, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist,
                            int device_ptrs, const uint64_t *const *q_rows, const uint64_t *const *r_rows)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
     if (nq == 0 || nr == 0) return MHX_OK;
     if ((!q && !q_rows) || !q_len || (!r && !r_rows) || !r_len || !common || !denom) return fail(MHX_E_ARG, "null argument");
     if (device_ptrs && (q_rows || r_rows)) return fail(MHX_E_ARG, "row pointers are a host form");
@@ -61,7 +58,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
         auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t bq = up((size_t)nq * stride * 8), br = up((size_t)nr * stride * 8), bql = up((size_t)nq * 4), brl = up((size_t)nr * 4), bo = up(pairs * 4);
         uint8_t *base = nullptr;
-        rc = dist_stage(bq + br + bql + brl + 2 * bo, &base);
+        const int rc = dist_stage(bq + br + bql + brl + 2 * bo, &base);
         if (rc) return rc;
         uint8_t *dq = base, *dr = dq + bq, *dql = dr + br, *drl = dql + bql;
         dc = (uint32_t *)(drl + brl);
@@ -194,7 +191,7 @@ extern "C" int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t
                               uint32_t nr, uint32_t stride, int k, uint32_t s, uint32_t *common, uint32_t *denom, double *dist,
                               int device_ptrs)
 {
-    return guarded("mhx_dist_batch", [&] { return dist_batch_core(q, q_len, nq, r, r_len, nr, stride, k, s, common, denom, dist, device_ptrs, nullptr, nullptr); });
+    return entry("mhx_dist_batch", [&] { return dist_batch_core(q, q_len, nq, r, r_len, nr, stride, k, s, common, denom, dist, device_ptrs, nullptr, nullptr); });
 }
 
 namespace mhx {

@@ -1,5 +1,5 @@
-// mhx_engine_internal.h -- what the engine files (mhx_engine.cpp: engine state and sketcher, mhx_engine_dist.cpp,
-// mhx_engine_screen.cpp), mhx_files.cpp (file ingest and the calls that read sequence files) and mhx_files_sets.cpp (the
+// mhx_engine_internal.h -- what the engine files (mhx_engine.cpp: engine state and sketcher, mhx_engine_merge.cpp,
+// mhx_engine_dist.cpp, mhx_engine_screen.cpp), mhx_files.cpp (file ingest and the calls that read sequence files) and mhx_files_sets.cpp (the
 // file-level commands over sketch sets) share.  Internal; the public surface is include/mhx.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -152,6 +152,16 @@ struct Engine {
 };
 extern Engine &g;
 int require_engine();
+// What an int-returning entry point of the C ABI that needs the engine runs its work in: the guard (mhx_internal.h) around
+// the cleared error text, the engine check and the body.  An entry point that needs no engine uses guarded() as it is.
+template <class F> int entry(const char *name, F &&body)
+{
+    return guarded(name, [&]() -> int {
+        clear_error();
+        const int rc = require_engine();
+        return rc ? rc : body();
+    });
+}
 // room for `bytes` in g.dist_in, the device staging of a host-pointer distance call (mhx_engine_dist.cpp; the triangle's too)
 int dist_stage(size_t bytes, uint8_t **out);
 // what the two file-level files share (mhx_files.cpp): the text of a call into the caller's buffer (*need: its size with the

@@ -56,10 +56,7 @@ static int screener_clear(mhx_screener *sc)
 extern "C" int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32_t *ref_len, uint32_t nr, uint32_t stride, uint32_t s_ref,
                                    int with_set_size, int device_ptrs, mhx_screener **out)
 {
-    return guarded("mhx_screener_create", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_screener_create", [&]() -> int {
         if (!out) return fail(MHX_E_ARG, "null out pointer");
         if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
         if (nr && (!ref_rows || !ref_len || stride == 0)) return fail(MHX_E_ARG, "null reference rows");
@@ -105,7 +102,7 @@ extern "C" int mhx_screener_create(int k, const uint64_t *ref_rows, const uint32
         if (flags & kFlagTableFull) return fail(MHX_E_INTERNAL, "screen table overflowed while it was built");
         sc->probe->screen_T = T;
         sc->probe->last_T = T;
-        rc = screener_clear(sc.get());
+        int rc = screener_clear(sc.get());
         if (rc) return rc;
         if (with_set_size) {
             mhx_sketcher *ss = nullptr;
@@ -126,53 +123,49 @@ extern "C" void mhx_screener_destroy(mhx_screener *sc)
 
 extern "C" int mhx_screener_reset(mhx_screener *sc)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null screener");
-    rc = screener_clear(sc);
-    if (rc) return rc;
-    return sc->setsk ? mhx_sketcher_reset(sc->setsk.get()) : MHX_OK;
+    return entry("mhx_screener_reset", [&]() -> int {
+        if (!sc) return fail(MHX_E_ARG, "null screener");
+        int rc = screener_clear(sc);
+        if (rc) return rc;
+        return sc->setsk ? mhx_sketcher_reset(sc->setsk.get()) : MHX_OK;
+    });
 }
 
 extern "C" int mhx_screener_push_device(mhx_screener *sc, const void *d_bytes, uint64_t n, int fmt)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null argument");
-    rc = mhx_sketcher_push_device(sc->probe.get(), d_bytes, n, fmt);
-    if (rc || !sc->setsk) return rc;
-    return mhx_sketcher_push_device(sc->setsk.get(), d_bytes, n, fmt); // a second launch over the same resident bytes
+    return entry("mhx_screener_push_device", [&]() -> int {
+        if (!sc) return fail(MHX_E_ARG, "null argument");
+        int rc = mhx_sketcher_push_device(sc->probe.get(), d_bytes, n, fmt);
+        if (rc || !sc->setsk) return rc;
+        return mhx_sketcher_push_device(sc->setsk.get(), d_bytes, n, fmt); // a second launch over the same resident bytes
+    });
 }
 
 extern "C" int mhx_screener_push_host(mhx_screener *sc, const void *h_bytes, uint64_t n, int fmt)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc || (!h_bytes && n)) return fail(MHX_E_ARG, "null argument");
-    if (n == 0) return MHX_OK;
-    mhx_sketcher *p = sc->probe.get();
-    // one staging buffer (the prober's) for both: earlier pushes of either that may still read it come first
-    rc = settle(p);
-    if (!rc && sc->setsk) rc = settle(sc->setsk.get());
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(g.stream));
-    if (p->d_stage.cap() < n + 64) HIPCHK(p->d_stage.grow((size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1))));
-    HIPCHK(hipMemcpyAsync(p->d_stage, h_bytes, n, hipMemcpyHostToDevice, g.stream));
-    return mhx_screener_push_device(sc, p->d_stage, n, fmt);
+    return entry("mhx_screener_push_host", [&]() -> int {
+        if (!sc || (!h_bytes && n)) return fail(MHX_E_ARG, "null argument");
+        if (n == 0) return MHX_OK;
+        mhx_sketcher *p = sc->probe.get();
+        // one staging buffer (the prober's) for both: earlier pushes of either that may still read it come first
+        int rc = settle(p);
+        if (!rc && sc->setsk) rc = settle(sc->setsk.get());
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(g.stream));
+        if (p->d_stage.cap() < n + 64) HIPCHK(p->d_stage.grow((size_t)((n + 64 + (1u << 20) - 1) & ~(uint64_t)((1u << 20) - 1))));
+        HIPCHK(hipMemcpyAsync(p->d_stage, h_bytes, n, hipMemcpyHostToDevice, g.stream));
+        return mhx_screener_push_device(sc, p->d_stage, n, fmt);
+    });
 }
 
 extern "C" int mhx_screener_sync(mhx_screener *sc)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    if (!sc) return fail(MHX_E_ARG, "null argument");
-    rc = mhx_sketcher_sync(sc->probe.get());
-    if (rc || !sc->setsk) return rc;
-    return mhx_sketcher_sync(sc->setsk.get());
+    return entry("mhx_screener_sync", [&]() -> int {
+        if (!sc) return fail(MHX_E_ARG, "null argument");
+        int rc = mhx_sketcher_sync(sc->probe.get());
+        if (rc || !sc->setsk) return rc;
+        return mhx_sketcher_sync(sc->setsk.get());
+    });
 }
 
 namespace mhx {
@@ -213,12 +206,9 @@ static int screener_winner_passes(mhx_screener *sc, const uint64_t *ref_length, 
 static int screener_finish_impl(mhx_screener *sc, bool winner, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
                                 uint32_t *counts)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
     if (!sc || (sc->nr && (!shared || !median))) return fail(MHX_E_ARG, "null argument");
     mhx_sketcher *p = sc->probe.get();
-    rc = settle(p); // the repair pass of long reads, if one is due
+    int rc = settle(p); // the repair pass of long reads, if one is due
     if (rc) return rc;
     uint64_t st[kStatCount];
     rc = fetch_stats(p, st);
@@ -253,11 +243,11 @@ static int screener_finish_impl(mhx_screener *sc, bool winner, const uint64_t *r
 
 extern "C" int mhx_screener_finish(mhx_screener *sc, uint32_t *shared, uint32_t *median, double *set_size, uint32_t *counts)
 {
-    return guarded("mhx_screener_finish", [&] { return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts); });
+    return entry("mhx_screener_finish", [&] { return screener_finish_impl(sc, false, nullptr, shared, median, set_size, counts); });
 }
 
 extern "C" int mhx_screener_finish_winner(mhx_screener *sc, const uint64_t *ref_length, uint32_t *shared, uint32_t *median, double *set_size,
                                           uint32_t *counts)
 {
-    return guarded("mhx_screener_finish_winner", [&] { return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts); });
+    return entry("mhx_screener_finish_winner", [&] { return screener_finish_impl(sc, true, ref_length, shared, median, set_size, counts); });
 }

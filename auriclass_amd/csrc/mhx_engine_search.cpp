@@ -231,11 +231,8 @@ extern "C" int mhx_dist_search(const uint64_t *q, const uint32_t *q_len, uint32_
                                uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist,
                                uint32_t *n_hits, int device_ptrs)
 {
-    return guarded("mhx_dist_search", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
-        rc = search_check(nq, nr, stride, k, s, max_dist, top);
+    return entry("mhx_dist_search", [&]() -> int {
+        int rc = search_check(nq, nr, stride, k, s, max_dist, top);
         if (rc) return rc;
         if (nq == 0) return MHX_OK;
         if (!n_hits) return fail(MHX_E_ARG, "null argument");

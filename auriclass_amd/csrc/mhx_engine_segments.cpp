@@ -118,10 +118,7 @@ int segments_resident(const uint8_t *d_bytes, const uint64_t *h_off, uint32_t n_
 extern "C" int mhx_sketch_segments(const void *bytes, uint64_t n, const uint64_t *seg_off, uint32_t n_seg, int k, uint32_t s, uint64_t *rows,
                                    uint32_t *len, uint32_t stride, int device_ptrs)
 {
-    return guarded("mhx_sketch_segments", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_sketch_segments", [&]() -> int {
         if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
         if (s == 0) return fail(MHX_E_ARG, "sketch_segments: sketch size 0");
         if (n_seg == 0) return MHX_OK;
@@ -136,7 +133,7 @@ extern "C" int mhx_sketch_segments(const void *bytes, uint64_t n, const uint64_t
             h_off = off_copy.data();
         }
         uint32_t need = 0;
-        rc = check_offsets(h_off, n_seg, n, k, s, &need);
+        int rc = check_offsets(h_off, n_seg, n, k, s, &need);
         if (rc) return rc;
         if (stride < need) return fail(MHX_E_ARG, "sketch_segments: stride %u, but a segment may fill %u entries", stride, need);
         if (need && !rows) return fail(MHX_E_ARG, "sketch_segments: null argument");

@@ -1274,10 +1274,8 @@ int sketch_records(const uint8_t *d_stream, const uint8_t *h_stream, uint64_t st
 extern "C" int mhx_sketch_files_individual(const char *const *paths, int n_paths, int k, uint32_t s, const char *out_msh, char *stderr_buf,
                                            size_t stderr_cap, size_t *stderr_need, uint64_t *n_refs_out)
 {
-    return guarded("mhx_sketch_files_individual", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_sketch_files_individual", [&]() -> int {
+        int rc = MHX_OK;
         if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
         for (int i = 0; i < n_paths; ++i)
             if (!paths[i]) return fail(MHX_E_ARG, "sketch: input path %d is null", i);
@@ -1338,79 +1336,72 @@ extern "C" int mhx_sketch_files_individual(const char *const *paths, int n_paths
 // way (sketch_read_set).  Tally on the device (opts->winner: winner-take-all), columns and the -i / -v filters on the host.
 struct ScreenerDestroy { void operator()(mhx_screener *sc) const { mhx_screener_destroy(sc); } };
 
-static int mhx_screen_files_impl(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
-                                 size_t cap, size_t *need, double *set_size_out)
-{
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
-    bool winner = false;
-    double min_identity = -1.0, max_p = 1.0;
-    if (opts) {
-        if (opts->struct_size != sizeof(mhx_screen_opts)) return fail(MHX_E_ARG, "screen: mhx_screen_opts of %u bytes, expected %zu", opts->struct_size, sizeof(mhx_screen_opts));
-        if (!(opts->min_identity <= 1.0)) return fail(MHX_E_ARG, "screen: minimum identity must be at most 1");
-        if (!(opts->max_p_value >= 0.0 && opts->max_p_value <= 1.0)) return fail(MHX_E_ARG, "screen: maximum p-value must be within [0, 1]");
-        winner = opts->winner != 0; min_identity = opts->min_identity; max_p = opts->max_p_value;
-    }
-    if (!ref_msh || !paths || n_paths <= 0) return fail(MHX_E_ARG, "screen: a reference sketch path and at least one read file required");
-    for (int i = 0; i < n_paths; ++i)
-        if (!paths[i]) return fail(MHX_E_ARG, "screen: read file path %d is null", i);
-    SketchSet R;
-    rc = msh_read_file(ref_msh, R);
-    if (rc) return rc;
-    if (R.hash_seed != 42) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches use hash seed %u; reads are hashed with seed 42", R.hash_seed);
-    if (R.alphabet != "ACGT" || R.noncanonical) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches are not canonical nucleotide sketches");
-    const int k = (int)R.kmer_size;
-    if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
-    const uint32_t nr = (uint32_t)R.refs.size();
-    uint32_t stride = 1, s_ref = R.sketch_size;
-    std::vector<uint32_t> len(nr);
-    for (uint32_t i = 0; i < nr; ++i) {
-        if (!check_ascending(R.refs[i].hash_data(), R.refs[i].hash_count()))
-            return fail(MHX_E_FORMAT, "%s: hash list of reference %u is not ascending", ref_msh, i);
-        len[i] = (uint32_t)R.refs[i].hash_count();
-        stride = std::max(stride, len[i]);
-    }
-    s_ref = std::max<uint32_t>(std::max(s_ref, stride), 1);
-    std::vector<uint64_t> rows((size_t)nr * stride, 0);
-    for (uint32_t i = 0; i < nr; ++i)
-        if (len[i]) memcpy(rows.data() + (size_t)i * stride, R.refs[i].hash_data(), (size_t)len[i] * sizeof(uint64_t));
-    mhx_screener *raw = nullptr;
-    rc = mhx_screener_create(k, rows.data(), len.data(), nr, stride, s_ref, 0, 0, &raw);
-    if (rc) return rc;
-    std::unique_ptr<mhx_screener, ScreenerDestroy> scr(raw);
-    RefSketch mix;
-    uint64_t kmers = 0, count = 0;
-    std::string fname, fcomment;
-    rc = sketch_read_set(paths, n_paths, k, s_ref, 1, scr.get(), mix, kmers, count, fname, fcomment);
-    if (rc) return rc;
-    // (no record of k bases at all: mash warns and prints its rows; the sketch is empty and the set size 0)
-    const double set_size = set_size_estimate(k, mix.hashes.data(), mix.hashes.size());
-    std::vector<uint32_t> shared(nr), median(nr);
-    if (winner) {
-        std::vector<uint64_t> length(nr);
-        for (uint32_t i = 0; i < nr; ++i) length[i] = R.refs[i].length;
-        rc = mhx_screener_finish_winner(scr.get(), length.data(), shared.data(), median.data(), nullptr, nullptr);
-    } else {
-        rc = mhx_screener_finish(scr.get(), shared.data(), median.data(), nullptr, nullptr);
-    }
-    if (rc) return rc;
-    std::string text;
-    for (uint32_t i = 0; i < nr; ++i) {
-        const double identity = mhx_screen_identity(shared[i], len[i], k), p = mhx_screen_p_value(shared[i], len[i], set_size, k);
-        // mash screen -i / -v: -i 0 keeps identities above zero only, -i -1 everything
-        if (!(min_identity == 0.0 ? identity > 0.0 : identity >= min_identity) || !(p <= max_p)) continue;
-        text += fmt_g(identity) + "\t" + std::to_string(shared[i]) + "/" + std::to_string(len[i]) + "\t" + std::to_string(median[i]) + "\t" +
-                fmt_g(p) + "\t" + R.refs[i].name + "\t" + R.refs[i].comment + "\n";
-    }
-    if (set_size_out) *set_size_out = set_size;
-    return put_text(text, stdout_buf, cap, need);
-}
-
 extern "C" int mhx_screen_files_opts(const char *ref_msh, const char *const *paths, int n_paths, const mhx_screen_opts *opts, char *stdout_buf,
                                      size_t cap, size_t *need, double *set_size_out)
 {
-    return guarded("mhx_screen_files", [&] { return mhx_screen_files_impl(ref_msh, paths, n_paths, opts, stdout_buf, cap, need, set_size_out); });
+    return entry("mhx_screen_files", [&]() -> int {
+        bool winner = false;
+        double min_identity = -1.0, max_p = 1.0;
+        if (opts) {
+            if (opts->struct_size != sizeof(mhx_screen_opts)) return fail(MHX_E_ARG, "screen: mhx_screen_opts of %u bytes, expected %zu", opts->struct_size, sizeof(mhx_screen_opts));
+            if (!(opts->min_identity <= 1.0)) return fail(MHX_E_ARG, "screen: minimum identity must be at most 1");
+            if (!(opts->max_p_value >= 0.0 && opts->max_p_value <= 1.0)) return fail(MHX_E_ARG, "screen: maximum p-value must be within [0, 1]");
+            winner = opts->winner != 0; min_identity = opts->min_identity; max_p = opts->max_p_value;
+        }
+        if (!ref_msh || !paths || n_paths <= 0) return fail(MHX_E_ARG, "screen: a reference sketch path and at least one read file required");
+        for (int i = 0; i < n_paths; ++i)
+            if (!paths[i]) return fail(MHX_E_ARG, "screen: read file path %d is null", i);
+        SketchSet R;
+        int rc = msh_read_file(ref_msh, R);
+        if (rc) return rc;
+        if (R.hash_seed != 42) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches use hash seed %u; reads are hashed with seed 42", R.hash_seed);
+        if (R.alphabet != "ACGT" || R.noncanonical) return fail(MHX_E_MISMATCH, "ERROR: The reference sketches are not canonical nucleotide sketches");
+        const int k = (int)R.kmer_size;
+        if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
+        const uint32_t nr = (uint32_t)R.refs.size();
+        uint32_t stride = 1, s_ref = R.sketch_size;
+        std::vector<uint32_t> len(nr);
+        for (uint32_t i = 0; i < nr; ++i) {
+            if (!check_ascending(R.refs[i].hash_data(), R.refs[i].hash_count()))
+                return fail(MHX_E_FORMAT, "%s: hash list of reference %u is not ascending", ref_msh, i);
+            len[i] = (uint32_t)R.refs[i].hash_count();
+            stride = std::max(stride, len[i]);
+        }
+        s_ref = std::max<uint32_t>(std::max(s_ref, stride), 1);
+        std::vector<uint64_t> rows((size_t)nr * stride, 0);
+        for (uint32_t i = 0; i < nr; ++i)
+            if (len[i]) memcpy(rows.data() + (size_t)i * stride, R.refs[i].hash_data(), (size_t)len[i] * sizeof(uint64_t));
+        mhx_screener *raw = nullptr;
+        rc = mhx_screener_create(k, rows.data(), len.data(), nr, stride, s_ref, 0, 0, &raw);
+        if (rc) return rc;
+        std::unique_ptr<mhx_screener, ScreenerDestroy> scr(raw);
+        RefSketch mix;
+        uint64_t kmers = 0, count = 0;
+        std::string fname, fcomment;
+        rc = sketch_read_set(paths, n_paths, k, s_ref, 1, scr.get(), mix, kmers, count, fname, fcomment);
+        if (rc) return rc;
+        // (no record of k bases at all: mash warns and prints its rows; the sketch is empty and the set size 0)
+        const double set_size = set_size_estimate(k, mix.hashes.data(), mix.hashes.size());
+        std::vector<uint32_t> shared(nr), median(nr);
+        if (winner) {
+            std::vector<uint64_t> length(nr);
+            for (uint32_t i = 0; i < nr; ++i) length[i] = R.refs[i].length;
+            rc = mhx_screener_finish_winner(scr.get(), length.data(), shared.data(), median.data(), nullptr, nullptr);
+        } else {
+            rc = mhx_screener_finish(scr.get(), shared.data(), median.data(), nullptr, nullptr);
+        }
+        if (rc) return rc;
+        std::string text;
+        for (uint32_t i = 0; i < nr; ++i) {
+            const double identity = mhx_screen_identity(shared[i], len[i], k), p = mhx_screen_p_value(shared[i], len[i], set_size, k);
+            // mash screen -i / -v: -i 0 keeps identities above zero only, -i -1 everything
+            if (!(min_identity == 0.0 ? identity > 0.0 : identity >= min_identity) || !(p <= max_p)) continue;
+            text += fmt_g(identity) + "\t" + std::to_string(shared[i]) + "/" + std::to_string(len[i]) + "\t" + std::to_string(median[i]) + "\t" +
+                    fmt_g(p) + "\t" + R.refs[i].name + "\t" + R.refs[i].comment + "\n";
+        }
+        if (set_size_out) *set_size_out = set_size;
+        return put_text(text, stdout_buf, cap, need);
+    });
 }
 
 extern "C" int mhx_screen_files(const char *ref_msh, const char *const *paths, int n_paths, char *stdout_buf, size_t cap, size_t *need,
@@ -1444,10 +1435,8 @@ extern "C" int mhx_sketch_files(const char *const *paths, int n_paths, int k, ui
                                 const char *out_msh, char *stderr_buf, size_t stderr_cap, size_t *stderr_need,
                                 double *est_genome_size)
 {
-    return guarded("mhx_sketch_files", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_sketch_files", [&]() -> int {
+        int rc = MHX_OK;
         if (!paths || n_paths <= 0 || !out_msh) return fail(MHX_E_ARG, "sketch: paths and output required");
         if (!hash_k_supported(k)) return fail(MHX_E_ARG, "k-mer size %d not supported (1..32)", k);
         SketchSet set;

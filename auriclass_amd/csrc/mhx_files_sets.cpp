@@ -74,9 +74,7 @@ void pack_rows(const std::vector<const RefSketch *> &refs, uint32_t stride, std:
 // the all-vs-refs kernels in the shape they were made for (many queries x few references) instead of 1 x nr per sample.
 int dist_files(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
 {
-    clear_error();
-    int rc = require_engine();
-    if (rc) return rc;
+    int rc = MHX_OK;
     if (n_qry == 1 && (!ref_msh || !qry_msh || !qry_msh[0])) return fail(MHX_E_ARG, "dist: two sketch paths required");
     if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "dist: a reference sketch path and at least one query sketch path required");
     for (int i = 0; i < n_qry; ++i)
@@ -218,12 +216,12 @@ std::string newick_name(const std::string &name)
 
 extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_dist_files", [&] { return dist_files(ref_msh, &qry_msh, 1, stdout_buf, cap, need); });
+    return entry("mhx_dist_files", [&] { return dist_files(ref_msh, &qry_msh, 1, stdout_buf, cap, need); });
 }
 
 extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_msh, int n_qry, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_dist_files_multi", [&] { return dist_files(ref_msh, qry_msh, n_qry, stdout_buf, cap, need); });
+    return entry("mhx_dist_files_multi", [&] { return dist_files(ref_msh, qry_msh, n_qry, stdout_buf, cap, need); });
 }
 
 // `mash triangle a.msh [b.msh ...]`: every pair j < i of the set is compared on the device (mhx_dist_triangle, or
@@ -231,12 +229,9 @@ extern "C" int mhx_dist_files_multi(const char *ref_msh, const char *const *qry_
 // lower-triangle matrix, or the edge list with its two filters.
 extern "C" int mhx_triangle_files(const char *const *paths, int n_paths, const mhx_triangle_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_triangle_files", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_triangle_files", [&]() -> int {
         mhx_triangle_opts o{(uint32_t)sizeof(mhx_triangle_opts), 0, 0, 1.0, 1.0};
-        rc = take_opts("triangle", opts, o);
+        int rc = take_opts("triangle", opts, o);
         if (rc) return rc;
         if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "triangle: max_dist / max_p_value is not a number");
         const bool edge = o.edge != 0 || o.max_dist < 1.0 || o.max_p_value < 1.0; // -d and -v imply -E
@@ -287,12 +282,9 @@ extern "C" int mhx_triangle_files(const char *const *paths, int n_paths, const m
 // and prints a row per reference; the representatives, unchanged, are written as a sketch file of their own on request.
 extern "C" int mhx_cluster_files(const char *const *paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_cluster_files", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_cluster_files", [&]() -> int {
         mhx_cluster_opts o{(uint32_t)sizeof(mhx_cluster_opts), 0, 0, 1.0};
-        rc = take_opts("cluster", opts, o);
+        int rc = take_opts("cluster", opts, o);
         if (rc) return rc;
         if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "cluster: max_dist is not a number");
         if (o.rep != 0 && o.rep != 1) return fail(MHX_E_ARG, "cluster: rep must be 0 (first) or 1 (longest)");
@@ -351,12 +343,9 @@ extern "C" int mhx_cluster_files(const char *const *paths, int n_paths, const mh
 // its n - 1 merges in merge order, and the host prints them as a table or as a Newick dendrogram.
 extern "C" int mhx_tree_files(const char *const *paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_tree_files", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_tree_files", [&]() -> int {
         mhx_tree_opts o{(uint32_t)sizeof(mhx_tree_opts), 0, 0};
-        rc = take_opts("tree", opts, o);
+        int rc = take_opts("tree", opts, o);
         if (rc) return rc;
         SetOfFiles S;
         rc = read_set_of_files("tree", paths, n_paths, S);
@@ -419,15 +408,12 @@ extern "C" int mhx_tree_files(const char *const *paths, int n_paths, const mhx_t
 // references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.
 extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
-    return guarded("mhx_search_files", [&]() -> int {
-        clear_error();
-        int rc = require_engine();
-        if (rc) return rc;
+    return entry("mhx_search_files", [&]() -> int {
         if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "search: a reference sketch path and at least one query sketch path required");
         for (int i = 0; i < n_qry; ++i)
             if (!qry_msh[i]) return fail(MHX_E_ARG, "search: query sketch path %d is null", i);
         mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), 5, 1.0, 1.0};
-        rc = take_opts("search", opts, o);
+        int rc = take_opts("search", opts, o);
         if (rc) return rc;
         if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "search: top must be 1 .. 64");
         if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "search: max_dist / max_p_value is not a number");

@@ -1,6 +1,6 @@
-// mhx_sketcher.h -- the sketcher object as the host engine sees it: mhx_engine.cpp owns it, mhx_engine_screen.cpp runs a
-// screener on top of one in screen mode.  Internal to those two; the other callers hold an mhx_sketcher by pointer only
-// (mhx_engine_internal.h).
+// mhx_sketcher.h -- the sketcher object as the host engine sees it: mhx_engine.cpp owns it, mhx_engine_merge.cpp exports
+// and merges its table across shards, mhx_engine_screen.cpp runs a screener on top of one in screen mode.  Internal to
+// those three; the other callers hold an mhx_sketcher by pointer only (mhx_engine_internal.h).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -105,6 +105,23 @@ struct mhx_sketcher {
 namespace mhx {
 
 constexpr uint32_t kTicketWords = 4096; // tile launches between two clears of the ticket words
+
+// ---- when a sketch is exact: one rule for finish(), the binned merge and mhx_merge_shard_partials -----------------------
+// Below a threshold T every hash was admitted on every occurrence, so the list of qualifying (count >= m) entries <= T is
+// complete and its counts exact.  Either nothing was ever rejected (T still at hash_max) and whatever qualifies is the
+// (possibly short) sketch, or at least s qualifying entries lie below T and the first s are the sketch.  Fewer than s
+// below a lowered T means the bound was too tight for this input: MHX_E_CAPACITY, never a short sketch.  Each caller
+// says so in its own words.
+inline bool sketch_exact(uint64_t qualifying, uint32_t s, uint64_t T, uint64_t hash_max) { return qualifying >= s || T >= hash_max; }
+// The one hash value no table holds, 2^64-1 (kEmptyKey marks a vacant slot): its occurrences travel as a number beside
+// the table, and it is an entry of the result -- the last one -- when nothing was ever rejected and it qualifies.
+inline bool has_max_key_entry(uint64_t T, uint64_t occurrences, uint32_t m) { return T == ~0ull && occurrences >= m; }
+// Its count, and every summed count of a merge, saturates at 2^32-1 (max_key_count, mhx_merge_partials) -- except in
+// finish(), which has always truncated the occurrences of 2^64-1 to their low 32 bits and still does.
+inline uint32_t saturated_count(uint64_t c) { return c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c; }
+
+struct TableArgs;
+TableArgs table_args(mhx_sketcher *sk); // the sketcher's table as the table kernels take it (mhx_engine.cpp)
 
 // the sketcher calls a screener makes on its prober (mhx_engine.cpp)
 int settle(mhx_sketcher *sk);                      // decides the repair question of every unsettled FASTQ push

@@ -81,6 +81,27 @@ def test_sniffers_and_fasta_size(lib):
     assert engine.fasta_total_bases(REFDATA / "NC_001604.1.fasta.gz") == 39937
 
 
+# int-returning entry points that do not answer MHX_E_NO_DEVICE to null and zero arguments on a machine without a GPU, and why
+NEEDS_NO_ENGINE = {
+    "mhx_init": "the call that looks for the device: its own message",
+    "mhx_set_profiling": "a switch of the library, no work",
+    "mhx_bounds": "host only: text",
+    "mhx_msh_write": "host only: container writer",
+    "mhx_fasta_total_bases": "host only: file reader",
+    "mhx_sniff_fastq": "host only: file reader",
+    "mhx_sniff_fasta": "host only: file reader",
+    "mhx_fastq_tail_complete": "host only: a rule over bytes, returns a truth value",
+    "mhx_gunzip_buffer": "host only: decoder",
+    "mhx_gunzip_buffer_mt": "host only: decoder",
+    "mhx_last_inflate_stats": "host only: reads back counters",
+    "mhx_merge_partials": "host only: merge of lists",
+    "mhx_merge_shard_partials": "host only: merge of lists",
+    "mhx_sketcher_merge_info": "host only: reads back what the last merge recorded",
+    "mhx_mst_labels": "host only: labels from a tree",
+    "mhx_gunzip_device": "checks its arguments before the engine (MHX_E_ARG for null input); with input it does refuse: below",
+}
+
+
 @pytest.mark.skipif(HAVE_GPU, reason="checks the no-GPU behaviour")
 def test_compute_calls_fail_loudly_without_gpu(lib, tmp_path):
     with pytest.raises(engine.EngineError) as e:
@@ -99,13 +120,19 @@ def test_compute_calls_fail_loudly_without_gpu(lib, tmp_path):
     # The wrappers above stop in mhx_init.  The file-level set calls and the triangle family at their C entry points, with
     # nothing but null pointers and zeros: each is reached, refuses for want of an engine before it looks at an argument,
     # and says so.
-    for name in ("mhx_dist_files", "mhx_dist_files_multi", "mhx_triangle_files", "mhx_cluster_files", "mhx_tree_files", "mhx_search_files",
-                 "mhx_dist_batch", "mhx_dist_search", "mhx_dist_triangle", "mhx_dist_triangle_edges", "mhx_dist_cluster", "mhx_dist_mst"):
+    # So does every other int-returning entry point that the binding gives argument types to, but for the few named here.
+    compute = [n for n in engine.declared_symbols() if getattr(lib, n).argtypes and getattr(lib, n).restype is ctypes.c_int and n not in NEEDS_NO_ENGINE]
+    assert set(compute) >= {"mhx_dist_files", "mhx_dist_files_multi", "mhx_triangle_files", "mhx_cluster_files", "mhx_tree_files", "mhx_search_files",
+                            "mhx_dist_batch", "mhx_dist_search", "mhx_dist_triangle", "mhx_dist_triangle_edges", "mhx_dist_cluster", "mhx_dist_mst"}
+    assert len(compute) >= 40
+    for name in compute:
         fn = getattr(lib, name)
         assert fn.argtypes, name
         args = [None if t in (ctypes.c_char_p, ctypes.c_void_p) or hasattr(t, "contents") else t(0) for t in fn.argtypes]
         assert fn(*args) == engine.MHX_E_NO_DEVICE, name
         assert b"no GPU engine" in lib.mhx_last_error(), name
+    out_n = ctypes.c_size_t(0)
+    assert lib.mhx_gunzip_device(b"x", 1, None, 0, ctypes.byref(out_n)) == engine.MHX_E_NO_DEVICE and b"no GPU engine" in lib.mhx_last_error()
     # the host-only entry points keep working: bounds text, container writer, gunzip
     assert "Parameters (run with -h for details)" in engine.bounds(27, 0.99)
 
