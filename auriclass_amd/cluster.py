@@ -1,7 +1,9 @@
-"""`python -m auriclass_amd.cluster -d MAX_DIST [--rep first|longest] [-C] [-o REPS.msh] [-p N] SET.msh [SET.msh ...]`: the
-references of all sketch files are one set; those within MAX_DIST of each other are joined (single linkage) on the device,
+"""`python -m auriclass_amd.cluster -d MAX_DIST [--linkage single|complete|average] [--rep first|longest] [-C] [-o REPS.msh] [-p N]
+SET.msh [SET.msh ...]`: the references of all sketch files are one set; those within MAX_DIST of each other are joined (single linkage) on the device,
 and every reference gets a row "cluster\\tsize\\trepresentative\\tmember\\tdegree" (engine.cluster_files).  -o writes the
 representatives, unchanged, as a sketch file: the dereplicated set, which the search, `mash dist` and `mash screen` read.
+--linkage complete|average cuts the complete- or average-linkage merges at MAX_DIST instead (engine.linkage_files): with complete
+linkage every two members of a cluster are within MAX_DIST of each other; the rows have no degree column.
 Inputs are sketch files: a sequence file is refused with the hint to sketch it first.  -d is required: no bound is a sensible
 default for "the same thing".  Exit status 1 with the engine's message when the call fails.  -p (threads) is accepted and
 ignored: the engine has its own."""
@@ -17,6 +19,7 @@ from auriclass_amd import engine
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m auriclass_amd.cluster", description="single-linkage clusters of a sketch set and one representative of each")
     ap.add_argument("-d", dest="max_dist", type=float, required=True, help="references within this distance are neighbours (required)")
+    ap.add_argument("--linkage", choices=["single", "complete", "average"], default="single", help="how clusters are compared [single]")
     ap.add_argument("--rep", choices=sorted(engine.CLUSTER_REPS), default="first", help="representative of a cluster: its first or its longest member [first]")
     ap.add_argument("-C", dest="comment", action="store_true", help="print comments in place of names")
     ap.add_argument("-o", dest="out", default=None, metavar="REPS.msh", help="write the representatives as a sketch file")
@@ -31,7 +34,10 @@ def main(argv: List[str] = None) -> int:
             sys.stderr.write(f"ERROR: the clustering takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
             return 1
     try:
-        text = engine.cluster_files(args.sets, args.max_dist, comment=args.comment, rep=args.rep, out=args.out)
+        if args.linkage == "single":
+            text = engine.cluster_files(args.sets, args.max_dist, comment=args.comment, rep=args.rep, out=args.out)
+        else:
+            text = engine.linkage_files(args.sets, args.linkage, mode="cut", comment=args.comment, max_dist=args.max_dist, rep=args.rep, out=args.out)
     except engine.EngineError as exc:
         sys.stderr.write(exc.message + "\n")
         return 1

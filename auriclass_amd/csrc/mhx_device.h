@@ -255,6 +255,25 @@ hipError_t launch_mst_scan(const MstScan &o, hipStream_t st);
 hipError_t launch_mst_choose(const uint64_t *best, const uint32_t *comp, uint32_t *winner, uint32_t n, hipStream_t st);
 hipError_t launch_mst_hook(const MstHookArgs &o, hipStream_t st);
 
+// complete- and average-linkage agglomeration of one set (rules: mhx_linkage.h, kernels: mhx_linkage.hip): one 64-bit word
+// per cluster pair at the triangle's packed index, and the three launches of a step
+struct LinkArgs {
+    uint64_t *words;       // [n (n - 1) / 2]
+    uint32_t *size, *nn;   // [n] each: members of cluster i (0: none), the best active partner below i
+    uint32_t n;
+    int linkage, k;        // kLinkComplete / kLinkAverage
+    uint32_t *list;        // [n] rows to scan again, appended through ctl[4]
+    uint32_t *ctl;         // [0 .. 3] the pick of the step (LinkPick), [4] rows on the list, [5] non-zero: a pick found no pair
+    unsigned long long *total; // rows scanned again in all steps before the last pick
+    uint32_t *merge_a, *merge_b, *size_out; // [n - 1] the result, entry t written by step t
+    uint64_t *num, *den;
+    double *dist;          // may be null
+};
+hipError_t launch_link_init(const LinkArgs &a, const uint32_t *common, const uint32_t *denom, hipStream_t st);
+hipError_t launch_link_pick(const LinkArgs &a, uint32_t t, hipStream_t st);
+hipError_t launch_link_update(const LinkArgs &a, hipStream_t st);
+hipError_t launch_link_rescan(const LinkArgs &a, hipStream_t st);
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

@@ -1,7 +1,7 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
-// triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files), the single-linkage tree (mhx_tree_files) and the
-// reference-set search (mhx_search_files).  They read sketch files, call the device paths of the engine files and write
-// Mash's text; the ingest of sequence files is in mhx_files.cpp.
+// triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files), the single-linkage tree (mhx_tree_files), complete
+// and average linkage (mhx_linkage_files) and the reference-set search (mhx_search_files).  They read sketch files, call the
+// device paths of the engine files and write Mash's text; the ingest of sequence files is in mhx_files.cpp.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
 #include <fcntl.h>
@@ -212,6 +212,98 @@ std::string newick_name(const std::string &name)
     return out + "'";
 }
 
+// The dendrogram of m = n - 1 merges in merge order (ei / ej: a member, or the id, of either side; dist: the height) as
+// Newick: nodes 0 .. n - 1 are the leaves, node n + e the merge e; a node's height is its merge distance (leaves: 0), a branch
+// is as long as the parent is higher, never negative; the child whose lowest index is lower comes first.  n >= 1.
+template <class Shown>
+int newick_text(const char *what, uint32_t n, const std::vector<uint32_t> &ei, const std::vector<uint32_t> &ej, const std::vector<double> &dist, Shown shown,
+                std::string &text)
+{
+    const uint32_t m = n - 1;
+    std::vector<uint32_t> top(n), left(m), right(m), lowest((size_t)n + m), find(n);
+    std::vector<double> height((size_t)n + m, 0.0);
+    for (uint32_t i = 0; i < n; ++i) { top[i] = i; lowest[i] = i; find[i] = i; }
+    auto root = [&](uint32_t x) { while (find[x] != x) { find[x] = find[find[x]]; x = find[x]; } return x; };
+    for (uint32_t e = 0; e < m; ++e) {
+        const uint32_t ra = root(ei[e]), rb = root(ej[e]);
+        if (ra == rb) return fail(MHX_E_INTERNAL, "%s: merge %u joins one component with itself", what, e);
+        uint32_t a = top[ra], b = top[rb];
+        if (lowest[b] < lowest[a]) std::swap(a, b);
+        left[e] = a; right[e] = b;
+        lowest[n + e] = lowest[a];
+        height[n + e] = dist[e];
+        find[rb] = ra;
+        top[ra] = n + e;
+    }
+    // written without recursion: a chain of 65 535 merges is a tree of that depth
+    struct Item { uint32_t node; int stage; };
+    std::vector<Item> todo{{m ? n + m - 1 : 0u, 0}};
+    auto branch = [&](uint32_t child, uint32_t parent) { const double d = height[parent] - height[child]; return ":" + fmt_g(d > 0.0 ? d : 0.0); };
+    while (!todo.empty()) {
+        const Item it = todo.back();
+        todo.pop_back();
+        if (it.node < n) { text += newick_name(shown(it.node)); continue; }
+        const uint32_t e = it.node - n;
+        if (it.stage == 0) { text += "("; todo.push_back({it.node, 1}); todo.push_back({left[e], 0}); }
+        else if (it.stage == 1) { text += branch(left[e], it.node) + ","; todo.push_back({it.node, 2}); todo.push_back({right[e], 0}); }
+        else text += branch(right[e], it.node) + ")";
+    }
+    text += ";\n";
+    return MHX_OK;
+}
+
+// out_msh of a clustering is refused when a reference carries what that file cannot store
+int check_no_counts(const char *what, const std::vector<const RefSketch *> &refs)
+{
+    for (const RefSketch *r : refs)
+        if (!r->counts.empty())
+            return fail(MHX_E_ARG, "%s: %s carries multiplicity counts, which the output sketch file cannot store", what, r->name.c_str());
+    return MHX_OK;
+}
+
+// The table of a clustering from its labels (label[i]: the lowest member of i's cluster): clusters numbered from 1 by their
+// lowest member, members in index order, a representative per cluster in one pass, a row per reference -- with the degree
+// column when there are degrees --, and the representatives, unchanged, as a sketch file of their own on request.
+int cluster_table(const char *what, const SetOfFiles &S, const std::vector<uint32_t> &label, uint32_t n_clusters, const std::vector<uint32_t> *degree, bool comment,
+                  int rep_rule, const char *out_msh, std::string &text)
+{
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const uint32_t n = S.n();
+    // a cluster's number, size and representative by its label, O(n)
+    std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = label[i];
+        if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "%s: label %u of reference %u is not a cluster's lowest member", what, l, i);
+        if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
+        ++size[l];
+        if (rep_rule == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
+    }
+    if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "%s: %zu labels but %u clusters counted", what, order.size(), n_clusters);
+    auto shown = [&](uint32_t i) -> const std::string & { return comment ? refs[i]->comment : refs[i]->name; };
+    std::vector<std::vector<uint32_t>> members(order.size());
+    for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
+    for (size_t ci = 0; ci < order.size(); ++ci) {
+        const uint32_t l = order[ci];
+        for (uint32_t i : members[ci]) {
+            text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i);
+            if (degree) text += "\t" + std::to_string((*degree)[i]);
+            text += "\n";
+        }
+    }
+    if (!out_msh) return MHX_OK;
+    const uint32_t m = (uint32_t)order.size();
+    std::vector<const char *> names(m), comments(m);
+    std::vector<uint64_t> lengths(m);
+    std::vector<const uint64_t *> hashes(m);
+    std::vector<uint32_t> n_hashes(m);
+    for (uint32_t ci = 0; ci < m; ++ci) {
+        const RefSketch &r = *refs[rep[order[ci]]];
+        names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
+        hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
+    }
+    return mhx_msh_write(out_msh, S.k(), S.F[0].sketch_size, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
+}
+
 } // namespace
 
 extern "C" int mhx_dist_files(const char *ref_msh, const char *qry_msh, char *stdout_buf, size_t cap, size_t *need)
@@ -291,50 +383,16 @@ extern "C" int mhx_cluster_files(const char *const *paths, int n_paths, const mh
         SetOfFiles S;
         rc = read_set_of_files("cluster", paths, n_paths, S);
         if (rc) return rc;
-        const std::vector<const RefSketch *> &refs = S.refs;
         const uint32_t n = S.n();
-        if (out_msh)
-            for (const RefSketch *r : refs)
-                if (!r->counts.empty())
-                    return fail(MHX_E_ARG, "cluster: %s carries multiplicity counts, which the output sketch file cannot store", r->name.c_str());
+        if (out_msh) { rc = check_no_counts("cluster", S.refs); if (rc) return rc; }
         std::vector<uint32_t> label(n), degree(n);
         uint32_t n_clusters = 0;
         uint64_t n_edges = 0;
         rc = mhx_dist_cluster(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), o.max_dist, label.data(), degree.data(), &n_clusters, &n_edges, 0);
         if (rc) return rc;
-        // label[i] is the lowest member of i's cluster: a cluster's number, size and representative by its label, O(n)
-        std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t l = label[i];
-            if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "cluster: label %u of reference %u is not a cluster's lowest member", l, i);
-            if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
-            ++size[l];
-            if (o.rep == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
-        }
-        if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "cluster: %zu labels but %u clusters counted", order.size(), n_clusters);
-        auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
-        std::vector<std::vector<uint32_t>> members(order.size());
-        for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
         std::string text;
-        for (size_t ci = 0; ci < order.size(); ++ci) {
-            const uint32_t l = order[ci];
-            for (uint32_t i : members[ci])
-                text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i) + "\t" + std::to_string(degree[i]) + "\n";
-        }
-        if (out_msh) {
-            const uint32_t m = (uint32_t)order.size();
-            std::vector<const char *> names(m), comments(m);
-            std::vector<uint64_t> lengths(m);
-            std::vector<const uint64_t *> hashes(m);
-            std::vector<uint32_t> n_hashes(m);
-            for (uint32_t ci = 0; ci < m; ++ci) {
-                const RefSketch &r = *refs[rep[order[ci]]];
-                names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
-                hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
-            }
-            rc = mhx_msh_write(out_msh, S.k(), S.F[0].sketch_size, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
-            if (rc) return rc;
-        }
+        rc = cluster_table("cluster", S, label, n_clusters, &degree, o.comment != 0, o.rep, out_msh, text);
+        if (rc) return rc;
         return put_text(text, stdout_buf, cap, need);
     });
 }
@@ -368,37 +426,54 @@ extern "C" int mhx_tree_files(const char *const *paths, int n_paths, const mhx_t
             return put_text(text, stdout_buf, cap, need);
         }
         if (n == 0) return put_text(text, stdout_buf, cap, need);
-        // nodes 0 .. n - 1 are the leaves, node n + e the merge e; a node's height is its merge distance (leaves: 0), a branch
-        // is as long as the parent is higher, never negative; the child whose lowest index is lower comes first
-        std::vector<uint32_t> top(n), left(m), right(m), lowest((size_t)n + m), find(n);
-        std::vector<double> height((size_t)n + m, 0.0);
-        for (uint32_t i = 0; i < n; ++i) { top[i] = i; lowest[i] = i; find[i] = i; }
-        auto root = [&](uint32_t x) { while (find[x] != x) { find[x] = find[find[x]]; x = find[x]; } return x; };
-        for (uint32_t e = 0; e < m; ++e) {
-            const uint32_t ra = root(ei[e]), rb = root(ej[e]);
-            if (ra == rb) return fail(MHX_E_INTERNAL, "tree: merge %u joins one component with itself", e);
-            uint32_t a = top[ra], b = top[rb];
-            if (lowest[b] < lowest[a]) std::swap(a, b);
-            left[e] = a; right[e] = b;
-            lowest[n + e] = lowest[a];
-            height[n + e] = dist[e];
-            find[rb] = ra;
-            top[ra] = n + e;
+        rc = newick_text("tree", n, ei, ej, dist, shown, text);
+        if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// Complete / average linkage at file level: the set is read as the tree reads it, mhx_dist_linkage gives the n - 1 merges in
+// merge order, and the host prints them as a table, as a Newick dendrogram, or cuts them at max_dist and prints the clusters as
+// the dereplication does.
+extern "C" int mhx_linkage_files(const char *const *paths, int n_paths, const mhx_linkage_opts *opts, const char *out_msh, char *stdout_buf, size_t cap,
+                                 size_t *need)
+{
+    return entry("mhx_linkage_files", [&]() -> int {
+        mhx_linkage_opts o{(uint32_t)sizeof(mhx_linkage_opts), 0, 1, 0, 0, 1.0};
+        int rc = take_opts("linkage", opts, o);
+        if (rc) return rc;
+        if (o.linkage != 1 && o.linkage != 2) return fail(MHX_E_ARG, "linkage: linkage must be 1 (complete) or 2 (average)");
+        if (o.mode < 0 || o.mode > 2) return fail(MHX_E_ARG, "linkage: mode must be 0 (merges), 1 (Newick) or 2 (cut)");
+        if (o.rep != 0 && o.rep != 1) return fail(MHX_E_ARG, "linkage: rep must be 0 (first) or 1 (longest)");
+        if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "linkage: max_dist is not a number");
+        if (out_msh && o.mode != 2) return fail(MHX_E_ARG, "linkage: an output sketch file goes with the cut (mode 2) only");
+        SetOfFiles S;
+        rc = read_set_of_files("linkage", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        if (out_msh) { rc = check_no_counts("linkage", refs); if (rc) return rc; }
+        const uint32_t m = n ? n - 1 : 0;
+        std::vector<uint32_t> ma(m), mb(m), size(m);
+        std::vector<uint64_t> num(m), den(m);
+        std::vector<double> dist(m);
+        rc = mhx_dist_linkage(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), o.linkage, ma.data(), mb.data(), size.data(), num.data(), den.data(),
+                              dist.data(), 0);
+        if (rc) return rc;
+        auto shown = [&](uint32_t i) -> const std::string & { return o.comment ? refs[i]->comment : refs[i]->name; };
+        std::string text;
+        if (o.mode == 0) {
+            for (uint32_t e = 0; e < m; ++e)
+                text += shown(ma[e]) + "\t" + shown(mb[e]) + "\t" + fmt_g(dist[e]) + "\t" + std::to_string(size[e]) + "\t" + std::to_string(n - 1 - e) + "\n";
+        } else if (o.mode == 1) {
+            if (n) { rc = newick_text("linkage", n, ma, mb, dist, shown, text); if (rc) return rc; }
+        } else {
+            std::vector<uint32_t> label(n);
+            const int64_t n_clusters = mhx_linkage_labels(ma.data(), mb.data(), dist.data(), n, o.max_dist, label.data());
+            if (n_clusters < 0) return (int)n_clusters;
+            rc = cluster_table("linkage", S, label, (uint32_t)n_clusters, nullptr, o.comment != 0, o.rep, out_msh, text);
+            if (rc) return rc;
         }
-        // written without recursion: a chain of 65 535 merges is a tree of that depth
-        struct Item { uint32_t node; int stage; };
-        std::vector<Item> todo{{m ? n + m - 1 : 0u, 0}};
-        auto branch = [&](uint32_t child, uint32_t parent) { const double d = height[parent] - height[child]; return ":" + fmt_g(d > 0.0 ? d : 0.0); };
-        while (!todo.empty()) {
-            const Item it = todo.back();
-            todo.pop_back();
-            if (it.node < n) { text += newick_name(shown(it.node)); continue; }
-            const uint32_t e = it.node - n;
-            if (it.stage == 0) { text += "("; todo.push_back({it.node, 1}); todo.push_back({left[e], 0}); }
-            else if (it.stage == 1) { text += branch(left[e], it.node) + ","; todo.push_back({it.node, 2}); todo.push_back({right[e], 0}); }
-            else text += branch(right[e], it.node) + ")";
-        }
-        text += ";\n";
         return put_text(text, stdout_buf, cap, need);
     });
 }

@@ -174,6 +174,16 @@ def load() -> ctypes.CDLL:
                                    c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_mst_labels.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint32, c.c_int, c.c_double, c.c_void_p, u32p]
         L.mhx_tree_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(TreeOpts), c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_linkage"):   # (or older than complete / average linkage)
+        L.mhx_dist_linkage.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_int, c.c_void_p, c.c_void_p,
+                                       c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_last_linkage_rescans.restype = c.c_int
+        L.mhx_linkage_labels.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint32, c.c_double, c.c_void_p]
+        L.mhx_linkage_labels.restype = c.c_int64      # host only: the number of clusters, or a negative MHX_E_* code
+        L.mhx_linkage_fixed_distance.argtypes = [c.c_uint32, c.c_uint32, c.c_int]
+        L.mhx_linkage_fixed_distance.restype = c.c_uint64   # host only
+        L.mhx_linkage_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(LinkageOpts), c.c_char_p, c.c_char_p, c.c_size_t,
+                                        c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
         L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -371,6 +381,36 @@ def tree_files(paths: Sequence, comment: bool = False, newick: bool = False) -> 
     arr = (ctypes.c_char_p * len(files))(*files)
     opts = TreeOpts(ctypes.sizeof(TreeOpts), int(bool(comment)), int(bool(newick)))
     return _text_call(lambda buf, cap, need: load().mhx_tree_files(arr, len(files), ctypes.byref(opts), buf, cap, need), guess=1 << 20)
+
+
+class LinkageOpts(ctypes.Structure):
+    """mhx_linkage_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("linkage", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("rep", ctypes.c_int32), ("max_dist", ctypes.c_double)]
+
+
+LINKAGES = {"complete": 1, "average": 2}
+LINKAGE_MODES = {"merges": 0, "newick": 1, "cut": 2}
+
+
+def linkage_files(paths: Sequence, linkage: str, mode: str = "merges", comment: bool = False, max_dist: float = 1.0, rep: str = "first",
+                  out=None) -> str:
+    """Complete or average linkage of the references of all sketch files (one set).  mode "merges": a row per merge in merge
+    order, "name_a\\tname_b\\tdist\\tsize\\tclusters"; "newick": the dendrogram as tree_files prints one; "cut": the clusters
+    at max_dist, a row per reference "cluster\\tsize\\trepresentative\\tmember", ordered as cluster_files orders them, with rep
+    and out (the representatives as a sketch file) as there."""
+    if linkage not in LINKAGES:
+        raise ValueError("linkage_files: linkage must be 'complete' or 'average'")
+    if mode not in LINKAGE_MODES:
+        raise ValueError("linkage_files: mode must be 'merges', 'newick' or 'cut'")
+    if rep not in CLUSTER_REPS:
+        raise ValueError("linkage_files: rep must be 'first' or 'longest'")
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = LinkageOpts(ctypes.sizeof(LinkageOpts), int(bool(comment)), LINKAGES[linkage], LINKAGE_MODES[mode], CLUSTER_REPS[rep], float(max_dist))
+    out_path = None if out is None else os.fsencode(str(out))
+    return _text_call(lambda buf, cap, need: load().mhx_linkage_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -950,6 +990,64 @@ def mst_labels(edge_i, edge_j, common, denom, n: int, k: int, max_dist: float) -
     n_clusters = ctypes.c_uint32(0)
     _check(load().mhx_mst_labels(*(a.ctypes.data for a in cols), n, k, float(max_dist), label.ctypes.data, ctypes.byref(n_clusters)))
     return label, int(n_clusters.value)
+
+
+def _linkage_code(linkage) -> int:
+    code = LINKAGES.get(linkage, linkage)
+    if code not in (1, 2):
+        raise ValueError("linkage must be 'complete' or 'average'")
+    return int(code)
+
+
+def dist_linkage(rows: np.ndarray, lens: np.ndarray, k: int, s: int, linkage
+                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Complete ("complete", 1) or average ("average", 2: UPGMA) linkage of ONE set of hash lists (rows [n, stride], lens [n], as
+    dist_triangle takes them): the n - 1 merges in merge order, (merge_a, merge_b, size, num, den, dist) -- the two cluster ids
+    (a cluster's id is its lowest member, merge_a > merge_b, the merged cluster keeps merge_b), the members after the merge, the
+    linkage value num / den (complete: common / denom of the decisive leaf pair; average: the sum of the fixed-point distances
+    over |A| |B|) and the height (complete: the host libm distance of dist_triangle; average: num / den * 2^-32).
+    linkage_labels cuts the merges at any distance."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    m = max(n - 1, 0)
+    merge_a, merge_b, size = (np.zeros(m, dtype=np.uint32) for _ in range(3))
+    num, den = (np.zeros(m, dtype=np.uint64) for _ in range(2))
+    dist = np.zeros(m, dtype=np.float64)
+    _check(load().mhx_dist_linkage(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, _linkage_code(linkage), merge_a.ctypes.data,
+                                   merge_b.ctypes.data, size.ctypes.data, num.ctypes.data, den.ctypes.data, dist.ctypes.data, 0))
+    return merge_a, merge_b, size, num, den, dist
+
+
+def dist_linkage_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, linkage, merge_a_ptr: int, merge_b_ptr: int,
+                        size_ptr: int, num_ptr: int, den_ptr: int, dist_ptr: int = 0) -> int:
+    """Device pointers in and out (three uint32 [n - 1], two uint64 [n - 1] and dist, double [n - 1] or 0): the merges in merge
+    order, every integer exact and the same from call to call, dist in the device's arithmetic.  Returns the number of merges,
+    n - 1 (0 for n <= 1); the rows scanned again are load().mhx_last_linkage_rescans()."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_linkage(v(rows_ptr), v(len_ptr), n, stride, k, s, _linkage_code(linkage), v(merge_a_ptr), v(merge_b_ptr), v(size_ptr),
+                                   v(num_ptr), v(den_ptr), v(dist_ptr or None), 1))
+    return max(n - 1, 0)
+
+
+def linkage_labels(merge_a, merge_b, dist, n: int, max_dist: float) -> Tuple[np.ndarray, int]:
+    """The clusters of the merges of dist_linkage at max_dist, on the host (mhx_linkage_labels: no device needed): the merges
+    from the first one on while dist[t] <= max_dist; (label, n_clusters), label[i] = the lowest index of i's cluster."""
+    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (merge_a, merge_b))
+    d = np.ascontiguousarray(dist, dtype=np.float64)
+    assert all(x.shape == (max(n - 1, 0),) for x in (a, b, d))
+    label = np.zeros(n, dtype=np.uint32)
+    rc = load().mhx_linkage_labels(a.ctypes.data, b.ctypes.data, d.ctypes.data, n, float(max_dist), label.ctypes.data)
+    if rc < 0:
+        _check(int(rc))
+    return label, int(rc)
+
+
+def linkage_fixed_distance(common: int, denom: int, k: int) -> int:
+    """The fixed-point distance of average linkage in units of 2^-32 (mhx_linkage_fixed_distance: integers alone, no device
+    needed); 2^64 - 1 for arguments outside its domain."""
+    return int(load().mhx_linkage_fixed_distance(common, denom, k))
 
 
 def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0

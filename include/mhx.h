@@ -23,6 +23,10 @@
  *                        linkage tree of a set, every cut of mhx_dist_cluster at once (buffer level; engine.dist_mst)
  *   mhx_tree_files    <- no mash command: the same for sketch files, as a table of merges or a Newick dendrogram
  *                        (python -m auriclass_amd.tree)
+ *   mhx_dist_linkage  <- no mash command: `mash triangle` followed by a hierarchical clustering on the host -- complete and
+ *                        average linkage (UPGMA) of a set on the device (buffer level; engine.dist_linkage)
+ *   mhx_linkage_files <- no mash command: the same for sketch files, as merges, a Newick dendrogram or the cut at a distance
+ *                        (python -m auriclass_amd.tree / auriclass_amd.cluster --linkage complete|average)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -375,7 +379,7 @@ int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len, uint32_t 
  * The triangle's blocks feed a lock-free union-find on the device: no edge list and nothing of
  * size n^2 exists anywhere; the workspace is the triangle's plus 4 (s + 1) bytes.  Geometry, MHX_TRI_GEOMETRY and
  * MHX_TRI_QBATCH are the triangle's; mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges
- * report this call too.  Not lifted here: the limit of 65 536 lists; linkages other than single. */
+ * report this call too.  Not lifted here: the limit of 65 536 lists.  Complete and average linkage: mhx_dist_linkage below. */
 int mhx_dist_cluster(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, double max_dist,
                      uint32_t *label, uint32_t *degree, uint32_t *n_clusters, uint64_t *n_edges, int device_ptrs);
 /* The same at file level: the references of all files form one set, read and checked as mhx_triangle_files does (k / seed /
@@ -426,7 +430,8 @@ int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_clust
  * passes (behind the set-up of parent and comp, which is not in it) to the last of the last round.
  * mhx_last_dist_fallback_blocks counts the blocks the generic kernel redid ONCE: those of the triangle (stored), those of the
  * FIRST round (recomputed, where every later round redoes the same blocks again without counting them).
- * mhx_last_dist_ranges is the triangle's.  Not built: average and complete linkage, a sorted device form, more than 65 536 lists. */
+ * mhx_last_dist_ranges is the triangle's.  Not built: a sorted device form, more than 65 536 lists (average and complete linkage:
+ * mhx_dist_linkage below). */
 int mhx_dist_mst(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, uint32_t *edge_i,
                  uint32_t *edge_j, uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
 int mhx_last_mst_rounds(void);
@@ -455,6 +460,61 @@ typedef struct mhx_tree_opts {
     int32_t newick;       /* non-zero: the dendrogram in Newick format in place of the merge table */
 } mhx_tree_opts;
 int mhx_tree_files(const char *const *msh_paths, int n_paths, const mhx_tree_opts *opts, char *stdout_buf, size_t cap, size_t *need);
+
+/* COMPLETE- and AVERAGE-linkage agglomeration of ONE set (linkage = 1 complete, 2 average; single linkage is mhx_dist_mst):
+ * rows / len / n / stride / k / s as mhx_dist_triangle takes them, with its checks (n > 65 536, k, s, stride, len[i] > stride,
+ * null pointers: MHX_E_ARG), s >= 2^20, another linkage value or a null output (dist excepted): MHX_E_ARG, all before anything
+ * is launched.  n == 0 and n == 1: MHX_OK, nothing written.
+ * Clusters carry the index of their lowest member.  Every step merges the pair of clusters with the smallest linkage value,
+ * among equal values the pair with the lower `lo` id, then the lower `hi` id; the merged cluster keeps id lo.  n - 1 steps.
+ *   complete: the value of a cluster pair is the (common, denom) of its worst leaf pair -- the smallest Jaccard index, compared
+ *             exactly as mhx_dist_mst compares (common == denom counts as 1/1); of two equal indices the greater denom stays.
+ *   average:  the exact rational num / den, num the sum over all leaf pairs of the fixed-point distance q (below), den = |A| |B|,
+ *             compared by the cross products in 128 bits (UPGMA).
+ * Outputs, [n - 1] each, in merge order in both pointer forms: merge_a > merge_b the two ids, size the members after the
+ * merge, num / den the value (complete: common / denom of the decisive pair), dist (may be NULL) the height -- complete: the
+ * distance mhx_dist_triangle gives for the decisive pair; average: ((double)num / (double)den) * 2^-32.  Host pointers: dist is
+ * host arithmetic (libm for complete).  device_ptrs != 0 => rows, len and the six outputs are device pointers; every integer
+ * output is exact and the same from run to run, dist is the device's arithmetic.
+ * On the device: the packed triangle of mhx_dist_triangle's dense mode becomes one 64-bit word per
+ * cluster pair; a step is three launches -- one workgroup picks among the rows' cached nearest partners, one thread per
+ * cluster combines its two words, the rows that lost their cached partner are scanned again -- and the host enqueues all steps
+ * without reading anything back between them.  Memory: 8 n (n - 1) / 2 bytes of words for the whole call plus as many for the
+ * triangle's two arrays until the words are made (peak 16 n (n - 1) / 2 bytes).  The words must fit MHX_LINKAGE_STORE_MB
+ * (default 4096: n <= 32 768), otherwise MHX_E_CAPACITY; there is no recomputed form.  mhx_last_linkage_rescans() reports the rows
+ * scanned again by the steps of the last call; the mhx_last_dist_* diagnostics report the triangle plus the steps.
+ * Not built: neighbour joining, Ward, a recomputed pair source, a p-value column, more than 65 536 lists. */
+int mhx_dist_linkage(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int linkage,
+                     uint32_t *merge_a, uint32_t *merge_b, uint32_t *size, uint64_t *num, uint64_t *den, double *dist, int device_ptrs);
+int mhx_last_linkage_rescans(void);
+/* The cut of those merges at max_dist, on the host (no device needed): the merges from the first one on while dist[t] <=
+ * max_dist, none behind the first that is not; label[n], label[i] = the lowest index of i's cluster.  Returns the number of
+ * clusters, or a negative MHX_E_* code (MHX_E_ARG: null pointers, a max_dist that is not a number, a merge that does not name
+ * ids merge_b < merge_a < n).  With complete linkage every two members of a cluster are within max_dist of each other. */
+int64_t mhx_linkage_labels(const uint32_t *merge_a, const uint32_t *merge_b, const double *dist, uint32_t n, double max_dist, uint32_t *label);
+/* The fixed-point distance of average linkage in units of 2^-32, integers alone (mhx_linkage.h), on the host: 0 for common ==
+ * denom, 2^32 for common == 0, else min(2^32, floor(floor(log2((common + denom) / (2 common)) * 2^40) * floor(ln 2 * 2^32) / 2^40) / k);
+ * within 4 units of the distance mhx_dist_triangle gives.  common > denom, denom >= 2^21 or k outside 1 .. 32: UINT64_MAX. */
+uint64_t mhx_linkage_fixed_distance(uint32_t common, uint32_t denom, int k);
+/* The same at file level: the set is read and checked as mhx_tree_files reads it.  mode 0, one row per merge in merge order:
+ *     name_a\tname_b\tdist\tsize\tclusters\n
+ * the names of the two ids (comments when `comment` is set), the height as the triangle prints a distance, the members of the
+ * merged cluster and the clusters left.  mode 1: the Newick dendrogram by the rules of mhx_tree_files.  mode 2: the cut at
+ * max_dist, one row per reference, clusters and members ordered as mhx_cluster_files orders them:
+ *     cluster\tsize\trepresentative\tmember\n
+ * rep and out_msh as there (out_msh in mode 2 only), the refusal for multiplicity counts included; no degree column: nothing
+ * here computes neighbours.  opts == NULL means {sizeof, 0, 1, 0, 0, 1.0}.  MHX_E_ARG: struct_size != sizeof(mhx_linkage_opts),
+ * linkage outside 1 .. 2, mode outside 0 .. 2, rep outside 0 .. 1, a max_dist that is not a number, out_msh outside mode 2. */
+typedef struct mhx_linkage_opts {
+    uint32_t struct_size; /* sizeof(mhx_linkage_opts) */
+    int32_t comment;      /* non-zero: print comments in place of names */
+    int32_t linkage;      /* 1 complete, 2 average */
+    int32_t mode;         /* 0 merge table, 1 Newick, 2 the cut at max_dist */
+    int32_t rep;          /* mode 2: 0 first, 1 longest */
+    double max_dist;      /* mode 2: merges up to this height */
+} mhx_linkage_opts;
+int mhx_linkage_files(const char *const *msh_paths, int n_paths, const mhx_linkage_opts *opts, const char *out_msh, char *stdout_buf,
+                      size_t cap, size_t *need);
 
 /* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
  * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
