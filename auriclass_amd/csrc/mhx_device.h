@@ -274,6 +274,28 @@ hipError_t launch_link_pick(const LinkArgs &a, uint32_t t, hipStream_t st);
 hipError_t launch_link_update(const LinkArgs &a, hipStream_t st);
 hipError_t launch_link_rescan(const LinkArgs &a, hipStream_t st);
 
+// neighbour joining over one set (rules: mhx_nj.h, kernels: mhx_nj.hip): one 64-bit distance word per pair of nodes at the
+// triangle's packed index, the row sums r, the compacted list of active ids with the running sums of their row lengths (twice:
+// join t reads copy t & 1, its update writes the other), and the three launches of a join
+struct NjCand;
+struct NjArgs {
+    uint64_t *words;       // [n (n - 1) / 2]
+    uint64_t *r;           // [n]
+    uint32_t n;
+    int k;
+    uint32_t *act[2];      // [n] each
+    uint64_t *pre[2];      // [n + 1] each
+    NjCand *cand;          // [kNjMaxBlocks] the candidates of the scan's workgroups
+    uint64_t *ctl;         // [0 .. 3] the pick of the step (NjPick: a, b, pos_a, d), [4] updates the clamp changed, [5] non-zero: a join found no pair
+    uint32_t *join_a, *join_b; // [n - 1] the result, entry t written by join t
+    uint64_t *d, *r_a, *r_b;
+    double *len_a, *len_b; // may be null
+};
+hipError_t launch_nj_init(const NjArgs &a, const uint32_t *common, const uint32_t *denom, hipStream_t st);
+hipError_t launch_nj_scan(const NjArgs &a, uint32_t t, hipStream_t st);   // join t among n - t > 2 nodes
+hipError_t launch_nj_join(const NjArgs &a, uint32_t t, hipStream_t st);
+hipError_t launch_nj_update(const NjArgs &a, uint32_t t, hipStream_t st); // n - t > 2
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

@@ -135,6 +135,7 @@ struct Engine {
     int last_mst_rounds = 0;     // Boruvka rounds of the last mhx_dist_mst call
     int last_mst_stored = -1;    // its pair source: 1 stored, 0 recomputed, -1 none ran
     int last_linkage_rescans = 0; // rows scanned again in the steps of the last mhx_dist_linkage call
+    uint64_t last_nj_clamps = 0;  // updates the clamp at 0 changed in the last mhx_dist_nj call
     PinnedArray<uint8_t> dist_img; // pinned image of the reference sketch file of mhx_dist_files
     // bulk file ingest: pinned staging ring (allocated on first use, kept)
     static constexpr int kPinnedSlots = 4;

@@ -1,7 +1,8 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
 // triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files), the single-linkage tree (mhx_tree_files), complete
-// and average linkage (mhx_linkage_files) and the reference-set search (mhx_search_files).  They read sketch files, call the
-// device paths of the engine files and write Mash's text; the ingest of sequence files is in mhx_files.cpp.
+// and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
+// (mhx_search_files).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
+// of sequence files is in mhx_files.cpp.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
 #include <fcntl.h>
@@ -474,6 +475,71 @@ extern "C" int mhx_linkage_files(const char *const *paths, int n_paths, const mh
             rc = cluster_table("linkage", S, label, (uint32_t)n_clusters, nullptr, o.comment != 0, o.rep, out_msh, text);
             if (rc) return rc;
         }
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// Neighbour joining at file level: the set is read as the tree reads it, mhx_dist_nj gives the n - 1 joins in join order, and
+// the host prints them as a table or as an UNROOTED Newick tree: every join but the last is a node "(X:len,Y:len)", the
+// root is the trifurcation of the two children of join n - 3 and the node that is left, whose branch is the distance of the
+// last join; children in the order of their lowest leaf (a node's id), lengths "%g" of max(0, len).
+extern "C" int mhx_nj_files(const char *const *paths, int n_paths, int comment, int newick, char *stdout_buf, size_t cap, size_t *need)
+{
+    return entry("mhx_nj_files", [&]() -> int {
+        SetOfFiles S;
+        int rc = read_set_of_files("nj", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        const uint32_t m = n ? n - 1 : 0;
+        std::vector<uint32_t> ja(m), jb(m);
+        std::vector<uint64_t> d(m), ra(m), rb(m);
+        std::vector<double> la(m), lb(m);
+        rc = mhx_dist_nj(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), ja.data(), jb.data(), d.data(), ra.data(), rb.data(), la.data(), lb.data(), 0);
+        if (rc) return rc;
+        auto shown = [&](uint32_t i) -> const std::string & { return comment ? refs[i]->comment : refs[i]->name; };
+        auto dist = [&](uint32_t t) { return (double)d[t] * (1.0 / 4294967296.0); };
+        std::string text;
+        if (!newick) {
+            for (uint32_t t = 0; t < m; ++t)
+                text += shown(ja[t]) + "\t" + shown(jb[t]) + "\t" + fmt_g(la[t]) + "\t" + fmt_g(lb[t]) + "\t" + fmt_g(dist(t)) + "\t" + std::to_string(n - 1 - t) + "\n";
+            return put_text(text, stdout_buf, cap, need);
+        }
+        if (n == 0) return put_text(text, stdout_buf, cap, need);
+        // nodes 0 .. n - 1 are the leaves, node n + t the join t; top[id]: the node that stands for the active id
+        struct Node { uint32_t kid[3]; double len[3]; int kids; };
+        std::vector<Node> nodes;
+        std::vector<uint32_t> top(n);
+        for (uint32_t i = 0; i < n; ++i) top[i] = i;
+        const uint32_t binary = n >= 3 ? n - 2 : m; // joins that are nodes; the last of them takes the third child
+        for (uint32_t t = 0; t < binary; ++t) {
+            if (ja[t] >= n || jb[t] >= ja[t]) return fail(MHX_E_INTERNAL, "nj: join %u does not name two nodes b < a", t);
+            nodes.push_back(Node{{top[jb[t]], top[ja[t]], 0}, {lb[t], la[t], 0.0}, 2});
+            top[jb[t]] = n + t;
+        }
+        if (n >= 3) {
+            Node &root = nodes.back();
+            const uint32_t u = jb[n - 3], other = ja[n - 2] == u ? jb[n - 2] : ja[n - 2];
+            if ((ja[n - 2] != u && jb[n - 2] != u) || other >= n || other == ja[n - 3]) return fail(MHX_E_INTERNAL, "nj: the last join does not take up the one before it");
+            int at = other < jb[n - 3] ? 0 : (other < ja[n - 3] ? 1 : 2); // by lowest leaf
+            for (int x = 2; x > at; --x) { root.kid[x] = root.kid[x - 1]; root.len[x] = root.len[x - 1]; }
+            root.kid[at] = top[other]; root.len[at] = dist(n - 2);
+            root.kids = 3;
+        }
+        // written without recursion: a chain of 65 535 joins is a tree of that depth
+        struct Item { uint32_t node; int at; };
+        std::vector<Item> todo{{nodes.empty() ? 0u : n + (uint32_t)nodes.size() - 1, 0}};
+        while (!todo.empty()) {
+            Item &it = todo.back();
+            if (it.node < n) { text += newick_name(shown(it.node)); todo.pop_back(); continue; }
+            const Node &nd = nodes[it.node - n];
+            if (it.at == 0) text += "(";
+            else text += ":" + fmt_g(nd.len[it.at - 1] > 0.0 ? nd.len[it.at - 1] : 0.0) + (it.at < nd.kids ? "," : ")");
+            if (it.at == nd.kids) { todo.pop_back(); continue; }
+            const uint32_t kid = nd.kid[it.at++];
+            todo.push_back({kid, 0});
+        }
+        text += ";\n";
         return put_text(text, stdout_buf, cap, need);
     });
 }

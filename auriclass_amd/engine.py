@@ -184,6 +184,11 @@ def load() -> ctypes.CDLL:
         L.mhx_linkage_fixed_distance.restype = c.c_uint64   # host only
         L.mhx_linkage_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(LinkageOpts), c.c_char_p, c.c_char_p, c.c_size_t,
                                         c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_nj"):   # (or older than neighbour joining)
+        L.mhx_dist_nj.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p,
+                                  c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_last_nj_clamps.restype = c.c_uint64
+        L.mhx_nj_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.c_int, c.c_int, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
         L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -411,6 +416,17 @@ def linkage_files(paths: Sequence, linkage: str, mode: str = "merges", comment: 
     opts = LinkageOpts(ctypes.sizeof(LinkageOpts), int(bool(comment)), LINKAGES[linkage], LINKAGE_MODES[mode], CLUSTER_REPS[rep], float(max_dist))
     out_path = None if out is None else os.fsencode(str(out))
     return _text_call(lambda buf, cap, need: load().mhx_linkage_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
+
+
+def nj_files(paths: Sequence, comment: bool = False, newick: bool = False) -> str:
+    """Neighbour joining over the references of all sketch files (one set), a row per join in join order:
+    "name_a\\tname_b\\tlen_a\\tlen_b\\tdist\\tnodes" -- the two nodes (a node is named by its lowest leaf; comments under
+    `comment`), their branch lengths, their distance and the nodes left after the join.  newick: the unrooted tree in Newick
+    format instead, its root the trifurcation the last two joins leave."""
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    return _text_call(lambda buf, cap, need: load().mhx_nj_files(arr, len(files), int(bool(comment)), int(bool(newick)), buf, cap, need), guess=1 << 20)
 
 
 def screen_identity(shared: int, n: int, k: int) -> float:
@@ -1048,6 +1064,37 @@ def linkage_fixed_distance(common: int, denom: int, k: int) -> int:
     """The fixed-point distance of average linkage in units of 2^-32 (mhx_linkage_fixed_distance: integers alone, no device
     needed); 2^64 - 1 for arguments outside its domain."""
     return int(load().mhx_linkage_fixed_distance(common, denom, k))
+
+
+def dist_nj(rows: np.ndarray, lens: np.ndarray, k: int, s: int
+            ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Neighbour joining over ONE set of hash lists (rows [n, stride], lens [n], as dist_triangle takes them): the n - 1 joins
+    in join order, (join_a, join_b, d, r_a, r_b, len_a, len_b) -- the two node ids (a node's id is its lowest leaf, join_a >
+    join_b, the new node keeps join_b), their distance and their row sums in units of 2^-32 as they were before the join, and
+    the two branch lengths (they may be negative).  Distances are the fixed-point distance of the average linkage and an
+    update never goes below 0 (a deviation from the textbook; load().mhx_last_nj_clamps() counts how often that mattered)."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    m = max(n - 1, 0)
+    join_a, join_b = (np.zeros(m, dtype=np.uint32) for _ in range(2))
+    d, r_a, r_b = (np.zeros(m, dtype=np.uint64) for _ in range(3))
+    len_a, len_b = (np.zeros(m, dtype=np.float64) for _ in range(2))
+    _check(load().mhx_dist_nj(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, join_a.ctypes.data, join_b.ctypes.data, d.ctypes.data,
+                              r_a.ctypes.data, r_b.ctypes.data, len_a.ctypes.data, len_b.ctypes.data, 0))
+    return join_a, join_b, d, r_a, r_b, len_a, len_b
+
+
+def dist_nj_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, join_a_ptr: int, join_b_ptr: int, d_ptr: int, r_a_ptr: int,
+                   r_b_ptr: int, len_a_ptr: int = 0, len_b_ptr: int = 0) -> int:
+    """Device pointers in and out (two uint32 [n - 1], three uint64 [n - 1] and len_a, len_b, double [n - 1], both or neither 0):
+    the joins in join order, the same bytes as dist_nj gives.  rows_ptr / len_ptr may be what sketch_segments_device wrote.
+    Returns the number of joins, n - 1 (0 for n <= 1)."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_nj(v(rows_ptr), v(len_ptr), n, stride, k, s, v(join_a_ptr), v(join_b_ptr), v(d_ptr), v(r_a_ptr), v(r_b_ptr),
+                              v(len_a_ptr or None), v(len_b_ptr or None), 1))
+    return max(n - 1, 0)
 
 
 def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0

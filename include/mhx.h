@@ -27,6 +27,10 @@
  *                        average linkage (UPGMA) of a set on the device (buffer level; engine.dist_linkage)
  *   mhx_linkage_files <- no mash command: the same for sketch files, as merges, a Newick dendrogram or the cut at a distance
  *                        (python -m auriclass_amd.tree / auriclass_amd.cluster --linkage complete|average)
+ *   mhx_dist_nj       <- no mash command: `mash triangle` followed by a neighbour-joining tool on the host (the mashtree
+ *                        workflow) -- the unrooted tree of a set on the device (buffer level; engine.dist_nj)
+ *   mhx_nj_files      <- no mash command: the same for sketch files, as a table of joins or an unrooted Newick tree
+ *                        (python -m auriclass_amd.tree --nj)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -483,7 +487,7 @@ int mhx_tree_files(const char *const *msh_paths, int n_paths, const mhx_tree_opt
  * triangle's two arrays until the words are made (peak 16 n (n - 1) / 2 bytes).  The words must fit MHX_LINKAGE_STORE_MB
  * (default 4096: n <= 32 768), otherwise MHX_E_CAPACITY; there is no recomputed form.  mhx_last_linkage_rescans() reports the rows
  * scanned again by the steps of the last call; the mhx_last_dist_* diagnostics report the triangle plus the steps.
- * Not built: neighbour joining, Ward, a recomputed pair source, a p-value column, more than 65 536 lists. */
+ * Neighbour joining: mhx_dist_nj below.  Not built: Ward, a recomputed pair source, a p-value column, more than 65 536 lists. */
 int mhx_dist_linkage(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int linkage,
                      uint32_t *merge_a, uint32_t *merge_b, uint32_t *size, uint64_t *num, uint64_t *den, double *dist, int device_ptrs);
 int mhx_last_linkage_rescans(void);
@@ -515,6 +519,43 @@ typedef struct mhx_linkage_opts {
 } mhx_linkage_opts;
 int mhx_linkage_files(const char *const *msh_paths, int n_paths, const mhx_linkage_opts *opts, const char *out_msh, char *stdout_buf,
                       size_t cap, size_t *need);
+
+/* NEIGHBOUR JOINING over ONE set: the unrooted tree of the distances of all pairs.  rows / len / n / stride / k / s as
+ * mhx_dist_triangle takes them, with its checks (n > 65 536, k, s, stride, len[i] > stride, null pointers: MHX_E_ARG), s >= 2^20
+ * or a null output (len_a and len_b excepted, which may both be NULL): MHX_E_ARG, all before anything is launched.  n == 0 and
+ * n == 1: MHX_OK, nothing written.
+ * The rule, all of it in integers: d(i, j) of two leaves is mhx_linkage_fixed_distance of the pair, in units of 2^-32.  A node
+ * carries the id of its lowest leaf; m = n nodes are active at the start; r_i is the sum of d(i, c) over the active c != i.
+ * While m > 2 the pair with the smallest Q(i, j) = (m - 2) d(i, j) - r_i - r_j (signed 64 bits) joins, among equal Q the pair with
+ * the lower `lo` id, then the lower `hi` id.  With b < a, b becomes the new node u and a dies; for every other active c
+ *     d(u, c) = max(0, (d(a, c) + d(b, c) - d(a, b)) >> 1)          (floor)
+ * r_c += d(u, c) - d(a, c) - d(b, c), and r_u is the sum of the d(u, c).  The clamp at 0 is a deliberate deviation from
+ * textbook neighbour joining, which lets negative distances stand: it keeps every distance in 0 .. 2^32.  On an additive matrix
+ * it never acts; mhx_last_nj_clamps() reports how many updates of the last call it changed.
+ * Outputs, [n - 1] each, in join order and the same bytes in both pointer forms: join_a > join_b the two ids, d their distance
+ * and r_a, r_b their sums, all as they were before the join (join t is made with m = n - t nodes active); the last record joins
+ * the two nodes that are left and has r_a = r_b = 0.  len_a, len_b (both or neither NULL), the branch lengths, for m > 2:
+ *     len_a = (double)(d (m - 2) + r_a - r_b) / (double)(2 (m - 2)) * 2^-32,   len_b the same with r_a and r_b swapped
+ * -- integers below 2^53, one division: every host and the device give the same double -- and len_a = d * 2^-32, len_b = 0 in
+ * the last record.  Lengths may be negative and are reported as computed.  device_ptrs != 0 => rows, len and the outputs are
+ * device pointers.
+ * On the device: the packed triangle of mhx_dist_triangle's dense mode becomes one 64-bit word per
+ * pair; a join is three launches -- a scan of the words of the active rows in equal spans of words, one workgroup that reduces
+ * the spans' candidates and writes the record, one thread per node for the update -- and the host enqueues all joins without
+ * reading anything back between them.  O(n^3) words are read in all.  Memory and MHX_LINKAGE_STORE_MB as for mhx_dist_linkage
+ * (MHX_E_CAPACITY); the mhx_last_dist_* diagnostics report the triangle plus the joins.
+ * Not built: an exact pruning of the scan, a recomputed pair source, more than 65 536 lists. */
+int mhx_dist_nj(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, uint32_t *join_a, uint32_t *join_b,
+                uint64_t *d, uint64_t *r_a, uint64_t *r_b, double *len_a, double *len_b, int device_ptrs);
+uint64_t mhx_last_nj_clamps(void);
+/* The same at file level: the set is read and checked as mhx_tree_files reads it.  newick == 0, one row per join in join order:
+ *     name_a\tname_b\tlen_a\tlen_b\tdist\tnodes\n
+ * the names of the two ids (comments when `comment` is set), the two branch lengths and dist = d * 2^-32 as the triangle prints
+ * a distance, and the nodes left after the join.  newick != 0: the UNROOTED tree.  Every join but the last is a node
+ * "(X:len,Y:len)"; for n >= 3 the root is the trifurcation of the two children of join n - 3 and the node that is left, the
+ * latter with the dist of the last join as its length; children in the order of their lowest leaf; lengths "%g" of max(0, len);
+ * names quoted as mhx_tree_files quotes them.  n == 2: "(name0:0,name1:d);", n == 1: "name;", n == 0: an empty text. */
+int mhx_nj_files(const char *const *msh_paths, int n_paths, int comment, int newick, char *stdout_buf, size_t cap, size_t *need);
 
 /* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
  * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
