@@ -24,6 +24,7 @@
 
 #include "mhx_hd.h"
 #include "mhx_device_consts.h"
+#include "mhx_tail_lut.h"
 
 // rare branches are laid out of line: the hot path falls through instead of jumping over the cold block
 #define MHX_UNLIKELY(x) __builtin_expect(!!(x), 0)
@@ -398,13 +399,36 @@ template <int K> MHX_HD uint64_t xor_tail_len(uint64_t h, uint64_t k)
     return make64(xor3((uint32_t)h, (uint32_t)k, (uint32_t)K), (uint32_t)(h >> 32) ^ (uint32_t)(k >> 32));
 }
 constexpr uint64_t kMurmurSeed = 42; // mash's hash seed
-// w: the K bytes as little-endian dwords, bytes beyond K zero
-template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
+// Does the tail block's partial 8-byte word come out of a table (mhx_tail_lut.h)?  64-bit hashes whose partial word holds
+// 1..5 bases: K = 17..21 (the partial k1) and K = 25..29 (the partial k2, behind a full k1).
+template <int K> constexpr bool tail_lut_applies() { return K > 16 && (K & 7) >= 1 && (K & 7) <= 5; }
+// The hot loop's choice: the table on the device, the multiplications on the host; -DMHX_NO_TAIL_LUT brings the
+// multiplications back on the device too (the A/B of profiles/tail_lut_ab.txt).
+template <int K> constexpr bool hot_tail_lut()
 {
-    constexpr uint64_t c1 = 0x87c37b91114253d5ull, c2 = 0x4cf5ad432745937full;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MHX_NO_TAIL_LUT)
+    return tail_lut_applies<K>();
+#else
+    return false;
+#endif
+}
+// K's table: as many bases as its partial word holds, the k2 form when that word is the tail block's second
+template <int K> MHX_HD TailLutPtr tail_lut_of() { return tail_lut_table<K & 7, ((K & 15) > 8)>(); }
+// w: the K bytes as little-endian dwords, bytes beyond K zero.
+// LUT: the partial word's k from the table.  ONLY the sketch kernel's hot loop asks for it (process_group_regs): a window
+// with a byte that is not A/C/G/T then hashes to the value of the letters its bytes alias to, and every such window is
+// dropped behind the loop (mhx_tail_lut.h).  Everything that hashes a window for good keeps the multiplications.
+// lut: tail_lut_of<K>(), fetched once by the caller for all the windows it hashes (LUT = false: unused).
+template <int K, bool LUT = false> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8], TailLutPtr lut = nullptr)
+{
+    static_assert(!LUT || tail_lut_applies<K>(), "no table for this K");
+    constexpr uint64_t c1 = kMurmurC1, c2 = kMurmurC2;
     constexpr int NBLK = K / 16, TAIL = K & 15;
     uint64_t h1 = kMurmurSeed, h2 = kMurmurSeed;
     uint32_t zero = 0; // see mul64c
+    // the gather is issued first, as soon as the partial word's dwords exist, and consumed at the xor behind the blocks
+    uint64_t k_lut = 0;
+    if constexpr (LUT) k_lut = lut[tail_lut_index<K & 7>(w[(K / 8) * 2], w[((K / 8) * 2 + 1) & 7])];
 #pragma unroll
     for (int b = 0; b < NBLK; ++b) {
         uint64_t k1 = make64(w[4 * b], w[4 * b + 1]);
@@ -422,13 +446,17 @@ template <int K> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8])
     // the tail block's xor and the xor of the length meet in the low word: h ^ k ^ K there is one three-input operation
     if (TAIL > 8) {
         uint64_t k2 = make64(w[(4 * NBLK + 2) & 7], w[(4 * NBLK + 3) & 7]);
-        k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); h2 = xor_tail_len<K>(h2, k2);
+        if constexpr (LUT) k2 = k_lut;
+        else { k2 = rotl64<33>(mul64c<c2>(k2, zero)); k2 = mul64c<c1>(k2, zero); }
+        h2 = xor_tail_len<K>(h2, k2);
     } else {
         h2 ^= (uint64_t)K;
     }
     if (TAIL > 0) {
         uint64_t k1 = make64(w[(4 * NBLK) & 7], w[(4 * NBLK + 1) & 7]);
-        k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); h1 = xor_tail_len<K>(h1, k1);
+        if constexpr (LUT && TAIL <= 8) k1 = k_lut;
+        else { k1 = rotl64<31>(mul64c<c1>(k1, zero)); k1 = mul64c<c2>(k1, zero); }
+        h1 = xor_tail_len<K>(h1, k1);
     } else {
         h1 ^= (uint64_t)K;
     }
@@ -920,11 +948,13 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     strand_views<ND>(src, U, R, Wr, Cc);
     constexpr bool kHash32 = K <= 16; // mash keeps 32 bits when 4^k <= 2^32
     uint32_t ninserted = 0;
+    TailLutPtr lut = nullptr; // the tail table, one address for the eight windows (and, hoisted, for the whole loop)
+    if constexpr (hot_tail_lut<K>()) lut = tail_lut_of<K>();
 #define MHX_WINDOW(J)                                                                         \
     {                                                                                         \
         uint32_t w[8];                                                                        \
         canonical_words<K, J, ND>(U, R, Wr, Cc, w);                                           \
-        const Murmur3Tail tail = murmur3_core<K>(w);                                          \
+        const Murmur3Tail tail = murmur3_core<K, hot_tail_lut<K>()>(w, lut);                  \
         /* necessary condition of h <= T, see Murmur3Tail (32-bit hashes: the exact low word) */ \
         const uint32_t low = kHash32 ? tail.low32() : 0u;                                     \
         const bool candidate = kHash32 ? low <= (uint32_t)T : tail.high_bound() <= limit;     \

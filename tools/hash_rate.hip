@@ -1,6 +1,9 @@
 // tools/hash_rate.hip -- isolates the arithmetic of the sketch kernel from its memory phases:
-//   (1) murmur3_h1<21> alone, (2) the whole work item (process_group<21>) on an LDS-resident tile.
-// Reports cycles per wave per window at 1..4 workgroups (of 256 threads) per CU.
+//   (1) the hash of K = 21 alone, (2) the whole work item (process_group<21>) on an LDS-resident tile.
+// Reports cycles per wave per window at 1..7 workgroups (of 256 threads) per CU.
+// Both take the tail block the way the hot loop does: from the table (mhx_tail_lut.h), or by the two multiplications
+// when built with -DMHX_NO_TAIL_LUT.  Nothing else uses the vector L1 here, so the pair of builds shows what the gather
+// costs when its 8 KB stay resident.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <vector>
@@ -33,9 +36,11 @@ template <int MODE> __global__ __launch_bounds__(256) void k(unsigned long long 
     const uint64_t t0 = clock64();
     if (MODE == 0) {
         uint32_t w[8] = {b[tid], b[tid + 1], b[tid + 2], b[tid + 3], b[tid + 4], b[tid + 5] & 0xFF, 0, 0};
+        const TailLutPtr lut = hot_tail_lut<21>() ? tail_lut_of<21>() : nullptr;
         for (int it = 0; it < iters * 8; ++it) {
-            const uint64_t h = murmur3_h1<21>(w);
+            const uint64_t h = murmur3_core<21, hot_tail_lut<21>()>(w, lut).finish();
             w[0] ^= (uint32_t)h; w[3] += (uint32_t)(h >> 32);
+            w[4] ^= (uint32_t)(h >> 13); w[5] = (w[5] + (uint32_t)(h >> 50)) & 0xFF; // a new table entry every time
             acc += h;
         }
     } else {
@@ -73,10 +78,19 @@ template <int MODE> void run(const char *name, unsigned long long *d, uint32_t d
     printf("\n");
 }
 
+static const char *hot_tail_lut_host_name()
+{
+#if defined(MHX_NO_TAIL_LUT)
+    return "hash of K = 21 only, tail block multiplied";
+#else
+    return "hash of K = 21 only, tail block from the table";
+#endif
+}
+
 int main()
 {
     unsigned long long *d; hipMalloc(&d, (2 + 2048 * 4) * 8); hipMemset(d, 0, (2 + 2048 * 4) * 8);
-    run<0>("murmur3_h1<21> only", d, 0);
+    run<0>(hot_tail_lut_host_name(), d, 0);
     run<1>("process_group<21> (8 windows)", d, 0);
     run<1>("process_group, waves desynchronised", d, 50000);
     return 0;
