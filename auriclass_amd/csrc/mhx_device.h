@@ -296,6 +296,23 @@ hipError_t launch_nj_scan(const NjArgs &a, uint32_t t, hipStream_t st);   // joi
 hipError_t launch_nj_join(const NjArgs &a, uint32_t t, hipStream_t st);
 hipError_t launch_nj_update(const NjArgs &a, uint32_t t, hipStream_t st); // n - t > 2
 
+// the jackknife over the hashes of one set (rules: mhx_resample.h, kernels: mhx_resample.hip): replicate `replicate` of rows /
+// len [n] into out_rows / out_len (the same stride, another place), and the smallest kept count of the full lists in *s_r
+struct ResampleArgs {
+    const uint64_t *rows;
+    const uint32_t *len;
+    uint32_t n, stride, s;
+    uint64_t seed, threshold; // threshold: T of mhx_resample.h, 1 .. 2^32
+    uint32_t replicate;
+    uint64_t *out_rows;
+    uint32_t *out_len;
+    uint32_t *s_r;            // one word
+};
+// *s_r = s, then the kept hashes of every row in order, their count and the minimum over the full rows into *s_r
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t st);
+// every out_len cut to *s_r and the rows zero behind it up to the stride
+hipError_t launch_resample_clamp(const ResampleArgs &a, hipStream_t st);
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

@@ -483,64 +483,96 @@ extern "C" int mhx_linkage_files(const char *const *paths, int n_paths, const mh
 // the host prints them as a table or as an UNROOTED Newick tree: every join but the last is a node "(X:len,Y:len)", the
 // root is the trifurcation of the two children of join n - 3 and the node that is left, whose branch is the distance of the
 // last join; children in the order of their lowest leaf (a node's id), lengths "%g" of max(0, len).
+// With o.replicates = R > 0 (mhx_nj_files_opts) the joins come from mhx_dist_nj_support with their support c: the table gets a
+// seventh column "c/R", and the node of every join t <= n - 4 the label floor(100 c / R) behind its ")".
+static int nj_files_text(const char *const *paths, int n_paths, const mhx_nj_opts &o, char *stdout_buf, size_t cap, size_t *need)
+{
+    const int comment = o.comment, newick = o.newick;
+    const uint32_t R = o.replicates;
+    SetOfFiles S;
+    int rc = read_set_of_files("nj", paths, n_paths, S);
+    if (rc) return rc;
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const uint32_t n = S.n();
+    const uint32_t m = n ? n - 1 : 0;
+    std::vector<uint32_t> ja(m), jb(m);
+    std::vector<uint64_t> d(m), ra(m), rb(m);
+    std::vector<double> la(m), lb(m);
+    std::vector<uint32_t> support(R ? m : 0);
+    rc = R ? mhx_dist_nj_support(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), R, o.keep, o.seed, ja.data(), jb.data(), d.data(), ra.data(), rb.data(),
+                                 la.data(), lb.data(), support.data(), nullptr, nullptr, nullptr, 0)
+           : mhx_dist_nj(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), ja.data(), jb.data(), d.data(), ra.data(), rb.data(), la.data(), lb.data(), 0);
+    if (rc) return rc;
+    auto shown = [&](uint32_t i) -> const std::string & { return comment ? refs[i]->comment : refs[i]->name; };
+    auto dist = [&](uint32_t t) { return (double)d[t] * (1.0 / 4294967296.0); };
+    std::string text;
+    if (!newick) {
+        for (uint32_t t = 0; t < m; ++t)
+            text += shown(ja[t]) + "\t" + shown(jb[t]) + "\t" + fmt_g(la[t]) + "\t" + fmt_g(lb[t]) + "\t" + fmt_g(dist(t)) + "\t" + std::to_string(n - 1 - t) +
+                    (R ? "\t" + std::to_string(support[t]) + "/" + std::to_string(R) : std::string()) + "\n";
+        return put_text(text, stdout_buf, cap, need);
+    }
+    if (n == 0) return put_text(text, stdout_buf, cap, need);
+    // nodes 0 .. n - 1 are the leaves, node n + t the join t; top[id]: the node that stands for the active id
+    struct Node { uint32_t kid[3]; double len[3]; int kids; };
+    std::vector<Node> nodes;
+    std::vector<uint32_t> top(n);
+    for (uint32_t i = 0; i < n; ++i) top[i] = i;
+    const uint32_t binary = n >= 3 ? n - 2 : m; // joins that are nodes; the last of them takes the third child
+    for (uint32_t t = 0; t < binary; ++t) {
+        if (ja[t] >= n || jb[t] >= ja[t]) return fail(MHX_E_INTERNAL, "nj: join %u does not name two nodes b < a", t);
+        nodes.push_back(Node{{top[jb[t]], top[ja[t]], 0}, {lb[t], la[t], 0.0}, 2});
+        top[jb[t]] = n + t;
+    }
+    if (n >= 3) {
+        Node &root = nodes.back();
+        const uint32_t u = jb[n - 3], other = ja[n - 2] == u ? jb[n - 2] : ja[n - 2];
+        if ((ja[n - 2] != u && jb[n - 2] != u) || other >= n || other == ja[n - 3]) return fail(MHX_E_INTERNAL, "nj: the last join does not take up the one before it");
+        int at = other < jb[n - 3] ? 0 : (other < ja[n - 3] ? 1 : 2); // by lowest leaf
+        for (int x = 2; x > at; --x) { root.kid[x] = root.kid[x - 1]; root.len[x] = root.len[x - 1]; }
+        root.kid[at] = top[other]; root.len[at] = dist(n - 2);
+        root.kids = 3;
+    }
+    // written without recursion: a chain of 65 535 joins is a tree of that depth
+    struct Item { uint32_t node; int at; };
+    std::vector<Item> todo{{nodes.empty() ? 0u : n + (uint32_t)nodes.size() - 1, 0}};
+    while (!todo.empty()) {
+        Item &it = todo.back();
+        if (it.node < n) { text += newick_name(shown(it.node)); todo.pop_back(); continue; }
+        const Node &nd = nodes[it.node - n];
+        if (it.at == 0) text += "(";
+        else text += ":" + fmt_g(nd.len[it.at - 1] > 0.0 ? nd.len[it.at - 1] : 0.0) + (it.at < nd.kids ? "," : ")");
+        if (it.at == nd.kids) {
+            const uint32_t t = it.node - n; // an inner node but the root: its support in per cent, floored
+            if (R && (uint64_t)t + 4 <= n) text += std::to_string((uint64_t)100 * support[t] / R);
+            todo.pop_back();
+            continue;
+        }
+        const uint32_t kid = nd.kid[it.at++];
+        todo.push_back({kid, 0});
+    }
+    text += ";\n";
+    return put_text(text, stdout_buf, cap, need);
+}
+
 extern "C" int mhx_nj_files(const char *const *paths, int n_paths, int comment, int newick, char *stdout_buf, size_t cap, size_t *need)
 {
     return entry("mhx_nj_files", [&]() -> int {
-        SetOfFiles S;
-        int rc = read_set_of_files("nj", paths, n_paths, S);
+        return nj_files_text(paths, n_paths, mhx_nj_opts{(uint32_t)sizeof(mhx_nj_opts), comment, newick, 0, 0.5, 42}, stdout_buf, cap, need);
+    });
+}
+
+extern "C" int mhx_nj_files_opts(const char *const *paths, int n_paths, const mhx_nj_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    return entry("mhx_nj_files_opts", [&]() -> int {
+        mhx_nj_opts o{(uint32_t)sizeof(mhx_nj_opts), 0, 0, 0, 0.5, 42};
+        int rc = take_opts("nj", opts, o);
         if (rc) return rc;
-        const std::vector<const RefSketch *> &refs = S.refs;
-        const uint32_t n = S.n();
-        const uint32_t m = n ? n - 1 : 0;
-        std::vector<uint32_t> ja(m), jb(m);
-        std::vector<uint64_t> d(m), ra(m), rb(m);
-        std::vector<double> la(m), lb(m);
-        rc = mhx_dist_nj(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), ja.data(), jb.data(), d.data(), ra.data(), rb.data(), la.data(), lb.data(), 0);
-        if (rc) return rc;
-        auto shown = [&](uint32_t i) -> const std::string & { return comment ? refs[i]->comment : refs[i]->name; };
-        auto dist = [&](uint32_t t) { return (double)d[t] * (1.0 / 4294967296.0); };
-        std::string text;
-        if (!newick) {
-            for (uint32_t t = 0; t < m; ++t)
-                text += shown(ja[t]) + "\t" + shown(jb[t]) + "\t" + fmt_g(la[t]) + "\t" + fmt_g(lb[t]) + "\t" + fmt_g(dist(t)) + "\t" + std::to_string(n - 1 - t) + "\n";
-            return put_text(text, stdout_buf, cap, need);
+        if (o.replicates) { // refused before a file is read
+            if (!(o.keep > 0.0) || !(o.keep <= 1.0)) return fail(MHX_E_ARG, "nj: keep must lie in (0, 1] (%g)", o.keep);
+            if (o.replicates > 10000) return fail(MHX_E_ARG, "nj: too many replicates (%u, at most 10000)", o.replicates);
         }
-        if (n == 0) return put_text(text, stdout_buf, cap, need);
-        // nodes 0 .. n - 1 are the leaves, node n + t the join t; top[id]: the node that stands for the active id
-        struct Node { uint32_t kid[3]; double len[3]; int kids; };
-        std::vector<Node> nodes;
-        std::vector<uint32_t> top(n);
-        for (uint32_t i = 0; i < n; ++i) top[i] = i;
-        const uint32_t binary = n >= 3 ? n - 2 : m; // joins that are nodes; the last of them takes the third child
-        for (uint32_t t = 0; t < binary; ++t) {
-            if (ja[t] >= n || jb[t] >= ja[t]) return fail(MHX_E_INTERNAL, "nj: join %u does not name two nodes b < a", t);
-            nodes.push_back(Node{{top[jb[t]], top[ja[t]], 0}, {lb[t], la[t], 0.0}, 2});
-            top[jb[t]] = n + t;
-        }
-        if (n >= 3) {
-            Node &root = nodes.back();
-            const uint32_t u = jb[n - 3], other = ja[n - 2] == u ? jb[n - 2] : ja[n - 2];
-            if ((ja[n - 2] != u && jb[n - 2] != u) || other >= n || other == ja[n - 3]) return fail(MHX_E_INTERNAL, "nj: the last join does not take up the one before it");
-            int at = other < jb[n - 3] ? 0 : (other < ja[n - 3] ? 1 : 2); // by lowest leaf
-            for (int x = 2; x > at; --x) { root.kid[x] = root.kid[x - 1]; root.len[x] = root.len[x - 1]; }
-            root.kid[at] = top[other]; root.len[at] = dist(n - 2);
-            root.kids = 3;
-        }
-        // written without recursion: a chain of 65 535 joins is a tree of that depth
-        struct Item { uint32_t node; int at; };
-        std::vector<Item> todo{{nodes.empty() ? 0u : n + (uint32_t)nodes.size() - 1, 0}};
-        while (!todo.empty()) {
-            Item &it = todo.back();
-            if (it.node < n) { text += newick_name(shown(it.node)); todo.pop_back(); continue; }
-            const Node &nd = nodes[it.node - n];
-            if (it.at == 0) text += "(";
-            else text += ":" + fmt_g(nd.len[it.at - 1] > 0.0 ? nd.len[it.at - 1] : 0.0) + (it.at < nd.kids ? "," : ")");
-            if (it.at == nd.kids) { todo.pop_back(); continue; }
-            const uint32_t kid = nd.kid[it.at++];
-            todo.push_back({kid, 0});
-        }
-        text += ";\n";
-        return put_text(text, stdout_buf, cap, need);
+        return nj_files_text(paths, n_paths, o, stdout_buf, cap, need);
     });
 }
 

@@ -189,6 +189,14 @@ def load() -> ctypes.CDLL:
                                   c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_last_nj_clamps.restype = c.c_uint64
         L.mhx_nj_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.c_int, c.c_int, c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_nj_support"):   # (or older than the jackknife support of the neighbour-joining tree)
+        L.mhx_resample_rows.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint64, c.c_uint32, c.c_double, c.c_void_p,
+                                        c.c_void_p, u32p, c.c_int]
+        L.mhx_dist_nj_support.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_uint32, c.c_double, c.c_uint64,
+                                          c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                          c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_nj_files_opts.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(NjOpts), c.c_char_p, c.c_size_t, c.POINTER(c.c_size_t)]
+        # mhx_nj_split_support is host only and is called with explicit ctypes values (nj_split_support): no argtypes here
     if hasattr(L, "mhx_dist_search"):   # (or older than the reference-set search)
         L.mhx_dist_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -418,14 +426,26 @@ def linkage_files(paths: Sequence, linkage: str, mode: str = "merges", comment: 
     return _text_call(lambda buf, cap, need: load().mhx_linkage_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
 
 
-def nj_files(paths: Sequence, comment: bool = False, newick: bool = False) -> str:
+class NjOpts(ctypes.Structure):
+    """mhx_nj_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("newick", ctypes.c_int32), ("replicates", ctypes.c_uint32),
+                ("keep", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+def nj_files(paths: Sequence, comment: bool = False, newick: bool = False, replicates: int = 0, keep: float = 0.5, seed: int = 42) -> str:
     """Neighbour joining over the references of all sketch files (one set), a row per join in join order:
     "name_a\\tname_b\\tlen_a\\tlen_b\\tdist\\tnodes" -- the two nodes (a node is named by its lowest leaf; comments under
     `comment`), their branch lengths, their distance and the nodes left after the join.  newick: the unrooted tree in Newick
-    format instead, its root the trifurcation the last two joins leave."""
+    format instead, its root the trifurcation the last two joins leave.
+    replicates = R > 0: jackknife support (dist_nj_support; every replicate keeps the share `keep` of the hashes, chosen by
+    `seed`) -- a seventh column "c/R" in the table, the label floor(100 c / R) behind the ")" of every inner node but the root in
+    the Newick text."""
     init()
     files = [os.fsencode(str(p)) for p in paths]
     arr = (ctypes.c_char_p * len(files))(*files)
+    if replicates > 0:
+        opts = NjOpts(ctypes.sizeof(NjOpts), int(bool(comment)), int(bool(newick)), int(replicates), float(keep), int(seed))
+        return _text_call(lambda buf, cap, need: load().mhx_nj_files_opts(arr, len(files), ctypes.byref(opts), buf, cap, need), guess=1 << 20)
     return _text_call(lambda buf, cap, need: load().mhx_nj_files(arr, len(files), int(bool(comment)), int(bool(newick)), buf, cap, need), guess=1 << 20)
 
 
@@ -1095,6 +1115,72 @@ def dist_nj_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: 
     _check(load().mhx_dist_nj(v(rows_ptr), v(len_ptr), n, stride, k, s, v(join_a_ptr), v(join_b_ptr), v(d_ptr), v(r_a_ptr), v(r_b_ptr),
                               v(len_a_ptr or None), v(len_b_ptr or None), 1))
     return max(n - 1, 0)
+
+
+def resample_rows(rows: np.ndarray, lens: np.ndarray, s: int, seed: int, replicate: int, keep: float) -> Tuple[np.ndarray, np.ndarray, int]:
+    """One jackknife replicate of a set of hash lists (mhx_resample_rows): every list keeps the hashes the keep function of
+    include/mhx.h admits, in order, and all are cut to s_r, the smallest kept count among the full lists (len == s).
+    (rows [n, stride] with zeros behind the new lengths, lens [n], s_r)."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    out_rows = np.zeros_like(rows)
+    out_len = np.zeros_like(lens)
+    s_r = ctypes.c_uint32(0)
+    _check(load().mhx_resample_rows(rows.ctypes.data, lens.ctypes.data, rows.shape[0], rows.shape[1], s, seed, replicate, float(keep),
+                                    out_rows.ctypes.data, out_len.ctypes.data, ctypes.byref(s_r), 0))
+    return out_rows, out_len, int(s_r.value)
+
+
+def dist_nj_support(rows: np.ndarray, lens: np.ndarray, k: int, s: int, replicates: int, keep: float = 0.5, seed: int = 42):
+    """Neighbour joining with jackknife support (mhx_dist_nj_support): (join_a, join_b, d, r_a, r_b, len_a, len_b) exactly as
+    dist_nj gives them, then support [n - 1] -- in how many of the `replicates` trees the split of each join is found --,
+    rep_join_a and rep_join_b [replicates, n - 1], the joins of every replicate, and rep_s [replicates], its sketch size."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    m = max(n - 1, 0)
+    join_a, join_b = (np.zeros(m, dtype=np.uint32) for _ in range(2))
+    d, r_a, r_b = (np.zeros(m, dtype=np.uint64) for _ in range(3))
+    len_a, len_b = (np.zeros(m, dtype=np.float64) for _ in range(2))
+    support = np.zeros(m, dtype=np.uint32)
+    rep_a, rep_b = (np.zeros((replicates, m), dtype=np.uint32) for _ in range(2))
+    rep_s = np.zeros(replicates, dtype=np.uint32)
+    _check(load().mhx_dist_nj_support(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, replicates, float(keep), seed, join_a.ctypes.data,
+                                      join_b.ctypes.data, d.ctypes.data, r_a.ctypes.data, r_b.ctypes.data, len_a.ctypes.data, len_b.ctypes.data,
+                                      support.ctypes.data, rep_a.ctypes.data, rep_b.ctypes.data, rep_s.ctypes.data, 0))
+    return join_a, join_b, d, r_a, r_b, len_a, len_b, support, rep_a, rep_b, rep_s
+
+
+def dist_nj_support_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, replicates: int, keep: float, seed: int, join_a_ptr: int,
+                           join_b_ptr: int, d_ptr: int, r_a_ptr: int, r_b_ptr: int, len_a_ptr: int = 0, len_b_ptr: int = 0):
+    """Device pointers for the rows, the lengths and the seven outputs of the main tree (as dist_nj_device takes them; what
+    sketch_segments_device wrote goes straight in); the support values come back on the host: (support [n - 1], rep_join_a,
+    rep_join_b [replicates, n - 1], rep_s [replicates])."""
+    init()
+    v = ctypes.c_void_p
+    m = max(n - 1, 0)
+    support = np.zeros(m, dtype=np.uint32)
+    rep_a, rep_b = (np.zeros((replicates, m), dtype=np.uint32) for _ in range(2))
+    rep_s = np.zeros(replicates, dtype=np.uint32)
+    _check(load().mhx_dist_nj_support(v(rows_ptr), v(len_ptr), n, stride, k, s, replicates, float(keep), seed, v(join_a_ptr), v(join_b_ptr), v(d_ptr),
+                                      v(r_a_ptr), v(r_b_ptr), v(len_a_ptr or None), v(len_b_ptr or None), support.ctypes.data, rep_a.ctypes.data,
+                                      rep_b.ctypes.data, rep_s.ctypes.data, 1))
+    return support, rep_a, rep_b, rep_s
+
+
+def nj_split_support(join_a, join_b, rep_join_a, rep_join_b, n: int) -> np.ndarray:
+    """support [n - 1] of the joins of a tree among the replicate trees rep_join_a / rep_join_b [replicates, n - 1], on the
+    host (mhx_nj_split_support: no device needed, exact): the number of replicates that hold the split of each join; a split
+    with at most one leaf on a side is in every tree."""
+    m = max(n - 1, 0)
+    a, b = (np.ascontiguousarray(x, dtype=np.uint32) for x in (join_a, join_b))
+    ra, rb = (np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, m) if m else np.zeros((0, 0), np.uint32) for x in (rep_join_a, rep_join_b))
+    assert a.shape == (m,) and b.shape == (m,) and ra.shape == rb.shape
+    support = np.zeros(m, dtype=np.uint32)
+    v = ctypes.c_void_p
+    _check(load().mhx_nj_split_support(v(a.ctypes.data), v(b.ctypes.data), v(ra.ctypes.data), v(rb.ctypes.data), ctypes.c_uint32(n),
+                                       ctypes.c_uint32(ra.shape[0]), v(support.ctypes.data)))
+    return support
 
 
 def dist_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, top: int, max_dist: float = 1.0

@@ -31,6 +31,11 @@
  *                        workflow) -- the unrooted tree of a set on the device (buffer level; engine.dist_nj)
  *   mhx_nj_files      <- no mash command: the same for sketch files, as a table of joins or an unrooted Newick tree
  *                        (python -m auriclass_amd.tree --nj)
+ *   mhx_dist_nj_support <- no mash command: a jackknife over the sketch hashes (as the tools that build Mash trees ship one) --
+ *                        in how many trees of resampled sketches each split of the neighbour-joining tree is found
+ *                        (buffer level; engine.dist_nj_support; mhx_resample_rows is one replicate of a set)
+ *   mhx_nj_files_opts <- no mash command: the same for sketch files, the support as a column or as Newick node labels
+ *                        (python -m auriclass_amd.tree --nj --support R)
  *   mhx_bounds        <- `mash bounds -k K -p P`            auriclass/classes.py:305-318
  *   mhx_screen_files  <- `mash screen REF.msh reads...`     (not called by AuriClass: the containment question its
  *                        distance check cannot answer, docs/faq.md entries 3 and 4)
@@ -556,6 +561,69 @@ uint64_t mhx_last_nj_clamps(void);
  * latter with the dist of the last join as its length; children in the order of their lowest leaf; lengths "%g" of max(0, len);
  * names quoted as mhx_tree_files quotes them.  n == 2: "(name0:0,name1:d);", n == 1: "name;", n == 0: an empty text. */
 int mhx_nj_files(const char *const *msh_paths, int n_paths, int comment, int newick, char *stdout_buf, size_t cap, size_t *need);
+
+/* JACKKNIFE SUPPORT of the neighbour-joining tree: which of its splits survive the sampling noise of the sketch hashes.
+ * The rule (auriclass_amd/csrc/mhx_resample.h, restated in tests/resample_rule.py and tests/nj_support_rule.py), all of it in
+ * integers.  A hash h is kept in replicate r (0-based) of a call with seed `seed` iff (z >> 32) < T, arithmetic mod 2^64:
+ *     z = h + seed + (r + 1) * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB;     z ^= z >> 31
+ * with T = floor(keep * 2^32) from the double keep, 0 < keep <= 1.  The decision depends on the hash alone: two lists that share
+ * a hash keep it both or drop it both.  List i of the replicate is the kept hashes of list i, in order; a list with len[i] == s
+ * is full, a shorter one a complete set; s_r is the smallest kept count among the full lists (s when none is full) and every
+ * list is cut to its first min(kept, s_r) hashes, which makes each a bottom-s_r sketch.  s_r == 0: MHX_E_ARG, the message names
+ * the replicate and keep.  The replicate's tree is the rule of mhx_dist_nj over these lists at sketch size s_r, the same k.
+ * The leaf set of the node of join t is the union of those of its two ids; canon(X) = X if leaf 0 is not in X, else its
+ * complement; the splits of a tree are canon of the leaf sets of its n - 1 joins.  support[t] of the main tree (the records
+ * mhx_dist_nj gives) is the number of replicates whose splits hold canon(leaf set of join t); a split with 0, 1, n - 1 or n
+ * leaves on a side is in every tree and gets `replicates`.
+ *
+ * mhx_resample_rows: one replicate of a set.  out_rows [n][stride] receives the cut lists, zero behind out_len[i] up to the
+ * stride (another place than rows), *s_out (HOST in both forms) s_r.  device_ptrs != 0 => rows, len, out_rows and out_len are
+ * device pointers.  MHX_E_ARG before anything is launched: keep outside (0, 1] or not a number, n > 65 536, s or stride 0, a
+ * null pointer, len[i] > stride (host form).  n == 0: MHX_OK, *s_out = s.
+ * On the device: one workgroup per row, chunks of 256 hashes, the keep flags of a wave as one ballot, an item's place from the
+ * set bits below its lane and the waves' totals through LDS; the full rows fold their count into one word (atomicMin); a second
+ * launch cuts every row to it and zeroes the rest. */
+int mhx_resample_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, uint32_t s, uint64_t seed, uint32_t replicate,
+                      double keep, uint64_t *out_rows, uint32_t *out_len, uint32_t *s_out, int device_ptrs);
+/* The main tree exactly as mhx_dist_nj gives it (the same checks, the same seven outputs in both pointer forms, the same
+ * mhx_last_nj_clamps), then `replicates` jackknife trees and the support of every join of the main tree.  HOST pointers in both
+ * forms: support [n - 1]; rep_join_a, rep_join_b [replicates][n - 1] (both or neither NULL), the joins of every replicate;
+ * rep_s [replicates] (may be NULL), its s_r.  device_ptrs != 0 => rows, len and the seven main-tree outputs are device pointers.
+ * MHX_E_ARG before anything is launched: whatever mhx_dist_nj refuses, keep outside (0, 1] or not a number, replicates > 10 000,
+ * a NULL support with replicates > 0.  n <= 1: MHX_OK, nothing written.  replicates == 0: the main tree only, support untouched.
+ * n == 2: support[0] = replicates.
+ * On the device: the rows are staged once; the pair words, the triangle's two arrays, the state of the
+ * joins and one replicate row matrix are allocated once.  A replicate is resample, cut, one 4-byte readback of s_r, dense
+ * triangle, init and joins, and the copy of its join_a / join_b to the host, where its splits are counted at once (bitsets,
+ * compared exactly; n^2 / 8 bytes of host memory for the main tree's).  Memory: 16 n (n - 1) / 2 bytes for the whole call -- the
+ * triangle's arrays stay -- and a second row matrix; the words must fit MHX_LINKAGE_STORE_MB (MHX_E_CAPACITY).  The
+ * mhx_last_dist_* time is the sum over the main tree and all replicates.
+ * Not built: support for the linkage trees, one batched launch for many small replicates, Felsenstein's bootstrap (which
+ * sketches resampled sequence again). */
+int mhx_dist_nj_support(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, uint32_t replicates, double keep,
+                        uint64_t seed, uint32_t *join_a, uint32_t *join_b, uint64_t *d, uint64_t *r_a, uint64_t *r_b, double *len_a, double *len_b,
+                        uint32_t *support, uint32_t *rep_join_a, uint32_t *rep_join_b, uint32_t *rep_s, int device_ptrs);
+/* The count alone, on the host (no device needed): support [n - 1] of the joins join_a / join_b [n - 1] among the trees
+ * rep_join_a / rep_join_b [replicates][n - 1], exact (bitsets).  n <= 1: MHX_OK, nothing written.  MHX_E_ARG: null pointers,
+ * n > 65 536, joins that are no tree of n leaves (ids b < a < n, both nodes at the time of the join). */
+int mhx_nj_split_support(const uint32_t *join_a, const uint32_t *join_b, const uint32_t *rep_join_a, const uint32_t *rep_join_b, uint32_t n,
+                         uint32_t replicates, uint32_t *support);
+/* mhx_nj_files with support values.  replicates == 0 prints exactly what mhx_nj_files prints.  replicates = R > 0: the table
+ * gets a seventh column "c/R", c the support of the join; in the Newick text the node of every join t <= n - 4 (the inner nodes
+ * but the root) carries the label floor(100 c / R) between ")" and ":", as in "(A:0.1,B:0.2)87:0.05".  The trifurcation carries
+ * none: the split of join n - 3 is that of the branch of its third child.  opts == NULL means {sizeof, 0, 0, 0, 0.5, 42}.
+ * MHX_E_ARG: struct_size != sizeof(mhx_nj_opts), and what mhx_dist_nj_support refuses.  Pinned by the restated rules
+ * (tests/nj_rule.py, tests/nj_support_rule.py). */
+typedef struct mhx_nj_opts {
+    uint32_t struct_size; /* sizeof(mhx_nj_opts) */
+    int32_t comment;      /* non-zero: print comments in place of names */
+    int32_t newick;       /* non-zero: the unrooted tree in Newick format in place of the table of joins */
+    uint32_t replicates;  /* jackknife replicates, 0: none */
+    double keep;          /* the share of the hashes a replicate keeps, (0, 1] */
+    uint64_t seed;
+} mhx_nj_opts;
+int mhx_nj_files_opts(const char *const *msh_paths, int n_paths, const mhx_nj_opts *opts, char *stdout_buf, size_t cap, size_t *need);
 
 /* Reference-set search: for every query the `top` (1 .. 64) closest references whose distance is <= max_dist, ranked and
  * filtered on the device; no [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as
