@@ -313,6 +313,28 @@ hipError_t launch_resample(const ResampleArgs &a, hipStream_t st);
 // every out_len cut to *s_r and the rows zero behind it up to the stride
 hipError_t launch_resample_clamp(const ResampleArgs &a, hipStream_t st);
 
+// jackknife support of search hits (rules: mhx_support.h, kernels: mhx_support.hip): one batch of queries, everything on the
+// device.  q / q_len / cand / n_cand and the outputs point at the batch's first query; cand null: candidates 0 .. top - 1.
+struct SupportArgs {
+    const uint64_t *q, *r;
+    const uint32_t *q_len, *r_len;
+    uint32_t nq, nr, stride, s;
+    const uint32_t *cand, *n_cand; // [nq][top], [nq]
+    uint32_t top, replicates;
+    uint64_t seed, threshold;      // threshold: T of mhx_resample.h
+    uint32_t q0;                   // the batch's first query within the call, for *bad
+    uint32_t *kept;                // [nq][top + 1][replicates] slot 0 the query, slot 1 + i candidate i
+    uint32_t *s_r;                 // [nq][replicates]
+    uint32_t *common, *denom;      // [nq][top][replicates]
+    uint32_t *best;                // [nq][replicates] may be null
+    uint32_t *first;               // [nq][top], zero before the launch
+    unsigned long long *bad;       // the smallest (query << 32 | replicate) whose s_r is 0; all ones before the first batch
+};
+hipError_t launch_support_count(const SupportArgs &a, hipStream_t st); // kept
+hipError_t launch_support_s(const SupportArgs &a, hipStream_t st);     // s_r, *bad
+hipError_t launch_support_pairs(const SupportArgs &a, hipStream_t st); // common, denom
+hipError_t launch_support_best(const SupportArgs &a, hipStream_t st);  // best, first
+
 // reference-set search (rules: mhx_search.h, kernels: mhx_search.hip).  A block's results lie block-local as above; every
 // query of the call has a best list of at most `top` hits, best first, in hit_ref / hit_common / hit_denom [queries][top]
 // with its length in n_hits [queries] (zero before the first block), which the take-out pass of every block merges into.

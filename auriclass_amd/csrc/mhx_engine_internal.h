@@ -174,8 +174,27 @@ bool parallel_pread(int fd, uint8_t *dst, uint64_t off, size_t len, int nthreads
 // caller has put on the device: rows [nr][stride] and len [nr] there, `longest` the largest len.  Outputs as the host form
 // of mhx_dist_search.  What mhx_search_files runs per batch of queries: the references are staged once per call.
 struct SearchRefs { const uint64_t *rows; const uint32_t *len; uint32_t nr, stride, longest; };
+// where search_rows has left the queries on the device ([nq][refs.stride] and [nq], in g.dist_in): good until the next call that stages
+struct SearchStaged { const uint64_t *q; const uint32_t *q_len; };
 int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
-                uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits);
+                uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits,
+                SearchStaged *staged = nullptr);
+// Jackknife support of search hits (mhx_engine_support.cpp) with everything on the device: what mhx_dist_support's device form
+// runs, and mhx_search_files_support on the rows its search has staged.  first [nq][top] is a device pointer; the rep_*
+// outputs (each may be null) are device pointers too, or host pointers with host_out.  Uses g.dist_ws, not g.dist_in.
+struct SupportCall {
+    const uint64_t *q, *r;
+    const uint32_t *q_len, *r_len;
+    uint32_t nq, nr, stride, s;
+    const uint32_t *cand, *n_cand; // cand null: candidates 0 .. top - 1
+    uint32_t top, replicates;
+    double keep;
+    uint64_t seed, T;              // T: support_check's threshold of keep
+    uint32_t *first, *rep_best, *rep_s, *rep_common, *rep_denom;
+    bool host_out;
+};
+int support_check(uint32_t stride, uint32_t s, uint32_t top, uint32_t replicates, double keep, uint64_t *T);
+int support_device(const SupportCall &c);
 
 } // namespace mhx
 

@@ -159,7 +159,7 @@ int search_check(uint32_t nq, uint32_t nr, uint32_t stride, int k, uint32_t s, d
 // falls as the index rises), so nothing that belongs into a list was pushed out of it by one that does not.
 int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len,
                 const SearchRefs *refs, uint32_t nr, uint32_t stride, int k, uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref,
-                uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits)
+                uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits, SearchStaged *staged = nullptr)
 {
     for (uint32_t i = 0; i < nq; ++i) if (q_len[i] > stride) return fail(MHX_E_ARG, "q_len[%u] exceeds stride", i);
     if (!refs) for (uint32_t i = 0; i < nr; ++i) if (r_len[i] > stride) return fail(MHX_E_ARG, "r_len[%u] exceeds stride", i);
@@ -189,6 +189,7 @@ int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
     c.jmin = tri_jmin(max_dist, k);
     c.hit_ref = (uint32_t *)dh; c.hit_common = (uint32_t *)(dh + bh); c.hit_denom = (uint32_t *)(dh + 2 * bh); c.n_hits = (uint32_t *)(dh + 3 * bh);
     c.hit_dist = nullptr; // distances in host libm below
+    if (staged) *staged = SearchStaged{c.q, c.q_len};
     rc = search_device(c);
     if (rc) return rc;
     const size_t cells = (size_t)nq * top;
@@ -217,13 +218,13 @@ int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
 
 namespace mhx {
 int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
-                uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits)
+                uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits, SearchStaged *staged)
 {
     int rc = search_check(nq, refs.nr, refs.stride, k, s, max_dist, top);
     if (rc || nq == 0) return rc;
     if (refs.nr == 0) { memset(n_hits, 0, (size_t)nq * 4); return MHX_OK; }
     return search_host(nullptr, q_rows, q_len, nq, nullptr, nullptr, &refs, refs.nr, refs.stride, k, s, max_dist, top, hit_ref, hit_common, hit_denom,
-                       hit_dist, n_hits);
+                       hit_dist, n_hits, staged);
 }
 } // namespace mhx
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <chrono>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "mhx_engine_internal.h"
@@ -576,91 +577,201 @@ extern "C" int mhx_nj_files_opts(const char *const *paths, int n_paths, const mh
     });
 }
 
+namespace {
+
+// AuriClass's clade_config.csv: a header line, then "filename,clade" split at the last comma.  clade[i] of reference i of R, whose
+// name must be a filename of the table; clade_id[i] numbers the distinct clades.
+int read_clades(const char *path, const SketchSet &R, std::vector<std::string> &clade, std::vector<uint32_t> &clade_id)
+{
+    std::vector<uint8_t> raw;
+    FILE *f = fopen(path, "rb");
+    if (!f) return fail(MHX_E_IO, "cannot open clade table %s", path);
+    uint8_t buf[65536];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) raw.insert(raw.end(), buf, buf + got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) return fail(MHX_E_IO, "cannot read clade table %s", path);
+    std::unordered_map<std::string, std::string> table;
+    size_t at = 0, line_no = 0;
+    while (at < raw.size()) {
+        size_t end = at;
+        while (end < raw.size() && raw[end] != '\n') ++end;
+        std::string line((const char *)raw.data() + at, end - at);
+        at = end + 1;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line_no++ == 0 || line.empty()) continue; // the header
+        const size_t comma = line.rfind(',');
+        if (comma == std::string::npos) return fail(MHX_E_FORMAT, "%s: line %zu has no comma", path, line_no);
+        table[line.substr(0, comma)] = line.substr(comma + 1);
+    }
+    std::unordered_map<std::string, uint32_t> ids;
+    clade.clear();
+    clade_id.clear();
+    for (const RefSketch &r : R.refs) {
+        const auto it = table.find(r.name);
+        if (it == table.end()) return fail(MHX_E_FORMAT, "%s: no clade for reference %s", path, r.name.c_str());
+        clade.push_back(it->second);
+        clade_id.push_back(ids.emplace(it->second, (uint32_t)ids.size()).first->second);
+    }
+    return MHX_OK;
+}
+
 // Reference-set search at file level: the reference file is read, checked and staged on the device ONCE; the query files
 // are read one after the other and searched in batches of sketches (mhx_dist_search's host form against the resident
 // references), so that host memory holds one batch whatever n_qry is.  Rows are `mash dist` rows, per query best first.
+// sup (may be null) with replicates > 0: the jackknife support of every query's hits (support_device on the rows the search
+// has staged, the hits as its candidates) as a further column "c/R", and with a clade table the clade of the row's reference
+// and "g/R", g the replicates whose best candidate has that clade.
+int search_files_text(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts &o, const mhx_search_support_opts *sup, uint64_t T,
+                      const char *clade_csv, char *stdout_buf, size_t cap, size_t *need)
+{
+    const uint32_t replicates = sup ? sup->replicates : 0;
+    SketchSet R;
+    int rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+    if (rc) return rc;
+    std::vector<std::string> clade;
+    std::vector<uint32_t> clade_id;
+    if (clade_csv) { rc = read_clades(clade_csv, R, clade, clade_id); if (rc) return rc; }
+    const int k = (int)R.kmer_size;
+    const uint32_t nr = (uint32_t)R.refs.size();
+    DevArray<uint64_t> d_rows;
+    DevArray<uint32_t> d_len, d_cand, d_ncand, d_first;
+    SearchRefs refs{nullptr, nullptr, nr, 0, 0};
+    uint32_t q_sketch_size = 0, s = 0;
+    std::string text;
+    constexpr size_t kBatch = 4096; // query sketches per device call
+    std::vector<SketchSet> held;    // the files of the current batch
+    std::vector<const RefSketch *> qs;
+    auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
+        for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
+        refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
+        if (nr == 0) return MHX_OK;
+        std::vector<const RefSketch *> lists;
+        for (const RefSketch &r : R.refs) lists.push_back(&r);
+        std::vector<uint64_t> rows;
+        std::vector<uint32_t> len;
+        pack_rows(lists, refs.stride, rows, len);
+        for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
+        if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
+        if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+        refs.rows = d_rows; refs.len = d_len;
+        return MHX_OK;
+    };
+    auto flush = [&]() -> int {
+        const uint32_t nq = (uint32_t)qs.size();
+        if (nq && nr) {
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq), first;
+            std::vector<double> hx((size_t)nq * o.top);
+            for (uint32_t i = 0; i < nq; ++i) {
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
+            }
+            SearchStaged staged{};
+            const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data(), &staged);
+            if (rc2) return rc2;
+            if (replicates) { // the hits, before the p-value drops rows, are the candidates; the queries are on the device still
+                const size_t cells = (size_t)nq * o.top;
+                if (d_cand.grow(cells) != hipSuccess || d_first.grow(cells) != hipSuccess || d_ncand.grow(nq) != hipSuccess)
+                    return fail(MHX_E_HIP, "hipMalloc failed for the candidates of the support");
+                if (hipMemcpy(d_cand, hr.data(), cells * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_ncand, nh.data(), (size_t)nq * 4, hipMemcpyHostToDevice) != hipSuccess)
+                    return fail(MHX_E_HIP, "H2D copy of the candidates failed");
+                SupportCall c{};
+                c.q = staged.q; c.q_len = staged.q_len; c.r = refs.rows; c.r_len = refs.len; c.nq = nq; c.nr = nr; c.stride = refs.stride; c.s = s;
+                c.cand = d_cand; c.n_cand = d_ncand; c.top = o.top; c.replicates = replicates; c.keep = sup->keep; c.seed = sup->seed; c.T = T;
+                c.first = d_first;
+                const int rc3 = support_device(c);
+                if (rc3) return rc3;
+                first.resize(cells);
+                if (hipMemcpy(first.data(), d_first, cells * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy of the support failed");
+            }
+            const std::string of = "/" + std::to_string(replicates);
+            for (uint32_t qi = 0; qi < nq; ++qi)
+                for (uint32_t t = 0; t < nh[qi]; ++t) {
+                    const size_t p = (size_t)qi * o.top + t;
+                    const RefSketch &ref = R.refs[hr[p]];
+                    const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                    if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
+                    std::string more;
+                    if (replicates) {
+                        more = std::to_string(first[p]) + of;
+                        if (clade_csv) {
+                            uint32_t same = 0; // replicates whose best candidate has this row's clade
+                            for (uint32_t x = 0; x < nh[qi]; ++x)
+                                if (clade_id[hr[(size_t)qi * o.top + x]] == clade_id[hr[p]]) same += first[(size_t)qi * o.top + x];
+                            more += "\t" + clade[hr[p]] + "\t" + std::to_string(same) + of;
+                        }
+                    }
+                    pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p], more);
+                }
+        }
+        qs.clear();
+        held.clear();
+        return MHX_OK;
+    };
+    for (int i = 0; i < n_qry; ++i) {
+        held.emplace_back();
+        SketchSet &Q = held.back();
+        rc = msh_read_file(qry_msh[i], Q);
+        if (rc) return rc;
+        if (i == 0) q_sketch_size = Q.sketch_size;
+        rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+        if (rc) return rc;
+        if (i == 0) {
+            s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+            rc = stage_refs();
+            if (rc) return rc;
+        }
+        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+    }
+    rc = flush();
+    if (rc) return rc;
+    return put_text(text, stdout_buf, cap, need);
+}
+
+int search_files_check(const char *cmd, const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts &o)
+{
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "%s: a reference sketch path and at least one query sketch path required", cmd);
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "%s: query sketch path %d is null", cmd, i);
+    if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "%s: top must be 1 .. 64", cmd);
+    if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "%s: max_dist / max_p_value is not a number", cmd);
+    return MHX_OK;
+}
+
+} // namespace
+
 extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
     return entry("mhx_search_files", [&]() -> int {
-        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "search: a reference sketch path and at least one query sketch path required");
-        for (int i = 0; i < n_qry; ++i)
-            if (!qry_msh[i]) return fail(MHX_E_ARG, "search: query sketch path %d is null", i);
         mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), 5, 1.0, 1.0};
-        int rc = take_opts("search", opts, o);
+        int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("search", opts, o) : MHX_OK;
+        if (rc == MHX_OK) rc = search_files_check("search", ref_msh, qry_msh, n_qry, o);
         if (rc) return rc;
-        if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "search: top must be 1 .. 64");
-        if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "search: max_dist / max_p_value is not a number");
-        SketchSet R;
-        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+        return search_files_text(ref_msh, qry_msh, n_qry, o, nullptr, 0, nullptr, stdout_buf, cap, need);
+    });
+}
+
+// The search with the jackknife support of its hits.  replicates == 0: exactly mhx_search_files.
+extern "C" int mhx_search_files_support(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_support_opts *opts, const char *clade_csv,
+                                        char *stdout_buf, size_t cap, size_t *need)
+{
+    return entry("mhx_search_files_support", [&]() -> int {
+        mhx_search_support_opts so{(uint32_t)sizeof(mhx_search_support_opts), 5, 1.0, 1.0, 0, 0.5, 42};
+        int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("search_support", opts, so) : MHX_OK;
+        const mhx_search_opts o{(uint32_t)sizeof(mhx_search_opts), so.top, so.max_dist, so.max_p_value};
+        if (rc == MHX_OK) rc = search_files_check("search", ref_msh, qry_msh, n_qry, o);
         if (rc) return rc;
-        const int k = (int)R.kmer_size;
-        const uint32_t nr = (uint32_t)R.refs.size();
-        DevArray<uint64_t> d_rows;
-        DevArray<uint32_t> d_len;
-        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
-        uint32_t q_sketch_size = 0, s = 0;
-        std::string text;
-        constexpr size_t kBatch = 4096; // query sketches per device call
-        std::vector<SketchSet> held;    // the files of the current batch
-        std::vector<const RefSketch *> qs;
-        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
-            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
-            refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
-            if (nr == 0) return MHX_OK;
-            std::vector<const RefSketch *> lists;
-            for (const RefSketch &r : R.refs) lists.push_back(&r);
-            std::vector<uint64_t> rows;
-            std::vector<uint32_t> len;
-            pack_rows(lists, refs.stride, rows, len);
-            for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
-            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
-            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
-            refs.rows = d_rows; refs.len = d_len;
-            return MHX_OK;
-        };
-        auto flush = [&]() -> int {
-            const uint32_t nq = (uint32_t)qs.size();
-            if (nq && nr) {
-                std::vector<const uint64_t *> qrows(nq);
-                std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq);
-                std::vector<double> hx((size_t)nq * o.top);
-                for (uint32_t i = 0; i < nq; ++i) {
-                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                    if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
-                }
-                const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data());
-                if (rc2) return rc2;
-                for (uint32_t qi = 0; qi < nq; ++qi)
-                    for (uint32_t t = 0; t < nh[qi]; ++t) {
-                        const size_t p = (size_t)qi * o.top + t;
-                        const RefSketch &ref = R.refs[hr[p]];
-                        const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
-                        if (pv <= o.max_p_value) pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p]); // drops a row, never promotes a lower-ranked pair
-                    }
-            }
-            qs.clear();
-            held.clear();
-            return MHX_OK;
-        };
-        for (int i = 0; i < n_qry; ++i) {
-            held.emplace_back();
-            SketchSet &Q = held.back();
-            rc = msh_read_file(qry_msh[i], Q);
-            if (rc) return rc;
-            if (i == 0) q_sketch_size = Q.sketch_size;
-            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-            if (rc) return rc;
-            if (i == 0) {
-                s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
-                rc = stage_refs();
-                if (rc) return rc;
-            }
-            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+        uint64_t T = 0;
+        if (so.replicates == 0) {
+            if (clade_csv) return fail(MHX_E_ARG, "search: a clade table needs replicates");
+            return search_files_text(ref_msh, qry_msh, n_qry, o, nullptr, 0, nullptr, stdout_buf, cap, need);
         }
-        rc = flush();
+        rc = support_check(1, 1, so.top, so.replicates, so.keep, &T); // refused before a file is read
         if (rc) return rc;
-        return put_text(text, stdout_buf, cap, need);
+        return search_files_text(ref_msh, qry_msh, n_qry, o, &so, T, clade_csv, stdout_buf, cap, need);
     });
 }

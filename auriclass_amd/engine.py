@@ -202,6 +202,12 @@ def load() -> ctypes.CDLL:
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_search_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(SearchOpts), c.c_char_p, c.c_size_t,
                                        c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_support"):   # (or older than the jackknife support of search hits)
+        L.mhx_dist_support.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p,
+                                       c.c_void_p, c.c_uint32, c.c_uint32, c.c_double, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                       c.c_void_p, c.c_int]
+        L.mhx_search_files_support.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(SearchSupportOpts), c.c_char_p, c.c_char_p,
+                                               c.c_size_t, c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -344,13 +350,28 @@ class SearchOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("top", ctypes.c_uint32), ("max_dist", ctypes.c_double), ("max_p_value", ctypes.c_double)]
 
 
-def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1.0, max_p_value: float = 1.0) -> str:
+class SearchSupportOpts(ctypes.Structure):
+    """mhx_search_support_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("top", ctypes.c_uint32), ("max_dist", ctypes.c_double), ("max_p_value", ctypes.c_double),
+                ("replicates", ctypes.c_uint32), ("keep", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
+def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1.0, max_p_value: float = 1.0, replicates: int = 0,
+                 keep: float = 0.5, seed: int = 42, clades=None) -> str:
     """For every query sketch of the files, in argument order and then file order, its `top` closest references of REF.msh
     with distance <= max_dist, best first, as `mash dist` rows "ref\\tquery\\tdist\\tp\\tcommon/denom"; a query without hits
-    prints nothing.  max_p_value drops rows from the `top` already chosen and never promotes a lower-ranked pair."""
+    prints nothing.  max_p_value drops rows from the `top` already chosen and never promotes a lower-ranked pair.
+    replicates = R > 0 (mhx_search_files_support): a sixth column "c/R", in how many of R jackknife replicates of the sketches
+    (keep, seed) the row's reference is the best of the query's hits; with `clades` (AuriClass's clade_config.csv) two more, the
+    clade of the row's reference and "g/R", the replicates whose best hit has that clade."""
     init()
     files = [os.fsencode(str(p)) for p in qry_paths]
     arr = (ctypes.c_char_p * len(files))(*files)
+    if replicates != 0 or clades is not None:
+        sopts = SearchSupportOpts(ctypes.sizeof(SearchSupportOpts), int(top), float(max_dist), float(max_p_value), int(replicates), float(keep), int(seed))
+        table = None if clades is None else os.fsencode(str(clades))
+        return _text_call(lambda buf, cap, need: load().mhx_search_files_support(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(sopts), table,
+                                                                                 buf, cap, need), guess=1 << 20)
     opts = SearchOpts(ctypes.sizeof(SearchOpts), int(top), float(max_dist), float(max_p_value))
     return _text_call(lambda buf, cap, need: load().mhx_search_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
                                                                      need), guess=1 << 20)
@@ -1213,4 +1234,54 @@ def dist_search_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_pt
     v = ctypes.c_void_p
     _check(load().mhx_dist_search(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s, float(max_dist), int(top), v(ref_ptr),
                                   v(common_ptr), v(denom_ptr), v(dist_ptr or None), v(n_hits_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
+
+
+def _support_cand(cand, n_cand, nq: int):
+    if cand is None:
+        return None, None
+    cand = np.ascontiguousarray(cand, dtype=np.uint32)
+    n_cand = np.ascontiguousarray(n_cand, dtype=np.uint32)
+    assert cand.ndim == 2 and cand.shape[0] == nq and n_cand.shape == (nq,)
+    return cand, n_cand
+
+
+def dist_support(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s: int, replicates: int, keep: float = 0.5, seed: int = 42,
+                 cand=None, n_cand=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Jackknife support of search hits (mhx_dist_support).  cand [nq, top] holds per query the indices of its candidate
+    references, the first n_cand [nq] of a row valid; cand None: references 0 .. nr - 1 (nr <= 64) for every query.  Returns
+    first [nq, top], in how many of the `replicates` resampled sketches each candidate is the best one, rep_best [nq, R] (the
+    best reference of every replicate, 0xFFFFFFFF without candidates), rep_s [nq, R] (its sketch size s_r), and rep_common,
+    rep_denom [nq, top, R], the pair results of every replicate."""
+    init()
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    cand, n_cand = _support_cand(cand, n_cand, nq)
+    top = nr if cand is None else cand.shape[1]
+    R = max(int(replicates), 0)
+    first = np.zeros((nq, top), dtype=np.uint32)
+    rep_best, rep_s = np.zeros((nq, R), dtype=np.uint32), np.zeros((nq, R), dtype=np.uint32)
+    rep_common, rep_denom = np.zeros((nq, top, R), dtype=np.uint32), np.zeros((nq, top, R), dtype=np.uint32)
+    _check(load().mhx_dist_support(q.ctypes.data, q_len.ctypes.data, nq, r.ctypes.data, r_len.ctypes.data, nr, stride, s,
+                                   None if cand is None else cand.ctypes.data, None if cand is None else n_cand.ctypes.data, top, int(replicates),
+                                   float(keep), seed, first.ctypes.data, rep_best.ctypes.data, rep_s.ctypes.data, rep_common.ctypes.data,
+                                   rep_denom.ctypes.data, 0))
+    return first, rep_best, rep_s, rep_common, rep_denom
+
+
+def dist_support_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_ptr: int, nr: int, stride: int, s: int, top: int, replicates: int,
+                        keep: float, seed: int, cand_ptr: int, n_cand_ptr: int, first_ptr: int, rep_best_ptr: int = 0, rep_s_ptr: int = 0,
+                        rep_common_ptr: int = 0, rep_denom_ptr: int = 0) -> float:
+    """Device pointers in and out (shapes as dist_support; cand_ptr 0: references 0 .. nr - 1, top == nr; each rep_* pointer
+    may be 0, rep_common and rep_denom both or neither): the same bytes as dist_support gives, left on the device.  The
+    hits of dist_search_device go straight in as candidates.  Returns the kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_support(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, s, v(cand_ptr or None), v(n_cand_ptr or None), int(top),
+                                   int(replicates), float(keep), seed, v(first_ptr), v(rep_best_ptr or None), v(rep_s_ptr or None),
+                                   v(rep_common_ptr or None), v(rep_denom_ptr or None), 1))
     return load().mhx_last_dist_kernel_ms()

@@ -1,5 +1,9 @@
-"""`python -m auriclass_amd.search [-n TOP] [-d MAX_DIST] [-v MAX_P] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: for every
+"""`python -m auriclass_amd.search [-n TOP] [-d MAX_DIST] [-v MAX_P] [-p N] [--support R [--keep F] [--seed N] [--clades FILE]]
+REF.msh QUERY.msh [QUERY.msh ...]`: for every
 query sketch its TOP closest references of REF.msh within MAX_DIST, best first, as `mash dist` rows (engine.search_files).
+--support R adds a column "c/R": in how many of R jackknife replicates of the sketches (each keeps the share --keep of the
+hashes, drawn from --seed) the row's reference is the best of the query's hits; --clades FILE (AuriClass's clade_config.csv)
+adds the clade of the row's reference and "g/R", the replicates whose best hit has that clade.
 Ranking and filtering happen on the device, so REF.msh may hold a reference set far too large to print in full.  Inputs are
 sketch files: a sequence file is refused with the hint to sketch it first.  Exit status 1 with the engine's message when
 the call fails.  -p (threads) is accepted and ignored: the engine has its own."""
@@ -18,6 +22,10 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("-d", dest="max_dist", type=float, default=1.0, help="maximum distance to report [1]")
     ap.add_argument("-v", dest="max_p_value", type=float, default=1.0, help="maximum p-value to report (drops rows, promotes none) [1]")
     ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
+    ap.add_argument("--support", dest="replicates", type=int, default=None, metavar="R", help="jackknife replicates, 0 .. 10000: a support column c/R [none]")
+    ap.add_argument("--keep", type=float, default=None, metavar="F", help="share of the hashes a replicate keeps, (0, 1] [0.5]; needs --support")
+    ap.add_argument("--seed", type=int, default=None, metavar="N", help="seed of the replicates [42]; needs --support")
+    ap.add_argument("--clades", default=None, metavar="FILE", help="clade table (filename,clade): clade and g/R columns; needs --support")
     ap.add_argument("reference", metavar="REF.msh")
     ap.add_argument("queries", metavar="QUERY.msh", nargs="+")
     try:
@@ -28,8 +36,19 @@ def main(argv: List[str] = None) -> int:
         if not str(path).endswith(".msh"):
             sys.stderr.write(f"ERROR: the search takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
             return 1
+    if args.replicates is None and (args.keep is not None or args.seed is not None or args.clades is not None):
+        sys.stderr.write("ERROR: --keep, --seed and --clades need --support R\n")
+        return 1
+    if args.replicates is not None and not 0 <= args.replicates <= 10000:
+        sys.stderr.write("ERROR: --support takes 0 .. 10000 replicates\n")
+        return 1
+    if args.seed is not None and not 0 <= args.seed < 1 << 64:
+        sys.stderr.write("ERROR: --seed takes 0 .. 2^64 - 1\n")
+        return 1
     try:
-        text = engine.search_files(args.reference, args.queries, top=args.top, max_dist=args.max_dist, max_p_value=args.max_p_value)
+        text = engine.search_files(args.reference, args.queries, top=args.top, max_dist=args.max_dist, max_p_value=args.max_p_value,
+                                   replicates=args.replicates or 0, keep=0.5 if args.keep is None else args.keep,
+                                   seed=42 if args.seed is None else args.seed, clades=args.clades)
     except engine.EngineError as exc:
         sys.stderr.write(exc.message + "\n")
         return 1

@@ -16,6 +16,11 @@
  *   mhx_search_files  <- no mash command: `mash dist REF.msh QUERY.msh ...` followed by a sort per query, for a reference
  *                        set too large to print in full -- per query sketch the `top` closest references within a
  *                        distance bound, as dist rows (python -m auriclass_amd.search)
+ *   mhx_dist_support  <- no mash command, and what AuriClass's QC_multiple_hits reads off one cell of `mash bounds`: a jackknife
+ *                        over the sketch hashes -- in how many resampled sketches each of a query's closest references is still
+ *                        the best one (buffer level; engine.dist_support)
+ *   mhx_search_files_support <- no mash command: the same for sketch files, as further columns of the search's rows, with the
+ *                        clades of AuriClass's clade_config.csv (python -m auriclass_amd.search --support R [--clades FILE])
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
@@ -667,6 +672,59 @@ typedef struct mhx_search_opts {
 } mhx_search_opts;
 int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf,
                      size_t cap, size_t *need);
+
+/* JACKKNIFE SUPPORT OF SEARCH HITS: in how many of `replicates` resampled sketches each of a query's closest references is
+ * still the best one.  The rule (auriclass_amd/csrc/mhx_support.h, restated in tests/support_rule.py), all of it in integers.
+ * For query q with candidates cand[q][0 .. n_cand[q]) (indices into r; at most top <= 64, distinct) and replicate
+ * r = 0 .. replicates - 1: the replicate of the jackknife above (keep function, T, "full" means len == s) over the set
+ * [query, candidate 0, ..]; s_r is the smallest kept count among the full lists of THAT set (s when none is full), so it
+ * belongs to the query; s_r == 0: MHX_E_ARG, the message names the query, the replicate and keep.  (common, denom) of candidate
+ * i are mhx_dist_batch's pair rule over the cut lists at sketch size s_r.  The best candidate of the replicate is the first in
+ * the order of mhx_dist_search (exact Jaccard index, common == denom as 1/1, ties by the lower reference index); first[q][i] is
+ * the number of replicates whose best candidate is i, so first[q][..] sums to `replicates` for a query with candidates.
+ * cand == NULL: candidates 0 .. nr - 1 for every query; needs nr <= 64 and top == nr (n_cand is not read).
+ * Outputs: first [nq][top] (entries behind n_cand[q] zero); rep_best [nq][replicates] the reference index of the best candidate,
+ * 0xFFFFFFFF for a query without candidates; rep_s [nq][replicates] s_r; rep_common, rep_denom [nq][top][replicates] (entries
+ * of candidates behind n_cand[q] unspecified).  Each rep_* may be NULL, rep_common and rep_denom both or neither.
+ * device_ptrs != 0 => every pointer is a device pointer; the outputs are the same bytes in both forms.
+ * MHX_E_ARG before anything is launched: s or stride 0, top outside 1 .. 64, keep outside (0, 1] or not a number, replicates
+ * outside 1 .. 10 000, cand == NULL with nr > 64 or top != nr, a null required pointer (q, q_len, first; r, r_len with nr > 0;
+ * n_cand with cand), and in the host form n_cand[q] > top, a candidate >= nr or named twice in a row, a len > stride.  The
+ * device form cannot see those: there an index or length that lies is clamped before it is used (n_cand to top, a candidate to
+ * nr - 1, a length to the stride), so no load leaves the matrices.  nq == 0: MHX_OK.
+ * On the device: given s_r the cut does not change a pair's result, so all replicates of a pair are
+ * counted in ONE ascending walk over the distinct values of the two original lists, the replicates on the lanes of a wave
+ * and every load the same for all lanes; the merged sequence is cut into one share per wave by merge-path diagonals.  Four
+ * launches per batch of queries (kept counts, s_r, pairs, best); nothing is rewritten and one 8-byte word is read back per call.
+ * Memory: (3 top + 3) * 4 * replicates bytes of workspace per query of a batch; the queries are cut into batches so that it
+ * stays below 256 MiB (MHX_SUPPORT_WORK_MB sets another bound in MiB; a batch holds at least one query, at most 32 768).
+ * mhx_last_dist_kernel_ms reports this call too.
+ * Not built: a column in AuriClass's report (needs calibration on real isolates), support for `mash dist`, percentile bounds
+ * of the replicate distances, kept counts shared between the queries of a common reference set, more than 64 candidates. */
+int mhx_dist_support(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr,
+                     uint32_t stride, uint32_t s, const uint32_t *cand, const uint32_t *n_cand, uint32_t top, uint32_t replicates,
+                     double keep, uint64_t seed, uint32_t *first, uint32_t *rep_best, uint32_t *rep_s, uint32_t *rep_common,
+                     uint32_t *rep_denom, int device_ptrs);
+/* mhx_search_files with support values: files, checks and the search itself as there.  replicates == 0 prints exactly what
+ * mhx_search_files prints, and clade_csv must then be NULL (MHX_E_ARG).  replicates = R > 0: the candidates of a query are its
+ * hits -- within max_dist, at most top, BEFORE max_p_value drops rows -- and mhx_dist_support runs on them on the device, on the
+ * rows the search has staged; every printed row gets a sixth column "c/R", c = first of its reference.  With clade_csv
+ * (AuriClass's clade_config.csv: a header line, then "filename,clade" lines split at the last comma) every row gets two more:
+ * the clade of its reference and "g/R", g the replicates whose best candidate has that clade.  A reference of REF.msh whose
+ * name is no filename of the table: MHX_E_FORMAT, the message names it; a table that cannot be read: MHX_E_IO.
+ * opts == NULL means {sizeof, 5, 1, 1, 0, 0.5, 42}.  MHX_E_ARG: struct_size != sizeof(mhx_search_support_opts), and what
+ * mhx_search_files and mhx_dist_support refuse.  Pinned by the restated rules (tests/search_rule.py, tests/support_rule.py). */
+typedef struct mhx_search_support_opts {
+    uint32_t struct_size; /* sizeof(mhx_search_support_opts) */
+    uint32_t top;         /* hits per query, 1 .. 64 */
+    double max_dist;      /* keep pairs with distance <= max_dist (1: all) */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+    uint32_t replicates;  /* jackknife replicates, 0: none */
+    double keep;          /* the share of the hashes a replicate keeps, (0, 1] */
+    uint64_t seed;
+} mhx_search_support_opts;
+int mhx_search_files_support(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_support_opts *opts,
+                             const char *clade_csv, char *stdout_buf, size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
  * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is
