@@ -222,6 +222,28 @@ hipError_t launch_tri_cluster(const ClusterOut &o, hipStream_t st);
 // parent[i] = the root of i, in a launch of its own; count (may be null) receives the number of roots on top of what it holds
 hipError_t launch_cluster_flatten(uint32_t *parent, uint32_t n, unsigned long long *count, hipStream_t st);
 
+// medoids of a partition of one set (rules: mhx_medoid.h, kernels: mhx_medoid.hip): a block's results, block-local as above,
+// add the distances of the pairs inside a cluster to sum[n]; then the pick, and the pair of every list with its target
+struct MedoidOut {
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;
+    uint32_t r0, nr, q0, nq; // the block (mhx_triangle.h: TriBlock)
+    const uint32_t *label;   // [n] the partition: label[i] the lowest index of i's cluster, checked by the host
+    unsigned long long *sum; // [n] zero before the first block
+    int k;
+};
+struct DistToArgs {
+    const uint64_t *rows;
+    const uint32_t *len;
+    uint32_t n, stride, s;
+    const uint32_t *target;   // [n] below n, checked by the host
+    uint32_t *common, *denom; // [n] the pair (i, target[i])
+};
+hipError_t launch_tri_medoid(const MedoidOut &o, hipStream_t st);
+// best [n] at all ones before the launch; medoid[i] = the member of i's cluster with the smallest (sum, index)
+hipError_t launch_medoid_pick(const uint32_t *label, const unsigned long long *sum, unsigned long long *best, uint32_t *medoid, uint32_t n, hipStream_t st);
+hipError_t launch_dist_to(const DistToArgs &a, hipStream_t st);
+
 // single-linkage tree of one set (rules: mhx_mst.h, kernels: mhx_mst.hip): the passes of one Boruvka round.  best [n] holds
 // the best outgoing edge of every list (mst_pack), winner [n] the list that stands for a component, comp [n] the flattened
 // parent of the round before (read-only within a round), parent [n] the union-find the hooks write.

@@ -136,6 +136,7 @@ struct Engine {
     int last_mst_stored = -1;    // its pair source: 1 stored, 0 recomputed, -1 none ran
     int last_linkage_rescans = 0; // rows scanned again in the steps of the last mhx_dist_linkage call
     uint64_t last_nj_clamps = 0;  // updates the clamp at 0 changed in the last mhx_dist_nj call
+    uint64_t last_medoid_blocks = 0; // blocks the last mhx_dist_medoids call ran << 32 | blocks of its schedule
     PinnedArray<uint8_t> dist_img; // pinned image of the reference sketch file of mhx_dist_files
     // bulk file ingest: pinned staging ring (allocated on first use, kept)
     static constexpr int kPinnedSlots = 4;

@@ -1,10 +1,11 @@
 // mhx_engine_triangle.cpp -- host side of the all-pairs distance within one sketch set (mhx_dist_triangle,
 // mhx_dist_triangle_edges and mhx_dist_cluster; the tree, mhx_dist_mst, is in mhx_engine_mst.cpp and takes its pairs from
-// here): staging of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE offsets table of
-// the whole set, the fallback of a flagged block to the generic pair kernel, one function per mode that rides the
+// here, and so do the medoids, mhx_dist_medoids in mhx_engine_medoid.cpp, whose block mode run_medoid lies here): staging
+// of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE offsets table of the whole set, the fallback of a flagged block to the generic pair kernel, one function per mode that rides the
 // schedule, the exact distance rule and the order of the edge list on the host, the bound of the clustering as a table
 // of integers.
-// Rules: mhx_triangle.h, mhx_cluster.h, mhx_mst.h; kernels: mhx_triangle.hip, mhx_cluster.hip, mhx_mst.hip and mhx_dist.hip.
+// Rules: mhx_triangle.h, mhx_cluster.h, mhx_mst.h, mhx_medoid.h; kernels: mhx_triangle.hip, mhx_cluster.hip, mhx_mst.hip,
+// mhx_medoid.hip and mhx_dist.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -15,6 +16,7 @@
 
 #include "mhx_device.h"
 #include "mhx_cluster.h"
+#include "mhx_medoid.h"
 #include "mhx_mst.h"
 #include "mhx_triangle.h"
 #include "mhx_engine_internal.h"
@@ -25,7 +27,7 @@ using namespace mhx;
 
 namespace {
 
-// The schedule of a call over the engine's stream, what the four modes below share.  The set's lists are split into value
+// The schedule of a call over the engine's stream, what the modes below share.  The set's lists are split into value
 // ranges ONCE (offsets() over all n lists); every block then runs the range pass and a finish pass into its block-local
 // [queries][32] results, and the mode's take-out kernel takes the pairs that count from there.  Block flags come back
 // once per group of blocks; a flagged block is redone by the generic pair kernel into the same block-local arrays.
@@ -69,6 +71,12 @@ struct TriSchedule {
         bytes = o;
     }
     uint64_t per() const { return (uint64_t)ranges + 1; } // offsets per list
+    // a mode that needs only some of the blocks drops the others (before place(); the workspace keeps its size)
+    template <class Keep> void keep_blocks(Keep keep)
+    {
+        blocks.erase(std::remove_if(blocks.begin(), blocks.end(), [&](const TriBlock &b) { return !keep(b); }), blocks.end());
+        nblocks = (uint32_t)blocks.size();
+    }
     // room of the mode's own behind the common part (before place()): where it lies, for at()
     size_t extra(size_t n) { const size_t o = bytes; bytes += up256(n); return o; }
     uint8_t *at(size_t o) const { return g.dist_ws + o; }
@@ -251,6 +259,60 @@ int run_cluster(const TriCall &c, const uint32_t *h_cmin, uint32_t *parent, uint
 } // namespace
 
 namespace mhx {
+
+// The medoid mode (mhx_medoid.h): the labels are known, and only the blocks that hold a pair of one cluster are run -- the
+// schedule's blocks filtered by the exact predicate on the host, the offsets table built when one is left.  Their take-out
+// pass adds the in-cluster distances to sum [n]; the pick and, on request, the pair kernel follow on the same stream.
+int run_medoid(const TriCall &c, const MedoidRun &m)
+{
+    g.last_medoid_blocks = 0;
+    const bool pairs = m.common != nullptr;
+    const DistToArgs to{c.rows, c.len, c.n, c.stride, c.s, m.medoid, m.common, m.denom};
+    auto reset = [&](hipError_t &le) { // sums at zero, no key yet
+        if (le == hipSuccess) le = hipMemsetAsync(m.sum, 0, (size_t)c.n * 8, g.stream);
+        if (le == hipSuccess) le = hipMemsetAsync(m.best, 0xFF, (size_t)c.n * 8, g.stream);
+    };
+    auto pick = [&](hipError_t &le) {
+        if (le == hipSuccess) le = launch_medoid_pick(m.label, m.sum, m.best, m.medoid, c.n, g.stream);
+        if (le == hipSuccess && pairs) le = launch_dist_to(to, g.stream);
+    };
+    if (c.n < 2) { // a list on its own: no triangle pass
+        hipError_t le = hipSuccess;
+        reset(le);
+        pick(le);
+        if (le == hipSuccess) le = hipStreamSynchronize(g.stream);
+        g.last_dist_ms = 0.0;
+        if (le != hipSuccess) return fail(MHX_E_HIP, "medoid kernel failed: %s", hipGetErrorString(le));
+        return MHX_OK;
+    }
+    TriSchedule sch(c);
+    const uint32_t scheduled = sch.nblocks;
+    {
+        std::vector<uint32_t> start((size_t)c.n + 1), member(c.n);
+        medoid_members(m.h_label, c.n, start.data(), member.data());
+        sch.keep_blocks([&](const TriBlock &b) { return medoid_block_runs(b, m.h_label, start.data(), member.data()); });
+    }
+    g.last_medoid_blocks = (uint64_t)sch.nblocks << 32 | scheduled;
+    int rc = sch.place();
+    if (rc) return rc;
+    hipError_t &le = sch.le;
+    sch.begin();
+    reset(le);
+    if (sch.nblocks) {
+        sch.offsets();
+        rc = sch.run_blocks(
+            [&](const TriBlock &b, const uint32_t *flag) {
+                MedoidOut t = sch.out_of<MedoidOut>(b, flag);
+                t.label = m.label; t.sum = m.sum; t.k = c.k;
+                return launch_tri_medoid(t, g.stream);
+            },
+            true);
+        if (rc) return rc;
+    }
+    pick(le);
+    rc = sch.end();
+    return rc ? rc : sch.wait();
+}
 
 // the dense mode: every pair into the packed triangle
 int run_dense(const TriCall &c, uint32_t *common, uint32_t *denom, double *dist)

@@ -28,6 +28,16 @@ int stage_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t s
 // the dense mode: every pair into the packed triangle [n (n - 1) / 2]; dist may be null
 int run_dense(const TriCall &c, uint32_t *common, uint32_t *denom, double *dist);
 
+// The medoid mode (mhx_medoid.h), everything on the device but h_label, the host's copy of label, which it has checked: the
+// blocks that hold a pair of one cluster add to sum [n], the pick writes medoid [n] through best [n], and with common / denom
+// (both or neither) the pair kernel compares every list with its medoid.  n >= 1; n == 1 runs no block.
+struct MedoidRun {
+    const uint32_t *h_label, *label;
+    unsigned long long *sum, *best;
+    uint32_t *medoid, *common, *denom;
+};
+int run_medoid(const TriCall &c, const MedoidRun &m);
+
 // The state of a single-linkage tree call (mhx_mst.h) between its rounds, everything on the device: what the five steps of
 // a round read and write, and the counters that come back once per round.
 struct MstRun {

@@ -1,5 +1,5 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
-// triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files), the single-linkage tree (mhx_tree_files), complete
+// triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files, mhx_cluster_reps_files), the single-linkage tree (mhx_tree_files), complete
 // and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
 // (mhx_search_files).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
 // of sequence files is in mhx_files.cpp.
@@ -18,6 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "mhx_triangle.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
 
@@ -263,47 +264,98 @@ int check_no_counts(const char *what, const std::vector<const RefSketch *> &refs
     return MHX_OK;
 }
 
-// The table of a clustering from its labels (label[i]: the lowest member of i's cluster): clusters numbered from 1 by their
-// lowest member, members in index order, a representative per cluster in one pass, a row per reference -- with the degree
-// column when there are degrees --, and the representatives, unchanged, as a sketch file of their own on request.
-int cluster_table(const char *what, const SetOfFiles &S, const std::vector<uint32_t> &label, uint32_t n_clusters, const std::vector<uint32_t> *degree, bool comment,
-                  int rep_rule, const char *out_msh, std::string &text)
+// A clustering from its labels (label[i]: the lowest member of i's cluster): clusters numbered from 1 by their lowest
+// member, their sizes and a representative per cluster in one pass -- the lowest member (rep_rule 0), the member of greatest
+// genome length (1), or medoid[i] of any member (2: mhx_dist_medoids) --, O(n).
+struct ClusterShape {
+    std::vector<uint32_t> number, size, rep, order; // by label: number, members, representative; order: the labels ascending
+};
+int cluster_shape(const char *what, const SetOfFiles &S, const std::vector<uint32_t> &label, uint32_t n_clusters, int rep_rule, const std::vector<uint32_t> *medoid,
+                  ClusterShape &sh)
 {
     const std::vector<const RefSketch *> &refs = S.refs;
     const uint32_t n = S.n();
-    // a cluster's number, size and representative by its label, O(n)
-    std::vector<uint32_t> number(n, 0), size(n, 0), rep(n, 0), order;
+    sh.number.assign(n, 0); sh.size.assign(n, 0); sh.rep.assign(n, 0); sh.order.clear();
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t l = label[i];
         if (l > i || label[l] != l) return fail(MHX_E_INTERNAL, "%s: label %u of reference %u is not a cluster's lowest member", what, l, i);
-        if (l == i) { order.push_back(i); number[i] = (uint32_t)order.size(); rep[i] = i; }
-        ++size[l];
-        if (rep_rule == 1 && refs[i]->length > refs[rep[l]]->length) rep[l] = i; // members come in index order: ties stay with the lower
+        if (l == i) { sh.order.push_back(i); sh.number[i] = (uint32_t)sh.order.size(); sh.rep[i] = rep_rule == 2 ? (*medoid)[i] : i; }
+        ++sh.size[l];
+        if (rep_rule == 1 && refs[i]->length > refs[sh.rep[l]]->length) sh.rep[l] = i; // members come in index order: ties stay with the lower
     }
-    if (order.size() != n_clusters) return fail(MHX_E_INTERNAL, "%s: %zu labels but %u clusters counted", what, order.size(), n_clusters);
+    if (sh.order.size() != n_clusters) return fail(MHX_E_INTERNAL, "%s: %zu labels but %u clusters counted", what, sh.order.size(), n_clusters);
+    return MHX_OK;
+}
+
+// The table of a clustering: members in index order, a row per reference "cluster\tsize\trepresentative\tmember" and what
+// column(i) adds behind it (nothing: no further column)
+template <class Column> void cluster_rows(const SetOfFiles &S, const std::vector<uint32_t> &label, const ClusterShape &sh, bool comment, Column column, std::string &text)
+{
+    const std::vector<const RefSketch *> &refs = S.refs;
+    const uint32_t n = S.n();
     auto shown = [&](uint32_t i) -> const std::string & { return comment ? refs[i]->comment : refs[i]->name; };
-    std::vector<std::vector<uint32_t>> members(order.size());
-    for (uint32_t i = 0; i < n; ++i) members[number[label[i]] - 1].push_back(i);
-    for (size_t ci = 0; ci < order.size(); ++ci) {
-        const uint32_t l = order[ci];
+    std::vector<std::vector<uint32_t>> members(sh.order.size());
+    for (uint32_t i = 0; i < n; ++i) members[sh.number[label[i]] - 1].push_back(i);
+    for (size_t ci = 0; ci < sh.order.size(); ++ci) {
+        const uint32_t l = sh.order[ci];
         for (uint32_t i : members[ci]) {
-            text += std::to_string(ci + 1) + "\t" + std::to_string(size[l]) + "\t" + shown(rep[l]) + "\t" + shown(i);
-            if (degree) text += "\t" + std::to_string((*degree)[i]);
+            text += std::to_string(ci + 1) + "\t" + std::to_string(sh.size[l]) + "\t" + shown(sh.rep[l]) + "\t" + shown(i);
+            const std::string more = column(i);
+            if (!more.empty()) text += "\t" + more;
             text += "\n";
         }
     }
-    if (!out_msh) return MHX_OK;
-    const uint32_t m = (uint32_t)order.size();
+}
+
+// the representatives, unchanged, in cluster order as a sketch file of their own
+int cluster_reps_msh(const SetOfFiles &S, const ClusterShape &sh, const char *out_msh)
+{
+    const uint32_t m = (uint32_t)sh.order.size();
     std::vector<const char *> names(m), comments(m);
     std::vector<uint64_t> lengths(m);
     std::vector<const uint64_t *> hashes(m);
     std::vector<uint32_t> n_hashes(m);
     for (uint32_t ci = 0; ci < m; ++ci) {
-        const RefSketch &r = *refs[rep[order[ci]]];
+        const RefSketch &r = *S.refs[sh.rep[sh.order[ci]]];
         names[ci] = r.name.c_str(); comments[ci] = r.comment.c_str(); lengths[ci] = r.length;
         hashes[ci] = r.hash_data(); n_hashes[ci] = (uint32_t)r.hash_count();
     }
     return mhx_msh_write(out_msh, S.k(), S.F[0].sketch_size, m, names.data(), comments.data(), lengths.data(), hashes.data(), n_hashes.data());
+}
+
+// The table of mhx_cluster_files and of the cut of mhx_linkage_files: a row per reference -- with the degree column when there
+// are degrees --, and the representatives as a sketch file on request.
+int cluster_table(const char *what, const SetOfFiles &S, const std::vector<uint32_t> &label, uint32_t n_clusters, const std::vector<uint32_t> *degree, bool comment,
+                  int rep_rule, const char *out_msh, std::string &text)
+{
+    ClusterShape sh;
+    const int rc = cluster_shape(what, S, label, n_clusters, rep_rule, nullptr, sh);
+    if (rc) return rc;
+    cluster_rows(S, label, sh, comment, [&](uint32_t i) { return degree ? std::to_string((*degree)[i]) : std::string(); }, text);
+    return out_msh ? cluster_reps_msh(S, sh, out_msh) : MHX_OK;
+}
+
+// The labels of the set at max_dist for mhx_cluster_reps_files: single linkage from mhx_dist_cluster, complete and average from
+// the merges of mhx_dist_linkage cut by mhx_linkage_labels
+int reps_labels(const SetOfFiles &S, int linkage, double max_dist, std::vector<uint32_t> &label, uint32_t *n_clusters)
+{
+    const uint32_t n = S.n();
+    label.assign(n, 0);
+    if (linkage == 0) {
+        uint64_t n_edges = 0;
+        return mhx_dist_cluster(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), max_dist, label.data(), nullptr, n_clusters, &n_edges, 0);
+    }
+    const uint32_t m = n ? n - 1 : 0;
+    std::vector<uint32_t> ma(m), mb(m), size(m);
+    std::vector<uint64_t> num(m), den(m);
+    std::vector<double> dist(m);
+    const int rc = mhx_dist_linkage(S.rows.data(), S.len.data(), n, S.stride, S.k(), S.s(), linkage, ma.data(), mb.data(), size.data(), num.data(), den.data(),
+                                    dist.data(), 0);
+    if (rc) return rc;
+    const int64_t found = mhx_linkage_labels(ma.data(), mb.data(), dist.data(), n, max_dist, label.data());
+    if (found < 0) return (int)found;
+    *n_clusters = (uint32_t)found;
+    return MHX_OK;
 }
 
 } // namespace
@@ -395,6 +447,52 @@ extern "C" int mhx_cluster_files(const char *const *paths, int n_paths, const mh
         std::string text;
         rc = cluster_table("cluster", S, label, n_clusters, &degree, o.comment != 0, o.rep, out_msh, text);
         if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// The dereplication with the distance of every member to its representative: labels by the linkage asked for, the
+// representative by the rule asked for -- the medoid from mhx_dist_medoids --, the pair (member, representative) of every row
+// from mhx_dist_to, printed as the triangle's edge row prints a pair.
+extern "C" int mhx_cluster_reps_files(const char *const *paths, int n_paths, const mhx_cluster_reps_opts *opts, const char *out_msh, char *stdout_buf, size_t cap,
+                                      size_t *need)
+{
+    return entry("mhx_cluster_reps_files", [&]() -> int {
+        mhx_cluster_reps_opts o{(uint32_t)sizeof(mhx_cluster_reps_opts), 0, 0, 2, 1.0};
+        int rc = take_opts("cluster_reps", opts, o);
+        if (rc) return rc;
+        if (o.linkage < 0 || o.linkage > 2) return fail(MHX_E_ARG, "cluster_reps: linkage must be 0 (single), 1 (complete) or 2 (average)");
+        if (o.rep < 0 || o.rep > 2) return fail(MHX_E_ARG, "cluster_reps: rep must be 0 (first), 1 (longest) or 2 (medoid)");
+        if (!(o.max_dist == o.max_dist)) return fail(MHX_E_ARG, "cluster_reps: max_dist is not a number");
+        SetOfFiles S;
+        rc = read_set_of_files("cluster_reps", paths, n_paths, S);
+        if (rc) return rc;
+        const std::vector<const RefSketch *> &refs = S.refs;
+        const uint32_t n = S.n();
+        const int k = S.k();
+        if (out_msh) { rc = check_no_counts("cluster_reps", refs); if (rc) return rc; }
+        std::vector<uint32_t> label, medoid(n), target(n), common(n), denom(n);
+        uint32_t n_clusters = 0;
+        rc = reps_labels(S, o.linkage, o.max_dist, label, &n_clusters);
+        if (rc) return rc;
+        if (o.rep == 2) {
+            rc = mhx_dist_medoids(S.rows.data(), S.len.data(), n, S.stride, k, S.s(), label.data(), medoid.data(), nullptr, nullptr, nullptr, 0);
+            if (rc) return rc;
+        }
+        ClusterShape sh;
+        rc = cluster_shape("cluster_reps", S, label, n_clusters, o.rep, &medoid, sh);
+        if (rc) return rc;
+        for (uint32_t i = 0; i < n; ++i) target[i] = sh.rep[label[i]];
+        rc = mhx_dist_to(S.rows.data(), S.len.data(), n, S.stride, k, S.s(), target.data(), common.data(), denom.data(), 0);
+        if (rc) return rc;
+        std::string text;
+        cluster_rows(S, label, sh, o.comment != 0,
+                     [&](uint32_t i) {
+                         const double pv = mhx_p_value(common[i], refs[i]->length, refs[target[i]]->length, k, denom[i]);
+                         return fmt_g(tri_distance(common[i], denom[i], k)) + "\t" + fmt_g(pv) + "\t" + std::to_string(common[i]) + "/" + std::to_string(denom[i]);
+                     },
+                     text);
+        if (out_msh) { rc = cluster_reps_msh(S, sh, out_msh); if (rc) return rc; }
         return put_text(text, stdout_buf, cap, need);
     });
 }

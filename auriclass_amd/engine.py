@@ -184,6 +184,13 @@ def load() -> ctypes.CDLL:
         L.mhx_linkage_fixed_distance.restype = c.c_uint64   # host only
         L.mhx_linkage_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(LinkageOpts), c.c_char_p, c.c_char_p, c.c_size_t,
                                         c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_medoids"):   # (or older than the medoids)
+        L.mhx_dist_medoids.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p,
+                                       c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_dist_to.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_last_medoid_blocks.restype = c.c_uint64
+        L.mhx_cluster_reps_files.argtypes = [c.POINTER(c.c_char_p), c.c_int, c.POINTER(ClusterRepsOpts), c.c_char_p, c.c_char_p, c.c_size_t,
+                                             c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_nj"):   # (or older than neighbour joining)
         L.mhx_dist_nj.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p,
                                   c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
@@ -445,6 +452,34 @@ def linkage_files(paths: Sequence, linkage: str, mode: str = "merges", comment: 
     opts = LinkageOpts(ctypes.sizeof(LinkageOpts), int(bool(comment)), LINKAGES[linkage], LINKAGE_MODES[mode], CLUSTER_REPS[rep], float(max_dist))
     out_path = None if out is None else os.fsencode(str(out))
     return _text_call(lambda buf, cap, need: load().mhx_linkage_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
+
+
+class ClusterRepsOpts(ctypes.Structure):
+    """mhx_cluster_reps_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("linkage", ctypes.c_int32), ("rep", ctypes.c_int32),
+                ("max_dist", ctypes.c_double)]
+
+
+CLUSTER_REPS_LINKAGES = {"single": 0, "complete": 1, "average": 2}
+CLUSTER_REPS_REPS = {"first": 0, "longest": 1, "medoid": 2}
+
+
+def cluster_reps_files(paths: Sequence, max_dist: float, linkage: str = "single", rep: str = "medoid", comment: bool = False, out=None) -> str:
+    """The clusters of the references of all sketch files (one set) at max_dist -- single linkage as cluster_files, complete or
+    average linkage as the cut of linkage_files -- with the distance of every member to its representative, a row per reference:
+    "cluster\\tsize\\trepresentative\\tmember\\tdist\\tp\\tcommon/denom", ordered as cluster_files orders its rows; the last
+    three fields are the triangle's edge-list fields of the pair (member, representative).  rep: "first", "longest" or "medoid"
+    (the member with the smallest sum of distances to the others, ties to the lower index).  out as in cluster_files."""
+    if linkage not in CLUSTER_REPS_LINKAGES:
+        raise ValueError("cluster_reps_files: linkage must be 'single', 'complete' or 'average'")
+    if rep not in CLUSTER_REPS_REPS:
+        raise ValueError("cluster_reps_files: rep must be 'first', 'longest' or 'medoid'")
+    init()
+    files = [os.fsencode(str(p)) for p in paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = ClusterRepsOpts(ctypes.sizeof(ClusterRepsOpts), int(bool(comment)), CLUSTER_REPS_LINKAGES[linkage], CLUSTER_REPS_REPS[rep], float(max_dist))
+    out_path = None if out is None else os.fsencode(str(out))
+    return _text_call(lambda buf, cap, need: load().mhx_cluster_reps_files(arr, len(files), ctypes.byref(opts), out_path, buf, cap, need), guess=1 << 20)
 
 
 class NjOpts(ctypes.Structure):
@@ -1007,6 +1042,57 @@ def dist_cluster_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int
     _check(load().mhx_dist_cluster(v(rows_ptr), v(len_ptr), n, stride, k, s, float(max_dist), v(label_ptr), v(degree_ptr or None),
                                    ctypes.byref(n_clusters), ctypes.byref(n_edges), 1))
     return int(n_clusters.value), int(n_edges.value)
+
+
+def dist_medoids(rows: np.ndarray, lens: np.ndarray, k: int, s: int, label) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The medoid of every cluster of a partition of ONE set of hash lists (rows [n, stride], lens [n], as dist_triangle takes
+    them; label[i] the lowest index of i's cluster, as dist_cluster, mst_labels and linkage_labels give it): (medoid, sum,
+    common, denom) with sum[i] the sum of linkage_fixed_distance over the other members of i's cluster, medoid[i] the member of
+    i's cluster with the smallest (sum, index), and common[i] / denom[i] the pair (i, medoid[i]).  Every value is an exact
+    integer; the blocks run of the blocks scheduled are load().mhx_last_medoid_blocks() (>> 32 and & 0xFFFFFFFF)."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    label = np.ascontiguousarray(label, dtype=np.uint32)
+    assert label.shape == (n,)
+    medoid, common, denom = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    total = np.zeros(n, dtype=np.uint64)
+    _check(load().mhx_dist_medoids(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, label.ctypes.data, medoid.ctypes.data, total.ctypes.data,
+                                   common.ctypes.data, denom.ctypes.data, 0))
+    return medoid, total, common, denom
+
+
+def dist_medoids_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, label_ptr: int, medoid_ptr: int, sum_ptr: int = 0,
+                        common_ptr: int = 0, denom_ptr: int = 0) -> int:
+    """Device pointers in and out (label and medoid uint32 [n]; sum uint64 [n] or 0; common and denom uint32 [n], both or
+    neither): the labels are copied to the host and checked there before anything is launched; the results equal the host
+    form's bit for bit and are the same from call to call.  Returns the blocks of the triangle the call ran."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_medoids(v(rows_ptr), v(len_ptr), n, stride, k, s, v(label_ptr), v(medoid_ptr), v(sum_ptr or None), v(common_ptr or None),
+                                   v(denom_ptr or None), 1))
+    return int(load().mhx_last_medoid_blocks() >> 32)
+
+
+def dist_to(rows: np.ndarray, lens: np.ndarray, k: int, s: int, target) -> Tuple[np.ndarray, np.ndarray]:
+    """(common, denom) of the pair (i, target[i]) of ONE set of hash lists for every i, by the pair rule of dist_triangle; a
+    list against itself goes through the rule like any other pair."""
+    init()
+    rows, lens = _triangle_rows(rows, lens)
+    n = rows.shape[0]
+    target = np.ascontiguousarray(target, dtype=np.uint32)
+    assert target.shape == (n,)
+    common, denom = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+    _check(load().mhx_dist_to(rows.ctypes.data, lens.ctypes.data, n, rows.shape[1], k, s, target.ctypes.data, common.ctypes.data, denom.ctypes.data, 0))
+    return common, denom
+
+
+def dist_to_device(rows_ptr: int, len_ptr: int, n: int, stride: int, k: int, s: int, target_ptr: int, common_ptr: int, denom_ptr: int) -> float:
+    """Device pointers in and out (three uint32 [n]); the targets are checked on the host first.  Returns the kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_to(v(rows_ptr), v(len_ptr), n, stride, k, s, v(target_ptr), v(common_ptr), v(denom_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
 
 
 def dist_mst(rows: np.ndarray, lens: np.ndarray, k: int, s: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:

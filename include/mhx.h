@@ -24,6 +24,12 @@
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
+ *   mhx_dist_medoids  <- no mash command: `mash triangle` followed by per-cluster sums on the host -- the member of every
+ *                        cluster with the smallest sum of distances to the others (buffer level; engine.dist_medoids, and
+ *                        mhx_dist_to: every list against one target)
+ *   mhx_cluster_reps_files <- no mash command: the dereplication for every linkage with the medoid as a third kind of
+ *                        representative and the distance of every member to its representative as columns
+ *                        (python -m auriclass_amd.cluster --rep medoid / --dist)
  *   mhx_dist_mst      <- no mash command: `mash triangle` followed by a sort of all pairs and a union-find -- the single-
  *                        linkage tree of a set, every cut of mhx_dist_cluster at once (buffer level; engine.dist_mst)
  *   mhx_tree_files    <- no mash command: the same for sketch files, as a table of merges or a Newick dendrogram
@@ -407,7 +413,8 @@ int mhx_dist_cluster(const uint64_t *rows, const uint32_t *len, uint32_t n, uint
  * cannot store, out_msh is refused with MHX_E_ARG (nothing is dropped silently).  opts == NULL means {sizeof, 0, 0, 1.0}.
  * MHX_E_ARG: struct_size != sizeof(mhx_cluster_opts), rep outside 0 .. 1, a max_dist that is not a number.  Not pinned by
  * mash output (mash has no such command): pinned by the restated rule (tests/cluster_rule.py), its pairs by the
- * mash-pinned distance path.  No p-value filter and no distance-to-representative column. */
+ * mash-pinned distance path.  No p-value filter; the medoid as representative and the distance-to-representative columns
+ * are mhx_cluster_reps_files' below. */
 typedef struct mhx_cluster_opts {
     uint32_t struct_size; /* sizeof(mhx_cluster_opts) */
     int32_t comment;      /* non-zero: print comments in place of names */
@@ -416,6 +423,52 @@ typedef struct mhx_cluster_opts {
 } mhx_cluster_opts;
 int mhx_cluster_files(const char *const *msh_paths, int n_paths, const mhx_cluster_opts *opts, const char *out_msh, char *stdout_buf,
                       size_t cap, size_t *need);
+
+/* MEDOIDS of a partition of ONE set: rows / len / n / stride / k / s as mhx_dist_triangle takes them, with its checks, and
+ * s >= 2^20 -> MHX_E_ARG as for mhx_dist_linkage.  label[n] is a partition as mhx_dist_cluster, mhx_mst_labels and
+ * mhx_linkage_labels return one -- label[i] the lowest index of i's cluster -- and ANY array with label[i] <= i and
+ * label[label[i]] == label[i] for all i is taken; another one is MHX_E_ARG.
+ * sum[i] (may be NULL) is the sum of mhx_linkage_fixed_distance(common, denom, k) (units of 2^-32) over the other members j
+ * of i's cluster, (common, denom) by the pair rule of the mash-pinned distance path; medoid[i] is the member of i's cluster
+ * with the smallest (sum, index) -- ties go to the lower index; a list on its own is its medoid with sum 0.  common[n] /
+ * denom[n] (both or neither, else MHX_E_ARG): the pair (i, medoid[i]) as mhx_dist_to gives it.
+ * device_ptrs != 0 => rows, len, label, medoid, sum, common and denom are device pointers.  In both forms label is
+ * validated on the HOST before anything is launched (the device form copies its 4 n bytes back first), so no kernel
+ * indexes with an unchecked value.  Every result is an exact integer: the sums are 64-bit integer atomics, the pick a 64-bit
+ * minimum over sum << 16 | index; two calls give identical outputs and the two forms agree bit for bit.
+ * Only the blocks of the triangle's schedule that hold a pair of one cluster are run (an exact test on the host,
+ * 32 binary searches per block); with all singletons nothing of the triangle is launched.  mhx_last_medoid_blocks: blocks the last call ran
+ * << 32 | blocks of the schedule.  Device memory: 16 n bytes on top of the triangle's workspace, nothing of size n^2.
+ * n == 0: MHX_OK; n == 1: medoid 0, sum 0 and the pair (0, 0), no triangle pass.  Geometry, MHX_TRI_GEOMETRY,
+ * MHX_TRI_QBATCH and MHX_DIST_GENERIC are the triangle's.  Not built: more than 65 536 lists,
+ * medoids of the neighbour-joining tree, a per-cluster radius (it follows from the pair columns on the host). */
+int mhx_dist_medoids(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, const uint32_t *label,
+                     uint32_t *medoid, uint64_t *sum, uint32_t *common, uint32_t *denom, int device_ptrs);
+/* common[i] / denom[i] of the pair (i, target[i]) by the pair rule of the distance path, one workgroup per list; the pair
+ * (i, i) goes through the rule like any other (common == denom == len[i] for len[i] <= s).  target[i] >= n: MHX_E_ARG,
+ * checked on the host in both forms; the other checks are mhx_dist_medoids'. */
+int mhx_dist_to(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, const uint32_t *target,
+                uint32_t *common, uint32_t *denom, int device_ptrs);
+uint64_t mhx_last_medoid_blocks(void);
+/* The dereplication at file level for every linkage, with the distance of every member to its representative: the set is
+ * read as mhx_cluster_files reads it; the labels come from mhx_dist_cluster (linkage 0, single) or from mhx_dist_linkage cut
+ * by mhx_linkage_labels (1 complete, 2 average) at max_dist; the representative of a cluster is its first (rep 0) or its
+ * longest member (rep 1) as there, or its medoid (rep 2, mhx_dist_medoids).  One row per reference, clusters and members
+ * ordered as mhx_cluster_files orders them:
+ *     cluster\tsize\trepresentative\tmember\tdist\tp\tcommon/denom\n
+ * dist, p and common/denom as the edge row of mhx_triangle_files prints them, for the pair (member, representative), which
+ * mhx_dist_to computes.  out_msh as in mhx_cluster_files, the refusal for multiplicity counts included.  opts == NULL means
+ * {sizeof, 0, 0, 2, 1.0}.  MHX_E_ARG: struct_size != sizeof(mhx_cluster_reps_opts), linkage outside 0 .. 2, rep outside
+ * 0 .. 2, a max_dist that is not a number.  Pinned by the restated rule (tests/medoid_rule.py).  Not built: a p-value filter. */
+typedef struct mhx_cluster_reps_opts {
+    uint32_t struct_size; /* sizeof(mhx_cluster_reps_opts) */
+    int32_t comment;      /* non-zero: print comments in place of names */
+    int32_t linkage;      /* 0 single, 1 complete, 2 average */
+    int32_t rep;          /* 0 first, 1 longest, 2 medoid */
+    double max_dist;      /* the bound of the clustering */
+} mhx_cluster_reps_opts;
+int mhx_cluster_reps_files(const char *const *msh_paths, int n_paths, const mhx_cluster_reps_opts *opts, const char *out_msh, char *stdout_buf,
+                           size_t cap, size_t *need);
 
 /* Single-linkage TREE of ONE set: the minimum spanning tree of the graph of all pairs, which is the single-linkage
  * dendrogram -- its n - 1 edges, sorted, are the merges, and cutting them at any D gives the clusters of mhx_dist_cluster at
