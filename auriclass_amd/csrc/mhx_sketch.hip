@@ -306,7 +306,8 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     const uint32_t qcap = (uint32_t)kGroupsPerTile - nitems; // QUEUE: the work list's unused tail holds the candidate queue
     CandidateQueue queue{sm, nitems, qcap};
     uint32_t ninsert = 0;
-    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE>(sm, sm.list[it], T, limit, ins, queue);
+    const TailLutPtr lut = hot_tail_table<K>(); // once per workgroup, in front of the loop
+    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE>(sm, sm.list[it], T, limit, ins, queue, lut);
     if (QUEUE) {
         __syncthreads();
         const uint32_t ncand = sm.misc[7];

@@ -75,6 +75,35 @@ template <int T> MHX_HD uint32_t tail_lut_index(uint32_t lo, uint32_t hi)
 #endif
 }
 
+// The digits of NDW = 2 or 3 consecutive dwords (8 or 12 bytes, lowest first) packed into one word: the digit of byte i on
+// bits 2i, 2i + 1.  Every dword goes the way of tail_lut_index -- mask, times 0x00820820, its four digits in the top byte --
+// and two v_perm_b32 put the top bytes side by side (selector 0x0c: a zero byte).  A window's index is then a 2T-bit field
+// of this word, tail_lut_index<T> of the T bytes from byte i on = bits 2i .. 2i + 2T - 1: the sketch kernel packs once per
+// group of eight windows what it would otherwise form per window (mhx_tile.h, TailDigits).  Like the index itself the
+// word is made of bits 1..2 of the bytes and nothing else, so any field of it lies inside the table for every byte value.
+MHX_HD uint32_t tail_lut_perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{ // v_perm_b32: out.byte[i] = byte sel.byte[i] of {hi:lo} (0..7), or zero (0x0c)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t both = ((uint64_t)hi << 32) | lo;
+    uint32_t o = 0;
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t s = (sel >> (8 * i)) & 0xFFu;
+        if (s < 8u) o |= (uint32_t)((both >> (8 * s)) & 0xFFu) << (8 * i);
+    }
+    return o;
+#endif
+}
+template <int NDW> MHX_HD uint32_t tail_lut_pack(uint32_t d0, uint32_t d1, uint32_t d2)
+{
+    static_assert(NDW == 2 || NDW == 3, "dwords packed");
+    const uint32_t p0 = (d0 & 0x06060606u) * 0x00820820u, p1 = (d1 & 0x06060606u) * 0x00820820u;
+    const uint32_t two = tail_lut_perm(p1, p0, 0x0c0c0703u); // {0, 0, top of p1, top of p0}
+    if constexpr (NDW == 2) return two;
+    return tail_lut_perm((d2 & 0x06060606u) * 0x00820820u, two, 0x0c070100u);
+}
+
 // The table itself.  On the device the address is made opaque in a scalar register pair: left as the constant it is,
 // hipcc materialises it anew in every basic block that loads from it (s_getpc_b64, two adds, an s_load_dwordx2 from the
 // GOT and an s_waitcnt on it in front of every gather); opaque, that happens once, outside the hash loop.  Behind the
@@ -85,6 +114,15 @@ typedef const __attribute__((address_space(1))) uint64_t *TailLutPtr;
 #else
 typedef const uint64_t *TailLutPtr;
 #endif
+// the entry at a byte offset (8 * index)
+MHX_HD uint64_t tail_lut_at(TailLutPtr lut, uint32_t byte_offset)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(TailLutPtr)((const __attribute__((address_space(1))) char *)lut + byte_offset);
+#else
+    return *(TailLutPtr)((const char *)lut + byte_offset);
+#endif
+}
 template <int T, bool SECOND> MHX_HD TailLutPtr tail_lut_table()
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -21,6 +21,7 @@
 // other, and the exact check then drops it).
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #include "mhx_hd.h"
 #include "mhx_device_consts.h"
@@ -419,16 +420,15 @@ template <int K> MHX_HD TailLutPtr tail_lut_of() { return tail_lut_table<K & 7, 
 // with a byte that is not A/C/G/T then hashes to the value of the letters its bytes alias to, and every such window is
 // dropped behind the loop (mhx_tail_lut.h).  Everything that hashes a window for good keeps the multiplications.
 // lut: tail_lut_of<K>(), fetched once by the caller for all the windows it hashes (LUT = false: unused).
-template <int K, bool LUT = false> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8], TailLutPtr lut = nullptr)
+// murmur3_blocks is the hash itself: with LUT it takes the partial word's k as the caller loaded it (k_lut) and reads
+// only the full 8-byte words of w; murmur3_core forms the table index from w's partial word and loads.
+template <int K, bool LUT> MHX_HD Murmur3Tail murmur3_blocks(const uint32_t (&w)[8], uint64_t k_lut)
 {
     static_assert(!LUT || tail_lut_applies<K>(), "no table for this K");
     constexpr uint64_t c1 = kMurmurC1, c2 = kMurmurC2;
     constexpr int NBLK = K / 16, TAIL = K & 15;
     uint64_t h1 = kMurmurSeed, h2 = kMurmurSeed;
     uint32_t zero = 0; // see mul64c
-    // the gather is issued first, as soon as the partial word's dwords exist, and consumed at the xor behind the blocks
-    uint64_t k_lut = 0;
-    if constexpr (LUT) k_lut = lut[tail_lut_index<K & 7>(w[(K / 8) * 2], w[((K / 8) * 2 + 1) & 7])];
 #pragma unroll
     for (int b = 0; b < NBLK; ++b) {
         uint64_t k1 = make64(w[4 * b], w[4 * b + 1]);
@@ -467,6 +467,13 @@ template <int K, bool LUT = false> MHX_HD Murmur3Tail murmur3_core(const uint32_
     // is a register pair and the sum one v_lshl_add_u64.  32-bit hashes never add them and keep the code they had.
     if (K > 16) { ka = opaque64(ka); kb = opaque64(kb); }
     return Murmur3Tail{ka, kb};
+}
+template <int K, bool LUT = false> MHX_HD Murmur3Tail murmur3_core(const uint32_t (&w)[8], TailLutPtr lut = nullptr)
+{
+    // the gather is issued first, as soon as the partial word's dwords exist, and consumed at the xor behind the blocks
+    uint64_t k_lut = 0;
+    if constexpr (LUT) k_lut = lut[tail_lut_index<K & 7>(w[(K / 8) * 2], w[((K / 8) * 2 + 1) & 7])];
+    return murmur3_blocks<K, LUT>(w, k_lut);
 }
 template <int K> MHX_HD uint64_t murmur3_h1(const uint32_t (&w)[8]) { return murmur3_core<K>(w).finish(); }
 
@@ -800,11 +807,15 @@ template <int K, int OFF, int N> MHX_HD void extract_words(const uint32_t (&src)
 
 // One window: the K bytes of its canonical strand as little-endian words.  U = folded forward chunk, R = its
 // reverse complement, Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented (the last two
-// only feed the strand decision).
-template <int K, int J, int ND>
-MHX_HD void canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
+// only feed the strand decision).  Returns the strand: true = the reverse complement.
+// BODY_ONLY (the hot loop with the tail block's partial word from packed digits, TailDigits below): only the full 8-byte
+// words in front of the partial word, w[0 .. 2 * (K / 8)), are made; the rest of w is zero, and the source dwords and the
+// funnel shifts that only the partial word read are not selected or made at all.
+template <int K, int J, int ND, bool BODY_ONLY = false>
+MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
                             const uint32_t (&Cc)[ND + 1], uint32_t (&w)[8])
 {
+    static_assert(!BODY_ONLY || K > 16, "the body-only form belongs to the tail table (64-bit hashes)");
     constexpr int NW = (K + 3) / 4;
     constexpr int OF = J;               // forward window starts at U byte OF
     constexpr int OR = ND * 4 - K - J;  // its reverse complement starts at R byte OR
@@ -842,23 +853,35 @@ MHX_HD void canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND 
         // compile-time constants (only WHICH of them applies is a per-lane run-time value, so the compiler cannot see it):
         //   neither strand reads S[NW]: it is not selected, and the last word is one bit-field extract of S[NW - 1];
         //   one strand reads it: that strand's dword is taken as it is, the other strand's garbage is masked away.
-        constexpr int TB = K - 4 * (NW - 1); // 1..4
-        constexpr bool need_f = OF % 4 + TB > 4, need_r = OR % 4 + TB > 4;
-        uint32_t S[NW];
+        if constexpr (BODY_ONLY) {
+            constexpr int NBW = 2 * (K / 8); // dwords of the full 8-byte words; NBW < NW, so S[NBW] is a dword of the window
+            static_assert(NBW < NW, "a partial word follows the body");
+            uint32_t S[NBW + 1];
 #pragma unroll
-        for (int i = 0; i < NW; ++i) S[i] = rc ? R[OR / 4 + i] : U[OF / 4 + i];
-        const uint32_t sh = rc ? 8u * (OR % 4) : 8u * (OF % 4);
+            for (int i = 0; i < NBW + 1; ++i) S[i] = rc ? R[OR / 4 + i] : U[OF / 4 + i];
+            const uint32_t sh = rc ? 8u * (OR % 4) : 8u * (OF % 4);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            w[i] = i < NW - 1 ? funnel_bits(S[i + 1], S[i], sh) : 0u;
-        if constexpr (!need_f && !need_r) {
-            if constexpr (TB == 4) w[NW - 1] = S[NW - 1]; // both shifts are 0
-            else w[NW - 1] = bit_field<8 * TB>(S[NW - 1], sh);
+            for (int i = 0; i < 8; ++i) w[i] = i < NBW ? funnel_bits(S[i + 1], S[i], sh) : 0u;
         } else {
-            const uint32_t last = need_f && need_r ? (rc ? R[OR / 4 + NW] : U[OF / 4 + NW]) : need_f ? U[OF / 4 + NW] : R[OR / 4 + NW];
-            w[NW - 1] = funnel_bits(last, S[NW - 1], sh);
-            if constexpr (TB < 4) w[NW - 1] &= (1u << (8 * TB)) - 1u;
+            constexpr int TB = K - 4 * (NW - 1); // 1..4
+            constexpr bool need_f = OF % 4 + TB > 4, need_r = OR % 4 + TB > 4;
+            uint32_t S[NW];
+#pragma unroll
+            for (int i = 0; i < NW; ++i) S[i] = rc ? R[OR / 4 + i] : U[OF / 4 + i];
+            const uint32_t sh = rc ? 8u * (OR % 4) : 8u * (OF % 4);
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                w[i] = i < NW - 1 ? funnel_bits(S[i + 1], S[i], sh) : 0u;
+            if constexpr (!need_f && !need_r) {
+                if constexpr (TB == 4) w[NW - 1] = S[NW - 1]; // both shifts are 0
+                else w[NW - 1] = bit_field<8 * TB>(S[NW - 1], sh);
+            } else {
+                const uint32_t last = need_f && need_r ? (rc ? R[OR / 4 + NW] : U[OF / 4 + NW]) : need_f ? U[OF / 4 + NW] : R[OR / 4 + NW];
+                w[NW - 1] = funnel_bits(last, S[NW - 1], sh);
+                if constexpr (TB < 4) w[NW - 1] &= (1u << (8 * TB)) - 1u;
+            }
         }
+        return rc;
     } else {
         uint32_t wf[8], wr[8];
         extract_words<K, OF>(U, wf);
@@ -866,6 +889,7 @@ MHX_HD void canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND 
         const bool rc = rc_is_smaller_full<NW>(wf, wr);
 #pragma unroll
         for (int i = 0; i < 8; ++i) w[i] = rc ? wr[i] : wf[i];
+        return rc;
     }
 }
 
@@ -920,6 +944,72 @@ MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint3
     U[ND] = R[ND] = Wr[ND] = Cc[ND] = 0;
 }
 
+// ---- the tail table's index from digits packed once per group --------------------------------------------------------
+// The partial word of window J (T = K mod 8 bases behind K / 8 full words) is bytes J + 8 (K / 8) .. of U on the forward
+// strand and bytes OR_J + 8 (K / 8) .., OR_J = 4 ND - K - J, of R on the reverse one.  Over J = 0..7 either range is T + 7
+// bytes at a fixed place: from the dword-aligned byte 8 (K / 8) of U on, and the last T + 7 bytes of R -- inside NDW = 2
+// (T = 1) or 3 consecutive dwords of each.  Their digits are packed once per group (tail_lut_pack) and kept as one 64-bit
+// value, the reverse strand's word above the forward strand's, both shifted left by 3: a window's byte offset into the
+// table is then v_cndmask (the shift: two inline constants per J, the reverse one 32 more), v_lshrrev_b64, v_and_b32 --
+// three instructions where tail_lut_index took five on top of the select and the two funnel shifts that made the partial
+// word itself.  (Selecting the word and the shift apart and extracting with v_bfe_u32 takes four, and measured a third less
+// of the gain: profiles/tail_digits_ab.txt.)  What the shift brings down from the other word lands above the field.
+// The offset equals 8 * tail_lut_index<T> of the partial word canonical_words yields: both are bits 1..2 of the same bytes
+// (tests/emul/tail_digits_emul.cpp checks every K, J, strand and byte value).
+template <int K> struct TailDigits {
+    static constexpr int T = K & 7, Q = K / 8, ND = GroupGeom<K>::ND;
+    static constexpr int NDW = (T + 7 + 3) / 4;  // dwords that hold the T + 7 bytes
+    static constexpr int FD = 2 * Q;             // first of them in U
+    static constexpr int RD = ND - NDW;          // first of them in R
+    static_assert(T >= 1 && T <= 5 && NDW <= 3, "partial words of 1..5 bases: 8..12 bytes per strand");
+    static_assert(FD + NDW <= ND + 1 && RD >= 0, "the packed dwords lie inside U[0..ND] and R[0..ND)");
+    static_assert(4 * ND - K - 7 + 8 * Q >= 4 * RD, "reverse window 7 starts inside the packed dwords");
+    static_assert(7 + 8 * Q + T <= 4 * (FD + NDW), "forward window 7 ends inside the packed dwords");
+    template <int J> static constexpr uint32_t shift_f() { return 2u * J; }
+    template <int J> static constexpr uint32_t shift_r() { return 2u * (uint32_t)(4 * ND - K - J + 8 * Q - 4 * RD); }
+    uint64_t both; // {pr : pf} << 3
+    MHX_HD TailDigits(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1])
+        : both(opaque64(make64(tail_lut_pack<NDW>(U[FD], U[FD + 1], U[FD + NDW - 1]), tail_lut_pack<NDW>(R[RD], R[RD + 1], R[RD + NDW - 1])) << 3)) {}
+    // (neither word reaches its top three bits, so the compiler shifts the halves apart: two v_lshlrev_b32 in every kernel form)
+    template <int J> MHX_HD uint32_t byte_offset(bool rc) const
+    {
+        static_assert(shift_f<J>() + 2 * T <= 8 * NDW && shift_r<J>() + 2 * T <= 8 * NDW, "the field lies inside the packed word");
+        static_assert(8 * NDW + 3 <= 32 && 2 * T + 3 <= 32 - (int)shift_f<7>(), "what the other word shifts in stays above the field");
+        uint32_t low = (uint32_t)(both >> (rc ? 32u + shift_r<J>() : shift_f<J>()));
+#if defined(__HIP_DEVICE_COMPILE__)
+        // opaque: left to see the truncation, the compiler masks the 64-bit value instead, and a 64-bit offset takes the
+        // gather from its scalar-base form to a v_lshl_add_u64 and a load from a register pair
+        asm("" : "+v"(low));
+#endif
+        return low & (((1u << (2 * T)) - 1u) << 3);
+    }
+};
+// Which K of the hot loop take the index this way: K = 21 alone.  Packing costs the group 15 instructions, and only a
+// partial word of five bases behind a full k1 word (tail_lut_index: 8 per window with its select and funnel shifts) pays
+// that back: -23 of 648 hot VALU per group at K = 21.  With fewer bases the per-window index was cheap already (K = 17..20:
+// +4..+12 per group), and the K = 25..29 kernels stand at 70..72 VGPRs, where the packed pair costs copies in the window blocks
+// (K = 25..28: +4..+22) or, at K = 29, a scratch allocation in the inline form (profiles/tail_digits_ab.txt, section 1).
+template <int K> constexpr bool tail_digits_apply() { return K == 21; }
+struct NoTailDigits { // stands in where the index is not taken from packed digits
+    template <class A, class B> MHX_HD NoTailDigits(const A &, const B &) {}
+};
+// One window of the hot loop, up to the last multiplication of the hash.  LUT: the tail block's partial word from the
+// table (the device's hot loop, hot_tail_lut<K>()); with a TailDigits<K> its index comes from the group's packed digits
+// and only the body words of the canonical strand are extracted, otherwise from the partial word itself.
+template <int K, int J, int ND, bool LUT, class Digits>
+MHX_HD Murmur3Tail window_partial_hash(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
+                                       const uint32_t (&Cc)[ND + 1], const Digits &digits, TailLutPtr lut)
+{
+    uint32_t w[8];
+    if constexpr (LUT && std::is_same<Digits, TailDigits<K>>::value) {
+        const bool rc = canonical_words<K, J, ND, true>(U, R, Wr, Cc, w);
+        return murmur3_blocks<K, true>(w, tail_lut_at(lut, digits.template byte_offset<J>(rc)));
+    } else {
+        canonical_words<K, J, ND>(U, R, Wr, Cc, w);
+        return murmur3_core<K, LUT>(w, lut);
+    }
+}
+
 // Cold path, reached by one window in ~2^64 / T: are bytes J .. J+K-1 of the chunk all A/C/G/T (either case)?
 // mash skips every window that holds anything else (Sketch.cpp addMinHashes).
 // (chunk: the raw or the case-folded bytes, the test folds anyway)
@@ -940,21 +1030,23 @@ template <int K, int J, int ND> MHX_HD bool window_is_acgt(const uint32_t (&chun
 // Two forms because each costs the other's workload something: with a small sketch (s = 1000, one candidate in 10^4
 // windows) the inline form is 0.8 % faster (the queue's cold branch changes the register allocation of the hot path by
 // one v_mov per window); with a large one (s = 50 000) the queue is 7 % faster.
+// lut: hot_tail_table<K>(), fetched by the caller in front of its loop over the groups (nullptr: formed here).
 template <int K, bool QUEUE, class Ins, class Cand>
-MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint32_t vm, uint64_t T, uint32_t limit, Ins &ins, Cand &cand)
+MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint32_t vm, uint64_t T, uint32_t limit, Ins &ins, Cand &cand,
+                                   TailLutPtr lut)
 {
     constexpr int ND = GroupGeom<K>::ND;
     uint32_t U[ND + 1], R[ND + 1], Wr[ND + 1], Cc[ND + 1];
     strand_views<ND>(src, U, R, Wr, Cc);
     constexpr bool kHash32 = K <= 16; // mash keeps 32 bits when 4^k <= 2^32
     uint32_t ninserted = 0;
-    TailLutPtr lut = nullptr; // the tail table, one address for the eight windows (and, hoisted, for the whole loop)
-    if constexpr (hot_tail_lut<K>()) lut = tail_lut_of<K>();
+    constexpr bool kLut = hot_tail_lut<K>();
+    // a K that keeps the per-window index also keeps the address where it was formed, here (hot_tail_table)
+    if constexpr (kLut && !tail_digits_apply<K>()) lut = tail_lut_of<K>();
+    const std::conditional_t<kLut && tail_digits_apply<K>(), TailDigits<K>, NoTailDigits> digits(U, R);
 #define MHX_WINDOW(J)                                                                         \
     {                                                                                         \
-        uint32_t w[8];                                                                        \
-        canonical_words<K, J, ND>(U, R, Wr, Cc, w);                                           \
-        const Murmur3Tail tail = murmur3_core<K, hot_tail_lut<K>()>(w, lut);                  \
+        const Murmur3Tail tail = window_partial_hash<K, J, ND, kLut>(U, R, Wr, Cc, digits, lut); \
         /* necessary condition of h <= T, see Murmur3Tail (32-bit hashes: the exact low word) */ \
         const uint32_t low = kHash32 ? tail.low32() : 0u;                                     \
         const bool candidate = kHash32 ? low <= (uint32_t)T : tail.high_bound() <= limit;     \
@@ -973,9 +1065,21 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     return ninserted;
 }
 
+// The tail table as the kernel fetches it in front of its loop over the groups, once per workgroup: fetched inside
+// process_group_regs, the address is formed anew in the header of every trip (tail_lut_table: s_getpc_b64, two adds, a
+// load from the GOT and a wait).  Only for the K that pack their digits; nullptr for every other K, whose kernels stay
+// the instructions they were: with the address in front of the loop for every K with a table, the queue form of K = 27
+// -- the same VALU count block for block, other registers -- measured 0.2..0.3 % slower than two builds of the commit
+// before in each of six rounds (profiles/tail_digits_ab.txt, section 3), so those K form it where they did.
+template <int K> MHX_HD TailLutPtr hot_tail_table()
+{
+    if constexpr (hot_tail_lut<K>() && tail_digits_apply<K>()) return tail_lut_of<K>();
+    else return nullptr;
+}
+
 // work item g of a staged tile (LDS source)
 template <int K, bool QUEUE, class Ins, class Cand>
-MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand)
+MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand, TailLutPtr lut)
 {
     constexpr int ND = GroupGeom<K>::ND;
     const uint32_t vm = reinterpret_cast<const uint8_t *>(sm.valid)[g] | (g << 8);
@@ -983,7 +1087,12 @@ MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32
     uint32_t src[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) src[d] = p[d];
-    return process_group_regs<K, QUEUE>(src, vm, T, limit, ins, cand);
+    return process_group_regs<K, QUEUE>(src, vm, T, limit, ins, cand, lut);
+}
+template <int K, bool QUEUE, class Ins, class Cand>
+MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand)
+{
+    return process_group<K, QUEUE>(sm, g, T, limit, ins, cand, hot_tail_table<K>());
 }
 
 // A queued candidate (code = (group << 3) | window), finished from the staged bytes with a window offset known only at

@@ -44,9 +44,10 @@ template <int MODE> __global__ __launch_bounds__(256) void k(unsigned long long 
             acc += h;
         }
     } else {
+        const TailLutPtr lut = hot_tail_table<21>(); // in front of the loop, as the kernel fetches it
         for (int it = 0; it < iters; ++it) {
             const uint32_t g = (tid + it * 256) % (kGroupsPerTile - 8);
-            CountCand cc{&acc}; acc += process_group<21, false>(sm, g, T, admission_limit(T), ins, cc);
+            CountCand cc{&acc}; acc += process_group<21, false>(sm, g, T, admission_limit(T), ins, cc, lut);
         }
     }
     const uint64_t t1 = clock64();
