@@ -375,4 +375,26 @@ hipError_t launch_search_take(const SearchOut &o, hipStream_t st);
 // tri_distance of the o.nq lists from query o.q0 on into hit_dist (entries behind n_hits are left alone)
 hipError_t launch_search_dist(const SearchOut &o, hipStream_t st);
 
+// containment of the references in the queries (rules: mhx_contain.h, kernels: mhx_contain.hip).  The two sets have a sketch
+// size each; eff / bound [lists] are written once per call by launch_contain_bounds and read by the other two, and the
+// passes of mhx_dist.hip that the range route reuses take eff for their lengths.  Results go straight to [q][r] of the
+// call's outputs, `out_stride` (the call's nr) words per query.
+struct ContainArgs {
+    const uint64_t *q, *r;           // [.][stride] the rows of the call
+    const uint32_t *q_len, *r_len;   // as the caller gave them (launch_contain_bounds only)
+    uint32_t nq, nr, stride, s_q, s_r;
+    uint32_t *q_eff, *r_eff;         // [nq], [nr] contain_eff_len
+    uint64_t *q_bound, *r_bound;     // [nq], [nr] contain_bound
+    uint32_t q0, bnq, r0, bnr;       // the block (mhx_search.h: SearchBlock)
+    const uint32_t *shift;           // range route: the word that holds the call's shift
+    uint32_t *shared, *n_qry, *n_ref;
+    uint32_t out_stride;
+};
+hipError_t launch_contain_bounds(const ContainArgs &a, hipStream_t st);
+// the finish pass of one block over w (offsets of the block's lists, byte counters, w.params[1] the block's flag: non-zero,
+// nothing is done); 16 <= w.ranges <= kDistRanges
+hipError_t launch_contain_finish(const ContainArgs &a, const DistWork &w, hipStream_t st);
+// the generic form: one workgroup per pair of the block
+hipError_t launch_contain_pairs(const ContainArgs &a, hipStream_t st);
+
 } // namespace mhx

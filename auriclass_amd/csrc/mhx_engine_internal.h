@@ -180,6 +180,11 @@ struct SearchStaged { const uint64_t *q; const uint32_t *q_len; };
 int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
                 uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits,
                 SearchStaged *staged = nullptr);
+// Containment (mhx_engine_contain.cpp) of host lists, every row where it lies (q_rows / r_rows: len entries each) or, with the
+// row pointers null, as the matrices q / r [.][stride]; host outputs [nq][nr].  What mhx_dist_contain's host form and
+// mhx_contain_files run.
+int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *const *r_rows,
+                 const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref);
 // Jackknife support of search hits (mhx_engine_support.cpp) with everything on the device: what mhx_dist_support's device form
 // runs, and mhx_search_files_support on the rows its search has staged.  first [nq][top] is a device pointer; the rep_*
 // outputs (each may be null) are device pointers too, or host pointers with host_out.  Uses g.dist_ws, not g.dist_in.

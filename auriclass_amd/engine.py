@@ -215,6 +215,11 @@ def load() -> ctypes.CDLL:
                                        c.c_void_p, c.c_int]
         L.mhx_search_files_support.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(SearchSupportOpts), c.c_char_p, c.c_char_p,
                                                c.c_size_t, c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_contain"):   # (or older than the containment from sketches)
+        L.mhx_dist_contain.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32,
+                                       c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_contain_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ContainOpts), c.c_char_p, c.c_size_t,
+                                        c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -382,6 +387,24 @@ def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1
     opts = SearchOpts(ctypes.sizeof(SearchOpts), int(top), float(max_dist), float(max_p_value))
     return _text_call(lambda buf, cap, need: load().mhx_search_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
                                                                      need), guess=1 << 20)
+
+
+class ContainOpts(ctypes.Structure):
+    """mhx_contain_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("min_identity", ctypes.c_double), ("max_p_value", ctypes.c_double)]
+
+
+def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p_value: float = 1.0, comment: bool = False) -> str:
+    """Which share of each reference sketch of REF.msh every query sketch holds, from the sketches alone (mhx_contain_files):
+    one row "reference\\tquery\\tidentity\\tp-value\\tshared/n_ref\\tshared/n_qry" per (query, reference), the queries in
+    argument then file order, the references in file order.  The sketch size of REF.msh may differ from the queries'.
+    min_identity and max_p_value drop rows; comment prints the comment fields in place of the names."""
+    init()
+    files = [os.fsencode(str(p)) for p in qry_paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = ContainOpts(ctypes.sizeof(ContainOpts), int(bool(comment)), float(min_identity), float(max_p_value))
+    return _text_call(lambda buf, cap, need: load().mhx_contain_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
+                                                                      need), guess=1 << 20)
 
 
 class ClusterOpts(ctypes.Structure):
@@ -1320,6 +1343,37 @@ def dist_search_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_pt
     v = ctypes.c_void_p
     _check(load().mhx_dist_search(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s, float(max_dist), int(top), v(ref_ptr),
                                   v(common_ptr), v(denom_ptr), v(dist_ptr or None), v(n_hits_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
+
+
+def dist_contain(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int
+                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Containment of every reference list in every query list (mhx_dist_contain): (shared, n_qry, n_ref) of shape [nq, nr].
+    Rows and lengths as dist_batch takes them, one stride for both sets; s_q and s_r are the sketch sizes of the two sets and
+    may differ.  Within tau, the smaller of the two lists' bounds, n_ref hashes of the reference and n_qry of the query lie,
+    `shared` of them in both: shared == n_ref when the query's input contains the reference's."""
+    init()
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    shared, n_qry, n_ref = (np.zeros((nq, nr), dtype=np.uint32) for _ in range(3))
+    _check(load().mhx_dist_contain(q.ctypes.data, q_len.ctypes.data, nq, int(s_q), r.ctypes.data, r_len.ctypes.data, nr, int(s_r), stride,
+                                   shared.ctypes.data, n_qry.ctypes.data, n_ref.ctypes.data, 0))
+    return shared, n_qry, n_ref
+
+
+def dist_contain_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: int, r_len_ptr: int, nr: int, s_r: int, stride: int,
+                        shared_ptr: int, n_qry_ptr: int, n_ref_ptr: int) -> float:
+    """Device pointers in and out ([nq, nr] each; a sketch_segments_device result goes straight in on either side): the same
+    integers as dist_contain.  Lengths the host cannot see are clipped to the stride and the sketch size.  Returns the
+    kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_contain(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, v(shared_ptr), v(n_qry_ptr),
+                                   v(n_ref_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
 
 

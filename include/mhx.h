@@ -21,6 +21,9 @@
  *                        the best one (buffer level; engine.dist_support)
  *   mhx_search_files_support <- no mash command: the same for sketch files, as further columns of the search's rows, with the
  *                        clades of AuriClass's clade_config.csv (python -m auriclass_amd.search --support R [--clades FILE])
+ *   mhx_contain_files <- no mash command, and what `mash screen` answers from the reads: which share of each reference's
+ *                        hashes a sample holds, from the two sketch files alone -- a contaminated or mixed sample keeps
+ *                        its identity where `mash dist` loses it (python -m auriclass_amd.contain; buffer level: mhx_dist_contain)
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
@@ -778,6 +781,54 @@ typedef struct mhx_search_support_opts {
 } mhx_search_support_opts;
 int mhx_search_files_support(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_support_opts *opts,
                              const char *clade_csv, char *stdout_buf, size_t cap, size_t *need);
+
+/* CONTAINMENT FROM SKETCHES: which share of each reference's hashes a query holds, read off the two bottom-s lists alone.
+ * The rule (auriclass_amd/csrc/mhx_contain.h, restated in tests/contain_rule.py), all of it in integers.  A list is the first
+ * min(len, stride, s) entries of its row, ascending and duplicate-free, s the sketch size of ITS set (s_q for q, s_r for r;
+ * the two may differ).  A list of s entries is the complete hash set of its input up to its last entry, a shorter one --
+ * the empty one too -- is the complete set: bound = the last entry of a list that holds s entries, 2^64 - 1 otherwise.
+ * tau = min(bound(query), bound(reference)); up to tau, tau included, both lists are complete, and
+ *   n_qry = #{x in query: x <= tau}   n_ref = #{x in reference: x <= tau}   shared = #{x in both: x <= tau}.
+ * 2^64 - 1 is a hash like any other; what a row holds behind its list (zeros, the 2^64 - 1 the segmented sketch appends)
+ * never counts.  A query whose input contains the reference's input gives shared == n_ref exactly, whatever else it holds:
+ * foreign hashes shrink the window, they do not lower the count.  No float is computed on the device; identity and p-value of
+ * a pair are mhx_screen_identity(shared, n_ref, k) and mhx_screen_p_value(shared, n_ref, set_size, k) on the host.
+ * Outputs: shared / n_qry / n_ref [nq][nr], query-major.  device_ptrs != 0 => every pointer is a device pointer (a result of
+ * mhx_sketch_segments goes straight in on either side); the outputs are the same integers in both forms and from run to run.
+ * nq == 0 or nr == 0: MHX_OK, nothing is written.  MHX_E_ARG: s_q, s_r or stride zero, a null pointer, and in the host form
+ * a len > stride; the device form cannot see the lengths and clips them to the stride and the sketch size.
+ * On the device: the schedule of mhx_dist_search -- one split of both sets into value ranges with
+ * one shift, reference slices of 32 lists and query batches as blocks, the range pass of mhx_dist_batch -- with a finish pass
+ * of its own that sums a pair's byte counters below the range of tau, walks the two slices of that range up to tau and
+ * writes the three counts straight into the outputs; a block whose flag went up (a slice above 255 entries, a crowded
+ * range: a short list against the full list of a large genome always) is redone by the generic pair kernel, one workgroup
+ * per pair, which also serves tiny calls, MHX_DIST_GENERIC and lists above 65 536 entries.  MHX_SEARCH_GEOMETRY and
+ * MHX_SEARCH_QBATCH are the search's; mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges
+ * report this call too.
+ * Not pinned by mash output (mash has no such command): pinned by the restated rule.
+ * Not built: the windowed range form (more than 1024 ranges; such lists go to the pair kernel), max-containment and the
+ * query-in-reference identity as columns, a containment column in AuriClass's report.tsv (needs calibration), a top-N
+ * ranking by containment. */
+int mhx_dist_contain(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r, const uint32_t *r_len,
+                     uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref, int device_ptrs);
+/* The same at file level: one row per (query sketch, reference sketch), the queries in argument order and then file order,
+ * the references of ref_msh in file order:
+ *   "reference\tquery\tidentity\tp-value\tshared/n_ref\tshared/n_qry\n"
+ * identity = 1 if shared == n_ref > 0, 0 if shared == 0 (also when n_ref == 0), else (shared / n_ref)^(1/k);
+ * p = mhx_screen_p_value(shared, n_ref, set_size, k) with set_size the length field of the QUERY sketch (mash stores the
+ * estimated set size there for reads, the genome length for assemblies), 1 when n_ref == 0; both printed with %g.  Rows with
+ * identity < min_identity or p > max_p_value are dropped; comment != 0 prints the comment fields in place of the names.
+ * opts == NULL means {sizeof, 0, 1, 0}.  The k-mer size and the hash seed must be the same in all files and the query files
+ * must share one sketch size (MHX_E_MISMATCH, Mash's messages); the sketch size of ref_msh may differ from the queries'.
+ * MHX_E_ARG: struct_size != sizeof(mhx_contain_opts), a bound that is not a number, a null path. */
+typedef struct mhx_contain_opts {
+    uint32_t struct_size; /* sizeof(mhx_contain_opts) */
+    int32_t comment;      /* comment fields in place of names */
+    double min_identity;  /* print rows with identity >= min_identity (0: all) */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+} mhx_contain_opts;
+int mhx_contain_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts, char *stdout_buf,
+                      size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
  * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is
