@@ -1,11 +1,15 @@
-"""`python -m auriclass_amd.contain [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: which share of
+"""`python -m auriclass_amd.contain [-w] [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: which share of
 each reference sketch of REF.msh every query sketch holds, from the sketch files alone (engine.contain_files).  One row per
 (query, reference): reference, query, identity, p-value, shared/n_ref, shared/n_qry -- within the window in which both
 sketches are complete, n_ref hashes of the reference and n_qry of the query lie, `shared` of them in both.  A sample that
 holds the reference next to anything else keeps identity 1 where `mash dist` moves away.  REF.msh may have another sketch
 size than the queries.  -i and -v drop rows, -C prints the comment fields in place of the names.  Inputs are sketch files: a
 sequence file is refused with the hint to sketch it first.  Exit status 1 with the engine's message when the call fails.
--p (threads) is accepted and ignored: the engine has its own."""
+-p (threads) is accepted and ignored: the engine has its own.
+-w: winner-take-all.  Every hash a query shares with the reference set is credited to one reference -- the one with the
+greatest shared/n_ref for that query, then the greatest genome length, then the first in the file -- and the rows show what
+each reference won in the place of `shared`, in all four columns; -i and -v filter on those values.  The members of a clade
+then no longer repeat one another's row."""
 from __future__ import annotations
 
 import argparse
@@ -19,6 +23,7 @@ def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m auriclass_amd.contain", description="share of each reference sketch inside a query sketch")
     ap.add_argument("-i", dest="min_identity", type=float, default=0.0, help="minimum identity to report [0]")
     ap.add_argument("-v", dest="max_p_value", type=float, default=1.0, help="maximum p-value to report [1]")
+    ap.add_argument("-w", dest="winner", action="store_true", help="winner-take-all: credit each shared hash to its best reference")
     ap.add_argument("-C", dest="comment", action="store_true", help="show comment fields in place of the names")
     ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
     ap.add_argument("reference", metavar="REF.msh")
@@ -32,7 +37,8 @@ def main(argv: List[str] = None) -> int:
             sys.stderr.write(f"ERROR: contain takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
             return 1
     try:
-        text = engine.contain_files(args.reference, args.queries, min_identity=args.min_identity, max_p_value=args.max_p_value, comment=args.comment)
+        text = engine.contain_files(args.reference, args.queries, min_identity=args.min_identity, max_p_value=args.max_p_value, comment=args.comment,
+                                    **({"winner": True} if args.winner else {}))
     except engine.EngineError as exc:
         sys.stderr.write(exc.message + "\n")
         return 1

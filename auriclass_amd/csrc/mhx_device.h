@@ -397,4 +397,19 @@ hipError_t launch_contain_finish(const ContainArgs &a, const DistWork &w, hipStr
 // the generic form: one workgroup per pair of the block
 hipError_t launch_contain_pairs(const ContainArgs &a, hipStream_t st);
 
+// winner-take-all containment (rules: mhx_contain_winner.h, kernels: mhx_contain_winner.hip) over the outputs of the plain
+// pass: a batch of a.bnq queries from a.q0 on against ALL a.nr references.  words [a.bnq][width] are the winner words of the
+// batch, one per position of a query's list (width >= every effective query length), zeroed by the caller.
+struct ContainWinnerArgs {
+    uint32_t *words;
+    uint32_t width;
+    const uint64_t *ref_length;   // [nr] genome lengths, or null: all equal
+    uint32_t *won;                // [nq][out_stride], zeroed by the caller once per call
+    unsigned long long *pairs;    // the pairs the claim pass walked (shared > 0), added up over the call
+};
+// the claim pass: one workgroup per pair; a pair with shared == 0 ends after that one load
+hipError_t launch_contain_claim(const ContainArgs &a, const ContainWinnerArgs &w, hipStream_t st);
+// the tally: one thread per word of the batch
+hipError_t launch_contain_tally(const ContainArgs &a, const ContainWinnerArgs &w, hipStream_t st);
+
 } // namespace mhx

@@ -2,6 +2,8 @@
 // of a host-pointer call, the bounds of every list, ONE split of both sets into value ranges, the search's schedule of (query
 // batch, reference slice) blocks with a finish pass that writes straight into the outputs, and the fallback of a flagged
 // block to the generic pair kernel.  Rules: mhx_contain.h; kernels: mhx_contain.hip and the passes of mhx_dist.hip.
+// The winner-take-all form (mhx_dist_contain_winner) is the same call with two more passes behind the plain one, per query
+// batch over all references: the claim pass and the tally (rules: mhx_contain_winner.h; kernels: mhx_contain_winner.hip).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -10,7 +12,7 @@
 #include <vector>
 
 #include "mhx_device.h"
-#include "mhx_contain.h"
+#include "mhx_contain_winner.h"
 #include "mhx_search.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
@@ -24,6 +26,8 @@ struct ContainCall { // everything on the device
     const uint32_t *q_len, *r_len;
     uint32_t nq, nr, stride, s_q, s_r, longest;
     uint32_t *shared, *n_qry, *n_ref;
+    uint32_t *won = nullptr;              // winner-take-all: [nq][nr], and the passes behind the plain one run
+    const uint64_t *ref_length = nullptr; // [nr] genome lengths or null (with `won` only)
 };
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -64,6 +68,10 @@ int contain_device(ContainCall &c)
     const size_t o_offr = o; if (fast) o += up256((size_t)c.nr * per * 4);
     const size_t o_cpart = o; if (fast) o += up256((size_t)qbatch * ranges * kTriSlice);
     const size_t o_words = o; o += up256((size_t)(2 + 2 * group) * 4);
+    // winner-take-all: a winner word per (query of a batch, position in its list), and the counter of the pairs walked
+    const uint32_t width = std::min(c.stride, c.s_q);
+    const size_t o_win = o; if (c.won) o += up256((size_t)qbatch * width * 4);
+    const size_t o_count = o; if (c.won) o += 256;
     if (g.dist_ws.grow(o, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the containment workspace (%zu bytes)", o);
     uint32_t *offq = (uint32_t *)(g.dist_ws + o_offq), *offr = (uint32_t *)(g.dist_ws + o_offr);
     uint32_t *words = (uint32_t *)(g.dist_ws + o_words), *flags = words + 2;
@@ -122,6 +130,20 @@ int contain_device(ContainCall &c)
                 ++g.last_dist_fallbacks;
             }
     }
+    // The plain pass of every block is queued.  Winner-take-all: per query batch, over ALL references, zero the batch's words,
+    // let every pair that shares something propose, and count what every reference holds at the end.
+    if (c.won && le == hipSuccess) {
+        ContainWinnerArgs wa{(uint32_t *)(g.dist_ws + o_win), width, c.ref_length, c.won, (unsigned long long *)(g.dist_ws + o_count)};
+        le = hipMemsetAsync(c.won, 0, (size_t)pairs * 4, g.stream);
+        if (le == hipSuccess) le = hipMemsetAsync(wa.pairs, 0, 8, g.stream);
+        for (uint32_t q0 = 0; q0 < c.nq && le == hipSuccess; q0 += qbatch) {
+            ContainArgs x = all;
+            x.q0 = q0; x.bnq = std::min(qbatch, c.nq - q0); x.r0 = 0; x.bnr = c.nr;
+            le = hipMemsetAsync(wa.words, 0, (size_t)x.bnq * width * 4, g.stream);
+            if (le == hipSuccess) le = launch_contain_claim(x, wa, g.stream);
+            if (le == hipSuccess) le = launch_contain_tally(x, wa, g.stream);
+        }
+    }
     hipEventRecord(g.ev1, g.stream);
     if (fast && (uint64_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
     if (le != hipSuccess) return fail(MHX_E_HIP, "containment kernel launch failed: %s", hipGetErrorString(le));
@@ -130,6 +152,11 @@ int contain_device(ContainCall &c)
     hipEventElapsedTime(&ms, g.ev0, g.ev1);
     g.last_dist_ms = ms;
     if (se != hipSuccess) return fail(MHX_E_HIP, "containment kernel failed: %s", hipGetErrorString(se));
+    if (c.won) {
+        unsigned long long walked = 0;
+        if (hipMemcpy(&walked, g.dist_ws + o_count, 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy of the claim pass's counter failed");
+        g.last_contain_winner_pairs = walked;
+    }
     return MHX_OK;
 }
 
@@ -144,16 +171,17 @@ int contain_check(uint32_t s_q, uint32_t s_r, uint32_t stride)
 namespace mhx {
 // Host rows, every one where it lies (q_rows / r_rows: q_len[i] / r_len[i] entries each), staged at `stride`; host outputs.
 int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *const *r_rows,
-                 const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref)
+                 const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref,
+                 const uint64_t *ref_length, uint32_t *won)
 {
     for (uint32_t i = 0; i < nq; ++i) if (q_len[i] > stride) return fail(MHX_E_ARG, "q_len[%u] exceeds stride", i);
     for (uint32_t i = 0; i < nr; ++i) if (r_len[i] > stride) return fail(MHX_E_ARG, "r_len[%u] exceeds stride", i);
     const size_t bq = up256((size_t)nq * stride * 8), bql = up256((size_t)nq * 4), br = up256((size_t)nr * stride * 8), brl = up256((size_t)nr * 4);
-    const size_t cells = (size_t)nq * nr, bo = up256(cells * 4);
+    const size_t cells = (size_t)nq * nr, bo = up256(cells * 4), bw = won ? bo : 0, bg = won && ref_length ? up256((size_t)nr * 8) : 0;
     uint8_t *base = nullptr;
-    int rc = dist_stage(bq + bql + br + brl + 3 * bo, &base);
+    int rc = dist_stage(bq + bql + br + brl + 3 * bo + bw + bg, &base);
     if (rc) return rc;
-    uint8_t *dq = base, *dql = dq + bq, *dr = dql + bql, *drl = dr + br, *dout = drl + brl;
+    uint8_t *dq = base, *dql = dq + bq, *dr = dql + bql, *drl = dr + br, *dout = drl + brl, *dwon = dout + 3 * bo, *dlen = dwon + bw;
     hipError_t ce = hipSuccess;
     auto rows_in = [&](uint8_t *dst, const uint64_t *const *rows, const uint64_t *flat, const uint32_t *len, uint32_t n) {
         if (!rows) { ce = hipMemcpyAsync(dst, flat, (size_t)n * stride * 8, hipMemcpyHostToDevice, g.stream); return; }
@@ -164,6 +192,7 @@ int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_
     if (ce == hipSuccess) rows_in(dr, r_rows, r, r_len, nr);
     if (ce == hipSuccess) ce = hipMemcpyAsync(dql, q_len, (size_t)nq * 4, hipMemcpyHostToDevice, g.stream);
     if (ce == hipSuccess) ce = hipMemcpyAsync(drl, r_len, (size_t)nr * 4, hipMemcpyHostToDevice, g.stream);
+    if (ce == hipSuccess && bg) ce = hipMemcpyAsync(dlen, ref_length, (size_t)nr * 8, hipMemcpyHostToDevice, g.stream);
     if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in dist_contain: %s", hipGetErrorString(ce));
     ContainCall c{};
     c.q = (const uint64_t *)dq; c.q_len = (const uint32_t *)dql; c.r = (const uint64_t *)dr; c.r_len = (const uint32_t *)drl;
@@ -171,8 +200,10 @@ int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_
     for (uint32_t i = 0; i < nq; ++i) c.longest = std::max(c.longest, contain_eff_len(q_len[i], stride, s_q));
     for (uint32_t i = 0; i < nr; ++i) c.longest = std::max(c.longest, contain_eff_len(r_len[i], stride, s_r));
     c.shared = (uint32_t *)dout; c.n_qry = (uint32_t *)(dout + bo); c.n_ref = (uint32_t *)(dout + 2 * bo);
+    if (won) { c.won = (uint32_t *)dwon; c.ref_length = bg ? (const uint64_t *)dlen : nullptr; }
     rc = contain_device(c);
     if (rc) return rc;
+    if (won && hipMemcpy(won, c.won, cells * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy failed in dist_contain_winner");
     if (hipMemcpy(shared, c.shared, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(n_qry, c.n_qry, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(n_ref, c.n_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MHX_E_HIP, "D2H copy failed in dist_contain");
@@ -196,3 +227,25 @@ extern "C" int mhx_dist_contain(const uint64_t *q, const uint32_t *q_len, uint32
         return contain_device(c);
     });
 }
+
+// The same call with the winner-take-all passes behind the plain one: `won` is a fourth output, ref_length ranks ties.
+extern "C" int mhx_dist_contain_winner(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r, const uint32_t *r_len, uint32_t nr,
+                                       uint32_t s_r, uint32_t stride, const uint64_t *ref_length, uint32_t *won, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref,
+                                       int device_ptrs)
+{
+    return entry("mhx_dist_contain_winner", [&]() -> int {
+        int rc = contain_check(s_q, s_r, stride);
+        if (rc) return rc;
+        if (nq == 0 || nr == 0) return MHX_OK;
+        if (!q || !q_len || !r || !r_len || !won || !shared || !n_qry || !n_ref) return fail(MHX_E_ARG, "null argument");
+        g.last_contain_winner_pairs = 0;
+        if (!device_ptrs) return contain_rows(nullptr, q, q_len, nq, s_q, nullptr, r, r_len, nr, s_r, stride, shared, n_qry, n_ref, ref_length, won);
+        ContainCall c{}; // as mhx_dist_contain: the kernels clip the lengths
+        c.q = q; c.q_len = q_len; c.r = r; c.r_len = r_len; c.nq = nq; c.nr = nr; c.stride = stride; c.s_q = s_q; c.s_r = s_r;
+        c.longest = std::min(stride, std::max(s_q, s_r));
+        c.shared = shared; c.n_qry = n_qry; c.n_ref = n_ref; c.won = won; c.ref_length = ref_length;
+        return contain_device(c);
+    });
+}
+
+extern "C" uint64_t mhx_last_contain_winner_pairs(void) { return g.last_contain_winner_pairs; }

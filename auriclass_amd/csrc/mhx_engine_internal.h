@@ -131,6 +131,7 @@ struct Engine {
     DevArray<uint8_t> dist_ws; // workspace of the all-vs-refs distance path
     DevArray<uint8_t> dist_in; // staging of a host-pointer distance batch (rows, lengths, outputs)
     int last_dist_fallbacks = 0;
+    uint64_t last_contain_winner_pairs = 0; // pairs the claim pass of the last mhx_dist_contain_winner call walked
     int last_dist_ranges = 0;    // value ranges per block of the last distance call (0: generic kernel only)
     int last_mst_rounds = 0;     // Boruvka rounds of the last mhx_dist_mst call
     int last_mst_stored = -1;    // its pair source: 1 stored, 0 recomputed, -1 none ran
@@ -182,9 +183,11 @@ int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t n
                 SearchStaged *staged = nullptr);
 // Containment (mhx_engine_contain.cpp) of host lists, every row where it lies (q_rows / r_rows: len entries each) or, with the
 // row pointers null, as the matrices q / r [.][stride]; host outputs [nq][nr].  What mhx_dist_contain's host form and
-// mhx_contain_files run.
+// mhx_contain_files run.  With `won` (host, [nq][nr]) the winner-take-all passes run behind the plain one, ref_length ([nr] genome
+// lengths or null) ranking ties: mhx_dist_contain_winner's host form and mhx_contain_files_winner.
 int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *const *r_rows,
-                 const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref);
+                 const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref,
+                 const uint64_t *ref_length = nullptr, uint32_t *won = nullptr);
 // Jackknife support of search hits (mhx_engine_support.cpp) with everything on the device: what mhx_dist_support's device form
 // runs, and mhx_search_files_support on the rows its search has staged.  first [nq][top] is a device pointer; the rep_*
 // outputs (each may be null) are device pointers too, or host pointers with host_out.  Uses g.dist_ws, not g.dist_in.

@@ -877,76 +877,90 @@ extern "C" int mhx_search_files_support(const char *ref_msh, const char *const *
 // Containment at file level: the reference file is read and checked once; the query files are read one after the other and
 // go to the device in batches of sketches (contain_rows, every list from where it lies), so that host memory holds one
 // batch whatever n_qry is.  The two sketch sizes stay apart: every set is cut at its own.
+// winner: the winner-take-all passes run behind the plain one, the genome lengths of the reference file ranking ties, and what a
+// reference won stands in the place of what it shares -- in identity, p-value, both fractions and the filters.
+static int contain_files_text(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts, bool winner, char *stdout_buf, size_t cap,
+                              size_t *need)
+{
+    mhx_contain_opts o{(uint32_t)sizeof(mhx_contain_opts), 0, 0.0, 1.0};
+    int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain", opts, o) : MHX_OK;
+    if (rc) return rc;
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "contain: a reference sketch path and at least one query sketch path required");
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "contain: query sketch path %d is null", i);
+    if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
+    SketchSet R;
+    rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+    if (rc) return rc;
+    const int k = (int)R.kmer_size;
+    const uint32_t nr = (uint32_t)R.refs.size(), s_r = std::max<uint32_t>(1, R.sketch_size);
+    std::vector<const uint64_t *> rrows(nr);
+    std::vector<uint32_t> rl(nr);
+    std::vector<uint64_t> r_length(nr);
+    uint32_t r_longest = 0;
+    for (uint32_t i = 0; i < nr; ++i) {
+        rrows[i] = R.refs[i].hash_data(); rl[i] = (uint32_t)R.refs[i].hash_count(); r_length[i] = R.refs[i].length;
+        r_longest = std::max(r_longest, rl[i]);
+    }
+    uint32_t q_sketch_size = 0;
+    std::string text;
+    constexpr size_t kBatch = 4096; // query sketches per device call
+    std::vector<SketchSet> held;    // the files of the current batch
+    std::vector<const RefSketch *> qs;
+    auto flush = [&]() -> int {
+        const uint32_t nq = (uint32_t)qs.size();
+        if (nq && nr) {
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq);
+            uint32_t longest = r_longest;
+            for (uint32_t i = 0; i < nq; ++i) {
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                longest = std::max(longest, ql[i]);
+            }
+            const size_t cells = (size_t)nq * nr;
+            std::vector<uint32_t> shared(cells), n_q(cells), n_r(cells), won(winner ? cells : 0);
+            const int rc2 = contain_rows(qrows.data(), nullptr, ql.data(), nq, std::max<uint32_t>(1, q_sketch_size), rrows.data(), nullptr, rl.data(), nr, s_r,
+                                         row_stride(longest), shared.data(), n_q.data(), n_r.data(), winner ? r_length.data() : nullptr, winner ? won.data() : nullptr);
+            if (rc2) return rc2;
+            if (winner) shared.swap(won); // the rows below print what was won
+            for (uint32_t qi = 0; qi < nq; ++qi)
+                for (uint32_t ri = 0; ri < nr; ++ri) {
+                    const size_t p = (size_t)qi * nr + ri;
+                    const double identity = n_r[p] == 0 ? 0.0 : mhx_screen_identity(shared[p], n_r[p], k);
+                    const double pv = n_r[p] == 0 ? 1.0 : mhx_screen_p_value(shared[p], n_r[p], (double)qs[qi]->length, k);
+                    if (!(identity >= o.min_identity) || !(pv <= o.max_p_value)) continue;
+                    text += (o.comment ? R.refs[ri].comment : R.refs[ri].name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) +
+                            "\t" + fmt_g(pv) + "\t" + std::to_string(shared[p]) + "/" + std::to_string(n_r[p]) + "\t" + std::to_string(shared[p]) + "/" +
+                            std::to_string(n_q[p]) + "\n";
+                }
+        }
+        qs.clear();
+        held.clear();
+        return MHX_OK;
+    };
+    for (int i = 0; i < n_qry; ++i) {
+        held.emplace_back();
+        SketchSet &Q = held.back();
+        rc = msh_read_file(qry_msh[i], Q);
+        if (rc) return rc;
+        if (i == 0) q_sketch_size = Q.sketch_size;
+        rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+        if (rc) return rc;
+        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+    }
+    rc = flush();
+    if (rc) return rc;
+    return put_text(text, stdout_buf, cap, need);
+}
+
 extern "C" int mhx_contain_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts, char *stdout_buf, size_t cap, size_t *need)
 {
-    return entry("mhx_contain_files", [&]() -> int {
-        mhx_contain_opts o{(uint32_t)sizeof(mhx_contain_opts), 0, 0.0, 1.0};
-        int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain", opts, o) : MHX_OK;
-        if (rc) return rc;
-        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "contain: a reference sketch path and at least one query sketch path required");
-        for (int i = 0; i < n_qry; ++i)
-            if (!qry_msh[i]) return fail(MHX_E_ARG, "contain: query sketch path %d is null", i);
-        if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
-        SketchSet R;
-        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
-        if (rc) return rc;
-        const int k = (int)R.kmer_size;
-        const uint32_t nr = (uint32_t)R.refs.size(), s_r = std::max<uint32_t>(1, R.sketch_size);
-        std::vector<const uint64_t *> rrows(nr);
-        std::vector<uint32_t> rl(nr);
-        uint32_t r_longest = 0;
-        for (uint32_t i = 0; i < nr; ++i) {
-            rrows[i] = R.refs[i].hash_data(); rl[i] = (uint32_t)R.refs[i].hash_count();
-            r_longest = std::max(r_longest, rl[i]);
-        }
-        uint32_t q_sketch_size = 0;
-        std::string text;
-        constexpr size_t kBatch = 4096; // query sketches per device call
-        std::vector<SketchSet> held;    // the files of the current batch
-        std::vector<const RefSketch *> qs;
-        auto flush = [&]() -> int {
-            const uint32_t nq = (uint32_t)qs.size();
-            if (nq && nr) {
-                std::vector<const uint64_t *> qrows(nq);
-                std::vector<uint32_t> ql(nq);
-                uint32_t longest = r_longest;
-                for (uint32_t i = 0; i < nq; ++i) {
-                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                    longest = std::max(longest, ql[i]);
-                }
-                const size_t cells = (size_t)nq * nr;
-                std::vector<uint32_t> shared(cells), n_q(cells), n_r(cells);
-                const int rc2 = contain_rows(qrows.data(), nullptr, ql.data(), nq, std::max<uint32_t>(1, q_sketch_size), rrows.data(), nullptr, rl.data(), nr, s_r,
-                                             row_stride(longest), shared.data(), n_q.data(), n_r.data());
-                if (rc2) return rc2;
-                for (uint32_t qi = 0; qi < nq; ++qi)
-                    for (uint32_t ri = 0; ri < nr; ++ri) {
-                        const size_t p = (size_t)qi * nr + ri;
-                        const double identity = n_r[p] == 0 ? 0.0 : mhx_screen_identity(shared[p], n_r[p], k);
-                        const double pv = n_r[p] == 0 ? 1.0 : mhx_screen_p_value(shared[p], n_r[p], (double)qs[qi]->length, k);
-                        if (!(identity >= o.min_identity) || !(pv <= o.max_p_value)) continue;
-                        text += (o.comment ? R.refs[ri].comment : R.refs[ri].name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) +
-                                "\t" + fmt_g(pv) + "\t" + std::to_string(shared[p]) + "/" + std::to_string(n_r[p]) + "\t" + std::to_string(shared[p]) + "/" +
-                                std::to_string(n_q[p]) + "\n";
-                    }
-            }
-            qs.clear();
-            held.clear();
-            return MHX_OK;
-        };
-        for (int i = 0; i < n_qry; ++i) {
-            held.emplace_back();
-            SketchSet &Q = held.back();
-            rc = msh_read_file(qry_msh[i], Q);
-            if (rc) return rc;
-            if (i == 0) q_sketch_size = Q.sketch_size;
-            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-            if (rc) return rc;
-            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-        }
-        rc = flush();
-        if (rc) return rc;
-        return put_text(text, stdout_buf, cap, need);
-    });
+    return entry("mhx_contain_files", [&]() -> int { return contain_files_text(ref_msh, qry_msh, n_qry, opts, false, stdout_buf, cap, need); });
+}
+
+extern "C" int mhx_contain_files_winner(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts, char *stdout_buf, size_t cap,
+                                        size_t *need)
+{
+    return entry("mhx_contain_files_winner", [&]() -> int { return contain_files_text(ref_msh, qry_msh, n_qry, opts, true, stdout_buf, cap, need); });
 }

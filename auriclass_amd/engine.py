@@ -220,6 +220,11 @@ def load() -> ctypes.CDLL:
                                        c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_contain_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ContainOpts), c.c_char_p, c.c_size_t,
                                         c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_contain_winner"):   # (or older than the winner-take-all containment)
+        L.mhx_dist_contain_winner.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32,
+                                              c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
+        L.mhx_last_contain_winner_pairs.restype = c.c_uint64
+        L.mhx_contain_files_winner.argtypes = L.mhx_contain_files.argtypes
     _lib = L
     return L
 
@@ -394,15 +399,22 @@ class ContainOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("min_identity", ctypes.c_double), ("max_p_value", ctypes.c_double)]
 
 
-def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p_value: float = 1.0, comment: bool = False) -> str:
+def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p_value: float = 1.0, comment: bool = False,
+                  winner: bool = False) -> str:
     """Which share of each reference sketch of REF.msh every query sketch holds, from the sketches alone (mhx_contain_files):
     one row "reference\\tquery\\tidentity\\tp-value\\tshared/n_ref\\tshared/n_qry" per (query, reference), the queries in
     argument then file order, the references in file order.  The sketch size of REF.msh may differ from the queries'.
-    min_identity and max_p_value drop rows; comment prints the comment fields in place of the names."""
+    min_identity and max_p_value drop rows; comment prints the comment fields in place of the names.
+    winner: winner-take-all rows (mhx_contain_files_winner) -- every shared hash is credited to the best-ranked reference it
+    was found in (ratio, then the genome length of REF.msh's length fields, then file order), and what a reference won
+    stands in the place of `shared` in every column and in both filters."""
     init()
     files = [os.fsencode(str(p)) for p in qry_paths]
     arr = (ctypes.c_char_p * len(files))(*files)
     opts = ContainOpts(ctypes.sizeof(ContainOpts), int(bool(comment)), float(min_identity), float(max_p_value))
+    if winner:
+        return _text_call(lambda buf, cap, need: load().mhx_contain_files_winner(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts),
+                                                                                 buf, cap, need), guess=1 << 20)
     return _text_call(lambda buf, cap, need: load().mhx_contain_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
                                                                       need), guess=1 << 20)
 
@@ -1374,6 +1386,40 @@ def dist_contain_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: in
     v = ctypes.c_void_p
     _check(load().mhx_dist_contain(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, v(shared_ptr), v(n_qry_ptr),
                                    v(n_ref_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
+
+
+def dist_contain_winner(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int, ref_length=None
+                        ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Winner-take-all containment (mhx_dist_contain_winner): (won, shared, n_qry, n_ref) of shape [nq, nr]; the last three are
+    dist_contain's.  Every value a query shares with the reference set is credited to the best-ranked reference it was found
+    in -- the greater shared / n_ref for this query, then the greater ref_length (u64 [nr], None: all equal), then the lower
+    index -- and won[q, r] counts what r was credited with."""
+    init()
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    if ref_length is not None:
+        ref_length = np.ascontiguousarray(ref_length, dtype=np.uint64)
+        assert ref_length.shape == (nr,)
+    won, shared, n_qry, n_ref = (np.zeros((nq, nr), dtype=np.uint32) for _ in range(4))
+    _check(load().mhx_dist_contain_winner(q.ctypes.data, q_len.ctypes.data, nq, int(s_q), r.ctypes.data, r_len.ctypes.data, nr, int(s_r), stride,
+                                          None if ref_length is None else ref_length.ctypes.data, won.ctypes.data, shared.ctypes.data,
+                                          n_qry.ctypes.data, n_ref.ctypes.data, 0))
+    return won, shared, n_qry, n_ref
+
+
+def dist_contain_winner_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: int, r_len_ptr: int, nr: int, s_r: int, stride: int,
+                               ref_length_ptr: int, won_ptr: int, shared_ptr: int, n_qry_ptr: int, n_ref_ptr: int) -> float:
+    """Device pointers in and out ([nq, nr] each; ref_length_ptr: u64 [nr] on the device, or 0): the same integers as
+    dist_contain_winner.  Returns the kernel time in ms, the plain pass included."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_contain_winner(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, v(ref_length_ptr or None),
+                                          v(won_ptr), v(shared_ptr), v(n_qry_ptr), v(n_ref_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
 
 

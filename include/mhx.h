@@ -24,6 +24,9 @@
  *   mhx_contain_files <- no mash command, and what `mash screen` answers from the reads: which share of each reference's
  *                        hashes a sample holds, from the two sketch files alone -- a contaminated or mixed sample keeps
  *                        its identity where `mash dist` loses it (python -m auriclass_amd.contain; buffer level: mhx_dist_contain)
+ *   mhx_contain_files_winner <- no mash command, `mash screen -w` for two sketch files: every shared hash credited to its best
+ *                        reference, so that the members of a clade stop repeating one another's row (python -m
+ *                        auriclass_amd.contain -w; buffer level: mhx_dist_contain_winner)
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
@@ -829,6 +832,41 @@ typedef struct mhx_contain_opts {
 } mhx_contain_opts;
 int mhx_contain_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts, char *stdout_buf,
                       size_t cap, size_t *need);
+
+/* WINNER-TAKE-ALL CONTAINMENT: every hash a query shares with the reference set is credited to ONE reference.  Inside a clade
+ * the references share almost all their hashes, so the plain counts give one genome near-identical rows for every member;
+ * here the best member takes the shared hashes and the others keep what only they hold (`mash screen -w`, for two sets of
+ * sketches).  The rule (auriclass_amd/csrc/mhx_contain_winner.h, restated in tests/contain_winner_rule.py), per query q, on top
+ * of mhx_dist_contain's list, bound, tau, shared, n_qry and n_ref:
+ *   found(q, r)  = {x in list(q) and list(r): x <= tau(q, r)}, so |found(q, r)| = shared(q, r); a value that a reference holds
+ *                  only above its own bound, or behind a list's effective length, is not found there
+ *   r ranks before r' by the greater exact ratio shared(q, r) / n_ref(q, r) (compared as shared_a * n_ref_b against
+ *                  shared_b * n_ref_a in 64 bits), then the greater ref_length[r], then the lower index; a reference with
+ *                  n_ref == 0 has found nothing and never competes
+ *   winner(q, x) = the best-ranked r with x in found(q, r), for every x found at all
+ *   won(q, r)    = #{x in found(q, r): winner(q, x) = r}
+ * So won <= shared, won == shared for the best-ranked reference of a query, and the sum of won(q, .) is the number of distinct
+ * values found for q.  The ranking differs per query and the window per pair.  2^64 - 1 is a hash like any other and can be won.
+ * Outputs won / shared / n_qry / n_ref [nq][nr], query-major; shared, n_qry and n_ref are exactly what mhx_dist_contain writes.
+ * ref_length: u64[nr] genome lengths, or NULL (all equal); with device_ptrs != 0 it is a device pointer like every other.
+ * Argument rules, no-op cases and the clipping of lengths are mhx_dist_contain's; a null `won` is MHX_E_ARG.  The integers are
+ * the same in both forms, from run to run, and whatever the query batch (MHX_SEARCH_QBATCH).
+ * On the device: the plain pass as it is, then per query batch over all references a claim pass --
+ * one 32-bit winner word per position of a query's list, every pair with shared > 0 walks its two prefixes and proposes
+ * r + 1 to the word of every value it found by compare-and-swap, the word moving only to a better-ranked reference -- and a
+ * tally of the words into `won`.  Nothing of size nq x nr exists beyond the four outputs.
+ * mhx_last_contain_winner_pairs: the pairs the claim pass of the last call walked, that is, the pairs with shared > 0.
+ * Not pinned by mash output: pinned by the restated rule.  Not built: see mhx_dist_contain. */
+int mhx_dist_contain_winner(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r,
+                            const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, const uint64_t *ref_length,
+                            uint32_t *won, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref, int device_ptrs);
+uint64_t mhx_last_contain_winner_pairs(void);
+/* mhx_contain_files with winner-take-all rows: the same options, checks, messages and six columns, with `won` in the place of
+ * `shared` -- in the identity, in the p-value and in both fractions -- and the filters on those values.  ref_length is the
+ * length field of every reference sketch of ref_msh.  The query files go to the device in batches of 4096 sketches; a
+ * query's winners depend on that query alone. */
+int mhx_contain_files_winner(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts,
+                             char *stdout_buf, size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
  * bytes[n] is an MHX_FMT_SEQ stream, seg_off[n_seg + 1] ascending byte offsets into it (seg_off[n_seg] <= n); segment i is
