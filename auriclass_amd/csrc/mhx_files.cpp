@@ -976,8 +976,10 @@ static int ensure_fasta_buffers(uint64_t n)
 // (d_raw[which]); on_device: the loader has already copied the bytes there on the copy stream (raw_ready[which] says when)
 static bool fasta_for_device(const uint8_t *raw, uint64_t n) { return n != 0 && raw[0] == '>' && n <= 0x7FFFFFFF00ull; }
 // the first half: raw bytes -> the dense stream in g.fasta.d_out (`total` bytes) and the sorted positions of the record
-// separators in it (separator i sits in front of record i)
-static int fasta_stream_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, std::vector<uint64_t> &seps, uint64_t &total)
+// separators in it (separator i sits in front of record i); *relaunches: how often the kernels ran again because the
+// record list had to grow
+static int fasta_stream_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, std::vector<uint64_t> &seps, uint64_t &total,
+                                  uint32_t *relaunches = nullptr)
 {
     FastaCtx &c = g.fasta;
     size_t os, oi, oo, of;
@@ -1005,6 +1007,7 @@ static int fasta_stream_on_device(const uint8_t *raw, uint64_t n, int which, boo
         if (attempt) return fail(MHX_E_INTERNAL, "FASTA record list kept growing");
         const uint32_t want = nsep + nsep / 4 + 16; // more records than there was room for: once more with room for all of them
         if (c.d_seps.grow(want) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for %u FASTA record positions", want);
+        if (relaunches) ++*relaunches;
     }
     // records: separator i sits in front of record i; its length is the distance to the next separator (or the end)
     seps.assign(nsep, 0);
@@ -1015,6 +1018,33 @@ static int fasta_stream_on_device(const uint8_t *raw, uint64_t n, int which, boo
     }
     std::sort(seps.begin(), seps.end());
     return MHX_OK;
+}
+
+// Test tool: the device FASTA parser alone.  The stream comes back in out[0, *total) and the sorted separator positions in
+// seps[0, *n_seps); either too small: the sizes are still reported (MHX_E_CAPACITY).  Returns kFastaNotForDevice (positive)
+// for a file the file-level calls hand to the host record parser: one that does not start with '>', or FASTQ syntax.
+extern "C" int mhx_fasta_stream(const void *h_bytes, uint64_t n, void *out, uint64_t cap, uint64_t *total, uint64_t *seps, uint64_t seps_cap,
+                                uint64_t *n_seps, uint32_t *relaunches)
+{
+    return entry("mhx_fasta_stream", [&]() -> int {
+        if ((!h_bytes && n) || !total || !n_seps || (!out && cap) || (!seps && seps_cap)) return fail(MHX_E_ARG, "fasta_stream: null argument");
+        *total = 0; *n_seps = 0;
+        if (relaunches) *relaunches = 0;
+        const uint8_t *raw = (const uint8_t *)h_bytes;
+        if (!fasta_for_device(raw, n)) return kFastaNotForDevice;
+        int rc = ensure_fasta_buffers(n);
+        if (rc) return rc;
+        std::vector<uint64_t> pos;
+        uint64_t tot = 0;
+        rc = fasta_stream_on_device(raw, n, 0, false, pos, tot, relaunches);
+        if (rc) return rc;
+        *total = tot; *n_seps = pos.size();
+        if (tot > cap || pos.size() > seps_cap)
+            return fail(MHX_E_CAPACITY, "fasta_stream: %llu stream bytes and %zu separators need more room", (unsigned long long)tot, pos.size());
+        if (tot) HIPCHK(hipMemcpy(out, g.fasta.d_out, tot, hipMemcpyDeviceToHost));
+        if (!pos.empty()) memcpy(seps, pos.data(), pos.size() * 8);
+        return MHX_OK;
+    });
 }
 
 static int sketch_fasta_on_device(const uint8_t *raw, uint64_t n, int which, bool on_device, int k, uint32_t s, std::vector<uint64_t> &hashes, FastaInfo &info)

@@ -128,6 +128,8 @@ def load() -> ctypes.CDLL:
     L.mhx_gunzip_buffer_mt.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t), c.c_int]
     L.mhx_gunzip_device.argtypes = [c.c_char_p, c.c_size_t, c.c_void_p, c.c_size_t, c.POINTER(c.c_size_t)]
     L.mhx_last_inflate_stats.argtypes = [c.c_void_p]
+    if hasattr(L, "mhx_fasta_stream"):   # (MHX_LIB may name an experiment build older than the parser's test entry)
+        L.mhx_fasta_stream.argtypes = [c.c_char_p, c.c_uint64, c.c_void_p, c.c_uint64, u64p, c.c_void_p, c.c_uint64, u64p, u32p]
     L.mhx_last_fastq_route.argtypes = []
     L.mhx_last_fastq_route.restype = c.c_int
     if hasattr(L, "mhx_screen_files"):   # (MHX_LIB may name an experiment build older than the screen: tools/ab.py)
@@ -878,6 +880,28 @@ def inflate_stats() -> dict:
     _check(load().mhx_last_inflate_stats(v.ctypes.data))
     keys = ("members", "segments", "redone", "hops", "host_bytes", "inflated", "ms", "reserved")
     return {k: int(x) for k, x in zip(keys, v)}
+
+
+FASTA_NOT_FOR_DEVICE = 1   # mhx_fasta_stream: the file-level calls hand such a file to the host record parser
+
+
+def fasta_stream(data: bytes):
+    """The device FASTA parser alone (mhx_fasta_stream, a test tool): (stream, seps, relaunches) -- the dense sequence
+    stream as bytes, the ascending positions of the record separators in it (np.uint64) and how often the kernels ran again
+    because the record list had to grow -- or None when the file is not for the device parser (it does not start with
+    '>', or a line starts with '@' or '+')."""
+    init()
+    L = load()
+    data = bytes(data)
+    out = np.empty(len(data) + 1, dtype=np.uint8)          # the stream is never longer than the file
+    seps = np.empty(len(data) // 2 + 1, dtype=np.uint64)   # a record takes two bytes at the least: '>' and a newline
+    total, nseps, relaunches = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    rc = L.mhx_fasta_stream(data, len(data), out.ctypes.data, out.size, ctypes.byref(total), seps.ctypes.data, seps.size,
+                            ctypes.byref(nseps), ctypes.byref(relaunches))
+    if rc == FASTA_NOT_FOR_DEVICE:
+        return None
+    _check(rc)
+    return out[:total.value].tobytes(), seps[:nseps.value].copy(), relaunches.value
 
 
 FASTQ_ROUTES = {0: None, 1: "device-streamed", 2: "device-whole", 3: "record-parser"}

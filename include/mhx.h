@@ -963,6 +963,17 @@ int mhx_gunzip_device(const void *gz, size_t n, void *d_out, size_t cap, size_t 
  * the call (profiling on), [7] reserved (0) */
 int mhx_last_inflate_stats(uint64_t *out8);
 
+/* test tool: the device FASTA parser alone (the first half of the FASTA path of mhx_sketch_files and of
+ * mhx_sketch_files_individual).  The n bytes of a FASTA in host memory go to the device as they are; the dense sequence
+ * stream the sketch kernel would hash (header lines dropped but for their newline, which stays as the one separator byte
+ * in front of every record; line breaks, blanks and DEL squeezed out of the sequence lines) comes back in out[0, *total) and
+ * the ascending positions of the separators in it in seps[0, *n_seps).  cap or seps_cap too small: *total and *n_seps are
+ * still set (MHX_E_CAPACITY).  *relaunches: how often the kernels ran again because the record list had to grow (it only
+ * grows within a process).  Returns MHX_OK, a negative MHX_E_* code, or 1 when the file is not for the device parser and
+ * the file-level calls take the host record parser: it does not start with '>', or a line starts with '@' or '+'. */
+int mhx_fasta_stream(const void *h_bytes, uint64_t n, void *out, uint64_t cap, uint64_t *total,
+                     uint64_t *seps, uint64_t seps_cap, uint64_t *n_seps, uint32_t *relaunches);
+
 #ifdef __cplusplus
 }
 #endif
