@@ -307,7 +307,8 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     CandidateQueue queue{sm, nitems, qcap};
     uint32_t ninsert = 0;
     const TailLutPtr lut = hot_tail_table<K>(); // once per workgroup, in front of the loop
-    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE>(sm, sm.list[it], T, limit, ins, queue, lut);
+    constexpr bool kPairs = pair_words_form<K>(FMT, QUEUE); // windows J and J + 4 share their funnel shifts (PairWords)
+    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE, kPairs>(sm, sm.list[it], T, limit, ins, queue, lut);
     if (QUEUE) {
         __syncthreads();
         const uint32_t ncand = sm.misc[7];

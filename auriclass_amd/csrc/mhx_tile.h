@@ -805,6 +805,48 @@ template <int K, int OFF, int N> MHX_HD void extract_words(const uint32_t (&src)
     if (K % 4) w[NW - 1] &= (1u << (8 * (K % 4))) - 1u;
 }
 
+// The strand of one window of K >= 8 bases: true = the reverse complement is the smaller one.  U = folded forward chunk,
+// R = its reverse complement, Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented (the last two feed
+// nothing but this decision).  The words themselves are made by canonical_words, or by PairWords for two windows at once.
+template <int K, int J, int ND>
+MHX_HD bool canonical_strand(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
+                             const uint32_t (&Cc)[ND + 1])
+{
+    static_assert(K >= 8, "shorter windows compare their extracted words");
+    constexpr int NW = (K + 3) / 4;
+    constexpr int OF = J;               // forward window starts at U byte OF
+    constexpr int OR = ND * 4 - K - J;  // its reverse complement starts at R byte OR
+    // memcmp(fwd, rc) compares big-endian; the first 8 bases of either strand, most
+    // significant first, are 8 little-endian bytes of Wr resp. Cc.  Equal first 8 bases
+    // (4^-8 of the windows) fall back to the full comparison.
+    const uint64_t top_f = load64<ND * 4 - 8 - J>(Wr);
+    const uint64_t top_r = load64<J + K - 8>(Cc);
+    bool rc = top_r < top_f;
+    if (MHX_UNLIKELY(K > 8 && top_r == top_f)) { // cold: exact comparison
+        // the copies go through an opaque barrier so that the compiler cannot hoist the
+        // word extraction of this 4^-8 case in front of the branch (it did: ~19 wasted
+        // instructions per window on the hot path)
+        uint32_t Uc[ND + 1], Rc[ND + 1];
+#pragma unroll
+        for (int i = 0; i < ND + 1; ++i) { Uc[i] = opaque(U[i]); Rc[i] = opaque(R[i]); }
+        // word by word, most significant first: two temporaries instead of two extracted windows (the hash loop has no
+        // registers to spare, and a spill here gives the whole kernel a scratch allocation)
+        constexpr uint32_t last_mask = (K % 4) ? (1u << (8 * (K % 4))) - 1u : 0xFFFFFFFFu;
+        bool rc_less = false, decided = false;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            uint32_t f = funnel(Uc[OF / 4 + i + 1], Uc[OF / 4 + i], OF % 4);
+            uint32_t r = funnel(Rc[OR / 4 + i + 1], Rc[OR / 4 + i], OR % 4);
+            if (i == NW - 1) { f &= last_mask; r &= last_mask; }
+            const uint32_t fb = opaque(__builtin_bswap32(f)), rb = opaque(__builtin_bswap32(r));
+            rc_less = decided ? rc_less : (rb < fb);
+            decided = decided || (fb != rb);
+        }
+        rc = rc_less;
+    }
+    return rc;
+}
+
 // One window: the K bytes of its canonical strand as little-endian words.  U = folded forward chunk, R = its
 // reverse complement, Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented (the last two
 // only feed the strand decision).  Returns the strand: true = the reverse complement.
@@ -820,34 +862,7 @@ MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND 
     constexpr int OF = J;               // forward window starts at U byte OF
     constexpr int OR = ND * 4 - K - J;  // its reverse complement starts at R byte OR
     if constexpr (K >= 8) {
-        // memcmp(fwd, rc) compares big-endian; the first 8 bases of either strand, most
-        // significant first, are 8 little-endian bytes of Wr resp. Cc.  Equal first 8 bases
-        // (4^-8 of the windows) fall back to the full comparison.
-        const uint64_t top_f = load64<ND * 4 - 8 - J>(Wr);
-        const uint64_t top_r = load64<J + K - 8>(Cc);
-        bool rc = top_r < top_f;
-        if (MHX_UNLIKELY(K > 8 && top_r == top_f)) { // cold: exact comparison
-            // the copies go through an opaque barrier so that the compiler cannot hoist the
-            // word extraction of this 4^-8 case in front of the branch (it did: ~19 wasted
-            // instructions per window on the hot path)
-            uint32_t Uc[ND + 1], Rc[ND + 1];
-#pragma unroll
-            for (int i = 0; i < ND + 1; ++i) { Uc[i] = opaque(U[i]); Rc[i] = opaque(R[i]); }
-            // word by word, most significant first: two temporaries instead of two extracted windows (the hash loop has no
-            // registers to spare, and a spill here gives the whole kernel a scratch allocation)
-            constexpr uint32_t last_mask = (K % 4) ? (1u << (8 * (K % 4))) - 1u : 0xFFFFFFFFu;
-            bool rc_less = false, decided = false;
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                uint32_t f = funnel(Uc[OF / 4 + i + 1], Uc[OF / 4 + i], OF % 4);
-                uint32_t r = funnel(Rc[OR / 4 + i + 1], Rc[OR / 4 + i], OR % 4);
-                if (i == NW - 1) { f &= last_mask; r &= last_mask; }
-                const uint32_t fb = opaque(__builtin_bswap32(f)), rb = opaque(__builtin_bswap32(r));
-                rc_less = decided ? rc_less : (rb < fb);
-                decided = decided || (fb != rb);
-            }
-            rc = rc_less;
-        }
+        const bool rc = canonical_strand<K, J, ND>(U, R, Wr, Cc);
         // select the source dwords first, extract once.  The last word keeps TB bytes, and a strand whose byte shift s has
         // s + TB <= 4 takes them all from S[NW - 1]: what it would pull in from S[NW] is masked away.  Both shifts are
         // compile-time constants (only WHICH of them applies is a per-lane run-time value, so the compiler cannot see it):
@@ -1010,6 +1025,80 @@ MHX_HD Murmur3Tail window_partial_hash(const uint32_t (&U)[ND + 1], const uint32
     }
 }
 
+// ---- the words of windows J and J + 4 from one funnel shift per strand -----------------------------------------------
+// canonical_words selects the strand's source dwords per window and funnels afterwards, because WHICH strand applies is a
+// per-lane run-time value.  The two byte shifts themselves are compile-time constants, J % 4 forward and (4 ND - K - J) % 4
+// reverse, and windows J and J + 4 (J = 0..3) share both: forward window J + 4 starts one dword behind window J, reverse
+// window J + 4 one dword in front of it.  So each strand is funnelled once per pair, NWD + 1 dwords for the NWD dwords of
+// either window -- F[0..NWD) / G[1..NWD] for J, F[1..NWD] / G[0..NWD) for J + 4 -- and a strand whose shift is 0 is its
+// source dwords as they stand.  A window is then its strand decision and one select per dword: per group of eight 30
+// funnel shifts and 32 selects at K = 21 where 8 x (6 selects + 4 funnel shifts) stood.
+// BODY_ONLY: NWD = 2 (K / 8), the full 8-byte words in front of the partial word, as canonical_words' form of that name
+// (the K whose table index comes from TailDigits); otherwise all (K + 3) / 4 dwords, the last one masked to its bytes.
+// (tests/emul/pair_words_emul.cpp compares the words with canonical_words' for every K, J and strand.)
+template <int K, int J, int ND, bool BODY_ONLY> struct PairWords {
+    static constexpr int NW = (K + 3) / 4;
+    static constexpr int NWD = BODY_ONLY ? 2 * (K / 8) : NW; // dwords of one window made here
+    static constexpr int OF = J, OR = 4 * ND - K - J;  // window J: first byte in U, first byte in R
+    static constexpr int SF = OF % 4, SR = OR % 4;     // the pair's two byte shifts
+    static constexpr int FD = OF / 4, RD = OR / 4 - 1; // first source dword: forward of window J, reverse of window J + 4
+    static_assert(J >= 0 && J < 4 && K > 16, "pairs (J, J + 4) of the 64-bit hashes");
+    static_assert(NWD > 0 && NWD <= 8 && 4 * NWD <= K + 3, "the dwords made lie inside the window");
+    static_assert((OF + 4) % 4 == SF && (OF + 4) / 4 == FD + 1, "forward window J + 4 starts one dword behind window J");
+    static_assert(OR - 4 >= 0 && (OR - 4) % 4 == SR && (OR - 4) / 4 == RD, "reverse window J + 4 starts at byte OR - 4 >= 0, one dword in front");
+    static_assert(FD + NWD + (SF ? 1 : 0) <= ND && RD + NWD + (SR ? 1 : 0) <= ND, "the source dwords lie inside U[0..ND] and R[0..ND]");
+    uint32_t F[NWD + 1], G[NWD + 1];
+    MHX_HD PairWords(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1])
+    {
+#pragma unroll
+        for (int i = 0; i < NWD + 1; ++i) {
+            F[i] = SF ? funnel(U[FD + i + 1], U[FD + i], SF) : U[FD + i];
+            G[i] = SR ? funnel(R[RD + i + 1], R[RD + i], SR) : R[RD + i];
+        }
+    }
+    // the words of window J (SECOND = false) or J + 4 on the strand rc, as canonical_words<K, J (+ 4), ND, BODY_ONLY> yields them
+    template <bool SECOND> MHX_HD void words(bool rc, uint32_t (&w)[8]) const
+    {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[i] = i < NWD ? (rc ? G[i + (SECOND ? 0 : 1)] : F[i + (SECOND ? 1 : 0)]) : 0u;
+        if constexpr (!BODY_ONLY && K % 4 != 0) w[NW - 1] &= (1u << (8 * (K % 4))) - 1u;
+    }
+};
+// Which K take their words from PairWords, and which kernel forms of such a K (fmt, queue: sketch_tile_kernel's FMT and
+// QUEUE).  The hot loop has no register to spare and the pair is alive across two windows, so a form takes the route only
+// where it stays at 72 VGPRs, no scratch and seven waves per SIMD, and a K only where the loop then loses at least 10 VALU
+// instructions per group (profiles/pair_words_ab.txt, section 1):
+//   K = 17, 18, 19, 21, 23: every form but the inline ones of the look-back repair kernel (FMT 1), which stand at 72 VGPRs
+//       already (K = 21: 12 bytes of scratch with the pair);
+//   K = 25, 26, 27, 29: the queue forms; the inline forms spill (12..68 bytes);
+//   K = 20, 24, 28: -6 per group, left alone; K = 22: left alone as the control of the A/B runs; K = 30..32: forms of these
+//       spill as they are, left alone.
+template <int K> constexpr bool pair_words_apply()
+{
+    return K == 17 || K == 18 || K == 19 || K == 21 || K == 23 || K == 25 || K == 26 || K == 27 || K == 29;
+}
+template <int K> constexpr bool pair_words_form(int fmt, bool queue)
+{
+    return pair_words_apply<K>() && (K > 24 ? queue : fmt != 1 || queue);
+}
+// Windows J (SECOND = false) and J + 4 of the hot loop by that route, up to the last multiplication of the hash: the
+// counterpart of window_partial_hash
+template <int K, int J, int ND, bool SECOND, bool LUT, bool BODY_ONLY, class Digits>
+MHX_HD Murmur3Tail window_pair_hash(const PairWords<K, J, ND, BODY_ONLY> &pair, const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1],
+                                    const uint32_t (&Wr)[ND + 1], const uint32_t (&Cc)[ND + 1], const Digits &digits, TailLutPtr lut)
+{
+    constexpr int JW = J + (SECOND ? 4 : 0);
+    uint32_t w[8];
+    const bool rc = canonical_strand<K, JW, ND>(U, R, Wr, Cc);
+    pair.template words<SECOND>(rc, w);
+    if constexpr (BODY_ONLY) {
+        static_assert(LUT && std::is_same<Digits, TailDigits<K>>::value, "the body-only form takes the table index from packed digits");
+        return murmur3_blocks<K, true>(w, tail_lut_at(lut, digits.template byte_offset<JW>(rc)));
+    } else {
+        return murmur3_core<K, LUT>(w, lut);
+    }
+}
+
 // Cold path, reached by one window in ~2^64 / T: are bytes J .. J+K-1 of the chunk all A/C/G/T (either case)?
 // mash skips every window that holds anything else (Sketch.cpp addMinHashes).
 // (chunk: the raw or the case-folded bytes, the test folds anyway)
@@ -1031,7 +1120,9 @@ template <int K, int J, int ND> MHX_HD bool window_is_acgt(const uint32_t (&chun
 // windows) the inline form is 0.8 % faster (the queue's cold branch changes the register allocation of the hot path by
 // one v_mov per window); with a large one (s = 50 000) the queue is 7 % faster.
 // lut: hot_tail_table<K>(), fetched by the caller in front of its loop over the groups (nullptr: formed here).
-template <int K, bool QUEUE, class Ins, class Cand>
+// PAIRS: the words of windows J and J + 4 from one PairWords (the kernel forms pair_words_form names).  The windows then
+// run (0,4)(1,5)(2,6)(3,7); what is done with each stays per window.
+template <int K, bool QUEUE, bool PAIRS = false, class Ins, class Cand>
 MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint32_t vm, uint64_t T, uint32_t limit, Ins &ins, Cand &cand,
                                    TailLutPtr lut)
 {
@@ -1044,9 +1135,18 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     // a K that keeps the per-window index also keeps the address where it was formed, here (hot_tail_table)
     if constexpr (kLut && !tail_digits_apply<K>()) lut = tail_lut_of<K>();
     const std::conditional_t<kLut && tail_digits_apply<K>(), TailDigits<K>, NoTailDigits> digits(U, R);
-#define MHX_WINDOW(J)                                                                         \
+    constexpr bool kDigits = kLut && tail_digits_apply<K>();
+    constexpr bool kPairs = PAIRS && pair_words_apply<K>();
+#define MHX_WINDOW(J) MHX_WINDOW_OF(J, (window_partial_hash<K, J, ND, kLut>(U, R, Wr, Cc, digits, lut)))
+#define MHX_PAIR(J)                                                                           \
     {                                                                                         \
-        const Murmur3Tail tail = window_partial_hash<K, J, ND, kLut>(U, R, Wr, Cc, digits, lut); \
+        const PairWords<K, J, ND, kDigits> pair(U, R);                                        \
+        MHX_WINDOW_OF(J, (window_pair_hash<K, J, ND, false, kLut>(pair, U, R, Wr, Cc, digits, lut)))    \
+        MHX_WINDOW_OF(J + 4, (window_pair_hash<K, J, ND, true, kLut>(pair, U, R, Wr, Cc, digits, lut))) \
+    }
+#define MHX_WINDOW_OF(J, HASH)                                                                \
+    {                                                                                         \
+        const Murmur3Tail tail = HASH;                                                        \
         /* necessary condition of h <= T, see Murmur3Tail (32-bit hashes: the exact low word) */ \
         const uint32_t low = kHash32 ? tail.low32() : 0u;                                     \
         const bool candidate = kHash32 ? low <= (uint32_t)T : tail.high_bound() <= limit;     \
@@ -1059,7 +1159,13 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
             }                                                                                 \
         }                                                                                     \
     }
-    MHX_WINDOW(0) MHX_WINDOW(1) MHX_WINDOW(2) MHX_WINDOW(3) MHX_WINDOW(4) MHX_WINDOW(5) MHX_WINDOW(6) MHX_WINDOW(7)
+    if constexpr (kPairs) {
+        MHX_PAIR(0) MHX_PAIR(1) MHX_PAIR(2) MHX_PAIR(3)
+    } else {
+        MHX_WINDOW(0) MHX_WINDOW(1) MHX_WINDOW(2) MHX_WINDOW(3) MHX_WINDOW(4) MHX_WINDOW(5) MHX_WINDOW(6) MHX_WINDOW(7)
+    }
+#undef MHX_WINDOW_OF
+#undef MHX_PAIR
 #undef MHX_WINDOW
     static_assert(kGroup == 8, "process_group unrolls 8 windows");
     return ninserted;
@@ -1078,7 +1184,7 @@ template <int K> MHX_HD TailLutPtr hot_tail_table()
 }
 
 // work item g of a staged tile (LDS source)
-template <int K, bool QUEUE, class Ins, class Cand>
+template <int K, bool QUEUE, bool PAIRS = false, class Ins, class Cand>
 MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand, TailLutPtr lut)
 {
     constexpr int ND = GroupGeom<K>::ND;
@@ -1087,7 +1193,7 @@ MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32
     uint32_t src[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) src[d] = p[d];
-    return process_group_regs<K, QUEUE>(src, vm, T, limit, ins, cand, lut);
+    return process_group_regs<K, QUEUE, PAIRS>(src, vm, T, limit, ins, cand, lut);
 }
 template <int K, bool QUEUE, class Ins, class Cand>
 MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand)
