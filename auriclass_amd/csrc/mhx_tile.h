@@ -806,23 +806,41 @@ template <int K, int OFF, int N> MHX_HD void extract_words(const uint32_t (&src)
 }
 
 // The strand of one window of K >= 8 bases: true = the reverse complement is the smaller one.  U = folded forward chunk,
-// R = its reverse complement, Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented (the last two feed
-// nothing but this decision).  The words themselves are made by canonical_words, or by PairWords for two windows at once.
+// R = its reverse complement: the two views the hash reads, and the decision reads nothing else.  The words themselves are
+// made by canonical_words, or by PairWords for two windows at once.
+// memcmp(fwd, rc) compares big-endian, and the first 8 bases decide all but 4^-8 of the windows.  With u[] the folded bytes
+// of the chunk, R[j] = comp(u[4 ND - 1 - j]).  The first 8 bases of the forward strand, most significant first, are the 8
+// little-endian bytes at byte 4 ND - 8 - J of the byte-reversed chunk: the bytewise complement of B, the 8 bytes of R at
+// that offset.  The first 8 bases of the reverse strand are the complements of the window's last 8 bytes, the 8 bytes A of
+// U at byte J + K - 8.  On {A, C, G, T} the complement reverses the order (A < C < G < T <-> T > G > C > A) and is
+// one-to-one, and the first differing byte decides a big-endian comparison, so
+//     comp(A) < comp(B)  <=>  A > B        comp(A) == comp(B)  <=>  A == B:
+// rc = B < A, and A == B falls back to the full comparison, is memcmp's answer for every window whose K bytes are A/C/G/T in
+// either case.  A window that holds any other byte may get either answer (U keeps the raw folded byte where the complement
+// table yields one of the four letters).  It does not matter: such a window is no set bit of the start mask (run_starts) or
+// fails window_is_acgt / process_deferred's base check, so whatever it hashes to is thrown away -- the argument of the
+// deferred base check and of the tail table.
 template <int K, int J, int ND>
-MHX_HD bool canonical_strand(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
-                             const uint32_t (&Cc)[ND + 1])
+MHX_HD bool canonical_strand(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1])
 {
     static_assert(K >= 8, "shorter windows compare their extracted words");
     constexpr int NW = (K + 3) / 4;
     constexpr int OF = J;               // forward window starts at U byte OF
     constexpr int OR = ND * 4 - K - J;  // its reverse complement starts at R byte OR
-    // memcmp(fwd, rc) compares big-endian; the first 8 bases of either strand, most
-    // significant first, are 8 little-endian bytes of Wr resp. Cc.  Equal first 8 bases
-    // (4^-8 of the windows) fall back to the full comparison.
-    const uint64_t top_f = load64<ND * 4 - 8 - J>(Wr);
-    const uint64_t top_r = load64<J + K - 8>(Cc);
-    bool rc = top_r < top_f;
-    if (MHX_UNLIKELY(K > 8 && top_r == top_f)) { // cold: exact comparison
+    static_assert(J >= 0 && J + K <= 4 * ND, "the window lies inside the chunk");
+    static_assert(J + K - 8 >= 0 && J + K <= 4 * (ND + 1), "A: 8 bytes inside U[0..ND]");
+    static_assert(4 * ND - 8 - J >= 0 && 4 * ND - J <= 4 * (ND + 1), "B: 8 bytes inside R[0..ND]");
+    if constexpr (K == 8 && J % 4 == 0) {
+        // A and B are the two strands' own dword pairs as they stand, those of windows 0 and 4 one dword apart.  Written as
+        // 64-bit values the compiler merges each pair into one 64-bit load of U resp. R, the overlapping loads keep both
+        // arrays in memory, and every K = 8 kernel gets 32 bytes of scratch.  Compared half by half they stay registers.
+        constexpr int QA = J / 4, QB = ND - 2 - J / 4;
+        return R[QB + 1] < U[QA + 1] || (R[QB + 1] == U[QA + 1] && R[QB] < U[QA]);
+    }
+    const uint64_t top_a = load64<J + K - 8>(U);      // the window's last 8 bytes
+    const uint64_t top_b = load64<ND * 4 - 8 - J>(R); // the reverse complement's last 8 bytes
+    bool rc = top_b < top_a;
+    if (MHX_UNLIKELY(K > 8 && top_a == top_b)) { // cold: exact comparison
         // the copies go through an opaque barrier so that the compiler cannot hoist the
         // word extraction of this 4^-8 case in front of the branch (it did: ~19 wasted
         // instructions per window on the hot path)
@@ -846,23 +864,28 @@ MHX_HD bool canonical_strand(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND
     }
     return rc;
 }
+// (the signature from when the decision read two views of its own, the forward chunk byte-reversed and complemented: the
+// CPU emulators under tests/emul call it)
+template <int K, int J, int ND>
+MHX_HD bool canonical_strand(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&)[ND + 1], const uint32_t (&)[ND + 1])
+{
+    return canonical_strand<K, J, ND>(U, R);
+}
 
 // One window: the K bytes of its canonical strand as little-endian words.  U = folded forward chunk, R = its
-// reverse complement, Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented (the last two
-// only feed the strand decision).  Returns the strand: true = the reverse complement.
+// reverse complement.  Returns the strand: true = the reverse complement.
 // BODY_ONLY (the hot loop with the tail block's partial word from packed digits, TailDigits below): only the full 8-byte
 // words in front of the partial word, w[0 .. 2 * (K / 8)), are made; the rest of w is zero, and the source dwords and the
 // funnel shifts that only the partial word read are not selected or made at all.
 template <int K, int J, int ND, bool BODY_ONLY = false>
-MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
-                            const uint32_t (&Cc)[ND + 1], uint32_t (&w)[8])
+MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], uint32_t (&w)[8])
 {
     static_assert(!BODY_ONLY || K > 16, "the body-only form belongs to the tail table (64-bit hashes)");
     constexpr int NW = (K + 3) / 4;
     constexpr int OF = J;               // forward window starts at U byte OF
     constexpr int OR = ND * 4 - K - J;  // its reverse complement starts at R byte OR
     if constexpr (K >= 8) {
-        const bool rc = canonical_strand<K, J, ND>(U, R, Wr, Cc);
+        const bool rc = canonical_strand<K, J, ND>(U, R);
         // select the source dwords first, extract once.  The last word keeps TB bytes, and a strand whose byte shift s has
         // s + TB <= 4 takes them all from S[NW - 1]: what it would pull in from S[NW] is masked away.  Both shifts are
         // compile-time constants (only WHICH of them applies is a per-lane run-time value, so the compiler cannot see it):
@@ -907,6 +930,13 @@ MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND 
         return rc;
     }
 }
+// (the four-view signature, as canonical_strand's)
+template <int K, int J, int ND, bool BODY_ONLY = false>
+MHX_HD bool canonical_words(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&)[ND + 1], const uint32_t (&)[ND + 1],
+                            uint32_t (&w)[8])
+{
+    return canonical_words<K, J, ND, BODY_ONLY>(U, R, w);
+}
 
 // P5: one work item = 8 consecutive window starts sharing one register chunk.
 template <int K> struct GroupGeom {
@@ -941,22 +971,30 @@ MHX_HD uint32_t complement4_raw(uint32_t v, uint32_t lut_lo)
 #endif
 }
 
-// The four views of a group's chunk that canonical_words takes (one dword of zero padding behind each)
-template <int ND>
-MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint32_t (&R)[ND + 1], uint32_t (&Wr)[ND + 1], uint32_t (&Cc)[ND + 1])
+// The two views of a group's chunk that canonical_strand, canonical_words and PairWords take: the folded forward chunk and
+// its reverse complement (one dword of zero padding behind each)
+template <int ND> MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint32_t (&R)[ND + 1])
 {
     const uint32_t lut_lo = complement_lut_lo();
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
         U[d] = src[d] & 0xDFDFDFDFu; // fold case: mash upper-cases before hashing
-        Cc[d] = complement4_raw(src[d], lut_lo);
+        R[d] = __builtin_bswap32(complement4_raw(src[ND - 1 - d], lut_lo));
     }
+    U[ND] = R[ND] = 0;
+}
+// (the four-view signature, as canonical_strand's: Wr = the forward chunk byte-reversed, Cc = the forward chunk complemented,
+// which nothing reads any more)
+template <int ND>
+MHX_HD void strand_views(const uint32_t (&src)[ND], uint32_t (&U)[ND + 1], uint32_t (&R)[ND + 1], uint32_t (&Wr)[ND + 1], uint32_t (&Cc)[ND + 1])
+{
+    strand_views<ND>(src, U, R);
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
-        R[d] = __builtin_bswap32(Cc[ND - 1 - d]);
         Wr[d] = __builtin_bswap32(U[ND - 1 - d]);
+        Cc[d] = __builtin_bswap32(R[ND - 1 - d]);
     }
-    U[ND] = R[ND] = Wr[ND] = Cc[ND] = 0;
+    Wr[ND] = Cc[ND] = 0;
 }
 
 // ---- the tail table's index from digits packed once per group --------------------------------------------------------
@@ -1004,6 +1042,8 @@ template <int K> struct TailDigits {
 // that back: -23 of 648 hot VALU per group at K = 21.  With fewer bases the per-window index was cheap already (K = 17..20:
 // +4..+12 per group), and the K = 25..29 kernels stand at 70..72 VGPRs, where the packed pair costs copies in the window blocks
 // (K = 25..28: +4..+22) or, at K = 29, a scratch allocation in the inline form (profiles/tail_digits_ab.txt, section 1).
+// Counted again with the strand decision on U and R alone: K = 25..28 +1..+22, K = 29 16 bytes of scratch in the queue forms
+// (profiles/strand_views_ab.txt, section 1).
 template <int K> constexpr bool tail_digits_apply() { return K == 21; }
 struct NoTailDigits { // stands in where the index is not taken from packed digits
     template <class A, class B> MHX_HD NoTailDigits(const A &, const B &) {}
@@ -1012,17 +1052,23 @@ struct NoTailDigits { // stands in where the index is not taken from packed digi
 // table (the device's hot loop, hot_tail_lut<K>()); with a TailDigits<K> its index comes from the group's packed digits
 // and only the body words of the canonical strand are extracted, otherwise from the partial word itself.
 template <int K, int J, int ND, bool LUT, class Digits>
-MHX_HD Murmur3Tail window_partial_hash(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&Wr)[ND + 1],
-                                       const uint32_t (&Cc)[ND + 1], const Digits &digits, TailLutPtr lut)
+MHX_HD Murmur3Tail window_partial_hash(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const Digits &digits, TailLutPtr lut)
 {
     uint32_t w[8];
     if constexpr (LUT && std::is_same<Digits, TailDigits<K>>::value) {
-        const bool rc = canonical_words<K, J, ND, true>(U, R, Wr, Cc, w);
+        const bool rc = canonical_words<K, J, ND, true>(U, R, w);
         return murmur3_blocks<K, true>(w, tail_lut_at(lut, digits.template byte_offset<J>(rc)));
     } else {
-        canonical_words<K, J, ND>(U, R, Wr, Cc, w);
+        canonical_words<K, J, ND>(U, R, w);
         return murmur3_core<K, LUT>(w, lut);
     }
+}
+// (the four-view signature, as canonical_strand's)
+template <int K, int J, int ND, bool LUT, class Digits>
+MHX_HD Murmur3Tail window_partial_hash(const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1], const uint32_t (&)[ND + 1],
+                                       const uint32_t (&)[ND + 1], const Digits &digits, TailLutPtr lut)
+{
+    return window_partial_hash<K, J, ND, LUT>(U, R, digits, lut);
 }
 
 // ---- the words of windows J and J + 4 from one funnel shift per strand -----------------------------------------------
@@ -1073,6 +1119,9 @@ template <int K, int J, int ND, bool BODY_ONLY> struct PairWords {
 //   K = 25, 26, 27, 29: the queue forms; the inline forms spill (12..68 bytes);
 //   K = 20, 24, 28: -6 per group, left alone; K = 22: left alone as the control of the A/B runs; K = 30..32: forms of these
 //       spill as they are, left alone.
+// (The figures are those of when the switch was set.  Since the strand decision reads U and R alone, the FMT 1 inline forms of
+// K = 17, 18, 19, 21, 23 and the inline forms of K = 25 would pass the rule, those of K = 26, 27, 29 still take scratch, and
+// K = 30..32 no longer spill: profiles/strand_views_ab.txt, section 1.  The switch stands as tests/test_pair_words.py pins it.)
 template <int K> constexpr bool pair_words_apply()
 {
     return K == 17 || K == 18 || K == 19 || K == 21 || K == 23 || K == 25 || K == 26 || K == 27 || K == 29;
@@ -1085,11 +1134,11 @@ template <int K> constexpr bool pair_words_form(int fmt, bool queue)
 // counterpart of window_partial_hash
 template <int K, int J, int ND, bool SECOND, bool LUT, bool BODY_ONLY, class Digits>
 MHX_HD Murmur3Tail window_pair_hash(const PairWords<K, J, ND, BODY_ONLY> &pair, const uint32_t (&U)[ND + 1], const uint32_t (&R)[ND + 1],
-                                    const uint32_t (&Wr)[ND + 1], const uint32_t (&Cc)[ND + 1], const Digits &digits, TailLutPtr lut)
+                                    const Digits &digits, TailLutPtr lut)
 {
     constexpr int JW = J + (SECOND ? 4 : 0);
     uint32_t w[8];
-    const bool rc = canonical_strand<K, JW, ND>(U, R, Wr, Cc);
+    const bool rc = canonical_strand<K, JW, ND>(U, R);
     pair.template words<SECOND>(rc, w);
     if constexpr (BODY_ONLY) {
         static_assert(LUT && std::is_same<Digits, TailDigits<K>>::value, "the body-only form takes the table index from packed digits");
@@ -1127,8 +1176,8 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
                                    TailLutPtr lut)
 {
     constexpr int ND = GroupGeom<K>::ND;
-    uint32_t U[ND + 1], R[ND + 1], Wr[ND + 1], Cc[ND + 1];
-    strand_views<ND>(src, U, R, Wr, Cc);
+    uint32_t U[ND + 1], R[ND + 1];
+    strand_views<ND>(src, U, R);
     constexpr bool kHash32 = K <= 16; // mash keeps 32 bits when 4^k <= 2^32
     uint32_t ninserted = 0;
     constexpr bool kLut = hot_tail_lut<K>();
@@ -1137,12 +1186,12 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     const std::conditional_t<kLut && tail_digits_apply<K>(), TailDigits<K>, NoTailDigits> digits(U, R);
     constexpr bool kDigits = kLut && tail_digits_apply<K>();
     constexpr bool kPairs = PAIRS && pair_words_apply<K>();
-#define MHX_WINDOW(J) MHX_WINDOW_OF(J, (window_partial_hash<K, J, ND, kLut>(U, R, Wr, Cc, digits, lut)))
+#define MHX_WINDOW(J) MHX_WINDOW_OF(J, (window_partial_hash<K, J, ND, kLut>(U, R, digits, lut)))
 #define MHX_PAIR(J)                                                                           \
     {                                                                                         \
         const PairWords<K, J, ND, kDigits> pair(U, R);                                        \
-        MHX_WINDOW_OF(J, (window_pair_hash<K, J, ND, false, kLut>(pair, U, R, Wr, Cc, digits, lut)))    \
-        MHX_WINDOW_OF(J + 4, (window_pair_hash<K, J, ND, true, kLut>(pair, U, R, Wr, Cc, digits, lut))) \
+        MHX_WINDOW_OF(J, (window_pair_hash<K, J, ND, false, kLut>(pair, U, R, digits, lut)))          \
+        MHX_WINDOW_OF(J + 4, (window_pair_hash<K, J, ND, true, kLut>(pair, U, R, digits, lut)))       \
     }
 #define MHX_WINDOW_OF(J, HASH)                                                                \
     {                                                                                         \
