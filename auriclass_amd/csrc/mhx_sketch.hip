@@ -215,6 +215,8 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     }
     const uint64_t tile_off = (uint64_t)tile * kTileBytes;
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(a.stats) + (tile % kStatReplicas) * kStatCount;
+    // the work list from the line list (phase_line_span / phase_line_items, mhx_tile.h): the forms line_items_form names
+    constexpr bool kLineItems = !kParseLoops && line_items_form<K>(FMT, QUEUE);
     if (tid == 0) { sm.misc[3] = 0; sm.misc[4] = 0; sm.misc[5] = 0; sm.misc[7] = 0; }
 #ifdef MHX_STAMPS
     uint64_t stamp_prev = clock64();
@@ -282,21 +284,53 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     }
     MHX_STAMP(); // 2: newline scan + look-back
     bool bad = false;
-    const uint32_t long_records = fast_parse
-        ? phase_good_events(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K)
-        : phase_good<FASTQ>(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
+    // workgroup-uniform: the tile's sequence lines become its work list as they stand; the lanes of the first wave take one
+    // each and read its two ends before the barrier, behind which the list and the start masks go where the events and the
+    // newline map were
+    bool by_lines = kLineItems && line_items_try(fast_parse, interior, line_base, tile_total);
+    uint32_t long_records, items_at = 0;
+    LineSpan span{0u, 0u, 0u, 0u};
+    if (kLineItems && by_lines) {
+        long_records = phase_event_checks(sm, tid, line_base, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
+        if (tid < (int)kLineItemLines) {
+            span = phase_line_span<K>(sm, (uint32_t)tid, line_base, tile_total);
+            // the two words the path leaves for the other waves are set here, by this wave, and nowhere else: set at the kernel's
+            // entry, in front of the stage loads of every tile, they cost a FASTQ of 10 kb reads 1.3 % (profiles/line_items_ab.txt, 4)
+            const bool too_long = __ballot(line_span_too_long(span)) != 0ull; // wave-uniform
+            if (tid == 0) { sm.misc[1] = 0u; sm.misc[6] = too_long ? 1u : 0u; }
+            items_at = atomicAdd(&sm.misc[1], span.ngroups); // behind lane 0's store in this wave's LDS order; a wave scan (DPP) and one LDS atomic
+        }
+    } else {
+        long_records = fast_parse
+            ? phase_good_events(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K)
+            : phase_good<FASTQ>(sm, tid, st, line_base, excl, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
+    }
     if (FASTQ && bad && once) atomicOr(&stats[kStatFlags], (unsigned long long)kFlagBadFastq);
     if (FASTQ && long_records) atomicAdd(&sm.misc[5], long_records);
     __syncthreads();
-    MHX_STAMP(); // 3: good-base map
+    MHX_STAMP(); // 3: good-base map, or the ends of the sequence lines
+    if (kLineItems && by_lines && MHX_UNLIKELY(sm.misc[6] != 0u)) { // a line above the bound: the maps after all, its checks are done
+        by_lines = false;
+        phase_good_events_map(sm, tid, st, line_base, excl, tile_total);
+        __syncthreads();
+    }
 
-    uint32_t items = 0;
-    const uint32_t kmers = phase_runs<K>(sm, tid, items);
-    if (kmers) atomicAdd(&sm.misc[3], kmers);
     uint32_t nitems = 0;
-    const uint32_t items_before = block_scan_excl<kBlock>(items, sm.cnt + 8, nitems); // barrier inside: sm.valid complete
-    phase_compact(sm, tid, items_before);
-    __syncthreads();
+    if (kLineItems && by_lines) {
+        if (tid < (int)kLineItemLines) {
+            if (span.kmers) atomicAdd(&sm.misc[3], span.kmers);
+            phase_line_items(sm, span, items_at);
+        }
+        __syncthreads();
+        nitems = sm.misc[1];
+    } else {
+        uint32_t items = 0;
+        const uint32_t kmers = phase_runs<K>(sm, tid, items);
+        if (kmers) atomicAdd(&sm.misc[3], kmers);
+        const uint32_t items_before = block_scan_excl<kBlock>(items, sm.cnt + 8, nitems); // barrier inside: sm.valid complete
+        phase_compact(sm, tid, items_before);
+        __syncthreads();
+    }
     MHX_STAMP(); // 4: valid starts + work list
     __builtin_amdgcn_s_setprio(0);
 

@@ -50,7 +50,7 @@ struct TileSmem {
         uint32_t maps[2 * kMapWords];
     };
     uint32_t cnt[16];                                  // wave partials of the two workgroup scans
-    uint32_t misc[8];                                  // 0: line base, 1: #items, 2: tile id, 3: k-mers, 4: inserts, 5: long records, 7: #queued candidates
+    uint32_t misc[8];                                  // 0: line base, 1: #items, 2: tile id, 3: k-mers, 4: inserts, 5: long records, 6: a sequence line too long for phase_line_items, 7: #queued candidates
 };
 
 MHX_HD uint32_t *tile_nlmap(TileSmem &sm) { return sm.maps; }             // 1 bit per byte: newline
@@ -694,10 +694,11 @@ MHX_HD bool seqline_is_long(const uint32_t *nlmap, const uint8_t *tile_bytes, ui
     return !(tile_bytes[after - 1u] == '\r' && ends_here);
 }
 
-// phase_good<true> for a tile whose newlines phase_events has listed (a barrier in between); the sum of the return
-// values over the workgroup is the tile's number of long records (which lane counts a record differs from phase_good)
-MHX_HD uint32_t phase_good_events(TileSmem &sm, int tid, const ThreadState &st, uint32_t line_base, uint32_t excl,
-                                  uint32_t tile_total, uint32_t check_limit, bool &bad_format, uint64_t tile_off, uint64_t end, uint32_t k)
+// phase_good<true> for a tile whose newlines phase_events has listed (a barrier in between), in its two halves: the
+// good map (phase_good_events_map) and the checks, one lane per newline (phase_event_checks); the sum of the checks'
+// return values over the workgroup is the tile's number of long records (which lane counts a record differs from
+// phase_good).  The line-item form below keeps the checks and skips the map.
+MHX_HD void phase_good_events_map(TileSmem &sm, int tid, const ThreadState &st, uint32_t line_base, uint32_t excl, uint32_t tile_total)
 {
     uint32_t line = line_base + excl;
 #pragma unroll
@@ -715,6 +716,10 @@ MHX_HD uint32_t phase_good_events(TileSmem &sm, int tid, const ThreadState &st, 
         tile_good(sm)[kTileBytes / 32 + 2] = 0;
         tile_good(sm)[kTileBytes / 32 + 3] = 0;
     }
+}
+MHX_HD uint32_t phase_event_checks(TileSmem &sm, int tid, uint32_t line_base, uint32_t tile_total, uint32_t check_limit,
+                                   bool &bad_format, uint64_t tile_off, uint64_t end, uint32_t k)
+{
     const uint8_t *tb = reinterpret_cast<const uint8_t *>(sm.bytes);
     const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
     uint32_t count = 0;
@@ -733,6 +738,104 @@ MHX_HD uint32_t phase_good_events(TileSmem &sm, int tid, const ThreadState &st, 
         }
     }
     return count;
+}
+MHX_HD uint32_t phase_good_events(TileSmem &sm, int tid, const ThreadState &st, uint32_t line_base, uint32_t excl,
+                                  uint32_t tile_total, uint32_t check_limit, bool &bad_format, uint64_t tile_off, uint64_t end, uint32_t k)
+{
+    phase_good_events_map(sm, tid, st, line_base, excl, tile_total);
+    return phase_event_checks(sm, tid, line_base, tile_total, check_limit, bad_format, tile_off, end, k);
+}
+
+// ---- FASTQ work list from the line list, not from byte maps ------------------------------------------------------------
+// For an interior FASTQ tile whose newlines phase_events has listed, the work list and the start masks follow from the lines
+// themselves (DESIGN.md 3.1 has the reasoning, the bounds and the measurements).  With n_0 < .. < n_{t-1} the tile's newlines
+// (t = tile_total) and h the first newline of the halo (none: beyond it), line i (0 <= i <= t) spans [a_i, b_i): a_0 = 0,
+// a_i = n_{i-1} + 1; b_i = n_i, b_t = h; its index is line_base + i.  For every line with index 1 (mod 4),
+// pmax = min(b_i - K, kTileBytes - 1); if pmax >= a_i
+//     the valid starts are a_i .. pmax, the items the groups a_i >> 3 .. pmax >> 3,
+//     bit j of group g's byte in sm.valid is set iff a_i <= 8 g + j <= pmax, and the tile has pmax - a_i + 1 k-mers more
+// (a CR in front of the newline is a line byte, as in seqline_mask): bit for bit what the maps give, in another order of sm.list.
+// Invariants: for K >= 8 two sequence lines never share a group (one writer per mask byte); a lane reads its line's two ends
+// (phase_line_span) BEFORE the barrier behind which the list and the masks are written over the events and the newline map
+// (phase_line_items).  One lane per sequence line, all in the first wave.  Taken where the tile is interior, its newlines are
+// listed, it holds kLineItemMinNewlines newlines at least and kLineItemLines sequence lines at most, and no sequence line has
+// more than kLineItemGroups groups; a lane that finds its line too long sends the whole workgroup back to the maps.
+constexpr uint32_t kLineItemLines = 64;
+constexpr uint32_t kLineItemGroups = 40;
+// Tiles with fewer newlines do not try: records whose lines are as long as 40 groups allow (320 + K - 1 bytes) put 48 into a
+// tile, so reads of 600 to 2700 bases, which self-synchronise, are spared the attempt and its extra barrier on every tile.
+constexpr uint32_t kLineItemMinNewlines = 48;
+static_assert(kLineItemLines <= 64, "the sequence lines of a tile take the lanes of one wave");
+// which K have the form at all (-DMHX_PARSE_MAPS: none, the A/B builds of tools/build_variants.sh)
+template <int K> constexpr bool line_items_apply()
+{
+#ifdef MHX_PARSE_MAPS
+    return false;
+#else
+    return K >= 8;
+#endif
+}
+// ... and which kernel forms of such a K (fmt, queue: sketch_tile_kernel's FMT and QUEUE), as pair_words_form has it:
+//   a form takes the path only where it stays at 22 720 B of LDS, 72 VGPRs, no scratch and seven waves per SIMD: the queue
+//       forms of K = 29 stand at 72 VGPRs and take 16 bytes of scratch with it, they keep the maps;
+//   the look-back kernels (FMT 1) keep the maps: with the path compiled into them a FASTQ of 10 kb reads, all of whose tiles
+//       they hash (on the map path), ran 4 % slower than the parent in every round, and level with it without
+//       (profiles/line_items_ab.txt, section 4).  In a real run they work on tiles of under six newlines, which never qualify.
+template <int K> constexpr bool line_items_form(int fmt, bool queue) { return line_items_apply<K>() && fmt == 2 && !(K == 29 && queue); }
+MHX_HD uint32_t seqline_first(uint32_t line_base) { return (1u - line_base) & 3u; } // i of the tile's first sequence line
+MHX_HD uint32_t seqline_count(uint32_t line_base, uint32_t tile_total)
+{
+    const uint32_t i0 = seqline_first(line_base);
+    return i0 <= tile_total ? (tile_total - i0) / 4u + 1u : 0u;
+}
+// the workgroup-uniform part of the choice
+MHX_HD bool line_items_try(bool fast_parse, bool interior, uint32_t line_base, uint32_t tile_total)
+{
+    return fast_parse && interior && tile_total >= kLineItemMinNewlines && seqline_count(line_base, tile_total) <= kLineItemLines;
+}
+struct LineSpan { uint32_t a, pmax, ngroups, kmers; }; // ngroups = 0: no valid start
+// the tile's j-th sequence line, from its two events (or the halo words of the newline map): before the barrier behind
+// which phase_line_items writes over both
+template <int K> MHX_HD LineSpan phase_line_span(const TileSmem &sm, uint32_t j, uint32_t line_base, uint32_t tile_total)
+{
+    const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
+    const uint32_t i = seqline_first(line_base) + 4u * j;
+    LineSpan s{0u, 0u, 0u, 0u};
+    if (i > tile_total) return s;
+    const uint32_t a = i ? (uint32_t)ev[i - 1u] + 1u : 0u;
+    uint32_t b;
+    if (i < tile_total) {
+        b = ev[i];
+    } else { // the line that runs into the halo
+        const uint32_t h0 = sm.maps[kTileBytes / 32], h1 = sm.maps[kTileBytes / 32 + 1];
+        b = h0 ? (uint32_t)kTileBytes + (uint32_t)__builtin_ctz(h0) : h1 ? (uint32_t)kTileBytes + 32u + (uint32_t)__builtin_ctz(h1) : (uint32_t)(kTileBytes + kHaloBytes);
+    }
+    int32_t pmax = (int32_t)b - K;
+    if (pmax > kTileBytes - 1) pmax = kTileBytes - 1;
+    if (pmax < (int32_t)a) return s;
+    s.a = a;
+    s.pmax = (uint32_t)pmax;
+    s.ngroups = ((uint32_t)pmax >> 3) - (a >> 3) + 1u;
+    s.kmers = (uint32_t)pmax - a + 1u;
+    return s;
+}
+MHX_HD bool line_span_too_long(const LineSpan &s) { return s.ngroups > kLineItemGroups; }
+// the line's groups -> sm.list[at .. at + ngroups), their start masks -> sm.valid
+MHX_HD void phase_line_items(TileSmem &sm, const LineSpan &s, uint32_t at)
+{
+    if (!s.ngroups) return;
+    uint8_t *vb = reinterpret_cast<uint8_t *>(sm.valid);
+    const uint32_t g0 = s.a >> 3, g1 = s.pmax >> 3;
+    const uint32_t first = (0xFFu << (s.a & 7u)) & 0xFFu, last = 0xFFu >> (7u - (s.pmax & 7u));
+    sm.list[at] = (uint16_t)g0;
+    vb[g0] = (uint8_t)(g0 == g1 ? first & last : first);
+    if (g0 == g1) return;
+    // every further group whole, and the last one's mask over it afterwards (same lane, same byte: LDS keeps the order)
+    for (uint32_t g = g0 + 1u; g <= g1; ++g) {
+        sm.list[++at] = (uint16_t)g;
+        vb[g] = 0xFFu;
+    }
+    vb[g1] = (uint8_t)last;
 }
 
 // P3: valid k-mer starts of this thread's positions -> sm.valid, #items -> sm.cnt

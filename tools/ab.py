@@ -3,7 +3,7 @@ made by tools/build_variants.sh); each round runs every variant once, in its own
 library), on the same synthetic reads; medians over rounds are compared.  Every run also checks its sketch against
 the oracle on a prefix, so a fast-but-wrong variant shows up as PARITY FAIL.
 
-    python tools/ab.py [--reads N] [--rounds R] [--k K --s S --m M] name1 name2 ...   (name "base" = lib/libmhx.so)
+    python tools/ab.py [--reads N] [--read-len L] [--rounds R] [--k K --s S --m M] name1 name2 ...   (name "base" = lib/libmhx.so)
 """
 import argparse
 import json
@@ -24,7 +24,7 @@ def child(args):
 
     engine.init(0)
     g = synth.make_genome(12_000_000, 42)
-    fq = synth.make_fastq(g, args.reads, 150, 43, device="cuda")
+    fq = synth.make_fastq(g, args.reads, args.read_len, 43, device="cuda")
     torch.cuda.synchronize()
     sk = engine.Sketcher(args.k, args.s, args.m, expected_bytes=fq.numel())
     engine.set_profiling(True)
@@ -39,8 +39,8 @@ def child(args):
     out = {"kernel_ms": float(np.median(ms[2:])), "step_ms": float(np.median(wall[2:])), "kmers": st["kmers"], "launches": st["launches"]}
     if args.parity:
         from oracle import mash_oracle as mo
-        n = min(args.reads, 300_000)
-        rb = synth.record_bytes(150)
+        n = min(args.reads, max(1, 300_000 * 150 // args.read_len))   # the oracle's share: 45 Mbases at the most
+        rb = synth.record_bytes(args.read_len)
         sk2 = engine.Sketcher(args.k, args.s, args.m, expected_bytes=n * rb)
         sk2.push_device(fq.data_ptr(), n * rb, engine.FMT_FASTQ4)
         got, _ = sk2.finish()
@@ -55,6 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("names", nargs="*")
     ap.add_argument("--reads", type=int, default=4_000_000)
+    ap.add_argument("--read-len", type=int, default=150, help="bases per read (10000 x 150000 reads: the long-read setting of profiles/line_items_ab.txt)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--k", type=int, default=21)
@@ -71,7 +72,7 @@ def main():
         for n in args.names:
             lib = ROOT / "auriclass_amd" / "lib" / "libmhx.so" if n == "base" else ROOT / "auriclass_amd" / "lib_variants" / f"{n}.so"
             env = dict(os.environ, MHX_LIB=str(lib))
-            cmd = [sys.executable, __file__, "--child", "--reads", str(args.reads), "--iters", str(args.iters), "--k", str(args.k),
+            cmd = [sys.executable, __file__, "--child", "--reads", str(args.reads), "--read-len", str(args.read_len), "--iters", str(args.iters), "--k", str(args.k),
                    "--s", str(args.s), "--m", str(args.m)] + (["--parity"] if rd == 0 else [])
             # nothing more is started on a GPU that a run may have faulted or hung: the failure is looked into first
             try:
