@@ -1,4 +1,4 @@
-"""`python -m auriclass_amd.contain [-w] [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: which share of
+"""`python -m auriclass_amd.contain [-w | -n TOP [-c MIN_SHARED]] [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: which share of
 each reference sketch of REF.msh every query sketch holds, from the sketch files alone (engine.contain_files).  One row per
 (query, reference): reference, query, identity, p-value, shared/n_ref, shared/n_qry -- within the window in which both
 sketches are complete, n_ref hashes of the reference and n_qry of the query lie, `shared` of them in both.  A sample that
@@ -9,7 +9,12 @@ sequence file is refused with the hint to sketch it first.  Exit status 1 with t
 -w: winner-take-all.  Every hash a query shares with the reference set is credited to one reference -- the one with the
 greatest shared/n_ref for that query, then the greatest genome length, then the first in the file -- and the rows show what
 each reference won in the place of `shared`, in all four columns; -i and -v filter on those values.  The members of a clade
-then no longer repeat one another's row."""
+then no longer repeat one another's row.
+-n TOP (1 .. 64): per query only the TOP references it holds the largest share of, ranked on the device -- by shared/n_ref
+exactly, then the larger `shared`, then the order in REF.msh -- best first; a query without hits prints nothing.  -i and -c
+(a hit shares at least MIN_SHARED hashes, default 1: a one-hash reference inside a tiny window reaches 1/1) say what a hit
+is and act before the cut; -v drops rows from the result already chosen and promotes none.  Not with -w, whose ranking is
+per hash, not per pair; -c needs -n."""
 from __future__ import annotations
 
 import argparse
@@ -24,6 +29,8 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("-i", dest="min_identity", type=float, default=0.0, help="minimum identity to report [0]")
     ap.add_argument("-v", dest="max_p_value", type=float, default=1.0, help="maximum p-value to report [1]")
     ap.add_argument("-w", dest="winner", action="store_true", help="winner-take-all: credit each shared hash to its best reference")
+    ap.add_argument("-n", dest="top", type=int, default=None, help="per query only the TOP (1 .. 64) best references, ranked by shared/n_ref")
+    ap.add_argument("-c", dest="min_shared", type=int, default=None, help="with -n: a hit shares at least this many hashes [1]")
     ap.add_argument("-C", dest="comment", action="store_true", help="show comment fields in place of the names")
     ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
     ap.add_argument("reference", metavar="REF.msh")
@@ -36,9 +43,23 @@ def main(argv: List[str] = None) -> int:
         if not str(path).endswith(".msh"):
             sys.stderr.write(f"ERROR: contain takes sketch files only; sketch {path} first (mash sketch [-i] -o <out> ...) and pass the .msh\n")
             return 1
+    if args.top is not None and args.winner:
+        sys.stderr.write("ERROR: contain -n ranks pairs and -w credits every hash to one reference: not both\n")
+        return 1
+    if args.min_shared is not None and args.top is None:
+        sys.stderr.write("ERROR: contain -c (minimum shared hashes of a hit) needs -n\n")
+        return 1
+    if args.top is not None and not 1 <= args.top <= 64:
+        sys.stderr.write("ERROR: contain -n: top must be 1 .. 64\n")
+        return 1
+    if args.min_shared is not None and args.min_shared < 1:
+        sys.stderr.write("ERROR: contain -c: a hit shares at least 1 hash\n")
+        return 1
+    more = {"winner": True} if args.winner else {}
+    if args.top is not None:
+        more = {"top": args.top, "min_shared": 1 if args.min_shared is None else args.min_shared}
     try:
-        text = engine.contain_files(args.reference, args.queries, min_identity=args.min_identity, max_p_value=args.max_p_value, comment=args.comment,
-                                    **({"winner": True} if args.winner else {}))
+        text = engine.contain_files(args.reference, args.queries, min_identity=args.min_identity, max_p_value=args.max_p_value, comment=args.comment, **more)
     except engine.EngineError as exc:
         sys.stderr.write(exc.message + "\n")
         return 1

@@ -23,7 +23,8 @@ __global__ __launch_bounds__(256) void contain_bounds_kernel(const ContainArgs a
 
 // 16 pairs per workgroup, the layout of dist_finish_kernel: thread (seg, pair) sums the byte counters of its R / 16 ranges
 // below the range of tau, then the 16 threads of segment 0 add the sums and walk the two slices of that range up to tau
-// (contain_finish_walk).  Nothing block-local is written: the three counts go to their place in the call's outputs.
+// (contain_finish_walk).  The three counts go to their place in the call's outputs, or, for the containment search, into its
+// block-local arrays (ContainArgs: out_base).
 __global__ __launch_bounds__(256) void contain_finish_kernel(const ContainArgs a, const DistWork w)
 {
     __shared__ uint32_t seg_shared[kDistSegs][16];
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void contain_finish_kernel(const ContainArgs a
     if (seg != 0 || !live) return;
     uint32_t shared, n_qry, n_ref;
     contain_finish_walk(x, &seg_shared[0][pl], 16, p_tau, tau, shared, n_qry, n_ref);
-    const uint64_t out = (uint64_t)qi * a.out_stride + ri;
+    const uint64_t out = (uint64_t)qi * a.out_stride + ri - a.out_base;
     a.shared[out] = shared;
     a.n_qry[out] = n_qry;
     a.n_ref[out] = n_ref;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(kContainPairThreads) void contain_pairs_kernel(cons
     uint32_t shared = 0;
     block_scan_excl<(int)kContainPairThreads>(c, wave_c, shared);
     if (threadIdx.x == 0) {
-        const uint64_t out = (uint64_t)qi * a.out_stride + ri;
+        const uint64_t out = (uint64_t)qi * a.out_stride + ri - a.out_base;
         a.shared[out] = shared;
         a.n_qry[out] = nB;
         a.n_ref[out] = nA;

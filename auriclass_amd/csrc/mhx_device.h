@@ -378,7 +378,9 @@ hipError_t launch_search_dist(const SearchOut &o, hipStream_t st);
 // containment of the references in the queries (rules: mhx_contain.h, kernels: mhx_contain.hip).  The two sets have a sketch
 // size each; eff / bound [lists] are written once per call by launch_contain_bounds and read by the other two, and the
 // passes of mhx_dist.hip that the range route reuses take eff for their lengths.  Results go straight to [q][r] of the
-// call's outputs, `out_stride` (the call's nr) words per query.
+// call's outputs, `out_stride` (the call's nr) words per query: cell (q, r) is q * out_stride + r - out_base.  out_base is zero
+// in mhx_dist_contain; the containment search sets out_stride = 32 and out_base = q0 * 32 + r0, which makes the outputs the
+// block-local [bnq][32] arrays its take-out pass reads.
 struct ContainArgs {
     const uint64_t *q, *r;           // [.][stride] the rows of the call
     const uint32_t *q_len, *r_len;   // as the caller gave them (launch_contain_bounds only)
@@ -389,6 +391,7 @@ struct ContainArgs {
     const uint32_t *shift;           // range route: the word that holds the call's shift
     uint32_t *shared, *n_qry, *n_ref;
     uint32_t out_stride;
+    uint64_t out_base;               // taken off every cell index (finish pass and pair kernel); zero: the call's [nq][nr]
 };
 hipError_t launch_contain_bounds(const ContainArgs &a, hipStream_t st);
 // the finish pass of one block over w (offsets of the block's lists, byte counters, w.params[1] the block's flag: non-zero,
@@ -411,5 +414,21 @@ struct ContainWinnerArgs {
 hipError_t launch_contain_claim(const ContainArgs &a, const ContainWinnerArgs &w, hipStream_t st);
 // the tally: one thread per word of the batch
 hipError_t launch_contain_tally(const ContainArgs &a, const ContainWinnerArgs &w, hipStream_t st);
+
+// containment search (rules: mhx_contain_search.h, kernel: mhx_contain_search.hip).  A block's three counts lie block-local,
+// [queries of the block][32]; every query of the call has a best list of at most `top` hits, best first, in hit_ref /
+// hit_shared / hit_n_ref / hit_n_qry [queries][top] with its length in n_hits [queries] (zero before the first block), which
+// the take-out pass of every block merges into.  need [need_limit + 1]: the hit test, shared >= need[n_ref].
+struct ContainSearchOut {
+    const uint32_t *loc_shared, *loc_n_qry, *loc_n_ref;
+    const uint32_t *flag;    // non-zero: nothing is done
+    uint32_t r0, nr, q0, nq; // the block (mhx_search.h: SearchBlock); q0 counts from the call's first query
+    uint32_t top;
+    const uint32_t *need;
+    uint32_t need_limit;
+    uint32_t *hit_ref, *hit_shared, *hit_n_ref, *hit_n_qry;
+    uint32_t *n_hits;
+};
+hipError_t launch_contain_take(const ContainSearchOut &o, hipStream_t st);
 
 } // namespace mhx

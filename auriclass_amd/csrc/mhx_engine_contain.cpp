@@ -19,6 +19,20 @@
 
 using namespace mhx;
 
+namespace mhx {
+// The geometry of the range route: the search's (tri_ranges, 16 entries per slice) up to kDistRanges, and kDistRanges itself
+// as far as the base form of the distance path goes (65 536 entries).  Longer lists have none here: the windowed form is
+// not built, the pair kernel takes them.  MHX_SEARCH_GEOMETRY=dist takes kDistRanges from the first entry on, as the search.
+// (The containment search, mhx_engine_contain_search.cpp, takes its geometry here too.)
+uint32_t contain_ranges(uint32_t longest)
+{
+    const char *geo = getenv("MHX_SEARCH_GEOMETRY");
+    const uint32_t R = geo && strcmp(geo, "dist") == 0 ? 0u : tri_ranges(longest);
+    if (R != 0 && R <= (uint32_t)kDistRanges) return R;
+    return dist_windows(longest) == 1 ? (uint32_t)kDistRanges : 0u;
+}
+} // namespace mhx
+
 namespace {
 
 struct ContainCall { // everything on the device
@@ -31,17 +45,6 @@ struct ContainCall { // everything on the device
 };
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// The geometry of the range route: the search's (tri_ranges, 16 entries per slice) up to kDistRanges, and kDistRanges itself
-// as far as the base form of the distance path goes (65 536 entries).  Longer lists have none here: the windowed form is
-// not built, the pair kernel takes them.  MHX_SEARCH_GEOMETRY=dist takes kDistRanges from the first entry on, as the search.
-uint32_t contain_ranges(uint32_t longest)
-{
-    const char *geo = getenv("MHX_SEARCH_GEOMETRY");
-    const uint32_t R = geo && strcmp(geo, "dist") == 0 ? 0u : tri_ranges(longest);
-    if (R != 0 && R <= (uint32_t)kDistRanges) return R;
-    return dist_windows(longest) == 1 ? (uint32_t)kDistRanges : 0u;
-}
 
 // Launches the whole call on the engine's stream and waits for it: the schedule of search_device (mhx_engine_search.cpp)
 // without its block-local arrays and its take-out pass.

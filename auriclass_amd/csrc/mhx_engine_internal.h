@@ -133,6 +133,11 @@ struct Engine {
     int last_dist_fallbacks = 0;
     uint64_t last_contain_winner_pairs = 0; // pairs the claim pass of the last mhx_dist_contain_winner call walked
     int last_dist_ranges = 0;    // value ranges per block of the last distance call (0: generic kernel only)
+    // the need table of the last containment search (mhx_engine_contain_search.cpp: need_table), on the host, and what it was built from
+    std::vector<uint32_t> contain_need;
+    int contain_need_k = 0;
+    double contain_need_min_identity = 0.0;
+    uint32_t contain_need_min_shared = 0;
     int last_mst_rounds = 0;     // Boruvka rounds of the last mhx_dist_mst call
     int last_mst_stored = -1;    // its pair source: 1 stored, 0 recomputed, -1 none ran
     int last_linkage_rescans = 0; // rows scanned again in the steps of the last mhx_dist_linkage call
@@ -188,6 +193,14 @@ int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t n
 int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *const *r_rows,
                  const uint64_t *r, const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref,
                  const uint64_t *ref_length = nullptr, uint32_t *won = nullptr);
+// the geometry of the containment's range route for lists of up to `longest` entries (0: none, the pair kernel takes the call)
+uint32_t contain_ranges(uint32_t longest);
+// Containment search (mhx_engine_contain_search.cpp) of host queries, every row where it lies (q_len[i] <= refs.stride entries
+// each), against a reference set that the caller has put on the device (SearchRefs as for search_rows).  Outputs as the host
+// form of mhx_dist_contain_search.  What mhx_contain_files_search runs per batch of queries.
+int contain_search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const SearchRefs &refs, uint32_t s_r, int k,
+                        double min_identity, uint32_t min_shared, uint32_t top, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
+                        uint32_t *hit_n_qry, uint32_t *n_hits);
 // Jackknife support of search hits (mhx_engine_support.cpp) with everything on the device: what mhx_dist_support's device form
 // runs, and mhx_search_files_support on the rows its search has staged.  first [nq][top] is a device pointer; the rep_*
 // outputs (each may be null) are device pointers too, or host pointers with host_out.  Uses g.dist_ws, not g.dist_in.

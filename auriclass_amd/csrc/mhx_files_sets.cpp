@@ -1,7 +1,7 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
 // triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files, mhx_cluster_reps_files), the single-linkage tree (mhx_tree_files), complete
 // and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
-// (mhx_search_files) and the containment from sketches (mhx_contain_files).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
+// (mhx_search_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
 // of sequence files is in mhx_files.cpp.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
@@ -963,4 +963,100 @@ extern "C" int mhx_contain_files_winner(const char *ref_msh, const char *const *
                                         size_t *need)
 {
     return entry("mhx_contain_files_winner", [&]() -> int { return contain_files_text(ref_msh, qry_msh, n_qry, opts, true, stdout_buf, cap, need); });
+}
+
+// Containment search at file level: the reference file is read, checked and staged on the device ONCE, every list cut at the
+// reference sketch size; the query files are read one after the other and searched in batches of sketches
+// (contain_search_rows against the resident references), so that host memory holds one batch and at most top rows per query
+// whatever n_qry and the size of the reference set are.  Rows are mhx_contain_files's, per query best first.
+extern "C" int mhx_contain_files_search(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_search_opts *opts, char *stdout_buf,
+                                        size_t cap, size_t *need)
+{
+    return entry("mhx_contain_files_search", [&]() -> int {
+        mhx_contain_search_opts o{(uint32_t)sizeof(mhx_contain_search_opts), 0, 5, 1, 0.0, 1.0};
+        int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain_search", opts, o) : MHX_OK;
+        if (rc) return rc;
+        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "contain: a reference sketch path and at least one query sketch path required");
+        for (int i = 0; i < n_qry; ++i)
+            if (!qry_msh[i]) return fail(MHX_E_ARG, "contain: query sketch path %d is null", i);
+        if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
+        if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "contain: top must be 1 .. 64");
+        if (o.min_shared < 1) return fail(MHX_E_ARG, "contain: min_shared must be at least 1");
+        SketchSet R;
+        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        const int k = (int)R.kmer_size;
+        const uint32_t nr = (uint32_t)R.refs.size(), s_r = std::max<uint32_t>(1, R.sketch_size);
+        DevArray<uint64_t> d_rows;
+        DevArray<uint32_t> d_len;
+        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
+        uint32_t q_sketch_size = 0, s_q = 1;
+        std::string text;
+        constexpr size_t kBatch = 4096; // query sketches per device call
+        std::vector<SketchSet> held;    // the files of the current batch
+        std::vector<const RefSketch *> qs;
+        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call, cut at its set's sketch size
+            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)std::min<size_t>(r.hash_count(), s_r));
+            refs.stride = row_stride(std::max(refs.longest, s_q));
+            if (nr == 0) return MHX_OK;
+            std::vector<uint64_t> rows((size_t)nr * refs.stride, 0);
+            std::vector<uint32_t> len(nr);
+            for (uint32_t i = 0; i < nr; ++i) {
+                len[i] = (uint32_t)std::min<size_t>(R.refs[i].hash_count(), s_r);
+                if (len[i]) memcpy(&rows[(size_t)i * refs.stride], R.refs[i].hash_data(), (size_t)len[i] * 8);
+                std::vector<uint64_t>().swap(R.refs[i].hashes); // packed: names and lengths stay for the text
+            }
+            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the containment search");
+            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+            refs.rows = d_rows; refs.len = d_len;
+            return MHX_OK;
+        };
+        auto flush = [&]() -> int {
+            const uint32_t nq = (uint32_t)qs.size();
+            if (nq && nr) {
+                std::vector<const uint64_t *> qrows(nq);
+                std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hs((size_t)nq * o.top), hnr((size_t)nq * o.top), hnq((size_t)nq * o.top), nh(nq);
+                for (uint32_t i = 0; i < nq; ++i) { // a list is the first s_q entries of its sketch at most
+                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)std::min<size_t>(qs[i]->hash_count(), s_q);
+                }
+                const int rc2 = contain_search_rows(qrows.data(), ql.data(), nq, s_q, refs, s_r, k, o.min_identity, o.min_shared, o.top, hr.data(), hs.data(),
+                                                    hnr.data(), hnq.data(), nh.data());
+                if (rc2) return rc2;
+                for (uint32_t qi = 0; qi < nq; ++qi)
+                    for (uint32_t t = 0; t < nh[qi]; ++t) {
+                        const size_t p = (size_t)qi * o.top + t;
+                        const RefSketch &ref = R.refs[hr[p]];
+                        const double identity = mhx_screen_identity(hs[p], hnr[p], k);
+                        const double pv = mhx_screen_p_value(hs[p], hnr[p], (double)qs[qi]->length, k);
+                        if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
+                        text += (o.comment ? ref.comment : ref.name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) + "\t" +
+                                fmt_g(pv) + "\t" + std::to_string(hs[p]) + "/" + std::to_string(hnr[p]) + "\t" + std::to_string(hs[p]) + "/" +
+                                std::to_string(hnq[p]) + "\n";
+                    }
+            }
+            qs.clear();
+            held.clear();
+            return MHX_OK;
+        };
+        for (int i = 0; i < n_qry; ++i) {
+            held.emplace_back();
+            SketchSet &Q = held.back();
+            rc = msh_read_file(qry_msh[i], Q);
+            if (rc) return rc;
+            if (i == 0) q_sketch_size = Q.sketch_size;
+            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+            if (rc) return rc;
+            if (i == 0) {
+                s_q = std::max<uint32_t>(1, q_sketch_size);
+                rc = stage_refs();
+                if (rc) return rc;
+            }
+            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+        }
+        rc = flush();
+        if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
+    });
 }

@@ -227,6 +227,12 @@ def load() -> ctypes.CDLL:
                                               c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_last_contain_winner_pairs.restype = c.c_uint64
         L.mhx_contain_files_winner.argtypes = L.mhx_contain_files.argtypes
+    if hasattr(L, "mhx_dist_contain_search"):   # (or older than the containment search)
+        L.mhx_dist_contain_search.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32,
+                                              c.c_int, c.c_double, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                              c.c_int]
+        L.mhx_contain_files_search.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ContainSearchOpts), c.c_char_p, c.c_size_t,
+                                               c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -401,18 +407,39 @@ class ContainOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("min_identity", ctypes.c_double), ("max_p_value", ctypes.c_double)]
 
 
+def _count(v) -> int:
+    """`top` / `min_shared` on their way into an unsigned word of the library, which refuses 0: a negative value goes in as 0 and
+    is refused with it, where as it is it would wrap to a large count; one beyond 32 bits stays as large as a word gets"""
+    return min(max(int(v), 0), 0xFFFFFFFF)
+
+
+class ContainSearchOpts(ctypes.Structure):
+    """mhx_contain_search_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("top", ctypes.c_uint32), ("min_shared", ctypes.c_uint32),
+                ("min_identity", ctypes.c_double), ("max_p_value", ctypes.c_double)]
+
+
 def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p_value: float = 1.0, comment: bool = False,
-                  winner: bool = False) -> str:
+                  winner: bool = False, top=None, min_shared: int = 1) -> str:
     """Which share of each reference sketch of REF.msh every query sketch holds, from the sketches alone (mhx_contain_files):
     one row "reference\\tquery\\tidentity\\tp-value\\tshared/n_ref\\tshared/n_qry" per (query, reference), the queries in
     argument then file order, the references in file order.  The sketch size of REF.msh may differ from the queries'.
     min_identity and max_p_value drop rows; comment prints the comment fields in place of the names.
     winner: winner-take-all rows (mhx_contain_files_winner) -- every shared hash is credited to the best-ranked reference it
     was found in (ratio, then the genome length of REF.msh's length fields, then file order), and what a reference won
-    stands in the place of `shared` in every column and in both filters."""
+    stands in the place of `shared` in every column and in both filters.
+    top = 1 .. 64 (mhx_contain_files_search): per query only the `top` references it holds the largest share of, ranked on the
+    device (share, then `shared`, then file order), best first; min_identity and min_shared (>= 1) say what a hit is and act
+    before the cut, max_p_value drops rows from the result already chosen.  Not with `winner`.  top=None: the full table."""
     init()
     files = [os.fsencode(str(p)) for p in qry_paths]
     arr = (ctypes.c_char_p * len(files))(*files)
+    if top is not None:
+        if winner:
+            raise EngineError(MHX_E_ARG, "contain: top ranks pairs, the winner-take-all form ranks per hash: not both")
+        sopts = ContainSearchOpts(ctypes.sizeof(ContainSearchOpts), int(bool(comment)), _count(top), _count(min_shared), float(min_identity), float(max_p_value))
+        return _text_call(lambda buf, cap, need: load().mhx_contain_files_search(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(sopts), buf,
+                                                                                 cap, need), guess=1 << 20)
     opts = ContainOpts(ctypes.sizeof(ContainOpts), int(bool(comment)), float(min_identity), float(max_p_value))
     if winner:
         return _text_call(lambda buf, cap, need: load().mhx_contain_files_winner(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts),
@@ -1410,6 +1437,43 @@ def dist_contain_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: in
     v = ctypes.c_void_p
     _check(load().mhx_dist_contain(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, v(shared_ptr), v(n_qry_ptr),
                                    v(n_ref_ptr), 1))
+    return load().mhx_last_dist_kernel_ms()
+
+
+def dist_contain_search(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int, k: int, top: int,
+                        min_identity: float = 0.0, min_shared: int = 1
+                        ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """For every query list the `top` (1 .. 64) references it holds the largest share of (mhx_dist_contain_search), ranked on the
+    device by the exact share shared / n_ref (ties: the larger `shared`, then the lower reference index): (hit_ref, hit_shared,
+    hit_n_ref, hit_n_qry) of shape [nq, top], best first and zero behind n_hits [nq].  The integers of a pair are
+    dist_contain's; a hit shares at least min_shared (>= 1) hashes and has identity(shared, n_ref, k) >= min_identity.  Rows
+    and lengths as dist_contain takes them; no [nq, nr] array exists anywhere."""
+    init()
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    cells = (nq, min(_count(top), 64))   # (a top the library refuses is refused before it writes)
+    ref, shared, n_ref, n_qry =(np.zeros(cells, dtype=np.uint32) for _ in range(4))
+    n_hits = np.zeros(nq, dtype=np.uint32)
+    _check(load().mhx_dist_contain_search(q.ctypes.data, q_len.ctypes.data, nq, int(s_q), r.ctypes.data, r_len.ctypes.data, nr, int(s_r), stride, int(k),
+                                          float(min_identity), _count(min_shared), _count(top), ref.ctypes.data, shared.ctypes.data, n_ref.ctypes.data,
+                                          n_qry.ctypes.data, n_hits.ctypes.data, 0))
+    return ref, shared, n_ref, n_qry, n_hits
+
+
+def dist_contain_search_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: int, r_len_ptr: int, nr: int, s_r: int, stride: int, k: int,
+                               top: int, min_identity: float, min_shared: int, ref_ptr: int, shared_ptr: int, n_ref_ptr: int, n_qry_ptr: int,
+                               n_hits_ptr: int) -> float:
+    """Device pointers in and out ([nq, top] lists and n_hits [nq]; a sketch_segments_device result goes straight in on either
+    side): the same lists as dist_contain_search, exact, entries behind n_hits unspecified.  Lengths the host cannot see are
+    clipped to the stride and the sketch size.  Returns the kernel time in ms."""
+    init()
+    v = ctypes.c_void_p
+    _check(load().mhx_dist_contain_search(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, int(k), float(min_identity),
+                                          _count(min_shared), _count(top), v(ref_ptr), v(shared_ptr), v(n_ref_ptr), v(n_qry_ptr), v(n_hits_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
 
 

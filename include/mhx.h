@@ -27,6 +27,9 @@
  *   mhx_contain_files_winner <- no mash command, `mash screen -w` for two sketch files: every shared hash credited to its best
  *                        reference, so that the members of a clade stop repeating one another's row (python -m
  *                        auriclass_amd.contain -w; buffer level: mhx_dist_contain_winner)
+ *   mhx_contain_files_search <- no mash command: mhx_contain_files followed by a sort per query, for a reference set too
+ *                        large to print in full -- per query sketch the `top` references it holds the largest share of
+ *                        (python -m auriclass_amd.contain -n TOP; buffer level: mhx_dist_contain_search)
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
@@ -810,8 +813,8 @@ int mhx_search_files_support(const char *ref_msh, const char *const *qry_msh, in
  * report this call too.
  * Not pinned by mash output (mash has no such command): pinned by the restated rule.
  * Not built: the windowed range form (more than 1024 ranges; such lists go to the pair kernel), max-containment and the
- * query-in-reference identity as columns, a containment column in AuriClass's report.tsv (needs calibration), a top-N
- * ranking by containment. */
+ * query-in-reference identity as columns, a containment column in AuriClass's report.tsv (needs calibration).  (The ranked
+ * form, a few best references per query in the place of the full table, is mhx_dist_contain_search below.) */
 int mhx_dist_contain(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r, const uint32_t *r_len,
                      uint32_t nr, uint32_t s_r, uint32_t stride, uint32_t *shared, uint32_t *n_qry, uint32_t *n_ref, int device_ptrs);
 /* The same at file level: one row per (query sketch, reference sketch), the queries in argument order and then file order,
@@ -866,6 +869,57 @@ uint64_t mhx_last_contain_winner_pairs(void);
  * length field of every reference sketch of ref_msh.  The query files go to the device in batches of 4096 sketches; a
  * query's winners depend on that query alone. */
 int mhx_contain_files_winner(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_opts *opts,
+                             char *stdout_buf, size_t cap, size_t *need);
+
+/* CONTAINMENT SEARCH: for every query the `top` (1 .. 64) references it holds the largest share of, ranked on the device --
+ * "which of 100 000 known plasmids, marker loci or genomes is IN this sample?" without the [nq][nr] table of
+ * mhx_dist_contain.  The Jaccard search (mhx_dist_search) cannot stand in: a plasmid inside a genome has an index near 0 and
+ * a containment of 1.  The rule (auriclass_amd/csrc/mhx_contain_search.h, restated in tests/contain_search_rule.py):
+ *   candidate(q, r) = (r, shared, n_ref, n_qry), the three integers of mhx_dist_contain for that pair (s_q, s_r: as there)
+ *   hit             = shared >= min_shared (>= 1: a pair that shares nothing is never a hit, nor one with n_ref == 0), and
+ *                     identity(shared, n_ref, k) >= min_identity, the identity as mhx_contain_files prints it: 1 when
+ *                     shared == n_ref, otherwise (shared / n_ref)^(1/k) in host libm doubles.  min_identity > 1: no hits.
+ *                     min_shared is there because a one-hash reference inside a tiny window reaches 1/1.
+ *   rank            = the larger shared / n_ref first, compared exactly as a 64-bit cross product; on equal shares the
+ *                     larger `shared` (200/200 before 3/3); on equal `shared` the lower reference index.  A total order.
+ *   result          = per query the first min(top, hits) hits in rank order
+ * Outputs hit_ref / hit_shared / hit_n_ref / hit_n_qry [nq][top], query-major, best first, and n_hits [nq].  Host form:
+ * entries behind n_hits[q] are zero; device form (device_ptrs != 0: every pointer is a device pointer, a result of
+ * mhx_sketch_segments goes straight in on either side): they are unspecified.  The result is exact and identical in both
+ * forms and from run to run: the host turns the identity bound into a table of integers with its own libm, need[n] = the
+ * least `shared` that is a hit at n_ref = n (n + 1: none) for n = 0 .. min(stride, s_r), and the device only tests
+ * shared >= need[n_ref] (as mhx_dist_cluster's distance bound; unlike mhx_dist_search, whose device form is prefiltered only).
+ * nq == 0: MHX_OK; nr == 0: MHX_OK and n_hits zeroed.  MHX_E_ARG: top outside 1 .. 64, min_shared == 0, min_identity not a
+ * number, k outside 1 .. 32, s_q, s_r or stride zero, a null pointer, and in the host form a len > stride; the device form
+ * clips the lengths as mhx_dist_contain does.
+ * On the device: the schedule of mhx_dist_contain -- bounds, one split of both sets, (query batch,
+ * reference slice) blocks, the range pass, flags read back per group of 4096 blocks -- with the finish pass writing a block's
+ * [queries][32] counts block-local and a take-out pass behind every block: one wave64 per query, lane i holding entry i of
+ * the query's best list, no atomics.  A flagged block is redone by the pair kernel and taken out then; the total order makes
+ * the late arrival harmless.  Tiny calls, MHX_DIST_GENERIC and lists above 65 536 entries go through the pair kernel per
+ * block with the same take-out.  Nothing of size nq x nr exists anywhere.  MHX_SEARCH_GEOMETRY and MHX_SEARCH_QBATCH are
+ * honoured; mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report this call too.
+ * Not pinned by mash output (mash has no such command): pinned by the restated rule.
+ * Not built: more than 64 hits per query, the ranking for the winner-take-all form, and what mhx_dist_contain lists. */
+int mhx_dist_contain_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r,
+                            const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, int k, double min_identity,
+                            uint32_t min_shared, uint32_t top, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
+                            uint32_t *hit_n_qry, uint32_t *n_hits, int device_ptrs);
+/* The same at file level: for every query sketch, in argument order and then file order, its result as mhx_contain_files
+ * rows, best first; the p-value is mhx_screen_p_value at the query's length field.  Rows with p > max_p_value are dropped
+ * from the result already chosen -- nothing moves up into their place (mhx_search_files' rule) -- while min_identity and
+ * min_shared act before the cut.  A query without hits prints nothing.  opts == NULL means {sizeof, 0, 5, 1, 0, 1}.  Checks
+ * and messages are mhx_contain_files's, and top outside 1 .. 64 or min_shared == 0 is MHX_E_ARG.  The reference file is read
+ * and staged on the device once; the query files go there in batches of 4096 sketches. */
+typedef struct mhx_contain_search_opts {
+    uint32_t struct_size; /* sizeof(mhx_contain_search_opts) */
+    int32_t comment;      /* comment fields in place of names */
+    uint32_t top;         /* hits per query, 1 .. 64 */
+    uint32_t min_shared;  /* a hit shares at least this many hashes, >= 1 */
+    double min_identity;  /* a hit has identity >= min_identity (0: all) */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+} mhx_contain_search_opts;
+int mhx_contain_files_search(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_search_opts *opts,
                              char *stdout_buf, size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
