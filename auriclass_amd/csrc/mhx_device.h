@@ -375,6 +375,41 @@ hipError_t launch_search_take(const SearchOut &o, hipStream_t st);
 // tri_distance of the o.nq lists from query o.q0 on into hit_dist (entries behind n_hits are left alone)
 hipError_t launch_search_dist(const SearchOut &o, hipStream_t st);
 
+// all references within a distance of each query, as CSR (rules: mhx_within.h, kernels: mhx_within.hip).  A block's results
+// lie block-local as above; the queries of a super-batch have one cell per slice of 32 references in mask / base
+// [queries][nslices], which the take-out pass of every block fills: the ballot of the exact integer rule, and where the
+// cell's keepers begin in the arrival list arr_common / arr_denom [room] (appended through *count, zero before the first
+// block of the super-batch; at or beyond room they are only counted).  base null: the counting form, no list.
+struct WithinOut {
+    const uint32_t *loc_common, *loc_denom;
+    const uint32_t *flag;    // non-zero: nothing is done
+    uint32_t r0, nr, q0, nq; // the block (mhx_search.h: SearchBlock); q0 counts from the super-batch's first query
+    const uint32_t *cmin;    // [s + 1] the bound as integers: a pair is a hit iff common >= cmin[denom]
+    uint32_t s, nslices;
+    uint32_t *mask, *base;
+    uint32_t *arr_common, *arr_denom;
+    uint32_t room;
+    uint32_t *count;
+};
+hipError_t launch_within_take(const WithinOut &o, hipStream_t st);
+// Behind the last block and the last fallback of a super-batch of nq queries.  row_off points at the entry of its first
+// query, which holds the hits of all queries before it (0 for the first super-batch of a call).
+struct WithinRows {
+    const uint32_t *mask, *base;
+    uint32_t nq, nslices;
+    uint64_t *row_off;       // [nq + 1]
+    const uint32_t *arr_common, *arr_denom;
+    uint32_t room;
+    uint32_t *hit_ref, *hit_common, *hit_denom; // [cap] of the call
+    double *hit_dist;        // may be null
+    uint64_t cap;
+    int k;
+};
+// row_off[1 .. nq]: the scan of the set bits of every query's cells, on top of row_off[0]
+hipError_t launch_within_scan(const WithinRows &o, hipStream_t st);
+// every cell's keepers from the arrival list to their final place (mhx_within.h: within_dest); places at or beyond cap are left out
+hipError_t launch_within_gather(const WithinRows &o, hipStream_t st);
+
 // containment of the references in the queries (rules: mhx_contain.h, kernels: mhx_contain.hip).  The two sets have a sketch
 // size each; eff / bound [lists] are written once per call by launch_contain_bounds and read by the other two, and the
 // passes of mhx_dist.hip that the range route reuses take eff for their lengths.  Results go straight to [q][r] of the

@@ -138,6 +138,13 @@ struct Engine {
     int contain_need_k = 0;
     double contain_need_min_identity = 0.0;
     uint32_t contain_need_min_shared = 0;
+    // mhx_dist_within (mhx_engine_within.cpp): the cells of a super-batch of queries (mask and base, at most kWithinCells words
+    // each), its arrival counter and its arrival list; and the cmin table of the last bound on the device with what it was built from
+    DevArray<uint8_t> within_ws;
+    DevArray<uint32_t> within_cmin;
+    uint32_t within_cmin_s = 0;
+    int within_cmin_k = 0;
+    double within_cmin_max_dist = 0.0;
     int last_mst_rounds = 0;     // Boruvka rounds of the last mhx_dist_mst call
     int last_mst_stored = -1;    // its pair source: 1 stored, 0 recomputed, -1 none ran
     int last_linkage_rescans = 0; // rows scanned again in the steps of the last mhx_dist_linkage call
@@ -186,6 +193,11 @@ struct SearchStaged { const uint64_t *q; const uint32_t *q_len; };
 int search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
                 uint32_t top, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits,
                 SearchStaged *staged = nullptr);
+// All references within max_dist (mhx_engine_within.cpp) of host queries, every row where it lies, against a reference set
+// that the caller has put on the device (SearchRefs as for search_rows).  Outputs as the host form of mhx_dist_within, the
+// capacity protocol included.  What mhx_within_files runs per batch of queries.
+int within_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, const SearchRefs &refs, int k, uint32_t s, double max_dist,
+                uint64_t *row_off, uint32_t *hit_ref, uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint64_t cap, uint64_t *n_out);
 // Containment (mhx_engine_contain.cpp) of host lists, every row where it lies (q_rows / r_rows: len entries each) or, with the
 // row pointers null, as the matrices q / r [.][stride]; host outputs [nq][nr].  What mhx_dist_contain's host form and
 // mhx_contain_files run.  With `won` (host, [nq][nr]) the winner-take-all passes run behind the plain one, ref_length ([nr] genome

@@ -1,7 +1,7 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
 // triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files, mhx_cluster_reps_files), the single-linkage tree (mhx_tree_files), complete
 // and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
-// (mhx_search_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
+// (mhx_search_files), the bounded neighbourhood (mhx_within_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
 // of sequence files is in mhx_files.cpp.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mhx_triangle.h"
+#include "mhx_within.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
 
@@ -850,6 +851,116 @@ extern "C" int mhx_search_files(const char *ref_msh, const char *const *qry_msh,
         if (rc == MHX_OK) rc = search_files_check("search", ref_msh, qry_msh, n_qry, o);
         if (rc) return rc;
         return search_files_text(ref_msh, qry_msh, n_qry, o, nullptr, 0, nullptr, stdout_buf, cap, need);
+    });
+}
+
+// `mash dist -d D -v P REF QUERY [QUERY ...]`: every reference within D of every query sketch.  The reference file is read,
+// checked and staged on the device once, as the search does; the query files are read one after the other and go to
+// within_rows in batches of sketches, whose CSR the host prints row by row -- in reference order, or every row of the CSR
+// sorted best first by search_better.  A batch whose hits exceed its buffers is repeated once with the size it reported.
+extern "C" int mhx_within_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_within_opts *opts, char *stdout_buf, size_t cap, size_t *need)
+{
+    return entry("mhx_within_files", [&]() -> int {
+        mhx_within_opts o{(uint32_t)sizeof(mhx_within_opts), 0, 1.0, 1.0};
+        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "within: a reference sketch path and at least one query sketch path required");
+        for (int i = 0; i < n_qry; ++i)
+            if (!qry_msh[i]) return fail(MHX_E_ARG, "within: query sketch path %d is null", i);
+        int rc = take_opts("within", opts, o);
+        if (rc) return rc;
+        if (o.order > 1) return fail(MHX_E_ARG, "within: order must be 0 (reference order) or 1 (best first)");
+        if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "within: max_dist / max_p_value is not a number");
+        SketchSet R;
+        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        const int k = (int)R.kmer_size;
+        const uint32_t nr = (uint32_t)R.refs.size();
+        DevArray<uint64_t> d_rows;
+        DevArray<uint32_t> d_len;
+        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
+        uint32_t q_sketch_size = 0, s = 0;
+        std::string text;
+        constexpr size_t kBatch = 4096; // query sketches per device call
+        constexpr uint64_t kFirstRoom = 4096; // hits the buffers hold before a batch has asked for more
+        std::vector<SketchSet> held;    // the files of the current batch
+        std::vector<const RefSketch *> qs;
+        std::vector<uint32_t> hr, hc, hd, order;
+        std::vector<double> hx;
+        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
+            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
+            refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
+            if (nr == 0) return MHX_OK;
+            std::vector<const RefSketch *> lists;
+            for (const RefSketch &r : R.refs) lists.push_back(&r);
+            std::vector<uint64_t> rows;
+            std::vector<uint32_t> len;
+            pack_rows(lists, refs.stride, rows, len);
+            for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
+            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of within");
+            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+            refs.rows = d_rows; refs.len = d_len;
+            return MHX_OK;
+        };
+        auto flush = [&]() -> int {
+            const uint32_t nq = (uint32_t)qs.size();
+            if (nq && nr) {
+                std::vector<const uint64_t *> qrows(nq);
+                std::vector<uint32_t> ql(nq);
+                std::vector<uint64_t> row_off((size_t)nq + 1);
+                for (uint32_t i = 0; i < nq; ++i) {
+                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                    if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
+                }
+                uint64_t found = 0, room = std::max<uint64_t>(hr.size(), std::min<uint64_t>((uint64_t)nq * nr, kFirstRoom));
+                int rc2 = MHX_OK;
+                for (int attempt = 0; attempt < 2; ++attempt) {
+                    if (hr.size() < room) { hr.resize(room); hc.resize(room); hd.resize(room); hx.resize(room); }
+                    rc2 = within_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, row_off.data(), hr.data(), hc.data(), hd.data(), hx.data(), hr.size(), &found);
+                    if (rc2 != MHX_E_CAPACITY) break;
+                    room = found;
+                }
+                if (rc2) return rc2;
+                clear_error();
+                for (uint32_t qi = 0; qi < nq; ++qi) {
+                    const uint64_t lo = row_off[qi], hi = row_off[qi + 1];
+                    order.resize((size_t)(hi - lo));
+                    for (uint64_t t = lo; t < hi; ++t) order[(size_t)(t - lo)] = (uint32_t)(t - lo);
+                    if (o.order == 1)
+                        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+                            return search_better(SearchHit{hr[lo + a], hc[lo + a], hd[lo + a]}, SearchHit{hr[lo + b], hc[lo + b], hd[lo + b]});
+                        });
+                    for (const uint32_t t : order) {
+                        const size_t p = (size_t)(lo + t);
+                        const RefSketch &ref = R.refs[hr[p]];
+                        const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                        if (!(pv <= o.max_p_value)) continue;
+                        pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p]);
+                    }
+                }
+            }
+            qs.clear();
+            held.clear();
+            return MHX_OK;
+        };
+        for (int i = 0; i < n_qry; ++i) {
+            held.emplace_back();
+            SketchSet &Q = held.back();
+            rc = msh_read_file(qry_msh[i], Q);
+            if (rc) return rc;
+            if (i == 0) q_sketch_size = Q.sketch_size;
+            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+            if (rc) return rc;
+            if (i == 0) {
+                s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+                rc = stage_refs();
+                if (rc) return rc;
+            }
+            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
+        }
+        rc = flush();
+        if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
     });
 }
 

@@ -211,6 +211,11 @@ def load() -> ctypes.CDLL:
                                       c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int]
         L.mhx_search_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(SearchOpts), c.c_char_p, c.c_size_t,
                                        c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_within"):   # (or older than the bounded neighbourhood call)
+        L.mhx_dist_within.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_int, c.c_uint32,
+                                      c.c_double, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, u64p, c.c_int]
+        L.mhx_within_files.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(WithinOpts), c.c_char_p, c.c_size_t,
+                                       c.POINTER(c.c_size_t)]
     if hasattr(L, "mhx_dist_support"):   # (or older than the jackknife support of search hits)
         L.mhx_dist_support.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32, c.c_void_p,
                                        c.c_void_p, c.c_uint32, c.c_uint32, c.c_double, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
@@ -399,6 +404,24 @@ def search_files(ref_msh, qry_paths: Sequence, top: int = 5, max_dist: float = 1
                                                                                  buf, cap, need), guess=1 << 20)
     opts = SearchOpts(ctypes.sizeof(SearchOpts), int(top), float(max_dist), float(max_p_value))
     return _text_call(lambda buf, cap, need: load().mhx_search_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
+                                                                     need), guess=1 << 20)
+
+
+class WithinOpts(ctypes.Structure):
+    """mhx_within_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("order", ctypes.c_uint32), ("max_dist", ctypes.c_double), ("max_p_value", ctypes.c_double)]
+
+
+def within_files(ref_msh, qry_paths: Sequence, max_dist: float, max_p_value: float = 1.0, order: int = 0) -> str:
+    """`mash dist -d max_dist -v max_p_value REF QUERY [QUERY ...]` stdout: for every query sketch of the files, in argument order
+    and then file order, EVERY reference of REF.msh with distance <= max_dist and p <= max_p_value as a `mash dist` row
+    "ref\\tquery\\tdist\\tp\\tcommon/denom" -- no cap on the hits of a query; a query without hits prints nothing.  order 0: the
+    hits of a query in reference order (what mash prints); order 1: best first, the order of search_files."""
+    init()
+    files = [os.fsencode(str(p)) for p in qry_paths]
+    arr = (ctypes.c_char_p * len(files))(*files)
+    opts = WithinOpts(ctypes.sizeof(WithinOpts), int(order), float(max_dist), float(max_p_value))
+    return _text_call(lambda buf, cap, need: load().mhx_within_files(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(opts), buf, cap,
                                                                      need), guess=1 << 20)
 
 
@@ -1407,6 +1430,66 @@ def dist_search_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_pt
     _check(load().mhx_dist_search(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s, float(max_dist), int(top), v(ref_ptr),
                                   v(common_ptr), v(denom_ptr), v(dist_ptr or None), v(n_hits_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
+
+
+def _within_rows(q, q_len, r, r_len):
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    assert q.ndim == 2 and r.ndim == 2 and q.shape[1] == r.shape[1]
+    return q, np.ascontiguousarray(q_len, dtype=np.uint32), r, np.ascontiguousarray(r_len, dtype=np.uint32)
+
+
+def dist_within(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, max_dist: float, cap: Optional[int] = None
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """For every query list ALL references with distance <= max_dist, as CSR: (row_off [nq + 1], ref, common, denom, dist);
+    the hits of query i are [row_off[i], row_off[i + 1]) of the four arrays, ascending by reference index.  Exact (the bound
+    reaches the device as integers) and the same from run to run.  Rows and lengths as dist_batch takes them; no [nq, nr] array
+    exists anywhere.  cap: room for that many hits (default 65 536); when it is too small the call is repeated once with
+    the size the library reported."""
+    init()
+    q, q_len, r, r_len = _within_rows(q, q_len, r, r_len)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    cap = 1 << 16 if cap is None else int(cap)
+    row_off = np.zeros(nq + 1, dtype=np.uint64)
+    found = ctypes.c_uint64(0)
+    for _ in range(2):
+        ref, common, denom = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        dist = np.zeros(cap, dtype=np.float64)
+        rc = load().mhx_dist_within(q.ctypes.data, q_len.ctypes.data, nq, r.ctypes.data, r_len.ctypes.data, nr, stride, k, s, float(max_dist),
+                                    row_off.ctypes.data, ref.ctypes.data, common.ctypes.data, denom.ctypes.data, dist.ctypes.data, cap,
+                                    ctypes.byref(found), 0)
+        if rc != MHX_E_CAPACITY or found.value <= cap:
+            break
+        cap = found.value
+    _check(rc)
+    m = found.value
+    return row_off, ref[:m].copy(), common[:m].copy(), denom[:m].copy(), dist[:m].copy()
+
+
+def dist_within_counts(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, k: int, s: int, max_dist: float) -> np.ndarray:
+    """The counting form of dist_within: row_off [nq + 1] alone (row_off[nq] the number of hits), no hit is stored."""
+    init()
+    q, q_len, r, r_len = _within_rows(q, q_len, r, r_len)
+    nq = q.shape[0]
+    row_off = np.zeros(nq + 1, dtype=np.uint64)
+    found = ctypes.c_uint64(0)
+    _check(load().mhx_dist_within(q.ctypes.data, q_len.ctypes.data, nq, r.ctypes.data, r_len.ctypes.data, r.shape[0], q.shape[1], k, s, float(max_dist),
+                                  row_off.ctypes.data, None, None, None, None, 0, ctypes.byref(found), 0))
+    return row_off
+
+
+def dist_within_device(q_ptr: int, q_len_ptr: int, nq: int, r_ptr: int, r_len_ptr: int, nr: int, stride: int, k: int, s: int, max_dist: float,
+                       row_off_ptr: int, ref_ptr: int, common_ptr: int, denom_ptr: int, dist_ptr: int, cap: int) -> int:
+    """Device pointers in and out (row_off [nq + 1] of 64-bit words, the hit arrays [cap]; a sketch_segments_device result goes
+    straight in on either side): the CSR stays on the device, exact and in its final order -- the integers are those of
+    dist_within bit for bit --, dist (may be 0) is the device's log.  ref_ptr == 0 with cap == 0 only counts.  Returns the
+    number of hits; EngineError(MHX_E_CAPACITY) when it exceeds cap (row_off is complete then, the message names the number)."""
+    init()
+    v = ctypes.c_void_p
+    found = ctypes.c_uint64(0)
+    _check(load().mhx_dist_within(v(q_ptr), v(q_len_ptr), nq, v(r_ptr), v(r_len_ptr), nr, stride, k, s, float(max_dist), v(row_off_ptr),
+                                  v(ref_ptr or None), v(common_ptr or None), v(denom_ptr or None), v(dist_ptr or None), int(cap), ctypes.byref(found), 1))
+    return int(found.value)
 
 
 def dist_contain(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int

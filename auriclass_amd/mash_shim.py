@@ -2,7 +2,8 @@
 `mash` launcher (auriclass_amd/bin) first on PATH and the reference's five subprocess call sites
 (/root/reference/auriclass/general.py:198-205 `mash -h`; classes.py:576-596 and 696-706
 `mash sketch`; classes.py:92-97 `mash dist`; classes.py:305-312 `mash bounds`) run on the GPU
-engine.  `mash screen REF.msh reads...` (containment) and `mash sketch -i` (one sketch per sequence of a file: how a
+engine.  `mash dist` also takes several queries and the filters -d / -v (every reference within a distance of each query:
+engine.within_files); without a filter its calls and its bytes are those of the two-argument form.  `mash screen REF.msh reads...` (containment) and `mash sketch -i` (one sketch per sequence of a file: how a
 reference set is made from one multi-FASTA) are served too, and `mash triangle SET.msh ...` (all pairs within a sketch
 set: matrix or, with -E / -d / -v, edge list); AuriClass itself calls none of them.  Only the argv subsets AuriClass uses are understood; stdout/stderr text and exit
 codes follow mash (sketch: exit 1 with 'ERROR: Did not find fasta records in ...')."""
@@ -80,10 +81,23 @@ def main(argv: List[str] = None) -> int:
             sys.stderr.write(text)
             return 0
         if cmd == "dist":
-            if len(args) != 2:
-                sys.stderr.write("ERROR: mash dist <reference> <query>\n")
+            for flag in ("-t", "-l", "-C", "-i", "-k", "-s", "-r", "-m", "-a", "-z", "-S", "-w", "-b", "-g", "-c", "-n", "-Z", "-M", "-I"):
+                if flag in args:
+                    sys.stderr.write(f"ERROR: mash dist {flag} is not supported by the mhx shim\n")
+                    return 1
+            _take(args, "-p", 1, int)   # threads: the engine has its own
+            max_dist = _take(args, "-d", None, float)
+            max_p = _take(args, "-v", None, float)
+            if len(args) < 2:
+                sys.stderr.write("ERROR: mash dist [-d <max distance>] [-v <max p-value>] <reference> <query> [<query> ...]\n")
                 return 1
-            sys.stdout.write(engine.dist_files(args[0], args[1]))
+            if max_dist is not None or max_p is not None:   # mash prints a pair iff distance <= -d && p <= -v, in reference order
+                sys.stdout.write(engine.within_files(args[0], args[1:], 1.0 if max_dist is None else max_dist,
+                                                     1.0 if max_p is None else max_p, order=0))
+            elif len(args) == 2:
+                sys.stdout.write(engine.dist_files(args[0], args[1]))
+            else:
+                sys.stdout.write(engine.dist_files_multi(args[0], args[1:]))
             return 0
         if cmd == "screen":
             for flag in ("-w", "-i", "-v", "-a"):

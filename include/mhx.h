@@ -357,7 +357,7 @@ int mhx_dist_batch(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const 
                    const uint32_t *r_len, uint32_t nr, uint32_t stride, int k, uint32_t s,
                    uint32_t *common, uint32_t *denom, double *dist, int device_ptrs);
 double mhx_last_dist_kernel_ms(void);
-/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* / mhx_dist_cluster / mhx_dist_search call: -1 = the generic pair kernel did all the work (tiny batch),
+/* diagnostics of the last mhx_dist_batch / mhx_dist_files / mhx_dist_triangle* / mhx_dist_cluster / mhx_dist_search / mhx_dist_within call: -1 = the generic pair kernel did all the work (tiny batch),
  * else the number of (query batch, reference slice) blocks the all-vs-refs fast path gave up to it (0 for uniform hashes) */
 int mhx_last_dist_fallback_blocks(void);
 /* value ranges every (query batch, reference slice) block of that call was cut into: 1024 x W, W = the smallest power of two
@@ -733,6 +733,52 @@ typedef struct mhx_search_opts {
     double max_p_value;   /* print rows with p <= max_p_value (1: all) */
 } mhx_search_opts;
 int mhx_search_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts *opts, char *stdout_buf,
+                     size_t cap, size_t *need);
+
+/* ALL REFERENCES WITHIN A DISTANCE OF EACH QUERY, AS CSR: the bounded neighbourhood call -- "which of the references we know
+ * lie within max_dist of this sample" -- without the 64-hit ceiling of mhx_dist_search and without a cell per pair; no
+ * [nq][nr] array exists anywhere and nq * nr is not limited.  q / q_len / r / r_len / stride as mhx_dist_batch takes them,
+ * (common, denom) of a pair are mhx_dist_batch's.
+ * Rule: a pair (q, r) is a hit iff the distance mhx_dist_batch computes on the host (libm) is <= max_dist.  max_dist >= 1
+ * keeps every pair, max_dist < 0 none; 0/0 (two empty lists) has distance 0.
+ * Outputs: the hits of query q are hit_ref / hit_common / hit_denom / hit_dist [row_off[q] .. row_off[q + 1]), ascending by
+ * reference index; row_off [nq + 1], row_off[nq] == *n_out (host, always).  hit_dist may be NULL.
+ * Exact in both forms: the bound reaches the kernels as the integer table cmin[0 .. s] of mhx_dist_cluster (built on the host
+ * with its libm, kept per (s, k, max_dist)), a pair is a hit iff common >= cmin[denom]; there is no prefilter and no host
+ * post-filter, and the two forms return the same integers bit for bit.  Host form: hit_dist are host libm doubles;
+ * device_ptrs != 0: all pointers but n_out are device pointers, hit_dist is the device's log.
+ * Deterministic: the result is the same from run to run, whatever the batch sizes are and whenever a flagged block is redone.
+ * Capacity: cap is the room of the hit arrays in entries.  *n_out > cap: MHX_E_CAPACITY; row_off and *n_out are complete and
+ * correct then (the hit arrays hold nothing of use), so the caller sizes the arrays exactly and calls once more.
+ * hit_ref == NULL with cap == 0 is the counting form: MHX_OK, only row_off and *n_out are written.
+ * nq == 0: MHX_OK, nothing written.  nr == 0: MHX_OK, row_off zeroed, *n_out = 0.  MHX_E_ARG, before anything is launched: a
+ * null required pointer, max_dist not a number, k outside 1 .. 32, s or stride zero, s >= 2^20, a len > stride (host form).
+ * On the device: the schedule of mhx_dist_search; behind every block one half-wave per (query, slice
+ * of 32 references) ballots the rule into one mask word and appends its keepers to an arrival list with one atomic per wave;
+ * behind the last block a scan of the mask words gives row_off and a gather puts every hit in its final place, so arrival
+ * order never shows.  The queries go through in super-batches of at most 2^22 (query, slice) cells (8 bytes each).
+ * MHX_WITHIN_GEOMETRY=dist takes mhx_dist_batch's geometry, MHX_WITHIN_QBATCH bounds the queries of a block, MHX_WITHIN_CELLS
+ * lowers the cells of a super-batch.  mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report
+ * this call too. */
+int mhx_dist_within(const uint64_t *q, const uint32_t *q_len, uint32_t nq, const uint64_t *r, const uint32_t *r_len, uint32_t nr,
+                    uint32_t stride, int k, uint32_t s, double max_dist, uint64_t *row_off, uint32_t *hit_ref, uint32_t *hit_common,
+                    uint32_t *hit_denom, double *hit_dist, uint64_t cap, uint64_t *n_out, int device_ptrs);
+/* The same at file level, `mash dist -d max_dist -v max_p_value REF QUERY [QUERY ...]`: for every query sketch, in argument
+ * order and then file order, every reference within max_dist as a `mash dist` row "ref\tquery\tdist\tp\tcommon/denom\n"
+ * (p = mhx_p_value); a query without hits prints nothing.  order 0: the hits of a query in reference order, what mash
+ * prints; order 1: best first in the order of mhx_dist_search (the host sorts each row of the CSR).  Rows with
+ * p > max_p_value are dropped on the host (mash's pass rule: distance <= -d && p <= -v).  opts == NULL means {sizeof, 0, 1, 1}.
+ * Mismatches (MHX_E_MISMATCH) and damaged files as mhx_search_files; MHX_E_ARG: struct_size != sizeof(mhx_within_opts), order
+ * outside 0 .. 1, a bound that is not a number.  The reference file is read, checked and staged once; the queries go in
+ * batches, a batch whose hits exceed its buffers is repeated once with the size the device reported.  No mash output is
+ * recorded for this mode: it is pinned by the restated rule (tests/within_rule.py) over the mash-pinned distance path. */
+typedef struct mhx_within_opts {
+    uint32_t struct_size; /* sizeof(mhx_within_opts) */
+    uint32_t order;       /* 0: reference order, 1: best first */
+    double max_dist;      /* keep pairs with distance <= max_dist (1: all) */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+} mhx_within_opts;
+int mhx_within_files(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_within_opts *opts, char *stdout_buf,
                      size_t cap, size_t *need);
 
 /* JACKKNIFE SUPPORT OF SEARCH HITS: in how many of `replicates` resampled sketches each of a query's closest references is
