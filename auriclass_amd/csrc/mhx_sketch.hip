@@ -182,6 +182,11 @@ constexpr bool kParseLoops = true;
 #else
 constexpr bool kParseLoops = false;
 #endif
+#ifdef MHX_LINE_CHECK_LEN   // A/B builds: the line path counts its long records in the checks (seqline_is_long), as the map path does
+constexpr bool kLineSpanRecords = false;
+#else
+constexpr bool kLineSpanRecords = true;
+#endif
 #ifndef MHX_MIN_WAVES
 #define MHX_MIN_WAVES 7   // 72 VGPRs: seven waves per SIMD, matching the seven workgroups per CU the LDS footprint admits
 #endif
@@ -289,11 +294,14 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     // newline map were
     bool by_lines = kLineItems && line_items_try(fast_parse, interior, line_base, tile_total);
     uint32_t long_records, items_at = 0;
-    LineSpan span{0u, 0u, 0u, 0u};
+    LineSpan span{0u, 0u, 0u, 0u, 0u};
     if (kLineItems && by_lines) {
-        long_records = phase_event_checks(sm, tid, line_base, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
+        // the '@' / '+' tests on every lane; the long records from the ends of the lines the first wave reads anyway, one lane
+        // per line, once per record whatever becomes of the tile behind the barrier (line_span_long_record, mhx_tile.h)
+        long_records = phase_event_checks<!kLineSpanRecords>(sm, tid, line_base, tile_total, check_limit, bad, tile_off, a.end, (uint32_t)K);
         if (tid < (int)kLineItemLines) {
             span = phase_line_span<K>(sm, (uint32_t)tid, line_base, tile_total);
+            if (kLineSpanRecords) long_records = span.long_record;
             // the two words the path leaves for the other waves are set here, by this wave, and nowhere else: set at the kernel's
             // entry, in front of the stage loads of every tile, they cost a FASTQ of 10 kb reads 1.3 % (profiles/line_items_ab.txt, 4)
             const bool too_long = __ballot(line_span_too_long(span)) != 0ull; // wave-uniform
@@ -309,7 +317,7 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     if (FASTQ && long_records) atomicAdd(&sm.misc[5], long_records);
     __syncthreads();
     MHX_STAMP(); // 3: good-base map, or the ends of the sequence lines
-    if (kLineItems && by_lines && MHX_UNLIKELY(sm.misc[6] != 0u)) { // a line above the bound: the maps after all, its checks are done
+    if (kLineItems && by_lines && MHX_UNLIKELY(sm.misc[6] != 0u)) { // a line above the bound: the maps after all, its checks are done and its records counted
         by_lines = false;
         phase_good_events_map(sm, tid, st, line_base, excl, tile_total);
         __syncthreads();

@@ -697,7 +697,8 @@ MHX_HD bool seqline_is_long(const uint32_t *nlmap, const uint8_t *tile_bytes, ui
 // phase_good<true> for a tile whose newlines phase_events has listed (a barrier in between), in its two halves: the
 // good map (phase_good_events_map) and the checks, one lane per newline (phase_event_checks); the sum of the checks'
 // return values over the workgroup is the tile's number of long records (which lane counts a record differs from
-// phase_good).  The line-item form below keeps the checks and skips the map.
+// phase_good).  The line-item form below skips the map and keeps the '@' / '+' checks (phase_event_checks<false>); its
+// long records are counted from the ends of the lines (line_span_long_record).
 MHX_HD void phase_good_events_map(TileSmem &sm, int tid, const ThreadState &st, uint32_t line_base, uint32_t excl, uint32_t tile_total)
 {
     uint32_t line = line_base + excl;
@@ -717,6 +718,9 @@ MHX_HD void phase_good_events_map(TileSmem &sm, int tid, const ThreadState &st, 
         tile_good(sm)[kTileBytes / 32 + 3] = 0;
     }
 }
+// SEQ_LEN = false: the '@' / '+' tests alone, for the line path, which counts the long records from the ends of the lines
+// it reads anyway (phase_line_span); the return value is 0 then.  A form of its own, not a run-time switch.
+template <bool SEQ_LEN = true>
 MHX_HD uint32_t phase_event_checks(TileSmem &sm, int tid, uint32_t line_base, uint32_t tile_total, uint32_t check_limit,
                                    bool &bad_format, uint64_t tile_off, uint64_t end, uint32_t k)
 {
@@ -730,9 +734,9 @@ MHX_HD uint32_t phase_event_checks(TileSmem &sm, int tid, uint32_t line_base, ui
         if (e < tile_total) {
             const uint32_t pos = (uint32_t)ev[e] + 1u;     // first byte of the line behind newline e (<= kTileBytes: staged)
             const uint32_t idx = (line_base + e + 1u) & 3u; // that line's index
-            if (idx == 1u) {
+            if (SEQ_LEN && idx == 1u) {
                 if (seqline_is_long(tile_nlmap(sm), tb, pos, tile_off, end, k)) ++count;
-            } else if (idx != 3u && pos < check_limit) {
+            } else if ((SEQ_LEN ? idx != 3u : !(idx & 1u)) && pos < check_limit) {
                 if (tb[pos] != (idx == 0u ? '@' : '+')) bad_format = true;
             }
         }
@@ -793,14 +797,33 @@ MHX_HD bool line_items_try(bool fast_parse, bool interior, uint32_t line_base, u
 {
     return fast_parse && interior && tile_total >= kLineItemMinNewlines && seqline_count(line_base, tile_total) <= kLineItemLines;
 }
-struct LineSpan { uint32_t a, pmax, ngroups, kmers; }; // ngroups = 0: no valid start
+// ngroups = 0: no valid start; long_record: 1 iff the line starts in this tile and its record counts (seqline_is_long)
+struct LineSpan { uint32_t a, pmax, ngroups, kmers, long_record; };
+// The record count of the line path.  phase_event_checks<true> gives the newline in front of every sequence line a lane,
+// which looks the line's first K bytes up in the newline map (seqline_is_long: 19 instructions and three LDS reads that all
+// four waves sit through).  On an interior tile the two ends [a, b) phase_line_span holds say the same:
+//     no newline among the first K bytes, all of them in the span    <=>  b - a >= K   (b is the next newline, or the end of
+//                                                                         the halo, which lies in the span and beyond a + K)
+//     the CR rule: the K-th byte is a '\r' and the line ends there   <=>  bytes[a + K - 1] == '\r' && b == a + K
+// and the checks count a line in the tile that holds the newline in front of it, so line i = 0 is not counted here (the
+// tile in front has it; in the tile that starts the span line 0 is a header) while line i = tile_total, which starts at
+// kTileBytes at the latest and has no k-mer start of this tile, is.
+// INVARIANT: a record is counted once, by the lane of its line, in front of the line-phase barrier, and by nothing else on
+// this path -- the checks run as phase_event_checks<false> there.  The count does not depend on the length bound of
+// phase_line_items, so a tile that falls back to the maps behind the barrier (sm.misc[6]) has its records counted already
+// and phase_good_events_map, which it then runs, counts nothing.
+template <int K> MHX_HD uint32_t line_span_long_record(const uint8_t *tile_bytes, uint32_t i, uint32_t a, uint32_t b)
+{
+    if (i == 0u || b - a < (uint32_t)K) return 0u; // b >= a: a line's end is not in front of its start
+    return (b == a + (uint32_t)K && tile_bytes[a + (uint32_t)K - 1u] == '\r') ? 0u : 1u;
+}
 // the tile's j-th sequence line, from its two events (or the halo words of the newline map): before the barrier behind
 // which phase_line_items writes over both
 template <int K> MHX_HD LineSpan phase_line_span(const TileSmem &sm, uint32_t j, uint32_t line_base, uint32_t tile_total)
 {
     const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
     const uint32_t i = seqline_first(line_base) + 4u * j;
-    LineSpan s{0u, 0u, 0u, 0u};
+    LineSpan s{0u, 0u, 0u, 0u, 0u};
     if (i > tile_total) return s;
     const uint32_t a = i ? (uint32_t)ev[i - 1u] + 1u : 0u;
     uint32_t b;
@@ -810,6 +833,7 @@ template <int K> MHX_HD LineSpan phase_line_span(const TileSmem &sm, uint32_t j,
         const uint32_t h0 = sm.maps[kTileBytes / 32], h1 = sm.maps[kTileBytes / 32 + 1];
         b = h0 ? (uint32_t)kTileBytes + (uint32_t)__builtin_ctz(h0) : h1 ? (uint32_t)kTileBytes + 32u + (uint32_t)__builtin_ctz(h1) : (uint32_t)(kTileBytes + kHaloBytes);
     }
+    s.long_record = line_span_long_record<K>(reinterpret_cast<const uint8_t *>(sm.bytes), i, a, b);
     int32_t pmax = (int32_t)b - K;
     if (pmax > kTileBytes - 1) pmax = kTileBytes - 1;
     if (pmax < (int32_t)a) return s;
