@@ -11,7 +11,7 @@
 
 #include "mhx_device.h"
 #include "mhx_dist.h"
-#include "mhx_engine_internal.h"
+#include "mhx_engine_sets.h"
 #include "mhx_internal.h"
 
 using namespace mhx;
@@ -55,8 +55,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     } else {
         for (uint32_t i = 0; i < nq; ++i) if (q_len[i] > stride) return fail(MHX_E_ARG, "q_len[%u] exceeds stride", i);
         for (uint32_t i = 0; i < nr; ++i) if (r_len[i] > stride) return fail(MHX_E_ARG, "r_len[%u] exceeds stride", i);
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t bq = up((size_t)nq * stride * 8), br = up((size_t)nr * stride * 8), bql = up((size_t)nq * 4), brl = up((size_t)nr * 4), bo = up(pairs * 4);
+        const size_t bq = up256((size_t)nq * stride * 8), br = up256((size_t)nr * stride * 8), bql = up256((size_t)nq * 4), brl = up256((size_t)nr * 4), bo = up256(pairs * 4);
         uint8_t *base = nullptr;
         const int rc = dist_stage(bq + br + bql + brl + 2 * bo, &base);
         if (rc) return rc;
@@ -113,7 +112,6 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     const uint32_t nslices = (nr + 31) / 32, nbatches = (nq + qbatch - 1) / qbatch, nblocks = nslices * nbatches;
     DistWork w{};
     uint32_t *d_params = nullptr;
-    constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together (a reference set of 131 072 sketches per group)
     if (fast) {
         size_t oq, orr, oc, ow, op;
         const size_t need = dist_work_bytes(qbatch, nr < 32 ? nr : 32, ranges, &oq, &orr, &oc, &ow, &op) + (size_t)std::min(nblocks, kBlockGroup) * 8;

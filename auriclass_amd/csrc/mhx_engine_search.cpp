@@ -1,7 +1,7 @@
-// mhx_engine_search.cpp -- host side of the reference-set search (mhx_dist_search): staging of a host-pointer call, ONE
-// split of both sets into value ranges, the schedule of (query batch, reference slice) blocks, the fallback of a flagged
-// block to the generic pair kernel, the take-out pass that merges a block's candidates into every query's best list, and
-// the exact distance rule on the host.  Rules: mhx_search.h; kernels: mhx_search.hip, mhx_triangle.hip and mhx_dist.hip.
+// mhx_engine_search.cpp -- host side of the reference-set search (mhx_dist_search): what it gives the schedule and the
+// staging of mhx_engine_sets.h -- its geometry, the block-local results, the finish pass, the generic pair kernel and the
+// take-out pass that merges a block's candidates into every query's best list -- and the exact distance rule on the host.
+// Rules: mhx_search.h; kernels: mhx_search.hip, mhx_triangle.hip and mhx_dist.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -14,7 +14,7 @@
 
 #include "mhx_device.h"
 #include "mhx_search.h"
-#include "mhx_engine_internal.h"
+#include "mhx_engine_sets.h"
 #include "mhx_internal.h"
 
 using namespace mhx;
@@ -32,117 +32,46 @@ struct SearchCall { // everything on the device
     double *hit_dist; // may be null
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Launches the whole call on the engine's stream and waits for it.  Both sets are split into value ranges ONCE, with one
-// shift (launch_dist_offsets_both); every block then runs the range pass and a finish pass into its block-local
-// [queries][32] results, and the take-out pass merges them into the best lists, which stay in device memory between the
-// blocks.  Block flags come back once per group of blocks; a flagged block is redone by the generic pair kernel into the
-// same block-local arrays and taken out then -- later than its neighbours, which the total order makes harmless.
+// Launches the whole call on the engine's stream and waits for it, on the schedule of mhx_engine_sets.h: every block's finish
+// pass writes its block-local [queries][32] results, and the take-out pass merges them into the best lists, which stay in
+// device memory between the blocks.  A flagged block is redone by the generic pair kernel into the same block-local arrays
+// and taken out then -- later than its neighbours, which the total order makes harmless.
 int search_device(SearchCall &c)
 {
-    const uint64_t pairs = (uint64_t)c.nq * c.nr;
     const char *geo = getenv("MHX_SEARCH_GEOMETRY");
     const uint32_t ranges = geo && strcmp(geo, "dist") == 0 ? tri_ranges_dist(c.longest) : tri_ranges(c.longest);
-    const bool fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)c.s >= 400000)) && ranges != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
-    uint32_t qbatch = tri_max_queries(fast ? ranges : kTriMinRanges);
-    if (const char *e = getenv("MHX_SEARCH_QBATCH")) { const long v = atol(e); if (v > 0 && (uint64_t)v < qbatch) qbatch = (uint32_t)v; }
-    qbatch = std::min(qbatch, c.nq);
-    const uint64_t nblocks = search_blocks(c.nq, c.nr, qbatch);
-    constexpr uint64_t kBlockGroup = 4096; // blocks whose flag words come back together
-    const uint32_t group = (uint32_t)std::min(nblocks, kBlockGroup);
-    // workspace: [offsets of the queries][offsets of the references][byte counters][window totals][block-local common,
-    // denom][words: shift, 0, then two per block of a group]
-    const uint64_t per = (uint64_t)ranges + 1;
-    size_t o = 0;
-    const size_t o_offq = o; if (fast) o += up256((size_t)c.nq * per * 4);
-    const size_t o_offr = o; if (fast) o += up256((size_t)c.nr * per * 4);
-    const size_t o_cpart = o; if (fast) o += up256((size_t)qbatch * ranges * kTriSlice);
-    const size_t o_wtot = o; if (fast && ranges > (uint32_t)kDistRanges) o += up256((size_t)qbatch * (ranges / kDistWindowRanges) * kTriSlice * 4);
-    const size_t o_lc = o; o += up256((size_t)qbatch * kTriSlice * 4);
-    const size_t o_ld = o; o += up256((size_t)qbatch * kTriSlice * 4);
-    const size_t o_words = o; o += up256((size_t)(2 + 2 * group) * 4);
-    if (g.dist_ws.grow(o, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the search workspace (%zu bytes)", o);
-    uint32_t *offq = (uint32_t *)(g.dist_ws + o_offq), *offr = (uint32_t *)(g.dist_ws + o_offr);
-    uint32_t *loc_c = (uint32_t *)(g.dist_ws + o_lc), *loc_d = (uint32_t *)(g.dist_ws + o_ld);
-    uint32_t *words = (uint32_t *)(g.dist_ws + o_words), *flags = words + 2;
-    DistWork w{};
-    w.cpart = g.dist_ws + o_cpart;
-    w.wtot = (uint32_t *)(g.dist_ws + o_wtot);
-    w.ranges = ranges;
+    SetSchedule sch(c.nq, c.nr, c.stride, SetGeometry{ranges, c.s, "MHX_SEARCH_QBATCH", c.nq, "search"});
+    const size_t o_lc = sch.extra((size_t)sch.qbatch * kTriSlice * 4), o_ld = sch.extra((size_t)sch.qbatch * kTriSlice * 4); // block-local common, denom
+    int rc = sch.place("the search workspace");
+    if (rc) return rc;
+    hipError_t &le = sch.le;
     DistArgs all{};
     all.q = c.q; all.q_len = c.q_len; all.nq = c.nq; all.r = c.r; all.r_len = c.r_len; all.nr = c.nr; all.stride = c.stride; all.s = c.s; all.k = c.k;
-    auto block_args = [&](const SearchBlock &b) {
-        DistArgs x = all;
-        x.q = c.q + (uint64_t)b.q0 * c.stride; x.q_len = c.q_len + b.q0; x.nq = b.nq;
-        x.r = c.r + (uint64_t)b.r0 * c.stride; x.r_len = c.r_len + b.r0; x.nr = b.nr;
-        x.common = loc_c; x.denom = loc_d; x.dist = nullptr; x.out_stride = kTriSlice; x.out_off = 0;
-        return x;
-    };
+    all.common = (uint32_t *)sch.at(o_lc); all.denom = (uint32_t *)sch.at(o_ld); all.dist = nullptr; all.out_stride = kTriSlice; all.out_off = 0;
     SearchOut out{};
-    out.loc_common = loc_c; out.loc_denom = loc_d; out.top = c.top; out.k = c.k; out.jmin = c.jmin;
+    out.loc_common = all.common; out.loc_denom = all.denom; out.top = c.top; out.k = c.k; out.jmin = c.jmin;
     out.hit_ref = c.hit_ref; out.hit_common = c.hit_common; out.hit_denom = c.hit_denom; out.n_hits = c.n_hits; out.hit_dist = c.hit_dist;
-    auto take_out = [&](const SearchBlock &b, const uint32_t *flag) {
-        SearchOut t = out;
-        t.flag = flag; t.r0 = b.r0; t.nr = b.nr; t.q0 = b.q0; t.nq = b.nq;
-        return launch_search_take(t, g.stream);
-    };
-    hipEventRecord(g.ev0, g.stream);
-    hipError_t le = hipMemsetAsync(words, 0, (size_t)(2 + 2 * group) * 4, g.stream);
+    sch.begin();
     if (le == hipSuccess) le = hipMemsetAsync(c.n_hits, 0, (size_t)c.nq * 4, g.stream);
-    g.last_dist_fallbacks = fast ? 0 : -1;
-    g.last_dist_ranges = 0;
-    if (fast && le == hipSuccess) {
-        DistWork wa = w;
-        wa.offs_q = offq; wa.offs_r = offr; wa.params = words; // words[0] the shift of the call, words[1] stays 0
-        le = launch_dist_offsets_both(all, wa, g.stream);
-    }
-    std::vector<uint32_t> back;
-    for (uint64_t b0 = 0; b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
-        const uint64_t b1 = std::min(nblocks, b0 + kBlockGroup);
-        if (b0 != 0) le = hipMemsetAsync(flags, 0, (size_t)2 * group * 4, g.stream);
-        for (uint64_t b = b0; b < b1 && le == hipSuccess; ++b) {
-            const SearchBlock blk = search_block(c.nq, c.nr, qbatch, b);
-            const DistArgs x = block_args(blk);
-            if (!fast) {
-                le = launch_dist_pairs(x, g.stream);
-                if (le == hipSuccess) le = take_out(blk, words + 1);
-                continue;
-            }
-            w.offs_q = offq + (uint64_t)blk.q0 * per;
-            w.offs_r = offr + (uint64_t)blk.r0 * per;
-            w.params = flags + 2 * (b - b0);
-            le = launch_dist_range_pass(x, w, g.stream);
-            if (le == hipSuccess) le = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
-            if (le == hipSuccess) le = take_out(blk, w.params + 1);
-        }
-        if (!fast || le != hipSuccess) continue;
-        back.resize((size_t)(b1 - b0) * 2);
-        if (hipMemcpyAsync(back.data(), flags, back.size() * 4, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
-            hipStreamSynchronize(g.stream) != hipSuccess)
-            return fail(MHX_E_HIP, "search kernel failed");
-        for (uint64_t b = b0; b < b1 && le == hipSuccess; ++b)
-            if (back[2 * (b - b0) + 1]) { // a value range overflowed the LDS table or the byte counters
-                const SearchBlock blk = search_block(c.nq, c.nr, qbatch, b);
-                le = launch_dist_pairs(block_args(blk), g.stream);
-                if (le == hipSuccess) le = take_out(blk, words + 1);
-                ++g.last_dist_fallbacks;
-            }
-    }
+    sch.offsets(all);
+    rc = sch.run(
+        0, c.nq, [&](const SearchBlock &, const DistArgs &x) { return launch_dist_pairs(x, g.stream); },
+        [&](const SearchBlock &, const DistArgs &x, const DistWork &w) {
+            return ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
+        },
+        [&](const SearchBlock &b, const uint32_t *flag) {
+            SearchOut t = out;
+            t.flag = flag; t.r0 = b.r0; t.nr = b.nr; t.q0 = b.q0; t.nq = b.nq;
+            return launch_search_take(t, g.stream);
+        });
+    if (rc) return rc;
     if (le == hipSuccess && c.hit_dist) {
         SearchOut t = out;
         t.q0 = 0; t.nq = c.nq;
         le = launch_search_dist(t, g.stream);
     }
-    hipEventRecord(g.ev1, g.stream);
-    if (fast && (uint64_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
-    if (le != hipSuccess) return fail(MHX_E_HIP, "search kernel launch failed: %s", hipGetErrorString(le));
-    const hipError_t se = hipStreamSynchronize(g.stream);
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, g.ev0, g.ev1);
-    g.last_dist_ms = ms;
-    if (se != hipSuccess) return fail(MHX_E_HIP, "search kernel failed: %s", hipGetErrorString(se));
-    return MHX_OK;
+    rc = sch.end();
+    return rc ? rc : sch.wait();
 }
 
 int search_check(uint32_t nq, uint32_t nr, uint32_t stride, int k, uint32_t s, double max_dist, uint32_t top)
@@ -161,38 +90,25 @@ int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
                 const SearchRefs *refs, uint32_t nr, uint32_t stride, int k, uint32_t s, double max_dist, uint32_t top, uint32_t *hit_ref,
                 uint32_t *hit_common, uint32_t *hit_denom, double *hit_dist, uint32_t *n_hits, SearchStaged *staged = nullptr)
 {
-    for (uint32_t i = 0; i < nq; ++i) if (q_len[i] > stride) return fail(MHX_E_ARG, "q_len[%u] exceeds stride", i);
-    if (!refs) for (uint32_t i = 0; i < nr; ++i) if (r_len[i] > stride) return fail(MHX_E_ARG, "r_len[%u] exceeds stride", i);
-    const size_t bq = up256((size_t)nq * stride * 8), bql = up256((size_t)nq * 4), bh = up256((size_t)nq * top * 4);
-    const size_t br = refs ? 0 : up256((size_t)nr * stride * 8), brl = refs ? 0 : up256((size_t)nr * 4);
-    uint8_t *base = nullptr;
-    int rc = dist_stage(bq + bql + br + brl + 3 * bh + bql, &base);
+    const size_t cells = (size_t)nq * top;
+    Carve lists; // the [nq][top] lists and their lengths
+    const size_t o_ref = lists.take(cells * 4), o_common = lists.take(cells * 4), o_denom = lists.take(cells * 4), o_n = lists.take((size_t)nq * 4);
+    StagedSets in{};
+    int rc = stage_sets("dist_search", HostSet{q, q_rows, q_len, nq}, HostSet{r, nullptr, r_len, nr}, refs, stride, lists.bytes, in);
     if (rc) return rc;
-    uint8_t *dq = base, *dql = dq + bq, *dr = dql + bql, *drl = dr + br, *dh = drl + brl;
-    hipError_t ce = hipSuccess;
-    if (q_rows) { // every row from its own place
-        for (uint32_t i = 0; i < nq && ce == hipSuccess; ++i)
-            if (q_len[i]) ce = hipMemcpyAsync(dq + (size_t)i * stride * 8, q_rows[i], (size_t)q_len[i] * 8, hipMemcpyHostToDevice, g.stream);
-    } else
-        ce = hipMemcpyAsync(dq, q, (size_t)nq * stride * 8, hipMemcpyHostToDevice, g.stream);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(dql, q_len, (size_t)nq * 4, hipMemcpyHostToDevice, g.stream);
-    if (!refs && ce == hipSuccess) ce = hipMemcpyAsync(dr, r, (size_t)nr * stride * 8, hipMemcpyHostToDevice, g.stream);
-    if (!refs && ce == hipSuccess) ce = hipMemcpyAsync(drl, r_len, (size_t)nr * 4, hipMemcpyHostToDevice, g.stream);
-    if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in dist_search: %s", hipGetErrorString(ce));
     SearchCall c{};
-    c.q = (const uint64_t *)dq; c.q_len = (const uint32_t *)dql;
-    c.r = refs ? refs->rows : (const uint64_t *)dr; c.r_len = refs ? refs->len : (const uint32_t *)drl;
+    c.q = in.q; c.q_len = in.q_len; c.r = in.r; c.r_len = in.r_len;
     c.nq = nq; c.nr = nr; c.stride = stride; c.s = s; c.k = k; c.top = top;
     c.longest = refs ? refs->longest : 0;
     for (uint32_t i = 0; i < nq; ++i) c.longest = std::max(c.longest, q_len[i]);
     if (!refs) for (uint32_t i = 0; i < nr; ++i) c.longest = std::max(c.longest, r_len[i]);
     c.jmin = tri_jmin(max_dist, k);
-    c.hit_ref = (uint32_t *)dh; c.hit_common = (uint32_t *)(dh + bh); c.hit_denom = (uint32_t *)(dh + 2 * bh); c.n_hits = (uint32_t *)(dh + 3 * bh);
+    c.hit_ref = (uint32_t *)(in.room + o_ref); c.hit_common = (uint32_t *)(in.room + o_common); c.hit_denom = (uint32_t *)(in.room + o_denom);
+    c.n_hits = (uint32_t *)(in.room + o_n);
     c.hit_dist = nullptr; // distances in host libm below
     if (staged) *staged = SearchStaged{c.q, c.q_len};
     rc = search_device(c);
     if (rc) return rc;
-    const size_t cells = (size_t)nq * top;
     if (hipMemcpy(hit_ref, c.hit_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hit_common, c.hit_common, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(hit_denom, c.hit_denom, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(n_hits, c.n_hits, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(MHX_E_HIP, "D2H copy failed in dist_search");

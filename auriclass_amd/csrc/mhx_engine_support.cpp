@@ -10,14 +10,10 @@
 
 #include "mhx_device.h"
 #include "mhx_support.h"
-#include "mhx_engine_internal.h"
+#include "mhx_engine_sets.h"
 #include "mhx_internal.h"
 
 using namespace mhx;
-
-namespace {
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-} // namespace
 
 namespace mhx {
 

@@ -1,9 +1,10 @@
 // mhx_engine_triangle.cpp -- host side of the all-pairs distance within one sketch set (mhx_dist_triangle,
 // mhx_dist_triangle_edges and mhx_dist_cluster; the tree, mhx_dist_mst, is in mhx_engine_mst.cpp and takes its pairs from
 // here, and so do the medoids, mhx_dist_medoids in mhx_engine_medoid.cpp, whose block mode run_medoid lies here): staging
-// of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE offsets table of the whole set, the fallback of a flagged block to the generic pair kernel, one function per mode that rides the
-// schedule, the exact distance rule and the order of the edge list on the host, the bound of the clustering as a table
-// of integers.
+// of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE offsets table of the whole set
+// (its loop over the groups of blocks and their flag words is mhx_engine_sets.h's, which the query-by-reference calls run
+// too), the fallback of a flagged block to the generic pair kernel, one function per mode that rides the schedule, the exact
+// distance rule and the order of the edge list on the host, the bound of the clustering as a table of integers.
 // Rules: mhx_triangle.h, mhx_cluster.h, mhx_mst.h, mhx_medoid.h; kernels: mhx_triangle.hip, mhx_cluster.hip, mhx_mst.hip,
 // mhx_medoid.hip and mhx_dist.hip.
 #include <hip/hip_runtime.h>
@@ -34,7 +35,6 @@ namespace {
 // A mode goes: construct (geometry and blocks, from the inputs alone), extra() for room of its own, place(), begin(), its
 // own setup, offsets(), run_blocks() once or once per round, its own last launches, end(), its own readback in wait().
 struct TriSchedule {
-    static constexpr uint32_t kBlockGroup = 4096; // blocks whose flag words come back together
     const TriCall c;
     uint32_t ranges, qbatch, nblocks, group;
     bool fast;
@@ -128,38 +128,28 @@ struct TriSchedule {
     // last block of every reference slice (and of every group).
     template <class TakeOut, class SliceDone> int run_blocks(TakeOut take_out, bool first, SliceDone slice_done)
     {
-        for (uint32_t b0 = 0; b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
-            const uint32_t b1 = std::min(nblocks, b0 + kBlockGroup);
-            if (b0 != 0 || !first) le = hipMemsetAsync(flags, 0, (size_t)2 * group * 4, g.stream);
-            for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b) {
+        auto generic = [&](uint64_t b) {
+            hipError_t e = launch_dist_pairs(block_args(blocks[b]), g.stream);
+            if (e == hipSuccess) e = take_out(blocks[b], words + 1);
+            return e;
+        };
+        return run_block_groups(
+            BlockGroups{nblocks, fast, flags, group, !first, true, first, "triangle"}, le,
+            [&](uint64_t b, uint32_t *params) {
+                if (!fast) return generic(b);
                 const TriBlock &blk = blocks[b];
                 const DistArgs x = block_args(blk);
-                if (!fast) {
-                    le = launch_dist_pairs(x, g.stream);
-                    if (le == hipSuccess) le = take_out(blk, words + 1);
-                    continue;
-                }
                 w.offs_q = offs + (uint64_t)blk.q0 * per();
                 w.offs_r = offs + (uint64_t)blk.r0 * per();
-                w.params = flags + 2 * (b - b0);
-                le = launch_dist_range_pass(x, w, g.stream);
-                if (le == hipSuccess) le = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
-                if (le == hipSuccess) le = take_out(blk, w.params + 1);
-                if (le == hipSuccess && (b + 1 == b1 || blocks[b + 1].r0 != blk.r0)) le = slice_done();
-            }
-            if (!fast || le != hipSuccess) continue;
-            std::vector<uint32_t> back((size_t)(b1 - b0) * 2);
-            if (hipMemcpyAsync(back.data(), flags, back.size() * 4, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
-                hipStreamSynchronize(g.stream) != hipSuccess)
-                return fail(MHX_E_HIP, "triangle kernel failed");
-            for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b)
-                if (back[2 * (b - b0) + 1]) { // a value range overflowed the LDS table or the byte counters
-                    le = launch_dist_pairs(block_args(blocks[b]), g.stream);
-                    if (le == hipSuccess) le = take_out(blocks[b], words + 1);
-                    if (first) ++g.last_dist_fallbacks;
-                }
-        }
-        return MHX_OK;
+                w.params = params;
+                hipError_t e = launch_dist_range_pass(x, w, g.stream);
+                if (e == hipSuccess) e = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
+                if (e == hipSuccess) e = take_out(blk, params + 1);
+                const bool last = (b + 1) % kBlockGroup == 0 || b + 1 == nblocks; // of its group
+                if (e == hipSuccess && (last || blocks[b + 1].r0 != blk.r0)) e = slice_done();
+                return e;
+            },
+            generic);
     }
     template <class TakeOut> int run_blocks(TakeOut take_out, bool first)
     {

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mhx_mst.h"
+#include "mhx_engine_sets.h"
 #include "mhx_internal.h"
 
 namespace mhx {
@@ -17,8 +18,6 @@ struct TriCall { // the inputs of a call, everything on the device
     uint32_t n, stride, s, longest;
     int k;
 };
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // what all calls check first; *done: nothing to compute (n <= 1)
 int triangle_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, bool *done);

@@ -2,7 +2,9 @@
 // triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files, mhx_cluster_reps_files), the single-linkage tree (mhx_tree_files), complete
 // and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
 // (mhx_search_files), the bounded neighbourhood (mhx_within_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
-// of sequence files is in mhx_files.cpp.
+// of sequence files is in mhx_files.cpp.  The commands of query files against one reference file (search, within, contain)
+// share their path check, the staging of the references on the device and the walk over the query files in batches
+// (set_paths_check, stage_refs, walk_query_files): a command supplies what follows its first query file and what a batch prints.
 #include <hip/hip_runtime.h>
 #include <ctype.h>
 #include <fcntl.h>
@@ -71,6 +73,77 @@ void pack_rows(const std::vector<const RefSketch *> &refs, uint32_t stride, std:
         len[i] = (uint32_t)refs[i]->hash_count();
         if (len[i]) memcpy(&rows[(size_t)i * stride], refs[i]->hash_data(), (size_t)len[i] * 8);
     }
+}
+
+// what every `REF QUERY [QUERY ...]` command over resident references checks of its paths, under its own name
+int set_paths_check(const char *cmd, const char *ref_msh, const char *const *qry_msh, int n_qry)
+{
+    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "%s: a reference sketch path and at least one query sketch path required", cmd);
+    for (int i = 0; i < n_qry; ++i)
+        if (!qry_msh[i]) return fail(MHX_E_ARG, "%s: query sketch path %d is null", cmd, i);
+    return MHX_OK;
+}
+
+// The reference set of a call on the device, for all its batches of queries: rows at a stride that holds any list of the call
+// (widest_query: the longest a query list gets), every list cut at `cut` entries.  The host's hash lists are released: names
+// and lengths stay for the text.  of: the call in the message ("the search").
+struct ResidentRefs {
+    DevArray<uint64_t> rows;
+    DevArray<uint32_t> len;
+    SearchRefs refs{nullptr, nullptr, 0, 0, 0};
+};
+int stage_refs(SketchSet &R, uint32_t cut, uint32_t widest_query, const char *of, ResidentRefs &d)
+{
+    SearchRefs &refs = d.refs;
+    refs.nr = (uint32_t)R.refs.size();
+    std::vector<uint32_t> len(refs.nr);
+    for (uint32_t i = 0; i < refs.nr; ++i) {
+        len[i] = (uint32_t)std::min<size_t>(R.refs[i].hash_count(), cut);
+        refs.longest = std::max(refs.longest, len[i]);
+    }
+    refs.stride = row_stride(std::max(refs.longest, widest_query));
+    if (refs.nr == 0) return MHX_OK;
+    std::vector<uint64_t> rows((size_t)refs.nr * refs.stride, 0);
+    for (uint32_t i = 0; i < refs.nr; ++i) {
+        if (len[i]) memcpy(&rows[(size_t)i * refs.stride], R.refs[i].hash_data(), (size_t)len[i] * 8);
+        std::vector<uint64_t>().swap(R.refs[i].hashes);
+    }
+    if (d.rows.grow(rows.size()) != hipSuccess || d.len.grow(refs.nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of %s", of);
+    if (hipMemcpy(d.rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d.len, len.data(), (size_t)refs.nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(MHX_E_HIP, "H2D copy of the reference set failed");
+    refs.rows = d.rows; refs.len = d.len;
+    return MHX_OK;
+}
+
+// The query files of a call against the reference file R, read one after the other, so that host memory holds one batch
+// whatever n_qry is: every file is checked against R and the first file, on_first_file(Q) follows the first one's check (the
+// sizes of the call, the staging of the references), and flush(qs) gets the sketches read so far whenever there are
+// kQueryBatch of them, and at the end.  A call without references flushes nothing.
+constexpr size_t kQueryBatch = 4096; // query sketches per device call
+template <class First, class Flush> int walk_query_files(const SketchSet &R, const char *const *qry_msh, int n_qry, First on_first_file, Flush flush)
+{
+    std::vector<SketchSet> held; // the files of the current batch
+    std::vector<const RefSketch *> qs;
+    uint32_t q_sketch_size = 0;
+    auto batch = [&]() -> int {
+        const int rc = qs.empty() || R.refs.empty() ? MHX_OK : flush(qs);
+        qs.clear();
+        held.clear();
+        return rc;
+    };
+    for (int i = 0; i < n_qry; ++i) {
+        held.emplace_back();
+        SketchSet &Q = held.back();
+        int rc = msh_read_file(qry_msh[i], Q);
+        if (rc) return rc;
+        if (i == 0) q_sketch_size = Q.sketch_size;
+        rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
+        if (rc == MHX_OK && i == 0) rc = on_first_file(Q);
+        if (rc) return rc;
+        for (const RefSketch &q : Q.refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
+        if (qs.size() >= kQueryBatch) { rc = batch(); if (rc) return rc; }
+    }
+    return batch();
 }
 
 // `mash dist REF QUERY [QUERY ...]`: mhx_dist_files is the n_qry == 1 case.  The reference file is read, parsed, checked and
@@ -734,108 +807,72 @@ int search_files_text(const char *ref_msh, const char *const *qry_msh, int n_qry
     if (clade_csv) { rc = read_clades(clade_csv, R, clade, clade_id); if (rc) return rc; }
     const int k = (int)R.kmer_size;
     const uint32_t nr = (uint32_t)R.refs.size();
-    DevArray<uint64_t> d_rows;
-    DevArray<uint32_t> d_len, d_cand, d_ncand, d_first;
-    SearchRefs refs{nullptr, nullptr, nr, 0, 0};
-    uint32_t q_sketch_size = 0, s = 0;
+    ResidentRefs resident;
+    const SearchRefs &refs = resident.refs;
+    DevArray<uint32_t> d_cand, d_ncand, d_first;
+    uint32_t s = 0;
     std::string text;
-    constexpr size_t kBatch = 4096; // query sketches per device call
-    std::vector<SketchSet> held;    // the files of the current batch
-    std::vector<const RefSketch *> qs;
-    auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
-        for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
-        refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
-        if (nr == 0) return MHX_OK;
-        std::vector<const RefSketch *> lists;
-        for (const RefSketch &r : R.refs) lists.push_back(&r);
-        std::vector<uint64_t> rows;
-        std::vector<uint32_t> len;
-        pack_rows(lists, refs.stride, rows, len);
-        for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
-        if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the search");
-        if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return fail(MHX_E_HIP, "H2D copy of the reference set failed");
-        refs.rows = d_rows; refs.len = d_len;
-        return MHX_OK;
+    auto on_first_file = [&](const SketchSet &Q) { // the sketch size of the call, the references on the device
+        s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+        return stage_refs(R, UINT32_MAX, Q.sketch_size, "the search", resident);
     };
-    auto flush = [&]() -> int {
+    auto flush = [&](const std::vector<const RefSketch *> &qs) -> int {
         const uint32_t nq = (uint32_t)qs.size();
-        if (nq && nr) {
-            std::vector<const uint64_t *> qrows(nq);
-            std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq), first;
-            std::vector<double> hx((size_t)nq * o.top);
-            for (uint32_t i = 0; i < nq; ++i) {
-                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
-            }
-            SearchStaged staged{};
-            const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data(), &staged);
-            if (rc2) return rc2;
-            if (replicates) { // the hits, before the p-value drops rows, are the candidates; the queries are on the device still
-                const size_t cells = (size_t)nq * o.top;
-                if (d_cand.grow(cells) != hipSuccess || d_first.grow(cells) != hipSuccess || d_ncand.grow(nq) != hipSuccess)
-                    return fail(MHX_E_HIP, "hipMalloc failed for the candidates of the support");
-                if (hipMemcpy(d_cand, hr.data(), cells * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_ncand, nh.data(), (size_t)nq * 4, hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(MHX_E_HIP, "H2D copy of the candidates failed");
-                SupportCall c{};
-                c.q = staged.q; c.q_len = staged.q_len; c.r = refs.rows; c.r_len = refs.len; c.nq = nq; c.nr = nr; c.stride = refs.stride; c.s = s;
-                c.cand = d_cand; c.n_cand = d_ncand; c.top = o.top; c.replicates = replicates; c.keep = sup->keep; c.seed = sup->seed; c.T = T;
-                c.first = d_first;
-                const int rc3 = support_device(c);
-                if (rc3) return rc3;
-                first.resize(cells);
-                if (hipMemcpy(first.data(), d_first, cells * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy of the support failed");
-            }
-            const std::string of = "/" + std::to_string(replicates);
-            for (uint32_t qi = 0; qi < nq; ++qi)
-                for (uint32_t t = 0; t < nh[qi]; ++t) {
-                    const size_t p = (size_t)qi * o.top + t;
-                    const RefSketch &ref = R.refs[hr[p]];
-                    const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
-                    if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
-                    std::string more;
-                    if (replicates) {
-                        more = std::to_string(first[p]) + of;
-                        if (clade_csv) {
-                            uint32_t same = 0; // replicates whose best candidate has this row's clade
-                            for (uint32_t x = 0; x < nh[qi]; ++x)
-                                if (clade_id[hr[(size_t)qi * o.top + x]] == clade_id[hr[p]]) same += first[(size_t)qi * o.top + x];
-                            more += "\t" + clade[hr[p]] + "\t" + std::to_string(same) + of;
-                        }
-                    }
-                    pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p], more);
-                }
+        std::vector<const uint64_t *> qrows(nq);
+        std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hc((size_t)nq * o.top), hd((size_t)nq * o.top), nh(nq), first;
+        std::vector<double> hx((size_t)nq * o.top);
+        for (uint32_t i = 0; i < nq; ++i) {
+            qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+            if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
         }
-        qs.clear();
-        held.clear();
+        SearchStaged staged{};
+        const int rc2 = search_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, o.top, hr.data(), hc.data(), hd.data(), hx.data(), nh.data(), &staged);
+        if (rc2) return rc2;
+        if (replicates) { // the hits, before the p-value drops rows, are the candidates; the queries are on the device still
+            const size_t cells = (size_t)nq * o.top;
+            if (d_cand.grow(cells) != hipSuccess || d_first.grow(cells) != hipSuccess || d_ncand.grow(nq) != hipSuccess)
+                return fail(MHX_E_HIP, "hipMalloc failed for the candidates of the support");
+            if (hipMemcpy(d_cand, hr.data(), cells * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_ncand, nh.data(), (size_t)nq * 4, hipMemcpyHostToDevice) != hipSuccess)
+                return fail(MHX_E_HIP, "H2D copy of the candidates failed");
+            SupportCall c{};
+            c.q = staged.q; c.q_len = staged.q_len; c.r = refs.rows; c.r_len = refs.len; c.nq = nq; c.nr = nr; c.stride = refs.stride; c.s = s;
+            c.cand = d_cand; c.n_cand = d_ncand; c.top = o.top; c.replicates = replicates; c.keep = sup->keep; c.seed = sup->seed; c.T = T;
+            c.first = d_first;
+            const int rc3 = support_device(c);
+            if (rc3) return rc3;
+            first.resize(cells);
+            if (hipMemcpy(first.data(), d_first, cells * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy of the support failed");
+        }
+        const std::string of = "/" + std::to_string(replicates);
+        for (uint32_t qi = 0; qi < nq; ++qi)
+            for (uint32_t t = 0; t < nh[qi]; ++t) {
+                const size_t p = (size_t)qi * o.top + t;
+                const RefSketch &ref = R.refs[hr[p]];
+                const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
+                std::string more;
+                if (replicates) {
+                    more = std::to_string(first[p]) + of;
+                    if (clade_csv) {
+                        uint32_t same = 0; // replicates whose best candidate has this row's clade
+                        for (uint32_t x = 0; x < nh[qi]; ++x)
+                            if (clade_id[hr[(size_t)qi * o.top + x]] == clade_id[hr[p]]) same += first[(size_t)qi * o.top + x];
+                        more += "\t" + clade[hr[p]] + "\t" + std::to_string(same) + of;
+                    }
+                }
+                pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p], more);
+            }
         return MHX_OK;
     };
-    for (int i = 0; i < n_qry; ++i) {
-        held.emplace_back();
-        SketchSet &Q = held.back();
-        rc = msh_read_file(qry_msh[i], Q);
-        if (rc) return rc;
-        if (i == 0) q_sketch_size = Q.sketch_size;
-        rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-        if (rc) return rc;
-        if (i == 0) {
-            s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
-            rc = stage_refs();
-            if (rc) return rc;
-        }
-        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-    }
-    rc = flush();
+    rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);
     if (rc) return rc;
     return put_text(text, stdout_buf, cap, need);
 }
 
 int search_files_check(const char *cmd, const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_search_opts &o)
 {
-    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "%s: a reference sketch path and at least one query sketch path required", cmd);
-    for (int i = 0; i < n_qry; ++i)
-        if (!qry_msh[i]) return fail(MHX_E_ARG, "%s: query sketch path %d is null", cmd, i);
+    const int rc = set_paths_check(cmd, ref_msh, qry_msh, n_qry);
+    if (rc) return rc;
     if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "%s: top must be 1 .. 64", cmd);
     if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "%s: max_dist / max_p_value is not a number", cmd);
     return MHX_OK;
@@ -862,10 +899,8 @@ extern "C" int mhx_within_files(const char *ref_msh, const char *const *qry_msh,
 {
     return entry("mhx_within_files", [&]() -> int {
         mhx_within_opts o{(uint32_t)sizeof(mhx_within_opts), 0, 1.0, 1.0};
-        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "within: a reference sketch path and at least one query sketch path required");
-        for (int i = 0; i < n_qry; ++i)
-            if (!qry_msh[i]) return fail(MHX_E_ARG, "within: query sketch path %d is null", i);
-        int rc = take_opts("within", opts, o);
+        int rc = set_paths_check("within", ref_msh, qry_msh, n_qry);
+        if (rc == MHX_OK) rc = take_opts("within", opts, o);
         if (rc) return rc;
         if (o.order > 1) return fail(MHX_E_ARG, "within: order must be 0 (reference order) or 1 (best first)");
         if (!(o.max_dist == o.max_dist) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "within: max_dist / max_p_value is not a number");
@@ -874,91 +909,55 @@ extern "C" int mhx_within_files(const char *ref_msh, const char *const *qry_msh,
         if (rc) return rc;
         const int k = (int)R.kmer_size;
         const uint32_t nr = (uint32_t)R.refs.size();
-        DevArray<uint64_t> d_rows;
-        DevArray<uint32_t> d_len;
-        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
-        uint32_t q_sketch_size = 0, s = 0;
+        ResidentRefs resident;
+        const SearchRefs &refs = resident.refs;
+        uint32_t s = 0;
         std::string text;
-        constexpr size_t kBatch = 4096; // query sketches per device call
         constexpr uint64_t kFirstRoom = 4096; // hits the buffers hold before a batch has asked for more
-        std::vector<SketchSet> held;    // the files of the current batch
-        std::vector<const RefSketch *> qs;
         std::vector<uint32_t> hr, hc, hd, order;
         std::vector<double> hx;
-        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call
-            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)r.hash_count());
-            refs.stride = row_stride(std::max(refs.longest, q_sketch_size));
-            if (nr == 0) return MHX_OK;
-            std::vector<const RefSketch *> lists;
-            for (const RefSketch &r : R.refs) lists.push_back(&r);
-            std::vector<uint64_t> rows;
-            std::vector<uint32_t> len;
-            pack_rows(lists, refs.stride, rows, len);
-            for (RefSketch &r : R.refs) std::vector<uint64_t>().swap(r.hashes); // packed: names and lengths stay for the text
-            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of within");
-            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
-            refs.rows = d_rows; refs.len = d_len;
-            return MHX_OK;
+        auto on_first_file = [&](const SketchSet &Q) { // the sketch size of the call, the references on the device
+            s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
+            return stage_refs(R, UINT32_MAX, Q.sketch_size, "within", resident);
         };
-        auto flush = [&]() -> int {
+        auto flush = [&](const std::vector<const RefSketch *> &qs) -> int {
             const uint32_t nq = (uint32_t)qs.size();
-            if (nq && nr) {
-                std::vector<const uint64_t *> qrows(nq);
-                std::vector<uint32_t> ql(nq);
-                std::vector<uint64_t> row_off((size_t)nq + 1);
-                for (uint32_t i = 0; i < nq; ++i) {
-                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                    if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
-                }
-                uint64_t found = 0, room = std::max<uint64_t>(hr.size(), std::min<uint64_t>((uint64_t)nq * nr, kFirstRoom));
-                int rc2 = MHX_OK;
-                for (int attempt = 0; attempt < 2; ++attempt) {
-                    if (hr.size() < room) { hr.resize(room); hc.resize(room); hd.resize(room); hx.resize(room); }
-                    rc2 = within_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, row_off.data(), hr.data(), hc.data(), hd.data(), hx.data(), hr.size(), &found);
-                    if (rc2 != MHX_E_CAPACITY) break;
-                    room = found;
-                }
-                if (rc2) return rc2;
-                clear_error();
-                for (uint32_t qi = 0; qi < nq; ++qi) {
-                    const uint64_t lo = row_off[qi], hi = row_off[qi + 1];
-                    order.resize((size_t)(hi - lo));
-                    for (uint64_t t = lo; t < hi; ++t) order[(size_t)(t - lo)] = (uint32_t)(t - lo);
-                    if (o.order == 1)
-                        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-                            return search_better(SearchHit{hr[lo + a], hc[lo + a], hd[lo + a]}, SearchHit{hr[lo + b], hc[lo + b], hd[lo + b]});
-                        });
-                    for (const uint32_t t : order) {
-                        const size_t p = (size_t)(lo + t);
-                        const RefSketch &ref = R.refs[hr[p]];
-                        const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
-                        if (!(pv <= o.max_p_value)) continue;
-                        pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p]);
-                    }
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq);
+            std::vector<uint64_t> row_off((size_t)nq + 1);
+            for (uint32_t i = 0; i < nq; ++i) {
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+                if (ql[i] > refs.stride) return fail(MHX_E_FORMAT, "query sketch %s holds more hashes than its sketch size", qs[i]->name.c_str());
+            }
+            uint64_t found = 0, room = std::max<uint64_t>(hr.size(), std::min<uint64_t>((uint64_t)nq * nr, kFirstRoom));
+            int rc2 = MHX_OK;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                if (hr.size() < room) { hr.resize(room); hc.resize(room); hd.resize(room); hx.resize(room); }
+                rc2 = within_rows(qrows.data(), ql.data(), nq, refs, k, s, o.max_dist, row_off.data(), hr.data(), hc.data(), hd.data(), hx.data(), hr.size(), &found);
+                if (rc2 != MHX_E_CAPACITY) break;
+                room = found;
+            }
+            if (rc2) return rc2;
+            clear_error();
+            for (uint32_t qi = 0; qi < nq; ++qi) {
+                const uint64_t lo = row_off[qi], hi = row_off[qi + 1];
+                order.resize((size_t)(hi - lo));
+                for (uint64_t t = lo; t < hi; ++t) order[(size_t)(t - lo)] = (uint32_t)(t - lo);
+                if (o.order == 1)
+                    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+                        return search_better(SearchHit{hr[lo + a], hc[lo + a], hd[lo + a]}, SearchHit{hr[lo + b], hc[lo + b], hd[lo + b]});
+                    });
+                for (const uint32_t t : order) {
+                    const size_t p = (size_t)(lo + t);
+                    const RefSketch &ref = R.refs[hr[p]];
+                    const double pv = mhx_p_value(hc[p], ref.length, qs[qi]->length, k, hd[p]);
+                    if (!(pv <= o.max_p_value)) continue;
+                    pair_row(text, ref.name, qs[qi]->name, hx[p], pv, hc[p], hd[p]);
                 }
             }
-            qs.clear();
-            held.clear();
             return MHX_OK;
         };
-        for (int i = 0; i < n_qry; ++i) {
-            held.emplace_back();
-            SketchSet &Q = held.back();
-            rc = msh_read_file(qry_msh[i], Q);
-            if (rc) return rc;
-            if (i == 0) q_sketch_size = Q.sketch_size;
-            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-            if (rc) return rc;
-            if (i == 0) {
-                s = std::max<uint32_t>(1, R.sketch_size < Q.sketch_size ? R.sketch_size : Q.sketch_size);
-                rc = stage_refs();
-                if (rc) return rc;
-            }
-            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-        }
-        rc = flush();
+        rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);
         if (rc) return rc;
         return put_text(text, stdout_buf, cap, need);
     });
@@ -996,9 +995,8 @@ static int contain_files_text(const char *ref_msh, const char *const *qry_msh, i
     mhx_contain_opts o{(uint32_t)sizeof(mhx_contain_opts), 0, 0.0, 1.0};
     int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain", opts, o) : MHX_OK;
     if (rc) return rc;
-    if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "contain: a reference sketch path and at least one query sketch path required");
-    for (int i = 0; i < n_qry; ++i)
-        if (!qry_msh[i]) return fail(MHX_E_ARG, "contain: query sketch path %d is null", i);
+    rc = set_paths_check("contain", ref_msh, qry_msh, n_qry);
+    if (rc) return rc;
     if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
     SketchSet R;
     rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
@@ -1015,52 +1013,35 @@ static int contain_files_text(const char *ref_msh, const char *const *qry_msh, i
     }
     uint32_t q_sketch_size = 0;
     std::string text;
-    constexpr size_t kBatch = 4096; // query sketches per device call
-    std::vector<SketchSet> held;    // the files of the current batch
-    std::vector<const RefSketch *> qs;
-    auto flush = [&]() -> int {
+    auto on_first_file = [&](const SketchSet &Q) { q_sketch_size = Q.sketch_size; return MHX_OK; };
+    auto flush = [&](const std::vector<const RefSketch *> &qs) -> int {
         const uint32_t nq = (uint32_t)qs.size();
-        if (nq && nr) {
-            std::vector<const uint64_t *> qrows(nq);
-            std::vector<uint32_t> ql(nq);
-            uint32_t longest = r_longest;
-            for (uint32_t i = 0; i < nq; ++i) {
-                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
-                longest = std::max(longest, ql[i]);
-            }
-            const size_t cells = (size_t)nq * nr;
-            std::vector<uint32_t> shared(cells), n_q(cells), n_r(cells), won(winner ? cells : 0);
-            const int rc2 = contain_rows(qrows.data(), nullptr, ql.data(), nq, std::max<uint32_t>(1, q_sketch_size), rrows.data(), nullptr, rl.data(), nr, s_r,
-                                         row_stride(longest), shared.data(), n_q.data(), n_r.data(), winner ? r_length.data() : nullptr, winner ? won.data() : nullptr);
-            if (rc2) return rc2;
-            if (winner) shared.swap(won); // the rows below print what was won
-            for (uint32_t qi = 0; qi < nq; ++qi)
-                for (uint32_t ri = 0; ri < nr; ++ri) {
-                    const size_t p = (size_t)qi * nr + ri;
-                    const double identity = n_r[p] == 0 ? 0.0 : mhx_screen_identity(shared[p], n_r[p], k);
-                    const double pv = n_r[p] == 0 ? 1.0 : mhx_screen_p_value(shared[p], n_r[p], (double)qs[qi]->length, k);
-                    if (!(identity >= o.min_identity) || !(pv <= o.max_p_value)) continue;
-                    text += (o.comment ? R.refs[ri].comment : R.refs[ri].name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) +
-                            "\t" + fmt_g(pv) + "\t" + std::to_string(shared[p]) + "/" + std::to_string(n_r[p]) + "\t" + std::to_string(shared[p]) + "/" +
-                            std::to_string(n_q[p]) + "\n";
-                }
+        std::vector<const uint64_t *> qrows(nq);
+        std::vector<uint32_t> ql(nq);
+        uint32_t longest = r_longest;
+        for (uint32_t i = 0; i < nq; ++i) {
+            qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)qs[i]->hash_count();
+            longest = std::max(longest, ql[i]);
         }
-        qs.clear();
-        held.clear();
+        const size_t cells = (size_t)nq * nr;
+        std::vector<uint32_t> shared(cells), n_q(cells), n_r(cells), won(winner ? cells : 0);
+        const int rc2 = contain_rows(qrows.data(), nullptr, ql.data(), nq, std::max<uint32_t>(1, q_sketch_size), rrows.data(), nullptr, rl.data(), nr, s_r,
+                                     row_stride(longest), shared.data(), n_q.data(), n_r.data(), winner ? r_length.data() : nullptr, winner ? won.data() : nullptr);
+        if (rc2) return rc2;
+        if (winner) shared.swap(won); // the rows below print what was won
+        for (uint32_t qi = 0; qi < nq; ++qi)
+            for (uint32_t ri = 0; ri < nr; ++ri) {
+                const size_t p = (size_t)qi * nr + ri;
+                const double identity = n_r[p] == 0 ? 0.0 : mhx_screen_identity(shared[p], n_r[p], k);
+                const double pv = n_r[p] == 0 ? 1.0 : mhx_screen_p_value(shared[p], n_r[p], (double)qs[qi]->length, k);
+                if (!(identity >= o.min_identity) || !(pv <= o.max_p_value)) continue;
+                text += (o.comment ? R.refs[ri].comment : R.refs[ri].name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) +
+                        "\t" + fmt_g(pv) + "\t" + std::to_string(shared[p]) + "/" + std::to_string(n_r[p]) + "\t" + std::to_string(shared[p]) + "/" +
+                        std::to_string(n_q[p]) + "\n";
+            }
         return MHX_OK;
     };
-    for (int i = 0; i < n_qry; ++i) {
-        held.emplace_back();
-        SketchSet &Q = held.back();
-        rc = msh_read_file(qry_msh[i], Q);
-        if (rc) return rc;
-        if (i == 0) q_sketch_size = Q.sketch_size;
-        rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-        if (rc) return rc;
-        for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-        if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-    }
-    rc = flush();
+    rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);
     if (rc) return rc;
     return put_text(text, stdout_buf, cap, need);
 }
@@ -1087,9 +1068,8 @@ extern "C" int mhx_contain_files_search(const char *ref_msh, const char *const *
         mhx_contain_search_opts o{(uint32_t)sizeof(mhx_contain_search_opts), 0, 5, 1, 0.0, 1.0};
         int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain_search", opts, o) : MHX_OK;
         if (rc) return rc;
-        if (!ref_msh || !qry_msh || n_qry < 1) return fail(MHX_E_ARG, "contain: a reference sketch path and at least one query sketch path required");
-        for (int i = 0; i < n_qry; ++i)
-            if (!qry_msh[i]) return fail(MHX_E_ARG, "contain: query sketch path %d is null", i);
+        rc = set_paths_check("contain", ref_msh, qry_msh, n_qry);
+        if (rc) return rc;
         if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
         if (o.top < 1 || o.top > 64) return fail(MHX_E_ARG, "contain: top must be 1 .. 64");
         if (o.min_shared < 1) return fail(MHX_E_ARG, "contain: min_shared must be at least 1");
@@ -1097,76 +1077,39 @@ extern "C" int mhx_contain_files_search(const char *ref_msh, const char *const *
         rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
         if (rc) return rc;
         const int k = (int)R.kmer_size;
-        const uint32_t nr = (uint32_t)R.refs.size(), s_r = std::max<uint32_t>(1, R.sketch_size);
-        DevArray<uint64_t> d_rows;
-        DevArray<uint32_t> d_len;
-        SearchRefs refs{nullptr, nullptr, nr, 0, 0};
-        uint32_t q_sketch_size = 0, s_q = 1;
+        const uint32_t s_r = std::max<uint32_t>(1, R.sketch_size);
+        ResidentRefs resident;
+        const SearchRefs &refs = resident.refs;
+        uint32_t s_q = 1;
         std::string text;
-        constexpr size_t kBatch = 4096; // query sketches per device call
-        std::vector<SketchSet> held;    // the files of the current batch
-        std::vector<const RefSketch *> qs;
-        auto stage_refs = [&]() -> int { // once, behind the first query file: rows that hold any list of the call, cut at its set's sketch size
-            for (const RefSketch &r : R.refs) refs.longest = std::max<uint32_t>(refs.longest, (uint32_t)std::min<size_t>(r.hash_count(), s_r));
-            refs.stride = row_stride(std::max(refs.longest, s_q));
-            if (nr == 0) return MHX_OK;
-            std::vector<uint64_t> rows((size_t)nr * refs.stride, 0);
-            std::vector<uint32_t> len(nr);
-            for (uint32_t i = 0; i < nr; ++i) {
-                len[i] = (uint32_t)std::min<size_t>(R.refs[i].hash_count(), s_r);
-                if (len[i]) memcpy(&rows[(size_t)i * refs.stride], R.refs[i].hash_data(), (size_t)len[i] * 8);
-                std::vector<uint64_t>().swap(R.refs[i].hashes); // packed: names and lengths stay for the text
-            }
-            if (d_rows.grow(rows.size()) != hipSuccess || d_len.grow(nr) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the reference set of the containment search");
-            if (hipMemcpy(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_len, len.data(), (size_t)nr * 4, hipMemcpyHostToDevice) != hipSuccess)
-                return fail(MHX_E_HIP, "H2D copy of the reference set failed");
-            refs.rows = d_rows; refs.len = d_len;
-            return MHX_OK;
+        auto on_first_file = [&](const SketchSet &Q) { // the queries' sketch size, the references on the device, cut at theirs
+            s_q = std::max<uint32_t>(1, Q.sketch_size);
+            return stage_refs(R, s_r, s_q, "the containment search", resident);
         };
-        auto flush = [&]() -> int {
+        auto flush = [&](const std::vector<const RefSketch *> &qs) -> int {
             const uint32_t nq = (uint32_t)qs.size();
-            if (nq && nr) {
-                std::vector<const uint64_t *> qrows(nq);
-                std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hs((size_t)nq * o.top), hnr((size_t)nq * o.top), hnq((size_t)nq * o.top), nh(nq);
-                for (uint32_t i = 0; i < nq; ++i) { // a list is the first s_q entries of its sketch at most
-                    qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)std::min<size_t>(qs[i]->hash_count(), s_q);
-                }
-                const int rc2 = contain_search_rows(qrows.data(), ql.data(), nq, s_q, refs, s_r, k, o.min_identity, o.min_shared, o.top, hr.data(), hs.data(),
-                                                    hnr.data(), hnq.data(), nh.data());
-                if (rc2) return rc2;
-                for (uint32_t qi = 0; qi < nq; ++qi)
-                    for (uint32_t t = 0; t < nh[qi]; ++t) {
-                        const size_t p = (size_t)qi * o.top + t;
-                        const RefSketch &ref = R.refs[hr[p]];
-                        const double identity = mhx_screen_identity(hs[p], hnr[p], k);
-                        const double pv = mhx_screen_p_value(hs[p], hnr[p], (double)qs[qi]->length, k);
-                        if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
-                        text += (o.comment ? ref.comment : ref.name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) + "\t" +
-                                fmt_g(pv) + "\t" + std::to_string(hs[p]) + "/" + std::to_string(hnr[p]) + "\t" + std::to_string(hs[p]) + "/" +
-                                std::to_string(hnq[p]) + "\n";
-                    }
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq), hr((size_t)nq * o.top), hs((size_t)nq * o.top), hnr((size_t)nq * o.top), hnq((size_t)nq * o.top), nh(nq);
+            for (uint32_t i = 0; i < nq; ++i) { // a list is the first s_q entries of its sketch at most
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)std::min<size_t>(qs[i]->hash_count(), s_q);
             }
-            qs.clear();
-            held.clear();
+            const int rc2 = contain_search_rows(qrows.data(), ql.data(), nq, s_q, refs, s_r, k, o.min_identity, o.min_shared, o.top, hr.data(), hs.data(),
+                                                hnr.data(), hnq.data(), nh.data());
+            if (rc2) return rc2;
+            for (uint32_t qi = 0; qi < nq; ++qi)
+                for (uint32_t t = 0; t < nh[qi]; ++t) {
+                    const size_t p = (size_t)qi * o.top + t;
+                    const RefSketch &ref = R.refs[hr[p]];
+                    const double identity = mhx_screen_identity(hs[p], hnr[p], k);
+                    const double pv = mhx_screen_p_value(hs[p], hnr[p], (double)qs[qi]->length, k);
+                    if (!(pv <= o.max_p_value)) continue; // drops a row, never promotes a lower-ranked pair
+                    text += (o.comment ? ref.comment : ref.name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) + "\t" +
+                            fmt_g(pv) + "\t" + std::to_string(hs[p]) + "/" + std::to_string(hnr[p]) + "\t" + std::to_string(hs[p]) + "/" +
+                            std::to_string(hnq[p]) + "\n";
+                }
             return MHX_OK;
         };
-        for (int i = 0; i < n_qry; ++i) {
-            held.emplace_back();
-            SketchSet &Q = held.back();
-            rc = msh_read_file(qry_msh[i], Q);
-            if (rc) return rc;
-            if (i == 0) q_sketch_size = Q.sketch_size;
-            rc = check_same_kind(R, Q, q_sketch_size, qry_msh[0], qry_msh[i]);
-            if (rc) return rc;
-            if (i == 0) {
-                s_q = std::max<uint32_t>(1, q_sketch_size);
-                rc = stage_refs();
-                if (rc) return rc;
-            }
-            for (const RefSketch &q : held.back().refs) qs.push_back(&q); // (a SketchSet that moves keeps its references where they are)
-            if (qs.size() >= kBatch) { rc = flush(); if (rc) return rc; }
-        }
-        rc = flush();
+        rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);
         if (rc) return rc;
         return put_text(text, stdout_buf, cap, need);
     });

@@ -136,6 +136,21 @@ def long_pair():
     return (tc.mutate(rng, g, 0.1),), (g,), 70000, 70000
 
 
+@functools.lru_cache(maxsize=None)
+def two_groups():
+    """140 x 960 lists of 64 hashes at s = 64 both (30 slices, 16 value ranges): with one query per block that is 4200 blocks,
+    the last 104 -- query 136 from slice 16 on and queries 137 to 139 -- in a second group of flag words.  The references are
+    close copies of 30 bases and independent lists; queries 136 to 139 derive from references of slices 21, 28 and 29, so that
+    blocks of the second group hold counts that are not zero.  Not in NAMES: only the GPU test of the group boundary runs it."""
+    rng = np.random.default_rng(4200)
+    s, nq, nr = 64, 140, 960
+    bases = [tc.sketch_like(rng, s) for _ in range(30)]
+    refs = [tc.mutate(rng, bases[j % 30], 0.02 * (j % 11)) if j % 3 else tc.sketch_like(rng, s) for j in range(nr)]
+    qrys = [tc.mutate(rng, refs[(7 * i) % nr], 0.03 * (i % 9)) for i in range(nq)]
+    qrys[136], qrys[137], qrys[138], qrys[139] = refs[700][::2].copy(), refs[900].copy(), refs[930][5:].copy(), tc.mutate(rng, refs[959], 0.1)
+    return tuple(qrys), tuple(refs), s, s
+
+
 NAMES = ("small", "mixed", "set200", "extreme", "extreme_mirrored", "crowded", "plasmids", "plasmids_swapped", "long_pair")
 
 

@@ -79,3 +79,20 @@ def expected(top, max_dist, nq=NQ, nr=200):
 
 def hits_per_query(max_dist, nq=NQ, nr=200):
     return (matrix()[2][:nq, :nr] <= max_dist).sum(axis=1)
+
+
+@functools.lru_cache(maxsize=None)
+def batch_boundary():
+    """(references, [lists of query file 0, 1, 2]) at s = 16 for the file-level calls, which send their queries to the device in
+    batches of 4096 sketches: 8 references and query files of 3000, 1200 and 50 random lists -- the first batch ends behind
+    file 1, the last holds file 2 alone.  Every 47th query is a reference and every 41st a close copy of one, in all three files."""
+    rng = np.random.default_rng(4250)
+    refs = [tc.sketch_like(rng, 16) for _ in range(8)]
+    files, i = [], 0
+    for n in (3000, 1200, 50):
+        lists = []
+        for _ in range(n):
+            lists.append(refs[i % 8].copy() if i % 47 == 0 else tc.mutate(rng, refs[i % 8], 0.25) if i % 41 == 0 else tc.sketch_like(rng, 16))
+            i += 1
+        files.append(lists)
+    return refs, files

@@ -76,6 +76,25 @@ def test_flagged_blocks_go_to_the_pair_kernel(lib, name):
             assert shared[q, r] == n_ref[q, r] and n_qry[q, r] == 1000
 
 
+def test_more_blocks_than_one_group_of_flag_words(lib, monkeypatch):
+    """The flag words of the blocks come back per group of 4096 blocks.  One query per block, 140 queries against 960 references
+    (30 slices) of 64 hashes: 4200 blocks, the last 104 in a second group, whose flag words are cleared and used again
+    (tests/contain_cases.py: two_groups).  Queries 136 to 139 derive from references of slices 21, 28 and 29: their blocks lie
+    in the second group and hold counts that are not zero.  No range is crowded, so no block falls back."""
+    monkeypatch.setenv("MHX_SEARCH_QBATCH", "1")
+    Q, q_len, R, r_len, s_q, s_r = cc.rows_of("two_groups")
+    nq, nr = len(q_len), len(r_len)
+    nblocks = nq * ((nr + 31) // 32)
+    assert nblocks > 4096 and 136 * 30 + 21 >= 4096   # query 136's block with slice 21 lies in the second group
+    got = engine.dist_contain(Q, q_len, R, r_len, s_q, s_r)
+    assert lib.mhx_last_dist_ranges() == 16 and lib.mhx_last_dist_fallback_blocks() == 0
+    want = cc.expected("two_groups")
+    check(got, want, "two_groups")
+    for q, r in ((136, 700), (137, 900), (138, 930), (139, 959)):
+        assert want[0][q, r] > 0 and got[0][q, r] == want[0][q, r]
+    assert want[0][137, 900] == want[2][137, 900] == 64   # a reference that is its query
+
+
 def test_a_pair_without_a_geometry(lib):
     """70 000 entries: above the base form of the range route"""
     got = run("long_pair")

@@ -49,6 +49,23 @@ def test_text_equals_the_rules_rows(files, which):
     assert engine.search_files(ref, paths, top=5, max_p_value=1e-10) == cut
 
 
+def test_query_files_across_the_batch_of_4096_sketches(tmp_path):
+    """query files of 3000, 1200 and 50 sketches at s = 16 (tests/search_cases.py: batch_boundary): the first batch goes to the
+    device behind file 1 with 4200 sketches, the last holds file 2 alone.  The text is that of the three files one by one."""
+    engine.init()
+    refs, files = sc.batch_boundary()
+    write(tmp_path / "ref.msh", "r", refs, s=16)
+    paths = [tmp_path / ("q%d.msh" % i) for i in range(3)]
+    for i, lists in enumerate(files):
+        write(paths[i], "q%d" % i, lists, s=16)
+    assert len(files[0]) < 4096 <= len(files[0]) + len(files[1])
+    for top, max_dist in ((5, 1.0), (2, 0.05)):
+        one_by_one = [engine.search_files(tmp_path / "ref.msh", [p], top=top, max_dist=max_dist) for p in paths]
+        assert all(t.count("\n") > 0 for t in one_by_one)
+        assert engine.search_files(tmp_path / "ref.msh", paths, top=top, max_dist=max_dist) == "".join(one_by_one)
+    assert one_by_one[0].count("\n") < 2 * len(files[0])   # the bound leaves most lists empty
+
+
 def test_mismatch_is_refused(files, tmp_path):
     d, R, Q = files
     write(tmp_path / "k19.msh", "k19", sc.queries()[:3], k=19)

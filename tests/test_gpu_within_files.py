@@ -56,6 +56,23 @@ def test_text_equals_the_rules_rows_in_both_orders(files):
     assert everything.count("\n") == 13 * wc.NR > 4096 and engine.within_files(d / "ref.msh", paths, 1.0, order=1) == everything
 
 
+def test_query_files_across_the_batch_of_4096_sketches(tmp_path):
+    """query files of 3000, 1200 and 50 sketches at s = 16 (tests/search_cases.py: batch_boundary): the first batch goes to the
+    device behind file 1 with 4200 sketches, the last holds file 2 alone, and the bound leaves hits in every file.  The text is
+    that of the three files one by one, in both orders."""
+    engine.init()
+    refs, lists = sc.batch_boundary()
+    write(tmp_path / "ref.msh", "r", refs, sc.K, 16)
+    paths = [tmp_path / ("q%d.msh" % i) for i in range(3)]
+    for i, q in enumerate(lists):
+        write(paths[i], "q%d" % i, q, sc.K, 16)
+    assert len(lists[0]) < 4096 <= len(lists[0]) + len(lists[1])
+    for order in (0, 1):
+        one_by_one = [engine.within_files(tmp_path / "ref.msh", [p], 0.05, order=order) for p in paths]
+        assert all(t.count("\n") > 0 for t in one_by_one)
+        assert engine.within_files(tmp_path / "ref.msh", paths, 0.05, order=order) == "".join(one_by_one)
+
+
 def test_mismatches_damaged_files_and_bad_options(files, tmp_path):
     d, R, Q = files
     _, qrys = wc.case_set()
