@@ -260,7 +260,26 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
         fast_parse = !kParseLoops && parse_events_fit(tile_total);
         if (fast_parse) phase_events(sm, tid, st, excl);
         // the tile that holds the start of the span begins a record there; every other tile looks at its own first lines
-        if (tid == 0) sm.misc[0] = tile == a.first_tile ? 0u : phase_selfsync(sm, check_limit);
+        // ... in the newline list where there is one (mhx_tile.h): four lanes of the first wave test the four triples side by
+        // side where that wave has listed six newlines itself (selfsync_triple; the self-synchronising kernels), thread 0
+        // takes the first six entries behind a barrier of its own otherwise (phase_selfsync_list) -- and in the map, word by
+        // word, on the tiles without a list.  A look-back launch that is no repair pass takes every phase from the chain
+        // and never reads what the tile finds: it does not search.  All three choices are workgroup-uniform.
+        const bool no_search = tile == a.first_tile || (kSelfsyncList && LOOKBACK && !a.repair);
+        const bool listed = kSelfsyncList && fast_parse && !no_search;
+        const bool by_lanes = SELFSYNC && listed && selfsync_from_list(fast_parse, false, sm.cnt[0]);
+        if (by_lanes) {
+            if (tid < 64) {
+                const bool pass = tid < (int)kSelfsyncTriples && selfsync_triple(sm, (uint32_t)tid, check_limit);
+                const uint32_t phase = selfsync_phase((uint32_t)__ballot(pass));
+                if (tid == 0) sm.misc[0] = phase;
+            }
+        } else if (listed) {
+            __syncthreads(); // the list is complete
+            if (tid == 0) sm.misc[0] = phase_selfsync_list(sm, st, tile_total, check_limit);
+        } else if (tid == 0) {
+            sm.misc[0] = no_search ? 0u : phase_selfsync(sm, check_limit);
+        }
         __syncthreads();
         const uint32_t self_phase = sm.misc[0];
         if (SELFSYNC) {

@@ -109,6 +109,15 @@ MHX_HD uint32_t opaque(uint32_t v)
 #endif
     return v;
 }
+// a value that is the same in every active lane (or held by the only active one), as a scalar: v_readfirstlane_b32
+MHX_HD uint32_t wave_uniform(uint32_t v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane(v);
+#else
+    return v;
+#endif
+}
 MHX_HD uint32_t funnel_bits(uint32_t hi, uint32_t lo, uint32_t bit_shift)
 { // bit_shift in 0..31
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -150,14 +159,71 @@ MHX_HD uint32_t byte_eq_flags(uint32_t v, uint32_t pattern)
 // 24..31 in byte order (the stray partial products fall on distinct bits below 24 or beyond 31, so nothing carries).
 MHX_HD uint32_t flags_to_byte(uint32_t f_lo, uint32_t f_hi) { return (((f_lo >> 4) | f_hi) * 0x00204081u) >> 24; }
 
-// newline mask of one 32-byte word (8 dwords at p)
-MHX_HD uint32_t newline_mask(const uint32_t *p)
+// ---- newline mask of one 32-byte word (8 dwords at p) ---------------------------------
+// Two dwords at a time ("The newline map on fewer instructions"):
+//   flags   byte_eq_flags on the pair.  ((v ^ 0x0A..) & 0x7F..) + 0x7F.. is at most 0xFE per byte, so nothing carries from
+//           a byte into the next, nor from the low dword into the high one: the add of a pair is ONE 64-bit add
+//           (v_lshl_add_u64 with shift 0, the constant in an SGPR pair); the xor-and in front of it and the
+//           ~(t | v) & 0x80.. behind it stay one v_bitop3_b32 per dword.  Five instructions per pair.
+//   gather  with f_lo, f_hi the flag words (bits 7, 15, 23, 31), f_lo * 0x02040810 + f_hi * 0x20408100 as a 64-bit value
+//           holds the eight flags in byte order in bits 32..39: f_lo's land there from 7 + 25, 15 + 18, 23 + 11, 31 + 4,
+//           f_hi's from 7 + 29, 15 + 22, 23 + 15, 31 + 8.  The twelve stray partial products below bit 32 fall on twelve
+//           distinct bits (11, 18, 19, 25, 26, 27 and 15, 22, 23, 29, 30, 31), so no carry reaches bit 32; the strays at
+//           bit 40 and above are cut off with the byte.  Two v_mad_u64_u32, the second with the first's result as its
+//           64-bit addend.
+//   merge   byte 0 of the four high dwords side by side: two v_perm_b32 and an or (which the compiler fuses with the
+//           span mask behind it into one v_bitop3_b32).
+// nl_pair_gather returns the high dword of that value: the mask byte in bits 0..7, strays above.
+// What hipcc had to be told: only the 64-bit add is asm -- the compiler proves by itself that no carry crosses bit 32
+// and splits a C++ add into two v_add_u32.  The chained v_mad_u64_u32 and the v_bitop3_b32 it emits from plain C++.
+// LANES = false is the same arithmetic in plain C++ (the host form): for thread 0's halo words, whose bytes are the
+// same for the whole wave -- the compiler does them on the scalar unit, which asm with vector operands would forbid.
+// -DMHX_NL_MUL32 keeps the form of before, one v_mul_lo_u32 per pair (flags_to_byte), for A/B builds (tools/build_variants.sh).
+constexpr uint64_t kNlPattern64 = 0x0A0A0A0A0A0A0A0Aull, kLow7x8 = 0x7F7F7F7F7F7F7F7Full, kTop1x8 = 0x8080808080808080ull;
+constexpr uint32_t kNlGatherLo = 0x02040810u, kNlGatherHi = 0x20408100u;
+template <bool LANES = true> MHX_HD uint64_t nl_pair_flags(uint32_t v_lo, uint32_t v_hi)
+{ // 0x80 in every byte of the pair that is '\n'
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (LANES) {
+        const uint32_t x_lo = __builtin_amdgcn_bitop3_b32(v_lo, 0x0A0A0A0Au, 0x7F7F7F7Fu, 0x28); // (a ^ b) & c
+        const uint32_t x_hi = __builtin_amdgcn_bitop3_b32(v_hi, 0x0A0A0A0Au, 0x7F7F7F7Fu, 0x28);
+        uint64_t t;
+        asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(t) : "v"(((uint64_t)x_hi << 32) | x_lo), "s"(kLow7x8));
+        const uint32_t f_lo = __builtin_amdgcn_bitop3_b32((uint32_t)t, v_lo, 0x80808080u, 0x02); // ~(a | b) & c
+        const uint32_t f_hi = __builtin_amdgcn_bitop3_b32((uint32_t)(t >> 32), v_hi, 0x80808080u, 0x02);
+        return ((uint64_t)f_hi << 32) | f_lo;
+    }
+#endif
+    const uint64_t v = ((uint64_t)v_hi << 32) | v_lo;
+    const uint64_t t = ((v ^ kNlPattern64) & kLow7x8) + kLow7x8;
+    return ~(t | v) & kTop1x8;
+}
+MHX_HD uint32_t nl_pair_gather(uint64_t f)
 {
+    const uint64_t g = (uint64_t)(uint32_t)f * kNlGatherLo + (uint64_t)(uint32_t)(f >> 32) * kNlGatherHi;
+    return (uint32_t)(g >> 32);
+}
+template <bool LANES = true> MHX_HD uint32_t newline_mask(const uint32_t *p)
+{
+#ifdef MHX_NL_MUL32
     uint32_t n = 0;
 #pragma unroll
     for (int d = 0; d < 8; d += 2)
         n |= flags_to_byte(byte_eq_flags(p[d], 0x0A0A0A0Au), byte_eq_flags(p[d + 1], 0x0A0A0A0Au)) << (4 * d);
     return n;
+#else
+    uint32_t h[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) h[d] = nl_pair_gather(nl_pair_flags<LANES>(p[2 * d], p[2 * d + 1]));
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (LANES) { // v_perm_b32 d, s0, s1, sel: selector 0..3 takes a byte of s1, 4..7 of s0, 0x0C is 0x00
+        const uint32_t n01 = __builtin_amdgcn_perm(h[1], h[0], 0x0C0C0400u);
+        const uint32_t n23 = __builtin_amdgcn_perm(h[3], h[2], 0x04000C0Cu);
+        return n01 | n23;
+    }
+#endif
+    return (h[0] & 0xFFu) | ((h[1] & 0xFFu) << 8) | ((h[2] & 0xFFu) << 16) | (h[3] << 24);
+#endif
 }
 // A/C/G/T (either case) mask of the four bytes of a dword, as flags 0x80 per byte
 MHX_HD uint32_t acgt_flags(uint32_t v)
@@ -536,7 +602,12 @@ MHX_HD void phase_classify(TileSmem &sm, int tid, ThreadState &st, uint64_t tile
 #pragma unroll
         for (int w = 0; w < 2; ++w) {
             st.hin[w] = interior ? 0xFFFFFFFFu : inrange_mask(tile_off + kTileBytes + 32u * w, begin, end);
-            st.hnl[w] = newline_mask(h + 8 * w) & st.hin[w];
+            // one lane's bytes: told so, the compiler does the word on the scalar unit in every kernel form (left to itself it
+            // did in the FASTQ forms and kept 90 VALU instructions for the two words in the others)
+            uint32_t hw[8];
+#pragma unroll
+            for (int d = 0; d < 8; ++d) hw[d] = wave_uniform(h[8 * w + d]);
+            st.hnl[w] = newline_mask<false>(hw) & st.hin[w];
             tile_nlmap(sm)[kTileBytes / 32 + w] = st.hnl[w];
         }
     }
@@ -679,6 +750,79 @@ MHX_HD void phase_events(TileSmem &sm, int tid, const ThreadState &st, uint32_t 
         }
         at += (uint32_t)__builtin_popcount(st.nl[w]);
     }
+}
+
+// ---- phase_selfsync from the newline list ------------------------------------------------------------------------------
+// phase_selfsync walks the newline map word by word on one lane, on the way to the barrier all four waves wait at.  Where
+// phase_events has listed the tile's newlines, its first six positions are the first six entries of the list, and the
+// four triples are tested side by side: lane i (0..3) takes the entries i, i + 1, i + 2 (selfsync_triple), the lowest
+// lane that passes gives the phase (selfsync_phase of the four-bit ballot).  The same answer as phase_selfsync on the same
+// bytes: the positions rise with i, so `p2 >= check_limit` at one i holds at every later one -- the search's `break` and a
+// failed test on that lane and all above it are one thing.
+// Taken where the first wave's own newline count (sm.cnt[0] behind block_scan_excl) is kSelfsyncNewlines at least: entries
+// 0..5 then come from lanes of the first wave, whose LDS operations complete in order, so that wave reads them behind
+// phase_events without a barrier (as the line path reads what its lane 0 stores).  Every other tile keeps the search.
+// -DMHX_SELFSYNC_MAP: no tile takes the list, the A/B builds of tools/build_variants.sh.
+constexpr uint32_t kSelfsyncNewlines = 6, kSelfsyncTriples = 4;
+#ifdef MHX_SELFSYNC_MAP
+constexpr bool kSelfsyncList = false;
+#else
+constexpr bool kSelfsyncList = true;
+#endif
+// workgroup-uniform part of the choice; wave0_newlines: the newlines of the tile's first kBlock / 4 threads
+MHX_HD bool selfsync_from_list(bool fast_parse, bool first_tile_of_span, uint32_t wave0_newlines)
+{
+    return kSelfsyncList && fast_parse && !first_tile_of_span && wave0_newlines >= kSelfsyncNewlines;
+}
+MHX_HD bool selfsync_triple(const TileSmem &sm, uint32_t i, uint32_t check_limit)
+{ // i < kSelfsyncTriples; needs entries i .. i + 2 of the list
+    const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(sm.bytes);
+    // the three entries, then the three bytes, then one verdict without a branch: two LDS round trips, not one per test
+    // (p2 <= kTileBytes is staged whatever check_limit says; a byte beyond the limit is read and not used)
+    const uint32_t p0 = (uint32_t)ev[i] + 1u, p1 = (uint32_t)ev[i + 1u] + 1u, p2 = (uint32_t)ev[i + 2u] + 1u;
+    const uint32_t c0 = b[p0], c1 = b[p1], c2 = b[p2];
+    return (p2 < check_limit) & (c0 == '@') & (c1 != '@') & (c1 != '+') & (c2 == '+');
+}
+MHX_HD uint32_t selfsync_phase(uint32_t passing)
+{ // bit i: triple i passes
+    passing &= (1u << kSelfsyncTriples) - 1u;
+    if (!passing) return 4u;
+    return (4u - (((uint32_t)__builtin_ctz(passing) + 1u) & 3u)) & 3u;
+}
+// The tiles the four lanes cannot take -- under six newlines in the first wave's bytes -- are the ones on which the search
+// of the map is slow: it reads the map word by word, one LDS round trip each, up to the sixth newline, and through all 514
+// words where the tile has fewer (reads of 10 kb: every tile, in both launches; some 25 us a tile, more than its hash loop).
+// The list holds the same positions in order; behind ONE more barrier, which completes it, thread 0 takes the first six
+// from it and, where the tile has fewer, goes on in the two halo words it has in registers (the map holds them, the
+// list does not).  phase_selfsync's answer on the same bytes, position for position.  Needs parse_events_fit(tile_total).
+MHX_HD uint32_t phase_selfsync_list(const TileSmem &sm, const ThreadState &st0, uint32_t tile_total, uint32_t check_limit)
+{
+    const uint16_t *ev = reinterpret_cast<const uint16_t *>(sm.valid);
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(sm.bytes);
+    // both loops unrolled, every index of pos a constant: an array indexed at run time would live in scratch memory
+    uint64_t halo = make64(st0.hnl[0], st0.hnl[1]);
+    uint32_t pos[6], n = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 6; ++j) {
+        pos[j] = 0;
+        if (j < tile_total) {
+            pos[j] = ev[j];
+            n = j + 1u;
+        } else if (halo) {
+            pos[j] = (uint32_t)kTileBytes + (uint32_t)__builtin_ctzll(halo);
+            halo &= halo - 1u;
+            n = j + 1u;
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        if (i + 2u >= n) break;
+        const uint32_t p0 = pos[i] + 1u, p1 = pos[i + 1] + 1u, p2 = pos[i + 2] + 1u;
+        if (p2 >= check_limit) break;
+        if (b[p0] == '@' && b[p1] != '@' && b[p1] != '+' && b[p2] == '+') return (4u - ((i + 1u) & 3u)) & 3u;
+    }
+    return 4u;
 }
 
 // LineLenCheck's test for the sequence line that starts at tile position pos: does the record count?
