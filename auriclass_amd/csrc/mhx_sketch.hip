@@ -94,6 +94,17 @@ struct CandidateQueue {
         if (slot < cap) sm.list[first + slot] = (uint16_t)((group << 3) | (uint32_t)window);
     }
 };
+// ... of a line-relative item (process_line_rel_item, mhx_tile.h), which hands over its byte position: the window's
+// position is the sum, and that is the number the code above stands for
+struct CandidateQueueAt {
+    TileSmem &sm;
+    uint32_t first, cap;
+    __device__ __forceinline__ void operator()(uint32_t pos, int window) const
+    {
+        const uint32_t slot = atomicAdd(&sm.misc[7], 1u);
+        if (slot < cap) sm.list[first + slot] = (uint16_t)(pos + (uint32_t)window);
+    }
+};
 
 // ---------------------------------------------------------------------------------------
 // Decoupled look-back over per-tile newline counts (wave 0 of the block).
@@ -222,6 +233,8 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     unsigned long long *stats = reinterpret_cast<unsigned long long *>(a.stats) + (tile % kStatReplicas) * kStatCount;
     // the work list from the line list (phase_line_span / phase_line_items, mhx_tile.h): the forms line_items_form names
     constexpr bool kLineItems = !kParseLoops && line_items_form<K>(FMT, QUEUE);
+    // ... as line-relative items (phase_line_rel_items): full groups from the line's first start, the tails behind them
+    constexpr bool kLineRel = kLineItems && line_rel_form<K>(FMT, QUEUE);
     if (tid == 0) { sm.misc[3] = 0; sm.misc[4] = 0; sm.misc[5] = 0; sm.misc[7] = 0; }
 #ifdef MHX_STAMPS
     uint64_t stamp_prev = clock64();
@@ -325,7 +338,7 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
             // entry, in front of the stage loads of every tile, they cost a FASTQ of 10 kb reads 1.3 % (profiles/line_items_ab.txt, 4)
             const bool too_long = __ballot(line_span_too_long(span)) != 0ull; // wave-uniform
             if (tid == 0) { sm.misc[1] = 0u; sm.misc[6] = too_long ? 1u : 0u; }
-            items_at = atomicAdd(&sm.misc[1], span.ngroups); // behind lane 0's store in this wave's LDS order; a wave scan (DPP) and one LDS atomic
+            items_at = atomicAdd(&sm.misc[1], kLineRel ? line_rel_counts(span) : span.ngroups); // behind lane 0's store in this wave's LDS order; a wave scan (DPP) and one LDS atomic
         }
     } else {
         long_records = fast_parse
@@ -342,14 +355,27 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
         __syncthreads();
     }
 
-    uint32_t nitems = 0;
+    uint32_t nitems = 0, nfull = 0; // nfull: the full items in front of the tails (line-relative items)
+    bool by_rel = false;            // workgroup-uniform: this tile takes the line-relative items (line_rel_choose)
     if (kLineItems && by_lines) {
         if (tid < (int)kLineItemLines) {
             if (span.kmers) atomicAdd(&sm.misc[3], span.kmers);
-            phase_line_items(sm, span, items_at);
+            if (kLineRel) { // the packed totals: complete since the barrier above
+                const uint32_t total = sm.misc[1];
+                if (line_rel_choose(total)) phase_line_rel_items(sm, span, items_at, total);
+                else phase_line_items(sm, span, line_rel_aligned(items_at));
+            } else {
+                phase_line_items(sm, span, items_at);
+            }
         }
         __syncthreads();
         nitems = sm.misc[1];
+        if (kLineRel) { // (nfull: compared on the scalar unit, once a trip)
+            const uint32_t total = wave_uniform(nitems);
+            by_rel = line_rel_choose(total);
+            nfull = line_rel_full(total);
+            nitems = by_rel ? line_rel_items(total) : line_rel_aligned(total);
+        }
     } else {
         uint32_t items = 0;
         const uint32_t kmers = phase_runs<K>(sm, tid, items);
@@ -366,10 +392,20 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
     std::conditional_t<PROBE, ScreenProber, DeviceInserter> ins{reinterpret_cast<unsigned long long *>(a.keys), a.cnts, a.slot_mask, stats};
     const uint32_t qcap = (uint32_t)kGroupsPerTile - nitems; // QUEUE: the work list's unused tail holds the candidate queue
     CandidateQueue queue{sm, nitems, qcap};
+    CandidateQueueAt queue_at{sm, nitems, qcap};
     uint32_t ninsert = 0;
     const TailLutPtr lut = hot_tail_table<K>(); // once per workgroup, in front of the loop
     constexpr bool kPairs = pair_words_form<K>(FMT, QUEUE); // windows J and J + 4 share their funnel shifts (PairWords)
-    for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE, kPairs>(sm, sm.list[it], T, limit, ins, queue, lut);
+    if (kLineRel && by_rel) {
+        // a wave's trip is 64 consecutive entries, and a lane in it means lane 0 in it: the trip's first entry, on the scalar
+        // unit, tells the trips of tails alone, which stop behind their longest tail, from the hot body
+        for (uint32_t it = it0; it < nitems; it += it_step) {
+            if (MHX_UNLIKELY(wave_uniform(it) >= nfull)) ninsert += process_line_rel_item<K, QUEUE, kPairs, true>(sm, sm.list[it], T, limit, ins, queue_at, lut);
+            else ninsert += process_line_rel_item<K, QUEUE, kPairs, false>(sm, sm.list[it], T, limit, ins, queue_at, lut);
+        }
+    } else {
+        for (uint32_t it = it0; it < nitems; it += it_step) ninsert += process_group<K, QUEUE, kPairs>(sm, sm.list[it], T, limit, ins, queue, lut);
+    }
     if (QUEUE) {
         __syncthreads();
         const uint32_t ncand = sm.misc[7];
@@ -378,6 +414,16 @@ template <int K, int FMT, bool QUEUE, bool PROBE, bool SPLIT = false> __global__
         } else { // the queue overflowed (T still admits a large share of all hashes): every valid window, whole hash, exact test
             for (uint32_t it = it0; it < nitems; it += it_step) {
                 const uint32_t g = sm.list[it];
+                if (kLineRel && by_rel) { // a line-relative item: its mask, and its windows from its byte position on
+                    const uint32_t vm = line_rel_vm(sm, g);
+                    uint32_t vmask = vm & 0xFFu;
+                    while (vmask) {
+                        const uint32_t j = (uint32_t)__builtin_ctz(vmask);
+                        vmask &= vmask - 1u;
+                        ninsert += finish_candidate<K>(sm, (vm >> 8) + j, T, ins);
+                    }
+                    continue;
+                }
                 uint32_t vmask = reinterpret_cast<const uint8_t *>(sm.valid)[g];
                 while (vmask) {
                     const uint32_t j = (uint32_t)__builtin_ctz(vmask);

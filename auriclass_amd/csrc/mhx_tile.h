@@ -118,6 +118,15 @@ MHX_HD uint32_t wave_uniform(uint32_t v)
     return v;
 #endif
 }
+// is v true in any active lane?  (the host runs one lane at a time)
+MHX_HD bool wave_any(bool v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(v) != 0ull;
+#else
+    return v;
+#endif
+}
 MHX_HD uint32_t funnel_bits(uint32_t hi, uint32_t lo, uint32_t bit_shift)
 { // bit_shift in 0..31
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1006,6 +1015,82 @@ MHX_HD void phase_line_items(TileSmem &sm, const LineSpan &s, uint32_t at)
     vb[g1] = (uint8_t)last;
 }
 
+// ---- line-relative items: the groups of a sequence line counted from its first valid start ------------------------------
+// phase_line_items lists the tile-aligned groups a line's starts a .. pmax touch: (n + 7) / 8 of them on average for n starts
+// at a random offset, the first and the last with about seven dead windows between them, all of which the hash loop runs.
+// Grouped from a instead, the line has n >> 3 FULL items at the byte positions a, a + 8, .. with eight valid windows each and,
+// if c = n & 7 is not 0, one TAIL item at a + 8 (n >> 3) with its first c windows valid.  An entry of sm.list is the item's
+// byte position (14 bits; no multiple of 4 any more: line_rel_source) with kLineRelFull set for a full item, which has no
+// mask byte; a tail's mask (1 << c) - 1 is byte position >> 3 of sm.valid (for K >= 8 two sequence lines never share a group
+// and the positions of one line lie in it, so one writer per byte as before).  All full items of the tile stand in front of
+// all its tails, so a wave's trip of 64 consecutive entries is made of full items, or of tails alone, but for the one trip
+// that holds the boundary: the kernel runs a trip that begins among the full items on its hot body and a trip that begins
+// among the tails on one that stops behind the longest tail of the trip (process_group_regs, TAIL).
+// (Telling full from tail by the entry's index instead of a flag, with the trip's first index carried on the scalar unit and
+// the masks looked at only in the trip that holds the boundary, is 631 VALU a trip where this is 635 -- and takes the inline
+// kernels of K = 21 to 36 bytes of scratch in each of three spellings tried: profiles/line_rel_items_ab.txt, section 1.)
+// All offsets of a lane come from ONE sum: line_rel_counts packs three counts of the line into a word -- its full items (13
+// bits: at most 2048 in a tile), its tail (7 bits: at most 64) and how many aligned groups it touches beyond those, 0 or 1 (7
+// bits) -- the kernel's one LDS atomic adds the words up (a wave scan, as it was for the groups), and what it returns and leaves
+// behind are the packed offsets and the packed totals: of the new items, and, as their sum, of the aligned list.
+// Never more entries than the aligned list: (n >> 3) + (c != 0) <= the groups a .. pmax touch.  The bounds that select the
+// path (line_items_try, line_span_too_long: on the ALIGNED group count, which the span holds anyway) are the same.
+// THE CHOICE PER TILE (line_rel_choose, workgroup-uniform behind the barrier, from the totals): trips are whole, and a trip of
+// the new hot body is a few instructions longer than one over aligned items and carries two replayed reads, so the new items
+// pay only where they save a trip of the hot body: where the full items alone fill fewer trips of 64 than the aligned groups,
+// ceil(full / 64) < ceil(aligned / 64).  The tails then ride in the rest of the last trip or take a short one.  A tile that does
+// not save one -- 148-base reads at K = 21: 128 starts a line, 843 full items, no tails, 14 trips either way -- lists its
+// aligned groups (phase_line_items, at the offset line_rel_aligned of the same packed prefix) and runs the loop it ran before.
+constexpr uint32_t kLineRelFull = 0x8000u, kLineRelPos = 0x3FFFu;
+static_assert(kTileBytes - 1 <= (int)kLineRelPos, "an item's byte position fits under the flag");
+// which kernel forms of the line path take the items this way (-DMHX_LINE_ITEMS_ALIGNED: none, the A/B builds; the emulator
+// of tests/emul/line_rel_items_emul.cpp runs both item forms in one build), by the rule of line_items_form: 22 720 B of LDS, <= 72 VGPRs, no scratch, seven waves.
+// With the two further loop bodies in them the inline forms of K = 18, 23, 28, 30, 31 and 32 (the plain and the split kernel:
+// 8 to 36 bytes) and the queue forms of K = 26 (16 bytes) took scratch at 72 VGPRs in one of the two builds counted: they keep
+// the aligned items and are the kernels they were (profiles/line_rel_items_ab.txt, section 1).
+template <int K> constexpr bool line_rel_form(int fmt, bool queue)
+{
+#ifdef MHX_LINE_ITEMS_ALIGNED
+    return false;
+#else
+    return line_items_form<K>(fmt, queue) && !(queue ? K == 26 : K == 18 || K == 23 || K == 28 || K >= 30);
+#endif
+}
+MHX_HD uint32_t line_rel_counts(const LineSpan &s)
+{
+    const uint32_t full = s.kmers >> 3, tail = (s.kmers & 7u) ? 1u : 0u;
+    return full | (tail << 13) | ((s.ngroups - full - tail) << 20); // ngroups is ceil(kmers / 8) or one more
+}
+MHX_HD uint32_t line_rel_full(uint32_t packed) { return packed & 0x1FFFu; }
+MHX_HD uint32_t line_rel_tails(uint32_t packed) { return (packed >> 13) & 0x7Fu; }
+MHX_HD uint32_t line_rel_items(uint32_t packed) { return line_rel_full(packed) + line_rel_tails(packed); }
+MHX_HD uint32_t line_rel_aligned(uint32_t packed) { return line_rel_items(packed) + (packed >> 20); }
+MHX_HD bool line_rel_choose(uint32_t total)
+{
+#ifdef MHX_LINE_REL_ALWAYS   // A/B builds: every tile of the path takes the new items (profiles/line_rel_items_ab.txt, section 4)
+    return true;
+#else
+    return ((line_rel_full(total) + 63u) >> 6) < ((line_rel_aligned(total) + 63u) >> 6);
+#endif
+}
+// the line's items: at = the packed counts of the lanes in front, total = those of the whole tile
+MHX_HD void phase_line_rel_items(TileSmem &sm, const LineSpan &s, uint32_t at, uint32_t total)
+{
+    if (!s.kmers) return;
+    uint32_t pos = s.a, i = line_rel_full(at);
+    // one 16-bit store and two additions per trip, as written: left to itself the compiler makes eight entries at a time with
+    // packed arithmetic and stores them 16 bytes wide at addresses that are multiples of 2 (+145 VALU in the kernel's text)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+#endif
+    for (uint32_t n = s.kmers >> 3; n; --n, pos += 8u) sm.list[i++] = (uint16_t)(pos | kLineRelFull);
+    const uint32_t c = s.kmers & 7u;
+    if (c) {
+        sm.list[line_rel_full(total) + line_rel_tails(at)] = (uint16_t)pos;
+        reinterpret_cast<uint8_t *>(sm.valid)[pos >> 3] = (uint8_t)((1u << c) - 1u);
+    }
+}
+
 // P3: valid k-mer starts of this thread's positions -> sm.valid, #items -> sm.cnt
 template <int K> MHX_HD uint32_t phase_runs(TileSmem &sm, int tid, uint32_t &items_out)
 {
@@ -1442,7 +1527,9 @@ template <int K, int J, int ND> MHX_HD bool window_is_acgt(const uint32_t (&chun
 // lut: hot_tail_table<K>(), fetched by the caller in front of its loop over the groups (nullptr: formed here).
 // PAIRS: the words of windows J and J + 4 from one PairWords (the kernel forms pair_words_form names).  The windows then
 // run (0,4)(1,5)(2,6)(3,7); what is done with each stays per window.
-template <int K, bool QUEUE, bool PAIRS = false, class Ins, class Cand>
+// TAIL: a trip made of tail items alone (line-relative items, phase_line_rel_items: the masks are (1 << c) - 1): the windows
+// run 0..7 one by one, without pairs, and the wave leaves in front of the first window no lane of it has -- a scalar test.
+template <int K, bool QUEUE, bool PAIRS = false, bool TAIL = false, class Ins, class Cand>
 MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint32_t vm, uint64_t T, uint32_t limit, Ins &ins, Cand &cand,
                                    TailLutPtr lut)
 {
@@ -1456,7 +1543,7 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     if constexpr (kLut && !tail_digits_apply<K>()) lut = tail_lut_of<K>();
     const std::conditional_t<kLut && tail_digits_apply<K>(), TailDigits<K>, NoTailDigits> digits(U, R);
     constexpr bool kDigits = kLut && tail_digits_apply<K>();
-    constexpr bool kPairs = PAIRS && pair_words_apply<K>();
+    constexpr bool kPairs = PAIRS && !TAIL && pair_words_apply<K>();
 #define MHX_WINDOW(J) MHX_WINDOW_OF(J, (window_partial_hash<K, J, ND, kLut>(U, R, digits, lut)))
 #define MHX_PAIR(J)                                                                           \
     {                                                                                         \
@@ -1466,6 +1553,7 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
     }
 #define MHX_WINDOW_OF(J, HASH)                                                                \
     {                                                                                         \
+        if constexpr (TAIL && (J) > 0) { if (!wave_any(((vm & 0xFFu) >> (J)) != 0u)) goto windows_done; } \
         const Murmur3Tail tail = HASH;                                                        \
         /* necessary condition of h <= T, see Murmur3Tail (32-bit hashes: the exact low word) */ \
         const uint32_t low = kHash32 ? tail.low32() : 0u;                                     \
@@ -1488,6 +1576,7 @@ MHX_HD uint32_t process_group_regs(const uint32_t (&src)[GroupGeom<K>::ND], uint
 #undef MHX_PAIR
 #undef MHX_WINDOW
     static_assert(kGroup == 8, "process_group unrolls 8 windows");
+windows_done:
     return ninserted;
 }
 
@@ -1519,6 +1608,36 @@ template <int K, bool QUEUE, class Ins, class Cand>
 MHX_HD uint32_t process_group(const TileSmem &sm, uint32_t g, uint64_t T, uint32_t limit, Ins &ins, Cand &cand)
 {
     return process_group<K, QUEUE>(sm, g, T, limit, ins, cand, hot_tail_table<K>());
+}
+
+// ---- a line-relative item (phase_line_rel_items) of a staged tile --------------------------------------------------------
+// The item's 4 ND source bytes begin at its byte position, which is no multiple of 4 any more (at most kTileBytes - 1, and
+// 4 ND <= 40: inside the halo).  One copy of 4 ND bytes at alignment 1, which the compiler makes wide DS reads of at the byte
+// address (ds_read_b96 + ds_read_b128 at K = 21).  Of the three spellings measured at the bench setting this is the fastest
+// (profiles/line_rel_items_ab.txt, section 5): ND + 1 aligned dwords with one v_alignbyte_b32 per source dword gave about a
+// quarter of the gain back, one dword read per source dword at the byte address was 4 % slower than the commit before.
+template <int ND> MHX_HD void line_rel_source(const TileSmem &sm, uint32_t pos, uint32_t (&src)[ND])
+{
+    __builtin_memcpy(src, reinterpret_cast<const uint8_t *>(sm.bytes) + pos, 4 * ND);
+}
+// the item's mask and position as process_group_regs takes them (vm: the mask below the position, which stands where the
+// group's number stood: a candidate of window J is the byte position (vm >> 8) + J)
+MHX_HD uint32_t line_rel_vm(const TileSmem &sm, uint32_t entry)
+{
+    const uint32_t pos = entry & kLineRelPos;
+    uint32_t mask = 0xFFu;
+    if (!(entry & kLineRelFull)) mask = reinterpret_cast<const uint8_t *>(sm.valid)[pos >> 3];
+    return mask | (pos << 8);
+}
+template <int K, bool QUEUE, bool PAIRS, bool TAIL, class Ins, class Cand>
+MHX_HD uint32_t process_line_rel_item(const TileSmem &sm, uint32_t entry, uint64_t T, uint32_t limit, Ins &ins, Cand &cand, TailLutPtr lut)
+{
+    constexpr int ND = GroupGeom<K>::ND;
+    static_assert(kTileBytes - 1 + 4 * ND <= kTileBytes + kHaloBytes, "an item's source bytes are staged");
+    const uint32_t vm = line_rel_vm(sm, entry);
+    uint32_t src[ND];
+    line_rel_source<ND>(sm, vm >> 8, src);
+    return process_group_regs<K, QUEUE, PAIRS, TAIL>(src, vm, T, limit, ins, cand, lut);
 }
 
 // A queued candidate (code = (group << 3) | window), finished from the staged bytes with a window offset known only at
