@@ -140,11 +140,8 @@ int contain_rows(const uint64_t *const *q_rows, const uint64_t *q, const uint32_
     if (won) { c.won = (uint32_t *)(in.room + o_won); c.ref_length = ref_length ? (const uint64_t *)(in.room + o_length) : nullptr; }
     rc = contain_device(c);
     if (rc) return rc;
-    if (won && hipMemcpy(won, c.won, cells * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy failed in dist_contain_winner");
-    if (hipMemcpy(shared, c.shared, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(n_qry, c.n_qry, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(n_ref, c.n_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(MHX_E_HIP, "D2H copy failed in dist_contain");
-    return MHX_OK;
+    if (won) rc = read_back("dist_contain_winner", {{won, c.won, cells * 4}});
+    return rc ? rc : read_back("dist_contain", {{shared, c.shared, cells * 4}, {n_qry, c.n_qry, cells * 4}, {n_ref, c.n_ref, cells * 4}});
 }
 } // namespace mhx
 

@@ -131,10 +131,9 @@ int contain_search_host(const uint64_t *q, const uint64_t *const *q_rows, const 
     c.hit_n_qry = (uint32_t *)(in.room + o_nqry); c.n_hits = (uint32_t *)(in.room + o_n);
     rc = contain_search_device(c);
     if (rc) return rc;
-    if (hipMemcpy(hit_ref, c.hit_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hit_shared, c.hit_shared, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hit_n_ref, c.hit_n_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hit_n_qry, c.hit_n_qry, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(n_hits, c.n_hits, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(MHX_E_HIP, "D2H copy failed in dist_contain_search");
+    rc = read_back("dist_contain_search", {{hit_ref, c.hit_ref, cells * 4}, {hit_shared, c.hit_shared, cells * 4}, {hit_n_ref, c.hit_n_ref, cells * 4}, {hit_n_qry, c.hit_n_qry, cells * 4},
+                                            {n_hits, c.n_hits, (size_t)nq * 4}});
+    if (rc) return rc;
     for (uint32_t i = 0; i < nq; ++i) { // what the staging held behind a list's end is not part of the result
         if (n_hits[i] > top) return fail(MHX_E_INTERNAL, "containment search list of query %u longer than top", i);
         for (size_t t = (size_t)i * top + n_hits[i]; t < (size_t)(i + 1) * top; ++t) hit_ref[t] = hit_shared[t] = hit_n_ref[t] = hit_n_qry[t] = 0;

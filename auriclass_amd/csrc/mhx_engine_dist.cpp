@@ -142,19 +142,12 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     if (!fast) { le = launch_dist_pairs(a, g.stream); g.last_dist_fallbacks = -1; }
     if (fast) g.last_dist_fallbacks = 0;
     g.last_dist_ranges = 0;
-    for (uint32_t b0 = 0; fast && b0 < nblocks && le == hipSuccess; b0 += kBlockGroup) {
-        const uint32_t b1 = std::min(nblocks, b0 + kBlockGroup);
-        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b) {
-            w.params = d_params + 2 * (b - b0);
-            le = launch_dist_ranges(block_args(b), w, g.stream);
-        }
-        if (le != hipSuccess) break;
-        std::vector<uint32_t> flags((size_t)(b1 - b0) * 2);
-        if (hipMemcpyAsync(flags.data(), d_params, flags.size() * 4, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
-            hipStreamSynchronize(g.stream) != hipSuccess)
-            return fail(MHX_E_HIP, "dist kernel failed");
-        for (uint32_t b = b0; b < b1 && le == hipSuccess; ++b)
-            if (flags[2 * (b - b0) + 1]) { le = launch_dist_pairs(block_args(b), g.stream); ++g.last_dist_fallbacks; } // a value range overflowed the LDS table
+    if (fast) {
+        const int rc = run_block_groups(
+            BlockGroups{nblocks, true, d_params, std::min(nblocks, kBlockGroup), false, false, true, "dist"}, le,
+            [&](uint64_t b, uint32_t *params) { w.params = params; return launch_dist_ranges(block_args((uint32_t)b), w, g.stream); },
+            [&](uint64_t b) { return launch_dist_pairs(block_args((uint32_t)b), g.stream); });
+        if (rc) return rc;
     }
     hipEventRecord(g.ev1, g.stream);
     if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges; // (0: the generic kernel did all the work)
@@ -170,17 +163,7 @@ static int dist_batch_core(const uint64_t *q, const uint32_t *q_len, uint32_t nq
     g.last_dist_ms = ms;
     if (se != hipSuccess) return fail(MHX_E_HIP, "dist kernel failed: %s", hipGetErrorString(se));
     if (!device_ptrs && dist) {
-        for (uint64_t i = 0; i < pairs; ++i) {
-            double d;
-            if (common[i] == denom[i]) d = 0.0;
-            else if (common[i] == 0) d = 1.0;
-            else {
-                const double j = (double)common[i] / (double)denom[i];
-                d = -log(2.0 * j / (1.0 + j)) / (double)k;
-                if (d > 1.0) d = 1.0;
-            }
-            dist[i] = d;
-        }
+        for (uint64_t i = 0; i < pairs; ++i) dist[i] = tri_distance(common[i], denom[i], k);
     }
     return MHX_OK;
 }

@@ -56,45 +56,38 @@ extern "C" int mhx_dist_linkage(const uint64_t *rows, const uint32_t *len, uint3
         if (s >= kMstMaxS) return fail(MHX_E_ARG, "sketch size too large for the linkage (%u, below %u)", s, kMstMaxS);
         if (done) return MHX_OK; // no pair, no merge
         if (!merge_a || !merge_b || !size || !num || !den) return fail(MHX_E_ARG, "null argument");
-        const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-        uint64_t budget_mb = 4096;
-        if (const char *e = getenv("MHX_LINKAGE_STORE_MB")) { const long long v = atoll(e); if (v >= 0) budget_mb = (uint64_t)v; }
-        if (8 * pairs > budget_mb << 20)
-            return fail(MHX_E_CAPACITY, "the pair words of %u lists (%llu bytes) do not fit MHX_LINKAGE_STORE_MB = %llu", n, (unsigned long long)(8 * pairs),
-                        (unsigned long long)budget_mb);
-        // staging: [size][nn][list][ctl, total], host form: [merge_a][merge_b][size][num][den], then rows and lengths
-        const size_t bn = up256((size_t)n * 4), be = up256(((size_t)n - 1) * 4), be8 = up256(((size_t)n - 1) * 8);
-        const size_t state = 3 * bn + 256;
+        rc = store_fits("MHX_LINKAGE_STORE_MB", n);
+        if (rc) return rc;
+        const size_t m = (size_t)n - 1;
+        Carve in; // staging: [size][nn][list][ctl, total], host form: [merge_a][merge_b][size][num][den], then rows and lengths
+        const size_t o_size = in.take((size_t)n * 4), o_nn = in.take((size_t)n * 4), o_list = in.take((size_t)n * 4), o_ctl = in.take(256);
+        const size_t o_a = in.take(device_ptrs ? 0 : m * 4), o_b = in.take(device_ptrs ? 0 : m * 4), o_sz = in.take(device_ptrs ? 0 : m * 4);
+        const size_t o_num = in.take(device_ptrs ? 0 : m * 8), o_den = in.take(device_ptrs ? 0 : m * 8);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? state : state + 3 * be + 2 * be8, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         LinkArgs a{};
-        a.size = (uint32_t *)base; a.nn = (uint32_t *)(base + bn); a.list = (uint32_t *)(base + 2 * bn);
-        a.ctl = (uint32_t *)(base + 3 * bn); a.total = (unsigned long long *)(base + 3 * bn + 64);
+        a.size = (uint32_t *)(base + o_size); a.nn = (uint32_t *)(base + o_nn); a.list = (uint32_t *)(base + o_list);
+        a.ctl = (uint32_t *)(base + o_ctl); a.total = (unsigned long long *)(base + o_ctl + 64);
         a.n = n; a.linkage = linkage; a.k = k;
         if (device_ptrs) { a.merge_a = merge_a; a.merge_b = merge_b; a.size_out = size; a.num = num; a.den = den; a.dist = dist; }
         else {
-            uint8_t *out = base + state;
-            a.merge_a = (uint32_t *)out; a.merge_b = (uint32_t *)(out + be); a.size_out = (uint32_t *)(out + 2 * be);
-            a.num = (uint64_t *)(out + 3 * be); a.den = (uint64_t *)(out + 3 * be + be8);
+            a.merge_a = (uint32_t *)(base + o_a); a.merge_b = (uint32_t *)(base + o_b); a.size_out = (uint32_t *)(base + o_sz);
+            a.num = (uint64_t *)(base + o_num); a.den = (uint64_t *)(base + o_den);
             a.dist = nullptr; // heights in host arithmetic below
         }
-        DevArray<uint64_t> words; // released when the call returns
-        DevArray<uint8_t> packed; // the triangle's two arrays: released behind the init pass
-        const size_t bp = up256((size_t)pairs * 4);
-        if (words.grow(pairs, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the pair words of the linkage (%llu bytes)", (unsigned long long)(8 * pairs));
-        if (packed.grow(2 * bp, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the stored pairs of the linkage (%zu bytes)", 2 * bp);
-        a.words = words;
-        uint32_t *p_common = (uint32_t *)(uint8_t *)packed, *p_denom = (uint32_t *)((uint8_t *)packed + bp);
-        rc = run_dense(c, p_common, p_denom, nullptr);
+        StoredTriangle tri; // the words: released when the call returns; the triangle's two arrays: behind the init pass
+        rc = tri.alloc((uint64_t)n * (n - 1) / 2, "the linkage", true);
         if (rc) return rc;
-        const double tri_ms = g.last_dist_ms;
-        hipEventRecord(g.ev0, g.stream);
-        hipError_t le = launch_link_init(a, p_common, p_denom, g.stream);
+        a.words = tri.words;
+        rc = run_dense(c, tri.common, tri.denom, nullptr);
+        if (rc) return rc;
+        StepsClock clock;
+        hipError_t le = launch_link_init(a, tri.common, tri.denom, g.stream);
         if (le == hipSuccess) le = launch_link_rescan(a, g.stream);
         if (le == hipSuccess && hipStreamSynchronize(g.stream) != hipSuccess) return fail(MHX_E_HIP, "linkage init kernel failed");
-        packed.reset();
+        tri.reset();
         // the steps: nothing comes back between them
         for (uint32_t t = 0; t + 1 < n && le == hipSuccess; ++t) {
             le = launch_link_pick(a, t, g.stream);
@@ -102,25 +95,20 @@ extern "C" int mhx_dist_linkage(const uint64_t *rows, const uint32_t *len, uint3
             if (le == hipSuccess) le = launch_link_rescan(a, g.stream);
         }
         if (le != hipSuccess) return fail(MHX_E_HIP, "linkage kernel launch failed: %s", hipGetErrorString(le));
-        hipEventRecord(g.ev1, g.stream);
+        clock.stop();
         uint32_t ctl[6] = {0, 0, 0, 0, 0, 0};
         unsigned long long total = 0;
         hipError_t se = hipMemcpyAsync(ctl, a.ctl, sizeof ctl, hipMemcpyDeviceToHost, g.stream);
         if (se == hipSuccess) se = hipMemcpyAsync(&total, a.total, 8, hipMemcpyDeviceToHost, g.stream);
         if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
         if (se != hipSuccess) return fail(MHX_E_HIP, "linkage kernel failed: %s", hipGetErrorString(se));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, g.ev0, g.ev1);
-        g.last_dist_ms = tri_ms + ms; // the triangle and the steps (the release of the triangle's arrays between them included)
+        clock.note(); // the triangle and the steps (the release of the triangle's arrays between them included)
         total += ctl[4];
         g.last_linkage_rescans = total > (unsigned long long)INT_MAX ? INT_MAX : (int)total;
         if (ctl[5]) return fail(MHX_E_INTERNAL, "a linkage step found no pair to merge");
         if (device_ptrs) return MHX_OK;
-        const size_t m = (size_t)n - 1;
-        if (hipMemcpy(merge_a, a.merge_a, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(merge_b, a.merge_b, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(size, a.size_out, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(num, a.num, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(den, a.den, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(MHX_E_HIP, "D2H copy failed in dist_linkage");
+        rc = read_back("dist_linkage", {{merge_a, a.merge_a, m * 4}, {merge_b, a.merge_b, m * 4}, {size, a.size_out, m * 4}, {num, a.num, m * 8}, {den, a.den, m * 8}});
+        if (rc) return rc;
         if (dist)
             for (size_t t = 0; t < m; ++t) dist[t] = link_height(linkage, num[t], den[t], k);
         return MHX_OK;

@@ -69,18 +69,20 @@ extern "C" int mhx_dist_medoids(const uint64_t *rows, const uint32_t *len, uint3
         const uint32_t bad = medoid_first_bad_label(h_label, n);
         if (bad < n) return fail(MHX_E_ARG, "label[%u] = %u is not the lowest index of a cluster", bad, h_label[bad]);
         // staging: [sum][best] in 64-bit words, [label][medoid][common][denom], then (host form) rows and lengths
-        const size_t b8 = up256((size_t)n * 8), b4 = up256((size_t)n * 4);
+        Carve in;
+        const size_t o_sum = in.take((size_t)n * 8), o_best = in.take((size_t)n * 8);
+        const size_t o_label = in.take((size_t)n * 4), o_medoid = in.take((size_t)n * 4), o_common = in.take((size_t)n * 4), o_denom = in.take((size_t)n * 4);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, 2 * b8 + 4 * b4, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         MedoidRun m{};
         m.h_label = h_label;
-        m.sum = (unsigned long long *)base;
-        m.best = (unsigned long long *)(base + b8);
-        uint32_t *d_label = (uint32_t *)(base + 2 * b8);
-        m.medoid = (uint32_t *)(base + 2 * b8 + b4);
-        if (common) { m.common = (uint32_t *)(base + 2 * b8 + 2 * b4); m.denom = (uint32_t *)(base + 2 * b8 + 3 * b4); }
+        m.sum = (unsigned long long *)(base + o_sum);
+        m.best = (unsigned long long *)(base + o_best);
+        uint32_t *d_label = (uint32_t *)(base + o_label);
+        m.medoid = (uint32_t *)(base + o_medoid);
+        if (common) { m.common = (uint32_t *)(base + o_common); m.denom = (uint32_t *)(base + o_denom); }
         if (device_ptrs) {
             m.label = label; m.medoid = medoid;
             if (sum) m.sum = (unsigned long long *)sum;
@@ -91,12 +93,8 @@ extern "C" int mhx_dist_medoids(const uint64_t *rows, const uint32_t *len, uint3
         }
         rc = run_medoid(c, m);
         if (rc || device_ptrs) return rc;
-        if (hipMemcpy(medoid, m.medoid, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            (sum && hipMemcpy(sum, m.sum, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (common && (hipMemcpy(common, m.common, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                        hipMemcpy(denom, m.denom, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)))
-            return fail(MHX_E_HIP, "D2H copy failed in dist_medoids");
-        return MHX_OK;
+        return read_back("dist_medoids", {{medoid, m.medoid, (size_t)n * 4}, {sum, m.sum, (size_t)n * 8, sum != nullptr},
+                                          {common, m.common, (size_t)n * 4, common != nullptr}, {denom, m.denom, (size_t)n * 4, common != nullptr}});
     });
 }
 
@@ -115,14 +113,15 @@ extern "C" int mhx_dist_to(const uint64_t *rows, const uint32_t *len, uint32_t n
         if (rc) return rc;
         for (uint32_t i = 0; i < n; ++i)
             if (h_target[i] >= n) return fail(MHX_E_ARG, "target[%u] = %u is no index of the set", i, h_target[i]);
-        const size_t b4 = up256((size_t)n * 4);
+        Carve in; // host form: [target][common][denom], then rows and lengths
+        const size_t b4 = device_ptrs ? 0 : (size_t)n * 4, o_target = in.take(b4), o_common = in.take(b4), o_denom = in.take(b4);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? 0 : 3 * b4, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         DistToArgs a{c.rows, c.len, n, stride, s, target, common, denom};
         if (!device_ptrs) {
-            a.target = (uint32_t *)base; a.common = (uint32_t *)(base + b4); a.denom = (uint32_t *)(base + 2 * b4);
+            a.target = (uint32_t *)(base + o_target); a.common = (uint32_t *)(base + o_common); a.denom = (uint32_t *)(base + o_denom);
             if (hipMemcpyAsync((void *)a.target, target, (size_t)n * 4, hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail(MHX_E_HIP, "H2D copy of the targets failed");
         }
         hipEventRecord(g.ev0, g.stream);
@@ -134,8 +133,6 @@ extern "C" int mhx_dist_to(const uint64_t *rows, const uint32_t *len, uint32_t n
         hipEventElapsedTime(&ms, g.ev0, g.ev1);
         g.last_dist_ms = ms;
         if (device_ptrs) return MHX_OK;
-        if (hipMemcpy(common, a.common, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(denom, a.denom, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(MHX_E_HIP, "D2H copy failed in dist_to");
-        return MHX_OK;
+        return read_back("dist_to", {{common, a.common, b4}, {denom, a.denom, b4}});
     });
 }

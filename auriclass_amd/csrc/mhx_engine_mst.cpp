@@ -105,48 +105,44 @@ extern "C" int mhx_dist_mst(const uint64_t *rows, const uint32_t *len, uint32_t 
         if (done) return MHX_OK; // no pair, no edge
         if (!edge_i || !edge_j || !common || !denom) return fail(MHX_E_ARG, "null argument");
         const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-        uint64_t budget_mb = 4096;
-        if (const char *e = getenv("MHX_MST_STORE_MB")) { const long long v = atoll(e); if (v >= 0) budget_mb = (uint64_t)v; }
-        bool stored = 8 * pairs <= budget_mb << 20;
+        bool stored = 8 * pairs <= store_budget_mb("MHX_MST_STORE_MB") << 20;
         if (const char *e = getenv("MHX_MST_STORE")) stored = strcmp(e, "0") != 0;
         // staging: [best][winner][parent][comp][counters], host form: [the four edge arrays], then rows and lengths
-        const size_t bn = up256((size_t)n * 4), be = up256(((size_t)n - 1) * 4);
-        const size_t state = 2 * bn + 3 * bn + 256;
+        const size_t e_n = (size_t)n - 1;
+        Carve in;
+        const size_t o_best = in.take((size_t)n * 8), o_winner = in.take((size_t)n * 4), o_parent = in.take((size_t)n * 4), o_comp = in.take((size_t)n * 4);
+        const size_t o_counters = in.take(16);
+        const size_t o_i = in.take(device_ptrs ? 0 : e_n * 4), o_j = in.take(device_ptrs ? 0 : e_n * 4);
+        const size_t o_common = in.take(device_ptrs ? 0 : e_n * 4), o_denom = in.take(device_ptrs ? 0 : e_n * 4);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? state : state + 4 * be, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         MstRun m{};
-        m.best = (uint64_t *)base;
-        m.winner = (uint32_t *)(base + 2 * bn); m.parent = (uint32_t *)(base + 3 * bn); m.comp = (uint32_t *)(base + 4 * bn);
-        m.counters = (unsigned long long *)(base + 5 * bn);
+        m.best = (uint64_t *)(base + o_best);
+        m.winner = (uint32_t *)(base + o_winner); m.parent = (uint32_t *)(base + o_parent); m.comp = (uint32_t *)(base + o_comp);
+        m.counters = (unsigned long long *)(base + o_counters);
         m.n = n; m.k = k;
         if (device_ptrs) { m.edge_i = edge_i; m.edge_j = edge_j; m.common = common; m.denom = denom; m.dist = dist; }
         else {
-            uint8_t *out = base + state;
-            m.edge_i = (uint32_t *)out; m.edge_j = (uint32_t *)(out + be); m.common = (uint32_t *)(out + 2 * be); m.denom = (uint32_t *)(out + 3 * be);
+            m.edge_i = (uint32_t *)(base + o_i); m.edge_j = (uint32_t *)(base + o_j); m.common = (uint32_t *)(base + o_common); m.denom = (uint32_t *)(base + o_denom);
             m.dist = nullptr; // distances in host libm below
         }
         if (stored) {
-            DevArray<uint8_t> packed; // released when the call returns
-            const size_t bp = up256((size_t)pairs * 4);
-            if (packed.grow(2 * bp, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the stored pairs of the tree (%zu bytes)", 2 * bp);
-            uint32_t *p_common = (uint32_t *)(uint8_t *)packed, *p_denom = (uint32_t *)((uint8_t *)packed + bp);
-            rc = run_dense(c, p_common, p_denom, nullptr);
+            StoredTriangle tri; // released when the call returns
+            rc = tri.alloc(pairs, "the tree", false);
+            if (rc == MHX_OK) rc = run_dense(c, tri.common, tri.denom, nullptr);
             if (rc) return rc;
             MstScan sc{};
-            sc.common = p_common; sc.denom = p_denom; sc.n = n; sc.comp = m.comp; sc.best = m.best;
-            const double tri_ms = g.last_dist_ms;
-            hipEventRecord(g.ev0, g.stream);
+            sc.common = tri.common; sc.denom = tri.denom; sc.n = n; sc.comp = m.comp; sc.best = m.best;
+            StepsClock clock;
             hipError_t le = mst_begin(m);
             rc = mst_rounds(m, le, [&](uint32_t) { le = launch_mst_scan(sc, g.stream); return MHX_OK; });
             if (rc) return rc;
             if (le != hipSuccess) return fail(MHX_E_HIP, "tree kernel launch failed: %s", hipGetErrorString(le));
-            hipEventRecord(g.ev1, g.stream);
+            clock.stop();
             if (hipStreamSynchronize(g.stream) != hipSuccess) return fail(MHX_E_HIP, "tree kernel failed");
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, g.ev0, g.ev1);
-            g.last_dist_ms = tri_ms + ms; // the triangle and the rounds; the recomputed source: the whole call
+            clock.note(); // the triangle and the rounds; the recomputed source: the whole call
         } else {
             const hipError_t le = mst_begin(m);
             if (le != hipSuccess) return fail(MHX_E_HIP, "tree kernel launch failed: %s", hipGetErrorString(le));
@@ -157,11 +153,9 @@ extern "C" int mhx_dist_mst(const uint64_t *rows, const uint32_t *len, uint32_t 
         g.last_mst_stored = stored ? 1 : 0;
         if (m.components != 1 || m.appended != (uint64_t)n - 1) return fail(MHX_E_INTERNAL, "the tree has %llu edges for %u lists", (unsigned long long)m.appended, n);
         if (device_ptrs) return MHX_OK; // the edges lie where the caller wants them, in the order of arrival
-        const size_t e_n = (size_t)n - 1;
         std::vector<uint32_t> ei(e_n), ej(e_n), ec(e_n), ed(e_n);
-        if (hipMemcpy(ei.data(), m.edge_i, e_n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ej.data(), m.edge_j, e_n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(ec.data(), m.common, e_n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ed.data(), m.denom, e_n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(MHX_E_HIP, "D2H copy failed in dist_mst");
+        rc = read_back("dist_mst", {{ei.data(), m.edge_i, e_n * 4}, {ej.data(), m.edge_j, e_n * 4}, {ec.data(), m.common, e_n * 4}, {ed.data(), m.denom, e_n * 4}});
+        if (rc) return rc;
         // the edge order: the merge order of the dendrogram
         std::vector<size_t> order(e_n);
         std::iota(order.begin(), order.end(), (size_t)0);

@@ -28,53 +28,46 @@ int nj_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t str
     return MHX_OK;
 }
 
-int nj_budget(uint32_t n)
+NjStateAt::NjStateAt(Carve &in, uint32_t n)
 {
-    const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-    uint64_t budget_mb = 4096;
-    if (const char *e = getenv("MHX_LINKAGE_STORE_MB")) { const long long v = atoll(e); if (v >= 0) budget_mb = (uint64_t)v; }
-    if (8 * pairs > budget_mb << 20)
-        return fail(MHX_E_CAPACITY, "the pair words of %u lists (%llu bytes) do not fit MHX_LINKAGE_STORE_MB = %llu", n, (unsigned long long)(8 * pairs),
-                    (unsigned long long)budget_mb);
-    return MHX_OK;
+    o_r = in.take((size_t)n * 8);
+    for (size_t &o : o_act) o = in.take((size_t)n * 4);
+    for (size_t &o : o_pre) o = in.take(((size_t)n + 1) * 8);
+    o_cand = in.take((size_t)kNjMaxBlocks * sizeof(NjCand));
+    o_ctl = in.take(256);
 }
-
-size_t nj_state_bytes(uint32_t n)
+void NjStateAt::place(NjArgs &a, uint8_t *base, uint32_t n, int k) const
 {
-    return up256((size_t)n * 8) + 2 * up256((size_t)n * 4) + 2 * up256(((size_t)n + 1) * 8) + up256((size_t)kNjMaxBlocks * sizeof(NjCand)) + 256;
-}
-size_t nj_records_bytes(uint32_t n) { return 2 * up256(((size_t)n - 1) * 4) + 3 * up256(((size_t)n - 1) * 8); }
-
-void nj_place_state(NjArgs &a, uint8_t *at, uint32_t n, int k)
-{
-    const size_t bn = up256((size_t)n * 4), bn8 = up256((size_t)n * 8), bp8 = up256(((size_t)n + 1) * 8), bc = up256((size_t)kNjMaxBlocks * sizeof(NjCand));
-    a.r = (uint64_t *)at;
-    a.act[0] = (uint32_t *)(at + bn8); a.act[1] = (uint32_t *)(at + bn8 + bn);
-    a.pre[0] = (uint64_t *)(at + bn8 + 2 * bn); a.pre[1] = (uint64_t *)(at + bn8 + 2 * bn + bp8);
-    a.cand = (NjCand *)(at + bn8 + 2 * bn + 2 * bp8);
-    a.ctl = (uint64_t *)(at + bn8 + 2 * bn + 2 * bp8 + bc);
+    a.r = (uint64_t *)(base + o_r);
+    for (int i = 0; i < 2; ++i) { a.act[i] = (uint32_t *)(base + o_act[i]); a.pre[i] = (uint64_t *)(base + o_pre[i]); }
+    a.cand = (NjCand *)(base + o_cand);
+    a.ctl = (uint64_t *)(base + o_ctl);
     a.n = n; a.k = k;
 }
-void nj_place_records(NjArgs &a, uint8_t *at, uint32_t n)
+NjRecordsAt::NjRecordsAt(Carve &in, uint32_t n, bool wanted)
 {
-    const size_t be = up256(((size_t)n - 1) * 4), be8 = up256(((size_t)n - 1) * 8);
-    a.join_a = (uint32_t *)at; a.join_b = (uint32_t *)(at + be);
-    a.d = (uint64_t *)(at + 2 * be); a.r_a = (uint64_t *)(at + 2 * be + be8); a.r_b = (uint64_t *)(at + 2 * be + 2 * be8);
+    const size_t m = wanted ? (size_t)n - 1 : 0;
+    o_a = in.take(m * 4); o_b = in.take(m * 4);
+    o_d = in.take(m * 8); o_ra = in.take(m * 8); o_rb = in.take(m * 8);
+}
+void NjRecordsAt::place(NjArgs &a, uint8_t *base) const
+{
+    a.join_a = (uint32_t *)(base + o_a); a.join_b = (uint32_t *)(base + o_b);
+    a.d = (uint64_t *)(base + o_d); a.r_a = (uint64_t *)(base + o_ra); a.r_b = (uint64_t *)(base + o_rb);
 }
 
 // The dense mode writes the packed common / denom once, the init pass turns them into the pair words and the row sums, and
 // every join is a scan of the active rows, the pick by one workgroup and an update by one thread per node.
-int nj_tree(const TriCall &c, const NjArgs &a, uint32_t *p_common, uint32_t *p_denom, DevArray<uint8_t> *release, uint64_t *clamps)
+int nj_tree(const TriCall &c, const NjArgs &a, StoredTriangle &tri, bool release, uint64_t *clamps)
 {
     const uint32_t n = c.n;
-    int rc = run_dense(c, p_common, p_denom, nullptr);
+    int rc = run_dense(c, tri.common, tri.denom, nullptr);
     if (rc) return rc;
-    const double tri_ms = g.last_dist_ms;
-    hipEventRecord(g.ev0, g.stream);
-    hipError_t le = launch_nj_init(a, p_common, p_denom, g.stream);
+    StepsClock clock;
+    hipError_t le = launch_nj_init(a, tri.common, tri.denom, g.stream);
     if (release) {
         if (le == hipSuccess && hipStreamSynchronize(g.stream) != hipSuccess) return fail(MHX_E_HIP, "neighbour joining init kernel failed");
-        release->reset();
+        tri.reset();
     }
     // the joins: nothing comes back between them
     for (uint32_t t = 0; t + 1 < n && le == hipSuccess; ++t) {
@@ -83,14 +76,12 @@ int nj_tree(const TriCall &c, const NjArgs &a, uint32_t *p_common, uint32_t *p_d
         if (le == hipSuccess && n - t > 2) le = launch_nj_update(a, t, g.stream);
     }
     if (le != hipSuccess) return fail(MHX_E_HIP, "neighbour joining kernel launch failed: %s", hipGetErrorString(le));
-    hipEventRecord(g.ev1, g.stream);
+    clock.stop();
     uint64_t ctl[6] = {0, 0, 0, 0, 0, 0};
     hipError_t se = hipMemcpyAsync(ctl, a.ctl, sizeof ctl, hipMemcpyDeviceToHost, g.stream);
     if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
     if (se != hipSuccess) return fail(MHX_E_HIP, "neighbour joining kernel failed: %s", hipGetErrorString(se));
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, g.ev0, g.ev1);
-    g.last_dist_ms = tri_ms + ms; // the triangle and the joins (the release of the triangle's arrays between them included)
+    clock.note(); // the triangle and the joins (the release of the triangle's arrays between them included)
     *clamps = ctl[4];
     if (ctl[5]) return fail(MHX_E_INTERNAL, "a join of neighbour joining found no pair");
     return MHX_OK;
@@ -111,37 +102,31 @@ extern "C" int mhx_dist_nj(const uint64_t *rows, const uint32_t *len, uint32_t n
         if (rc) return rc;
         if (done) return MHX_OK; // no pair, no join
         if (!join_a || !join_b || !d || !r_a || !r_b || !len_a != !len_b) return fail(MHX_E_ARG, "null argument");
-        rc = nj_budget(n);
+        rc = store_fits("MHX_LINKAGE_STORE_MB", n);
         if (rc) return rc;
-        const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-        // staging: the state, host form: the records behind it, then rows and lengths
-        const size_t state = nj_state_bytes(n);
+        Carve in; // staging: the state, host form: the records behind it, then rows and lengths
+        const NjStateAt state(in, n);
+        const NjRecordsAt records(in, n, !device_ptrs);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? state : state + nj_records_bytes(n), &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         NjArgs a{};
-        nj_place_state(a, base, n, k);
+        state.place(a, base, n, k);
         if (device_ptrs) { a.join_a = join_a; a.join_b = join_b; a.d = d; a.r_a = r_a; a.r_b = r_b; a.len_a = len_a; a.len_b = len_b; }
         else {
-            nj_place_records(a, base + state, n);
+            records.place(a, base);
             a.len_a = a.len_b = nullptr; // lengths in host arithmetic below: the same doubles
         }
-        DevArray<uint64_t> words; // released when the call returns
-        DevArray<uint8_t> packed; // the triangle's two arrays: released behind the init pass
-        const size_t bp = up256((size_t)pairs * 4);
-        if (words.grow(pairs, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the pair words of neighbour joining (%llu bytes)", (unsigned long long)(8 * pairs));
-        if (packed.grow(2 * bp, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the stored pairs of neighbour joining (%zu bytes)", 2 * bp);
-        a.words = words;
-        uint32_t *p_common = (uint32_t *)(uint8_t *)packed, *p_denom = (uint32_t *)((uint8_t *)packed + bp);
-        rc = nj_tree(c, a, p_common, p_denom, &packed, &g.last_nj_clamps);
+        StoredTriangle tri; // the words: released when the call returns; the triangle's two arrays: behind the init pass
+        rc = tri.alloc((uint64_t)n * (n - 1) / 2, "neighbour joining", true);
         if (rc) return rc;
-        if (device_ptrs) return MHX_OK;
+        a.words = tri.words;
+        rc = nj_tree(c, a, tri, true, &g.last_nj_clamps);
+        if (rc || device_ptrs) return rc;
         const size_t m = (size_t)n - 1;
-        if (hipMemcpy(join_a, a.join_a, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(join_b, a.join_b, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(d, a.d, m * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(r_a, a.r_a, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(r_b, a.r_b, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(MHX_E_HIP, "D2H copy failed in dist_nj");
+        rc = read_back("dist_nj", {{join_a, a.join_a, m * 4}, {join_b, a.join_b, m * 4}, {d, a.d, m * 8}, {r_a, a.r_a, m * 8}, {r_b, a.r_b, m * 8}});
+        if (rc) return rc;
         if (len_a)
             for (size_t t = 0; t < m; ++t) nj_lengths(NjRecord{join_a[t], join_b[t], d[t], r_a[t], r_b[t]}, n - (uint32_t)t, len_a[t], len_b[t]);
         return MHX_OK;

@@ -160,13 +160,15 @@ extern "C" int mhx_resample_rows(const uint64_t *rows, const uint32_t *len, uint
             for (uint32_t i = 0; i < n; ++i) if (len[i] > stride) return fail(MHX_E_ARG, "len[%u] exceeds stride", i);
         if (n == 0) { *s_out = s; return MHX_OK; } // no list is full
         // staging: [s_r], host form: [out rows][out lengths][rows][lengths]
-        const size_t br = up256((size_t)n * stride * 8), bl = up256((size_t)n * 4);
+        const size_t rows_bytes = device_ptrs ? 0 : (size_t)n * stride * 8, len_bytes = device_ptrs ? 0 : (size_t)n * 4;
+        Carve in;
+        const size_t o_word = in.take(4), o_out = in.take(rows_bytes), o_olen = in.take(len_bytes), o_rows = in.take(rows_bytes), o_len = in.take(len_bytes);
         uint8_t *base = nullptr;
-        rc = dist_stage(device_ptrs ? 256 : 256 + 2 * (br + bl), &base);
+        rc = dist_stage(in.bytes, &base);
         if (rc) return rc;
-        ResampleArgs ra{rows, len, n, stride, s, seed, T, replicate, out_rows, out_len, (uint32_t *)base};
+        ResampleArgs ra{rows, len, n, stride, s, seed, T, replicate, out_rows, out_len, (uint32_t *)(base + o_word)};
         if (!device_ptrs) {
-            uint8_t *d_out = base + 256, *d_olen = d_out + br, *d_rows = d_olen + bl, *d_len = d_rows + br;
+            uint8_t *d_out = base + o_out, *d_olen = base + o_olen, *d_rows = base + o_rows, *d_len = base + o_len;
             hipError_t ce = hipMemcpyAsync(d_rows, rows, (size_t)n * stride * 8, hipMemcpyHostToDevice, g.stream);
             if (ce == hipSuccess) ce = hipMemcpyAsync(d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, g.stream);
             if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in resample_rows: %s", hipGetErrorString(ce));
@@ -176,11 +178,8 @@ extern "C" int mhx_resample_rows(const uint64_t *rows, const uint32_t *len, uint
         uint32_t s_r = 0;
         rc = resample_once(ra, keep, &s_r);
         *s_out = s_r;
-        if (rc) return rc;
-        if (!device_ptrs && (hipMemcpy(out_rows, ra.out_rows, (size_t)n * stride * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                             hipMemcpy(out_len, ra.out_len, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            return fail(MHX_E_HIP, "D2H copy failed in resample_rows");
-        return MHX_OK;
+        if (rc || device_ptrs) return rc;
+        return read_back("resample_rows", {{out_rows, ra.out_rows, rows_bytes}, {out_len, ra.out_len, len_bytes}});
     });
 }
 
@@ -205,50 +204,45 @@ extern "C" int mhx_dist_nj_support(const uint64_t *rows, const uint32_t *len, ui
         if (done) return MHX_OK; // no pair, no join
         if (!join_a || !join_b || !d || !r_a || !r_b || !len_a != !len_b || !rep_join_a != !rep_join_b || (replicates && !support))
             return fail(MHX_E_ARG, "null argument");
-        rc = nj_budget(n);
+        rc = store_fits("MHX_LINKAGE_STORE_MB", n);
         if (rc) return rc;
-        const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
         const size_t m = (size_t)n - 1;
-        // staging: [state][s_r][replicate rows][replicate lengths][replicate records], host form: [main records], then rows and lengths
-        const size_t state = nj_state_bytes(n), records = nj_records_bytes(n), br = up256((size_t)n * stride * 8), bl = up256((size_t)n * 4);
-        const size_t o_word = state, o_rows = o_word + 256, o_len = o_rows + br, o_rep = o_len + bl, o_main = o_rep + records;
+        Carve in; // staging: [state][s_r][replicate rows][replicate lengths][replicate records], host form: [main records], then rows and lengths
+        const NjStateAt state(in, n);
+        const size_t o_word = in.take(4), o_rows = in.take((size_t)n * stride * 8), o_len = in.take((size_t)n * 4);
+        const NjRecordsAt rep_records(in, n), main_records(in, n, !device_ptrs);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? o_main : o_main + records, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         NjArgs a{};
-        nj_place_state(a, base, n, k);
+        state.place(a, base, n, k);
         if (device_ptrs) { a.join_a = join_a; a.join_b = join_b; a.d = d; a.r_a = r_a; a.r_b = r_b; a.len_a = len_a; a.len_b = len_b; }
         else {
-            nj_place_records(a, base + o_main, n);
+            main_records.place(a, base);
             a.len_a = a.len_b = nullptr; // lengths in host arithmetic below: the same doubles
         }
-        DevArray<uint64_t> words; // all of it released when the call returns
-        DevArray<uint8_t> packed;
-        const size_t bp = up256((size_t)pairs * 4);
-        if (words.grow(pairs, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the pair words of neighbour joining (%llu bytes)", (unsigned long long)(8 * pairs));
-        if (packed.grow(2 * bp, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the stored pairs of neighbour joining (%zu bytes)", 2 * bp);
-        a.words = words;
-        uint32_t *p_common = (uint32_t *)(uint8_t *)packed, *p_denom = (uint32_t *)((uint8_t *)packed + bp);
+        StoredTriangle tri; // all of it released when the call returns
+        rc = tri.alloc((uint64_t)n * (n - 1) / 2, "neighbour joining", true);
+        if (rc) return rc;
+        a.words = tri.words;
         // the main tree, exactly as mhx_dist_nj
         uint64_t main_clamps = 0;
-        rc = nj_tree(c, a, p_common, p_denom, nullptr, &main_clamps);
+        rc = nj_tree(c, a, tri, false, &main_clamps);
         g.last_nj_clamps = main_clamps;
         if (rc) return rc;
         double total_ms = g.last_dist_ms;
         std::vector<uint32_t> h_ja, h_jb; // device form: the main joins on the host, for the count
         const uint32_t *main_a = join_a, *main_b = join_b;
         if (!device_ptrs) {
-            if (hipMemcpy(join_a, a.join_a, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(join_b, a.join_b, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(d, a.d, m * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(r_a, a.r_a, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(r_b, a.r_b, m * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(MHX_E_HIP, "D2H copy failed in dist_nj_support");
+            rc = read_back("dist_nj_support", {{join_a, a.join_a, m * 4}, {join_b, a.join_b, m * 4}, {d, a.d, m * 8}, {r_a, a.r_a, m * 8}, {r_b, a.r_b, m * 8}});
+            if (rc) return rc;
             if (len_a)
                 for (size_t t = 0; t < m; ++t) nj_lengths(NjRecord{join_a[t], join_b[t], d[t], r_a[t], r_b[t]}, n - (uint32_t)t, len_a[t], len_b[t]);
         } else if (replicates) {
             h_ja.resize(m); h_jb.resize(m);
-            if (hipMemcpy(h_ja.data(), a.join_a, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(h_jb.data(), a.join_b, m * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(MHX_E_HIP, "D2H copy failed in dist_nj_support");
+            rc = read_back("dist_nj_support", {{h_ja.data(), a.join_a, m * 4}, {h_jb.data(), a.join_b, m * 4}});
+            if (rc) return rc;
             main_a = h_ja.data(); main_b = h_jb.data();
         }
         if (replicates == 0) return MHX_OK; // the main tree only: support stays as it is
@@ -258,7 +252,7 @@ extern "C" int mhx_dist_nj_support(const uint64_t *rows, const uint32_t *len, ui
         if (!rep_join_a) { one_a.resize(m); one_b.resize(m); }
         // the replicates: no allocation from here on
         NjArgs ar = a;
-        nj_place_records(ar, base + o_rep, n);
+        rep_records.place(ar, base);
         ar.len_a = ar.len_b = nullptr;
         ResampleArgs ra{c.rows, c.len, n, stride, s, seed, T, 0, (uint64_t *)(base + o_rows), (uint32_t *)(base + o_len), (uint32_t *)(base + o_word)};
         for (uint32_t r = 0; r < replicates; ++r) {
@@ -269,12 +263,12 @@ extern "C" int mhx_dist_nj_support(const uint64_t *rows, const uint32_t *len, ui
             if (rep_s) rep_s[r] = s_r;
             const TriCall cr{ra.out_rows, ra.out_len, n, stride, s_r, std::min(c.longest, s_r), k}; // no list is longer than s_r now
             uint64_t clamps = 0;
-            rc = nj_tree(cr, ar, p_common, p_denom, nullptr, &clamps);
+            rc = nj_tree(cr, ar, tri, false, &clamps);
             if (rc) return rc;
             total_ms += g.last_dist_ms;
             uint32_t *to_a = rep_join_a ? rep_join_a + r * m : one_a.data(), *to_b = rep_join_a ? rep_join_b + r * m : one_b.data();
-            if (hipMemcpy(to_a, ar.join_a, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(to_b, ar.join_b, m * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                return fail(MHX_E_HIP, "D2H copy failed in dist_nj_support");
+            rc = read_back("dist_nj_support", {{to_a, ar.join_a, m * 4}, {to_b, ar.join_b, m * 4}});
+            if (rc) return rc;
             if (!sc.add(to_a, to_b, r, count.data())) return fail(MHX_E_INTERNAL, "the joins of replicate %u are no tree of %u leaves", r, n);
         }
         sc.finish(replicates, count.data());

@@ -109,9 +109,8 @@ int search_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
     if (staged) *staged = SearchStaged{c.q, c.q_len};
     rc = search_device(c);
     if (rc) return rc;
-    if (hipMemcpy(hit_ref, c.hit_ref, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hit_common, c.hit_common, cells * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hit_denom, c.hit_denom, cells * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(n_hits, c.n_hits, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(MHX_E_HIP, "D2H copy failed in dist_search");
+    rc = read_back("dist_search", {{hit_ref, c.hit_ref, cells * 4}, {hit_common, c.hit_common, cells * 4}, {hit_denom, c.hit_denom, cells * 4}, {n_hits, c.n_hits, (size_t)nq * 4}});
+    if (rc) return rc;
     for (uint32_t i = 0; i < nq; ++i) {
         uint32_t *hr = hit_ref + (size_t)i * top, *hc = hit_common + (size_t)i * top, *hd = hit_denom + (size_t)i * top;
         double *hx = hit_dist ? hit_dist + (size_t)i * top : nullptr;

@@ -1,12 +1,14 @@
-// mhx_engine_sets.h -- what the host sides of the set calls share: the rounding and the carving of a workspace, the loop over
-// groups of blocks whose flag words come back together (the all-pairs schedule, TriSchedule in mhx_engine_triangle.cpp, runs
-// it too), the schedule of the query-by-reference calls (mhx_engine_search.cpp, mhx_engine_within.cpp, mhx_engine_contain.cpp,
-// mhx_engine_contain_search.cpp) and the staging of their host forms.  Internal, host only.
+// mhx_engine_sets.h -- what the host sides of the set calls share: the rounding and the carving of a workspace or a staging
+// area, the readback of a host form, the loop over groups of blocks whose flag words come back together, the block schedule
+// (BlockSchedule: route, query batch, workspace, clock and the passes of a block) with what the query-by-reference calls put on
+// it (SetSchedule: mhx_engine_search.cpp, mhx_engine_within.cpp, mhx_engine_contain.cpp, mhx_engine_contain_search.cpp; the
+// all-pairs calls' TriSchedule is in mhx_engine_triangle.cpp) and the staging of their host forms.  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "mhx_device.h"
@@ -63,48 +65,69 @@ template <class Launch, class Redo> int run_block_groups(const BlockGroups &p, h
     return MHX_OK;
 }
 
-// The schedule of a query-by-reference call over the engine's stream.  Both sets are split into value ranges ONCE, with one
-// shift (offsets()); every (query batch, slice of 32 references) block then runs the range pass, the call's finish pass and
-// the call's take-out pass; a flagged block is redone by the call's pair kernel and taken out then.
-// A call goes: construct (geometry, from the inputs alone), extra() for room of its own, place(), begin(), its own setup,
-// offsets(), run() once or once per range of queries, its own last launches, end(), its own readback in wait().
+// A short list of device arrays to the host, one after the other with hipMemcpy (each waits for the device); an entry that is
+// not wanted is left out.  name: the call's, for the message ("dist_mst").
+struct Readback {
+    void *to;
+    const void *from;
+    size_t bytes;
+    bool wanted = true;
+};
+inline int read_back(const char *name, std::initializer_list<Readback> list)
+{
+    for (const Readback &r : list)
+        if (r.wanted && hipMemcpy(r.to, r.from, r.bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy failed in %s", name);
+    return MHX_OK;
+}
+
+// What a set call is scheduled by, from its inputs alone.
 struct SetGeometry {
     uint32_t ranges;        // value ranges per block (0: none, the pair kernel takes the call)
     uint64_t weight;        // of a pair in the test for the range route
     const char *qbatch_env; // the variable that lowers the query batch
-    uint32_t most_queries;  // the most queries a run() covers
+    uint32_t most_queries;  // the most queries a block covers
     const char *what;       // the call in the messages: "<what> kernel failed"
 };
-struct SetSchedule {
-    uint32_t nr, stride, ranges, qbatch, group;
+
+// The schedule of (query batch, slice of 32 references) blocks over the engine's stream, what the query-by-reference calls
+// (SetSchedule below) and the all-pairs calls (TriSchedule, mhx_engine_triangle.cpp) share: the choice of the route and of the
+// query batch, the common workspace, the clock, and the passes of a block -- the range pass, the call's finish pass and the
+// call's take-out pass; a flagged block is redone by the call's pair kernel and taken out then.
+// A call goes: construct (geometry, from the inputs alone), extra() for room of its own, place(), begin(), its own setup,
+// offsets(), its blocks once or several times, its own last launches, end(), its own readback in wait().
+struct BlockSchedule {
+    uint32_t ranges, qbatch, group = 0, lead = 0;
     const char *what;
     bool fast;
-    bool clear_first = false, clear_later = true; // see BlockGroups
     // workspace in g.dist_ws: [offsets of the queries][offsets of the references][byte counters][window totals][words: shift, 0,
-    // then two per block of a group][what the call asked for through extra()]
+    // the schedule's own up to `lead`, then two per block of a group][what the call asked for through extra()]
     Carve ws;
-    size_t o_offq, o_offr, o_cpart, o_wtot, o_words;
+    size_t o_offq = 0, o_offr = 0, o_cpart = 0, o_wtot = 0, o_words = 0;
     uint32_t *offq = nullptr, *offr = nullptr, *words = nullptr, *flags = nullptr;
     DistWork w{};
-    DistArgs lists{};        // both sets as offsets() saw them; a block's lists are cut from here
-    uint64_t nblocks = 0;    // of all runs so far
+    uint64_t counted = 0;       // the blocks of the runs whose fallbacks are counted
     hipError_t le = hipSuccess; // the first launch error: nothing is launched after it, end() reports it
 
-    SetSchedule(uint32_t nq, uint32_t nr_, uint32_t stride_, const SetGeometry &geo) : nr(nr_), stride(stride_), ranges(geo.ranges), what(geo.what)
+    BlockSchedule(uint64_t pairs, const SetGeometry &geo) : ranges(geo.ranges), what(geo.what)
     {
-        const uint64_t pairs = (uint64_t)nq * nr;
         fast = (pairs >= 64 || (pairs >= 8 && pairs * geo.weight >= 400000)) && ranges != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
         qbatch = tri_max_queries(fast ? ranges : kTriMinRanges);
         if (const char *e = getenv(geo.qbatch_env)) { const long v = atol(e); if (v > 0 && (uint64_t)v < qbatch) qbatch = (uint32_t)v; }
         qbatch = std::min(qbatch, geo.most_queries);
-        group = (uint32_t)std::min<uint64_t>(search_blocks(geo.most_queries, nr, qbatch), kBlockGroup);
-        o_offq = ws.take(fast ? (size_t)nq * per() * 4 : 0);
-        o_offr = ws.take(fast ? (size_t)nr * per() * 4 : 0);
-        o_cpart = ws.take(fast ? (size_t)qbatch * ranges * kTriSlice : 0);
-        o_wtot = ws.take(fast && ranges > (uint32_t)kDistRanges ? (size_t)qbatch * (ranges / kDistWindowRanges) * kTriSlice * 4 : 0);
-        o_words = ws.take((size_t)(2 + 2 * group) * 4);
     }
     uint64_t per() const { return (uint64_t)ranges + 1; } // offsets per list
+    // the common workspace: offsets tables of n_q and of n_r lists (0: no such table), at most `blocks` blocks in a run, `lead_`
+    // words in front of the flag words
+    void carve(uint64_t n_q, uint64_t n_r, uint64_t blocks, uint32_t lead_)
+    {
+        group = (uint32_t)std::min<uint64_t>(blocks, kBlockGroup);
+        lead = lead_;
+        o_offq = ws.take(fast ? (size_t)n_q * per() * 4 : 0);
+        o_offr = ws.take(fast ? (size_t)n_r * per() * 4 : 0);
+        o_cpart = ws.take(fast ? (size_t)qbatch * ranges * kTriSlice : 0);
+        o_wtot = ws.take(fast && ranges > (uint32_t)kDistRanges ? (size_t)qbatch * (ranges / kDistWindowRanges) * kTriSlice * 4 : 0);
+        o_words = ws.take((size_t)(lead + 2 * group) * 4);
+    }
     // room of the call's own behind the common part (before place()): where it lies, for at()
     size_t extra(size_t n) { return ws.take(n); }
     uint8_t *at(size_t o) const { return g.dist_ws + o; }
@@ -112,7 +135,7 @@ struct SetSchedule {
     {
         if (g.dist_ws.grow(ws.bytes, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for %s (%zu bytes)", room, ws.bytes);
         offq = (uint32_t *)at(o_offq); offr = (uint32_t *)at(o_offr);
-        words = (uint32_t *)at(o_words); flags = words + 2;
+        words = (uint32_t *)at(o_words); flags = words + lead;
         w.cpart = at(o_cpart);
         w.wtot = (uint32_t *)at(o_wtot);
         w.ranges = ranges;
@@ -122,52 +145,43 @@ struct SetSchedule {
     void begin()
     {
         hipEventRecord(g.ev0, g.stream);
-        le = hipMemsetAsync(words, 0, (size_t)(2 + 2 * group) * 4, g.stream);
+        le = hipMemsetAsync(words, 0, (size_t)(lead + 2 * group) * 4, g.stream);
         g.last_dist_fallbacks = fast ? 0 : -1;
         g.last_dist_ranges = 0;
     }
-    // both sets as the passes of mhx_dist.hip see them, and their one split
-    void offsets(const DistArgs &both)
+    // what the one split of the lists into value ranges works on: words[0] the shift of the call, words[1] stays 0
+    DistWork offsets_work(uint32_t *offs_q, uint32_t *offs_r) const
     {
-        lists = both;
-        if (!fast || le != hipSuccess) return;
         DistWork wa = w;
-        wa.offs_q = offq; wa.offs_r = offr; wa.params = words; // words[0] the shift of the call, words[1] stays 0
-        le = launch_dist_offsets_both(lists, wa, g.stream);
+        wa.offs_q = offs_q; wa.offs_r = offs_r; wa.params = words;
+        return wa;
     }
-    // The blocks of queries [q_first, q_first + q_count), whose block coordinates count from q_first.  The call's passes, each
-    // returning its launch's hipError_t: pairs(blk, x) the pair kernel, finish(blk, x, w) the finish pass behind the range pass,
-    // take(blk, flag) the take-out pass, which does nothing where *flag is set; x: the lists of the block.
-    template <class Pairs, class Finish, class Take> int run(uint32_t q_first, uint32_t q_count, Pairs pairs, Finish finish, Take take)
+    // n blocks once; clear_first, clear_later, count: see BlockGroups.  where(b, x) makes x the lists of block b and points
+    // w.offs_q / w.offs_r at the offsets of its first query and first reference.  The passes of block b, each returning its
+    // launch's hipError_t: pairs(b, x) the pair kernel, finish(b, x, w) the finish pass behind the range pass, take(b, flag,
+    // generic) the take-out pass, which does nothing where *flag is set; generic: behind the pair kernel, whose blocks have
+    // words + 1, which stays 0, for a flag.
+    template <class Where, class Pairs, class Finish, class Take>
+    int run_blocks(uint64_t n, bool clear_first, bool clear_later, bool count, Where where, Pairs pairs, Finish finish, Take take)
     {
-        const uint64_t n = search_blocks(q_count, nr, qbatch);
-        nblocks += n;
-        auto block = [&](uint64_t b, SearchBlock &blk) {
-            blk = search_block(q_count, nr, qbatch, b);
-            DistArgs x = lists;
-            x.q = lists.q + (uint64_t)(q_first + blk.q0) * stride; x.q_len = lists.q_len + q_first + blk.q0; x.nq = blk.nq;
-            x.r = lists.r + (uint64_t)blk.r0 * stride; x.r_len = lists.r_len + blk.r0; x.nr = blk.nr;
-            return x;
-        };
+        if (count) counted += n;
         auto generic = [&](uint64_t b) {
-            SearchBlock blk;
-            const DistArgs x = block(b, blk);
-            hipError_t e = pairs(blk, x);
-            if (e == hipSuccess) e = take(blk, words + 1);
+            DistArgs x;
+            where(b, x);
+            hipError_t e = pairs(b, x);
+            if (e == hipSuccess) e = take(b, words + 1, true);
             return e;
         };
         return run_block_groups(
-            BlockGroups{n, fast, flags, group, clear_first, clear_later, true, what}, le,
+            BlockGroups{n, fast, flags, group, clear_first, clear_later, count, what}, le,
             [&](uint64_t b, uint32_t *params) {
                 if (!fast) return generic(b);
-                SearchBlock blk;
-                const DistArgs x = block(b, blk);
-                w.offs_q = offq + (uint64_t)(q_first + blk.q0) * per();
-                w.offs_r = offr + (uint64_t)blk.r0 * per();
+                DistArgs x;
+                where(b, x);
                 w.params = params;
                 hipError_t e = launch_dist_range_pass(x, w, g.stream);
-                if (e == hipSuccess) e = finish(blk, x, w);
-                if (e == hipSuccess) e = take(blk, params + 1);
+                if (e == hipSuccess) e = finish(b, x, w);
+                if (e == hipSuccess) e = take(b, params + 1, false);
                 return e;
             },
             generic);
@@ -176,7 +190,7 @@ struct SetSchedule {
     int end()
     {
         hipEventRecord(g.ev1, g.stream);
-        if (fast && (uint64_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
+        if (fast && (uint64_t)g.last_dist_fallbacks < counted) g.last_dist_ranges = (int)ranges;
         if (le != hipSuccess) return fail(MHX_E_HIP, "%s kernel launch failed: %s", what, hipGetErrorString(le));
         return MHX_OK;
     }
@@ -189,6 +203,44 @@ struct SetSchedule {
         g.last_dist_ms = ms;
         if (se != hipSuccess) return fail(MHX_E_HIP, "%s kernel failed: %s", what, hipGetErrorString(se));
         return MHX_OK;
+    }
+};
+
+// The schedule of a query-by-reference call.  Both sets are split into value ranges ONCE, with one shift (offsets()); run()
+// goes once or once per range of queries.
+struct SetSchedule : BlockSchedule {
+    uint32_t nr, stride;
+    bool clear_first = false, clear_later = true; // see BlockGroups
+    DistArgs lists{};                             // both sets as offsets() saw them; a block's lists are cut from here
+
+    SetSchedule(uint32_t nq, uint32_t nr_, uint32_t stride_, const SetGeometry &geo) : BlockSchedule((uint64_t)nq * nr_, geo), nr(nr_), stride(stride_)
+    {
+        carve(nq, nr, search_blocks(geo.most_queries, nr, qbatch), 2);
+    }
+    // both sets as the passes of mhx_dist.hip see them, and their one split
+    void offsets(const DistArgs &both)
+    {
+        lists = both;
+        if (fast && le == hipSuccess) le = launch_dist_offsets_both(lists, offsets_work(offq, offr), g.stream);
+    }
+    // The blocks of queries [q_first, q_first + q_count), whose block coordinates count from q_first.  The call's passes as
+    // BlockSchedule::run_blocks has them, with the block itself for its index: pairs(blk, x), finish(blk, x, w), take(blk, flag).
+    template <class Pairs, class Finish, class Take> int run(uint32_t q_first, uint32_t q_count, Pairs pairs, Finish finish, Take take)
+    {
+        auto block = [&](uint64_t b) { return search_block(q_count, nr, qbatch, b); };
+        return run_blocks(
+            search_blocks(q_count, nr, qbatch), clear_first, clear_later, true,
+            [&](uint64_t b, DistArgs &x) {
+                const SearchBlock blk = block(b);
+                x = lists;
+                x.q = lists.q + (uint64_t)(q_first + blk.q0) * stride; x.q_len = lists.q_len + q_first + blk.q0; x.nq = blk.nq;
+                x.r = lists.r + (uint64_t)blk.r0 * stride; x.r_len = lists.r_len + blk.r0; x.nr = blk.nr;
+                w.offs_q = offq + (uint64_t)(q_first + blk.q0) * per();
+                w.offs_r = offr + (uint64_t)blk.r0 * per();
+            },
+            [&](uint64_t b, const DistArgs &x) { return pairs(block(b), x); },
+            [&](uint64_t b, const DistArgs &x, DistWork &wk) { return finish(block(b), x, wk); },
+            [&](uint64_t b, uint32_t *flag, bool) { return take(block(b), flag); });
     }
 };
 

@@ -34,10 +34,11 @@ int support_device(const SupportCall &c)
     uint64_t limit = kSupportWorkLimit;
     if (const char *e = getenv("MHX_SUPPORT_WORK_MB")) { const long v = atol(e); if (v > 0) limit = (uint64_t)v << 20; }
     const uint32_t batch = std::min(support_batch(c.top, R, limit), c.nq);
-    const size_t b_kept = up256((size_t)batch * (c.top + 1) * R * 4), b_one = up256((size_t)batch * R * 4), b_pair = up256((size_t)batch * c.top * R * 4);
-    const size_t o_bad = 0, o_kept = 256, o_s = o_kept + b_kept, o_best = o_s + b_one, o_common = o_best + b_one, o_denom = o_common + b_pair;
-    if (g.dist_ws.grow(o_denom + b_pair, g.stream) != hipSuccess)
-        return fail(MHX_E_HIP, "hipMalloc failed for the support workspace (%zu bytes)", o_denom + b_pair);
+    const size_t b_one = (size_t)batch * R * 4, b_pair = (size_t)batch * c.top * R * 4;
+    Carve work;
+    const size_t o_bad = work.take(8), o_kept = work.take((size_t)batch * (c.top + 1) * R * 4), o_s = work.take(b_one), o_best = work.take(b_one);
+    const size_t o_common = work.take(b_pair), o_denom = work.take(b_pair);
+    if (g.dist_ws.grow(work.bytes, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the support workspace (%zu bytes)", work.bytes);
     uint8_t *ws = g.dist_ws;
     unsigned long long *bad = (unsigned long long *)(ws + o_bad);
     hipEventRecord(g.ev0, g.stream);
@@ -117,12 +118,13 @@ extern "C" int mhx_dist_support(const uint64_t *q, const uint32_t *q_len, uint32
                 }
             }
         // staging: [query rows][query lengths][reference rows][reference lengths][candidates][their numbers][first]
-        const size_t bq = up256((size_t)nq * stride * 8), bql = up256((size_t)nq * 4), br = up256((size_t)nr * stride * 8), brl = up256((size_t)nr * 4);
-        const size_t bc = up256((size_t)nq * top * 4);
+        Carve in;
+        const size_t o_q = in.take((size_t)nq * stride * 8), o_ql = in.take((size_t)nq * 4), o_r = in.take((size_t)nr * stride * 8), o_rl = in.take((size_t)nr * 4);
+        const size_t o_c = in.take((size_t)nq * top * 4), o_n = in.take((size_t)nq * 4), o_f = in.take((size_t)nq * top * 4);
         uint8_t *base = nullptr;
-        rc = dist_stage(bq + bql + br + brl + bc + bql + bc, &base);
+        rc = dist_stage(in.bytes, &base);
         if (rc) return rc;
-        uint8_t *dq = base, *dql = dq + bq, *dr = dql + bql, *drl = dr + br, *dc = drl + brl, *dn = dc + bc, *df = dn + bql;
+        uint8_t *dq = base + o_q, *dql = base + o_ql, *dr = base + o_r, *drl = base + o_rl, *dc = base + o_c, *dn = base + o_n, *df = base + o_f;
         hipError_t ce = hipMemcpyAsync(dq, q, (size_t)nq * stride * 8, hipMemcpyHostToDevice, g.stream);
         if (ce == hipSuccess) ce = hipMemcpyAsync(dql, q_len, (size_t)nq * 4, hipMemcpyHostToDevice, g.stream);
         if (ce == hipSuccess && nr) ce = hipMemcpyAsync(dr, r, (size_t)nr * stride * 8, hipMemcpyHostToDevice, g.stream);
@@ -135,8 +137,6 @@ extern "C" int mhx_dist_support(const uint64_t *q, const uint32_t *q_len, uint32
         c.first = (uint32_t *)df;
         c.host_out = true;
         rc = support_device(c);
-        if (rc) return rc;
-        if (hipMemcpy(first, c.first, (size_t)nq * top * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy failed in dist_support");
-        return MHX_OK;
+        return rc ? rc : read_back("dist_support", {{first, c.first, (size_t)nq * top * 4}});
     });
 }

@@ -2,9 +2,10 @@
 // mhx_dist_triangle_edges and mhx_dist_cluster; the tree, mhx_dist_mst, is in mhx_engine_mst.cpp and takes its pairs from
 // here, and so do the medoids, mhx_dist_medoids in mhx_engine_medoid.cpp, whose block mode run_medoid lies here): staging
 // of a host-pointer call, the schedule of (query batch, reference slice) blocks over ONE offsets table of the whole set
-// (its loop over the groups of blocks and their flag words is mhx_engine_sets.h's, which the query-by-reference calls run
-// too), the fallback of a flagged block to the generic pair kernel, one function per mode that rides the schedule, the exact
-// distance rule and the order of the edge list on the host, the bound of the clustering as a table of integers.
+// (what it shares with the query-by-reference calls -- route, workspace, clock, the passes of a block, the fallback of a
+// flagged block to the generic pair kernel -- is BlockSchedule in mhx_engine_sets.h), one function per mode that rides the
+// schedule, the exact distance rule and the order of the edge list on the host, the bound of the clustering as a table of
+// integers.
 // Rules: mhx_triangle.h, mhx_cluster.h, mhx_mst.h, mhx_medoid.h; kernels: mhx_triangle.hip, mhx_cluster.hip, mhx_mst.hip,
 // mhx_medoid.hip and mhx_dist.hip.
 #include <hip/hip_runtime.h>
@@ -28,84 +29,54 @@ using namespace mhx;
 
 namespace {
 
-// The schedule of a call over the engine's stream, what the modes below share.  The set's lists are split into value
-// ranges ONCE (offsets() over all n lists); every block then runs the range pass and a finish pass into its block-local
-// [queries][32] results, and the mode's take-out kernel takes the pairs that count from there.  Block flags come back
-// once per group of blocks; a flagged block is redone by the generic pair kernel into the same block-local arrays.
-// A mode goes: construct (geometry and blocks, from the inputs alone), extra() for room of its own, place(), begin(), its
-// own setup, offsets(), run_blocks() once or once per round, its own last launches, end(), its own readback in wait().
-struct TriSchedule {
-    const TriCall c;
-    uint32_t ranges, qbatch, nblocks, group;
-    bool fast;
-    std::vector<TriBlock> blocks;
-    // workspace in g.dist_ws: [offsets of the set][byte counters][window totals][block-local common, denom][words: shift, 0,
-    // the edge counter (two words), then two per block of a group][what the mode asked for through extra()]
-    size_t o_offs, o_cpart, o_wtot, o_lc, o_ld, o_words, bytes;
-    uint32_t *offs = nullptr, *loc_c = nullptr, *loc_d = nullptr, *words = nullptr, *flags = nullptr;
-    unsigned long long *counter = nullptr; // a mode's count of edges, zero after begin()
-    DistWork w{};
-    DistArgs all{};
-    hipError_t le = hipSuccess; // the first launch error: nothing is launched after it, end() reports it
+uint32_t tri_geometry(uint32_t longest)
+{
+    const char *geo = getenv("MHX_TRI_GEOMETRY");
+    return geo && strcmp(geo, "dist") == 0 ? tri_ranges_dist(longest) : tri_ranges(longest);
+}
 
-    explicit TriSchedule(const TriCall &call) : c(call)
+// The schedule of an all-pairs call, what the modes below share: BlockSchedule (mhx_engine_sets.h: route, query batch, common
+// workspace, clock, the passes of a block and the fallback of a flagged one) over ONE offsets table of the whole set, split
+// into value ranges ONCE (offsets() over all n lists), with a block list that a mode may filter, block-local [queries][32]
+// results that the finish pass and the generic pair kernel write and the mode's take-out kernel reads, and an edge counter.
+// A mode goes as BlockSchedule says, with run_blocks() once or once per round.
+struct TriSchedule : BlockSchedule {
+    const TriCall c;
+    uint32_t nblocks;
+    std::vector<TriBlock> blocks;
+    size_t o_lc, o_ld; // block-local common, denom, behind the common workspace
+    uint32_t *loc_c = nullptr, *loc_d = nullptr;
+    unsigned long long *counter = nullptr; // a mode's count of edges (words 2 and 3), zero after begin()
+    DistArgs all{};
+
+    explicit TriSchedule(const TriCall &call)
+        : BlockSchedule((uint64_t)call.n * (call.n - 1) / 2, SetGeometry{tri_geometry(call.longest), call.s, "MHX_TRI_QBATCH", call.n, "triangle"}), c(call)
     {
-        const uint64_t pairs = (uint64_t)c.n * (c.n - 1) / 2;
-        const char *geo = getenv("MHX_TRI_GEOMETRY");
-        ranges = geo && strcmp(geo, "dist") == 0 ? tri_ranges_dist(c.longest) : tri_ranges(c.longest);
-        fast = (pairs >= 64 || (pairs >= 8 && pairs * (uint64_t)c.s >= 400000)) && ranges != 0 && getenv("MHX_DIST_GENERIC") == nullptr;
-        qbatch = tri_max_queries(fast ? ranges : kTriMinRanges);
-        if (const char *e = getenv("MHX_TRI_QBATCH")) { const long v = atol(e); if (v > 0 && (uint64_t)v < qbatch) qbatch = (uint32_t)v; }
-        qbatch = std::min(qbatch, c.n);
         TriBlock b;
         for (bool more = tri_first_block(c.n, qbatch, b); more; more = tri_next_block(c.n, qbatch, b)) blocks.push_back(b);
         nblocks = (uint32_t)blocks.size();
-        group = std::min(nblocks, kBlockGroup);
-        size_t o = 0;
-        o_offs = o; if (fast) o += up256((size_t)c.n * per() * 4);
-        o_cpart = o; if (fast) o += up256((size_t)qbatch * ranges * kTriSlice);
-        o_wtot = o; if (fast && ranges > (uint32_t)kDistRanges) o += up256((size_t)qbatch * (ranges / kDistWindowRanges) * kTriSlice * 4);
-        o_lc = o; o += up256((size_t)qbatch * kTriSlice * 4);
-        o_ld = o; o += up256((size_t)qbatch * kTriSlice * 4);
-        o_words = o; o += up256((size_t)(4 + 2 * group) * 4);
-        bytes = o;
+        carve(c.n, 0, nblocks, 4);
+        o_lc = extra((size_t)qbatch * kTriSlice * 4);
+        o_ld = extra((size_t)qbatch * kTriSlice * 4);
     }
-    uint64_t per() const { return (uint64_t)ranges + 1; } // offsets per list
     // a mode that needs only some of the blocks drops the others (before place(); the workspace keeps its size)
     template <class Keep> void keep_blocks(Keep keep)
     {
         blocks.erase(std::remove_if(blocks.begin(), blocks.end(), [&](const TriBlock &b) { return !keep(b); }), blocks.end());
         nblocks = (uint32_t)blocks.size();
     }
-    // room of the mode's own behind the common part (before place()): where it lies, for at()
-    size_t extra(size_t n) { const size_t o = bytes; bytes += up256(n); return o; }
-    uint8_t *at(size_t o) const { return g.dist_ws + o; }
     int place()
     {
-        if (g.dist_ws.grow(bytes, g.stream) != hipSuccess) return fail(MHX_E_HIP, "hipMalloc failed for the triangle workspace (%zu bytes)", bytes);
-        offs = (uint32_t *)at(o_offs); loc_c = (uint32_t *)at(o_lc); loc_d = (uint32_t *)at(o_ld);
-        words = (uint32_t *)at(o_words); flags = words + 4;
+        const int rc = BlockSchedule::place("the triangle workspace");
+        if (rc) return rc;
+        loc_c = (uint32_t *)at(o_lc); loc_d = (uint32_t *)at(o_ld);
         counter = (unsigned long long *)(words + 2);
-        w.cpart = at(o_cpart);
-        w.wtot = (uint32_t *)at(o_wtot);
-        w.ranges = ranges;
         all.q = c.rows; all.q_len = c.len; all.nq = c.n; all.nr = 0; all.stride = c.stride; all.s = c.s; all.k = c.k;
         return MHX_OK;
     }
-    // the clock starts, the words are zero, nothing has fallen back yet
-    void begin()
-    {
-        hipEventRecord(g.ev0, g.stream);
-        le = hipMemsetAsync(words, 0, (size_t)(4 + 2 * group) * 4, g.stream);
-        g.last_dist_fallbacks = fast ? 0 : -1;
-        g.last_dist_ranges = 0;
-    }
     void offsets()
     {
-        if (!fast || le != hipSuccess) return;
-        DistWork wa = w;
-        wa.offs_q = offs; wa.offs_r = offs; wa.params = words; // words[0] the shift of the call, words[1] stays 0
-        le = launch_dist_offsets(all, wa, g.stream);
+        if (fast && le == hipSuccess) le = launch_dist_offsets(all, offsets_work(offq, offq), g.stream);
     }
     DistArgs block_args(const TriBlock &b) const
     {
@@ -125,53 +96,31 @@ struct TriSchedule {
     }
     // Every block once: range, finish and take-out pass, the flagged ones again through the generic kernel.  first: the flag
     // words are still zero and the fallbacks are counted (the tree runs the blocks once per round).  slice_done() follows the
-    // last block of every reference slice (and of every group).
+    // last block of every reference slice (and of every group) on the range route, never a block of the pair kernel.
     template <class TakeOut, class SliceDone> int run_blocks(TakeOut take_out, bool first, SliceDone slice_done)
     {
-        auto generic = [&](uint64_t b) {
-            hipError_t e = launch_dist_pairs(block_args(blocks[b]), g.stream);
-            if (e == hipSuccess) e = take_out(blocks[b], words + 1);
-            return e;
-        };
-        return run_block_groups(
-            BlockGroups{nblocks, fast, flags, group, !first, true, first, "triangle"}, le,
-            [&](uint64_t b, uint32_t *params) {
-                if (!fast) return generic(b);
-                const TriBlock &blk = blocks[b];
-                const DistArgs x = block_args(blk);
-                w.offs_q = offs + (uint64_t)blk.q0 * per();
-                w.offs_r = offs + (uint64_t)blk.r0 * per();
-                w.params = params;
-                hipError_t e = launch_dist_range_pass(x, w, g.stream);
-                if (e == hipSuccess) e = ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, w, g.stream) : launch_dist_finish(x, w, g.stream);
-                if (e == hipSuccess) e = take_out(blk, params + 1);
-                const bool last = (b + 1) % kBlockGroup == 0 || b + 1 == nblocks; // of its group
-                if (e == hipSuccess && (last || blocks[b + 1].r0 != blk.r0)) e = slice_done();
-                return e;
+        return BlockSchedule::run_blocks(
+            nblocks, !first, true, first,
+            [&](uint64_t b, DistArgs &x) {
+                x = block_args(blocks[b]);
+                w.offs_q = offq + (uint64_t)blocks[b].q0 * per();
+                w.offs_r = offq + (uint64_t)blocks[b].r0 * per();
             },
-            generic);
+            [&](uint64_t, const DistArgs &x) { return launch_dist_pairs(x, g.stream); },
+            [&](uint64_t, const DistArgs &x, const DistWork &wk) {
+                return ranges < (uint32_t)kDistRanges ? launch_tri_finish_small(x, wk, g.stream) : launch_dist_finish(x, wk, g.stream);
+            },
+            [&](uint64_t b, const uint32_t *flag, bool generic) {
+                const TriBlock &blk = blocks[b];
+                hipError_t e = take_out(blk, flag);
+                const bool last = (b + 1) % kBlockGroup == 0 || b + 1 == nblocks; // of its group
+                if (e == hipSuccess && !generic && (last || blocks[b + 1].r0 != blk.r0)) e = slice_done();
+                return e;
+            });
     }
     template <class TakeOut> int run_blocks(TakeOut take_out, bool first)
     {
         return run_blocks(take_out, first, [] { return hipSuccess; });
-    }
-    // the clock stops behind the mode's last launch; a launch that failed anywhere is reported here
-    int end()
-    {
-        hipEventRecord(g.ev1, g.stream);
-        if (fast && (uint32_t)g.last_dist_fallbacks < nblocks) g.last_dist_ranges = (int)ranges;
-        if (le != hipSuccess) return fail(MHX_E_HIP, "triangle kernel launch failed: %s", hipGetErrorString(le));
-        return MHX_OK;
-    }
-    // waits for the call, the mode's readback (se: how queueing it went) included, and notes the time
-    int wait(hipError_t se = hipSuccess)
-    {
-        if (se == hipSuccess) se = hipStreamSynchronize(g.stream);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, g.ev0, g.ev1);
-        g.last_dist_ms = ms;
-        if (se != hipSuccess) return fail(MHX_E_HIP, "triangle kernel failed: %s", hipGetErrorString(se));
-        return MHX_OK;
     }
 };
 
@@ -353,19 +302,18 @@ int triangle_check(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32
     return MHX_OK;
 }
 
-// The inputs of a call, and `extra` bytes of the staging area at *base for the caller (none asked for: *base stays null).
-// Device form: rows and lengths are where they are -- the lengths too, so the row stride bounds them.  Host form: they are
-// copied behind the caller's bytes.
-int stage_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, size_t extra, uint8_t **base,
-               TriCall &c)
+// The inputs of a call, and the regions `in` of the staging area that the caller has declared, at *base (none declared in
+// the device form: *base stays null).  Device form: rows and lengths are where they are -- the lengths too, so the row stride
+// bounds them.  Host form: they are copied behind the caller's regions.
+int stage_rows(const uint64_t *rows, const uint32_t *len, uint32_t n, uint32_t stride, int k, uint32_t s, int device_ptrs, Carve in, uint8_t **base, TriCall &c)
 {
     *base = nullptr;
     c = TriCall{rows, len, n, stride, s, stride, k};
-    if (device_ptrs) return extra ? dist_stage(up256(extra), base) : MHX_OK;
-    const size_t br = up256((size_t)n * stride * 8), bl = up256((size_t)n * 4);
-    const int rc = dist_stage(up256(extra) + br + bl, base);
+    if (device_ptrs) return in.bytes ? dist_stage(in.bytes, base) : MHX_OK;
+    const size_t o_rows = in.take((size_t)n * stride * 8), o_len = in.take((size_t)n * 4);
+    const int rc = dist_stage(in.bytes, base);
     if (rc) return rc;
-    uint8_t *dr = *base + up256(extra), *dl = dr + br;
+    uint8_t *dr = *base + o_rows, *dl = *base + o_len;
     hipError_t ce = hipMemcpyAsync(dr, rows, (size_t)n * stride * 8, hipMemcpyHostToDevice, g.stream);
     if (ce == hipSuccess) ce = hipMemcpyAsync(dl, len, (size_t)n * 4, hipMemcpyHostToDevice, g.stream);
     if (ce != hipSuccess) return fail(MHX_E_HIP, "H2D copy failed in dist_triangle: %s", hipGetErrorString(ce));
@@ -401,18 +349,16 @@ extern "C" int mhx_dist_cluster(const uint64_t *rows, const uint32_t *len, uint3
         }
         std::vector<uint32_t> cmin((size_t)s + 1);
         cluster_cmin_build(s, k, max_dist, cmin.data());
-        const size_t bn = up256((size_t)n * 4);
+        Carve in; // host form: [parent][degree], then rows and lengths
+        const size_t o_parent = in.take(device_ptrs ? 0 : (size_t)n * 4), o_deg = in.take(device_ptrs ? 0 : (size_t)n * 4);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? 0 : 2 * bn, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
-        uint32_t *parent = device_ptrs ? label : (uint32_t *)base, *deg = device_ptrs || !degree ? degree : (uint32_t *)(base + bn);
+        uint32_t *parent = device_ptrs ? label : (uint32_t *)(base + o_parent), *deg = device_ptrs || !degree ? degree : (uint32_t *)(base + o_deg);
         rc = run_cluster(c, cmin.data(), parent, deg, n_clusters, n_edges);
-        if (rc) return rc;
-        if (!device_ptrs && (hipMemcpy(label, parent, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                             (degree && hipMemcpy(degree, deg, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)))
-            return fail(MHX_E_HIP, "D2H copy failed in dist_cluster");
-        return MHX_OK;
+        if (rc || device_ptrs) return rc;
+        return read_back("dist_cluster", {{label, parent, (size_t)n * 4}, {degree, deg, (size_t)n * 4, degree != nullptr}});
     });
 }
 
@@ -425,17 +371,17 @@ extern "C" int mhx_dist_triangle(const uint64_t *rows, const uint32_t *len, uint
         if (rc || done) return rc;
         if (!common || !denom) return fail(MHX_E_ARG, "null argument");
         const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-        const size_t bo = up256(pairs * 4);
+        Carve in; // host form: [common][denom], then rows and lengths
+        const size_t o_common = in.take(device_ptrs ? 0 : pairs * 4), o_denom = in.take(device_ptrs ? 0 : pairs * 4);
         TriCall c;
         uint8_t *base = nullptr;
-        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, device_ptrs ? 0 : 2 * bo, &base, c);
+        rc = stage_rows(rows, len, n, stride, k, s, device_ptrs, in, &base, c);
         if (rc) return rc;
         if (device_ptrs) return run_dense(c, common, denom, dist);
-        uint32_t *d_common = (uint32_t *)base, *d_denom = (uint32_t *)(base + bo);
+        uint32_t *d_common = (uint32_t *)(base + o_common), *d_denom = (uint32_t *)(base + o_denom);
         rc = run_dense(c, d_common, d_denom, nullptr); // distances in host libm below
+        if (rc == MHX_OK) rc = read_back("dist_triangle", {{common, d_common, pairs * 4}, {denom, d_denom, pairs * 4}});
         if (rc) return rc;
-        if (hipMemcpy(common, d_common, pairs * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(denom, d_denom, pairs * 4, hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(MHX_E_HIP, "D2H copy failed in dist_triangle");
         if (dist)
             for (uint64_t i = 0; i < pairs; ++i) dist[i] = tri_distance(common[i], denom[i], k);
         return MHX_OK;
@@ -459,7 +405,7 @@ extern "C" int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len
         uint8_t *base = nullptr;
         uint64_t found = 0;
         if (device_ptrs) { // the list stays where it is: prefiltered only, in the order of arrival
-            rc = stage_rows(rows, len, n, stride, k, s, 1, 0, &base, c);
+            rc = stage_rows(rows, len, n, stride, k, s, 1, Carve{}, &base, c);
             if (rc == MHX_OK) rc = run_edges(c, PairsOut{common, denom, dist, edge_i, edge_j, cap, jmin}, &found);
             if (rc) return rc;
             *n_out = found;
@@ -471,10 +417,11 @@ extern "C" int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len
         uint64_t room = std::min<uint64_t>(pairs, std::max<uint64_t>(cap, 1u << 20));
         PairsOut d{};
         for (int attempt = 0;; ++attempt) {
-            const size_t be = up256(room * 4);
-            rc = stage_rows(rows, len, n, stride, k, s, 0, 4 * be, &base, c);
+            Carve in; // [edge_i][edge_j][common][denom], then rows and lengths
+            const size_t o_i = in.take(room * 4), o_j = in.take(room * 4), o_common = in.take(room * 4), o_denom = in.take(room * 4);
+            rc = stage_rows(rows, len, n, stride, k, s, 0, in, &base, c);
             if (rc) return rc;
-            d = PairsOut{(uint32_t *)(base + 2 * be), (uint32_t *)(base + 3 * be), nullptr, (uint32_t *)base, (uint32_t *)(base + be), room, jmin};
+            d = PairsOut{(uint32_t *)(base + o_common), (uint32_t *)(base + o_denom), nullptr, (uint32_t *)(base + o_i), (uint32_t *)(base + o_j), room, jmin};
             rc = run_edges(c, d, &found);
             if (rc) return rc;
             if (found <= room) break;
@@ -483,9 +430,8 @@ extern "C" int mhx_dist_triangle_edges(const uint64_t *rows, const uint32_t *len
         }
         const size_t m = (size_t)found;
         std::vector<uint32_t> ei(m), ej(m), ec(m), ed(m);
-        if (m && (hipMemcpy(ei.data(), d.edge_i, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ej.data(), d.edge_j, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                  hipMemcpy(ec.data(), d.common, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(ed.data(), d.denom, m * 4, hipMemcpyDeviceToHost) != hipSuccess))
-            return fail(MHX_E_HIP, "D2H copy failed in dist_triangle_edges");
+        rc = read_back("dist_triangle_edges", {{ei.data(), d.edge_i, m * 4, m != 0}, {ej.data(), d.edge_j, m * 4, m != 0}, {ec.data(), d.common, m * 4, m != 0}, {ed.data(), d.denom, m * 4, m != 0}});
+        if (rc) return rc;
         // the exact rule (the libm distance that is printed) on the survivors, then Mash's order: i ascending, j < i ascending
         std::vector<size_t> keep;
         keep.reserve(m);

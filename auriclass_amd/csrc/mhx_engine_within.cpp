@@ -156,13 +156,13 @@ int within_host(const uint64_t *q, const uint64_t *const *q_rows, const uint32_t
     c.n_out = n_out;
     rc = within_device(c);
     if (rc) return rc;
-    if (hipMemcpy(row_off, c.row_off, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(MHX_E_HIP, "D2H copy failed in dist_within");
+    rc = read_back("dist_within", {{row_off, c.row_off, ((size_t)nq + 1) * 8}});
+    if (rc) return rc;
     if (!hit_ref && cap == 0) return MHX_OK; // the counting form
     const uint64_t m = *n_out;
     if (m > cap) return too_small(m);
-    if (m && (hipMemcpy(hit_ref, c.hit_ref, m * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hit_common, c.hit_common, m * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-              hipMemcpy(hit_denom, c.hit_denom, m * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(MHX_E_HIP, "D2H copy failed in dist_within");
+    rc = read_back("dist_within", {{hit_ref, c.hit_ref, m * 4, m != 0}, {hit_common, c.hit_common, m * 4, m != 0}, {hit_denom, c.hit_denom, m * 4, m != 0}});
+    if (rc) return rc;
     if (hit_dist)
         for (uint64_t i = 0; i < m; ++i) hit_dist[i] = tri_distance(hit_common[i], hit_denom[i], k);
     return MHX_OK;

@@ -10,6 +10,8 @@ import torch   # before the engine's library, as in tests/test_gpu_screen.py: th
 
 from auriclass_amd import engine
 from oracle import mash_oracle as mo
+from tests import cluster_rule as cr
+from tests import mst_rule as mr
 from tests import triangle_cases as tc
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +70,40 @@ def test_crowded_values_fall_back_and_stay_exact(lib):
     got = run(lists, s)
     assert lib.mhx_last_dist_fallback_blocks() > 0
     check(got, tc.expected("crowded", K, 40))
+
+
+def test_flagged_blocks_in_both_groups_of_flag_words(lib, monkeypatch):
+    """The group boundary of the all-pairs schedule (tests/triangle_cases.py: flagged_groups): 512 lists at s = 64, one query
+    per block, 4336 blocks, the last 240 in a second group of flag words, and two slices crowded into one value range, one of
+    them with blocks in both groups.  The flagged blocks are exactly those of the two slices, 447 + 63; a flag word left
+    standing across the boundary would count as one more.  The dense triangle, the clustering (whose flatten pass follows the
+    last block of a slice and of a group) and the tree from the recomputed pairs (the blocks once per round, the words
+    cleared in front of the first group from the second round on) ride the same blocks."""
+    monkeypatch.setenv("MHX_TRI_QBATCH", "1")
+    lists, s = tc.flagged_groups()
+    n = len(lists)
+    want = tc.expected("flagged_groups")
+    block, r0 = tc.flagged_groups_blocks(n)
+    for lo in (64, 448):
+        assert len(np.unique(np.concatenate(lists[lo:lo + 32]))) > 1536   # more keys than a range table holds
+    assert block.max() + 1 == 4336 > 4096
+    shares = want[0] > 0
+    assert (shares & (r0 == 64)).any() and (shares & (r0 == 448)).any() and (shares & (block >= 4096)).any()
+    M, lens = tc.pad_rows(lists)
+    got = engine.dist_triangle(M, lens, K, s)
+    print("ranges", lib.mhx_last_dist_ranges(), "fallback blocks", lib.mhx_last_dist_fallback_blocks())
+    assert lib.mhx_last_dist_ranges() == 16 and lib.mhx_last_dist_fallback_blocks() == 447 + 63
+    check(got, want)
+    label, degree, clusters, n_edges = engine.dist_cluster(M, lens, K, s, 0.05)
+    assert lib.mhx_last_dist_fallback_blocks() == 447 + 63
+    w_label, w_degree, w_clusters, w_edges = cr.cluster(lists, s, K, 0.05, want)
+    assert (clusters, n_edges) == (w_clusters, w_edges) and np.array_equal(label, w_label) and np.array_equal(degree, w_degree)
+    monkeypatch.setenv("MHX_MST_STORE", "0")
+    ei, ej, ec, ed, dist = engine.dist_mst(M, lens, K, s)
+    assert lib.mhx_last_mst_stored() == 0 and lib.mhx_last_dist_fallback_blocks() == 447 + 63   # counted in the first round only
+    tree = mr.kruskal(want[0], want[1], n)
+    assert list(zip(ei.tolist(), ej.tolist(), ec.tolist(), ed.tolist())) == tree
+    assert np.array_equal(dist, mr.distances(tree, K))
 
 
 def test_tiny_sets_and_bad_arguments(lib):

@@ -87,6 +87,34 @@ def crowded(n=40):
     return tuple(lists), 3000
 
 
+@functools.lru_cache(maxsize=None)
+def flagged_groups():
+    """512 lists of 64 hashes at s = 64 (16 value ranges): with one query per block that is 4336 blocks, one per (slice, query)
+    -- slice r0 has the queries r0 + 1 .. 511 --, the last 240 in a second group of flag words; block 4096 is (slice 384,
+    query 461).  The lists are those of contain_search_cases.flagged_groups; slices 64..95 and 448..479 are then crowded into
+    one value range, more keys than the 1536 of a range table, so every block of these two slices raises its flag, 447 + 63 =
+    510 in all, in both groups (the table holds the references' keys only: no other block can).  Every fourth crowded list
+    derives from one of four crowded bases, so that pairs inside the crowd share hashes."""
+    rng = np.random.default_rng(4336)
+    s, n = 64, 512
+    bases = [sketch_like(rng, s) for _ in range(30)]
+    lists = [mutate(rng, bases[j % 30], 0.02 * (j % 11)) if j % 3 else sketch_like(rng, s) for j in range(n)]
+    crowd = [sketch_like(rng, s, hi=2 ** 20) for _ in range(4)]
+    for j in list(range(64, 96)) + list(range(448, 480)):
+        low = mutate(rng, crowd[(j // 4) % 4], 0.05, hi=2 ** 20) if j % 4 == 0 else sketch_like(rng, s, hi=2 ** 20)
+        lists[j] = np.uint64(1 << 62) + low
+    return tuple(lists), s
+
+
+def flagged_groups_blocks(n=512):
+    """the block of every packed pair (i, j), j < i, of flagged_groups under one query per block, in the order of oracle_pairs"""
+    first = np.cumsum([0] + [n - 1 - r0 for r0 in range(0, n, 32)])   # of every slice
+    ii = np.array([i for i in range(n) for j in range(i)], np.int64)
+    jj = np.array([j for i in range(n) for j in range(i)], np.int64)
+    r0 = jj // 32 * 32
+    return first[jj // 32] + (ii - r0 - 1), r0
+
+
 def oracle_pairs(lists, s, k):
     """packed (common, denom, dist) of mo.compare(list_i, list_j) for j < i"""
     n = len(lists)

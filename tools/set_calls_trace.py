@@ -4,7 +4,9 @@ must leave as it was is the ORDER of the kernels each call launches.
 The all-pairs calls (the default): cluster_rate's planted set at n = 200, s = 1000, k = 21, under MHX_TRI_QBATCH=48 (several
 blocks per reference slice, several slices):
 
-    dist_triangle, dist_triangle_edges and dist_cluster at 0.05, dist_mst recomputed (MHX_MST_STORE=0), then stored (=1)
+    dist_triangle, dist_triangle_edges and dist_cluster at 0.05, dist_mst recomputed (MHX_MST_STORE=0), then stored (=1),
+    dist_linkage complete and average, dist_nj, dist_nj_support with 3 replicates, dist_medoids on the labels of that
+    dist_cluster, dist_to on those medoids, resample_rows, and dist_cluster and dist_mst once more with device pointers
 
 The query-by-reference calls (--pairs): 150 queries derived from that set against it, device pointers, under
 MHX_SEARCH_QBATCH=48 and MHX_WITHIN_QBATCH=48 (four query batches by seven slices), MHX_WITHIN_CELLS=420 (three super-batches):
@@ -43,6 +45,8 @@ def digest(parts):
 
 def all_pairs():
     os.environ["MHX_TRI_QBATCH"] = "48"
+    import torch  # noqa: F401  before the engine's library: the two then share one device runtime
+
     from auriclass_amd import engine
     from cluster_rate import make_set
 
@@ -53,10 +57,44 @@ def all_pairs():
              ("dist_cluster 0.05", None, lambda: engine.dist_cluster(rows, lens, 21, 1000, 0.05)),
              ("dist_mst recomputed", "0", lambda: engine.dist_mst(rows, lens, 21, 1000)),
              ("dist_mst stored", "1", lambda: engine.dist_mst(rows, lens, 21, 1000))]
+    got = {}   # what a traced call returned, for the calls that go on from it
     for what, store, call in calls:
         if store is not None:
             os.environ["MHX_MST_STORE"] = store
-        print(f"{what}: {digest(call())}", flush=True)
+        got[what] = call()
+        print(f"{what}: {digest(got[what])}", flush=True)
+    del os.environ["MHX_MST_STORE"]
+    label = got["dist_cluster 0.05"][0]
+    more = [("dist_linkage complete", lambda: engine.dist_linkage(rows, lens, 21, 1000, "complete")),
+            ("dist_linkage average", lambda: engine.dist_linkage(rows, lens, 21, 1000, "average")),
+            ("dist_nj", lambda: engine.dist_nj(rows, lens, 21, 1000)),
+            ("dist_nj_support 3", lambda: engine.dist_nj_support(rows, lens, 21, 1000, 3)),
+            ("dist_medoids", lambda: engine.dist_medoids(rows, lens, 21, 1000, label)),
+            ("dist_to the medoids", lambda: engine.dist_to(rows, lens, 21, 1000, got["dist_medoids"][0])),
+            ("resample_rows", lambda: engine.resample_rows(rows, lens, 1000, 42, 0, 0.5)),
+            ("dist_cluster 0.05 device", lambda: device_forms(engine, rows, lens, "cluster")),
+            ("dist_mst device", lambda: device_forms(engine, rows, lens, "mst"))]
+    for what, call in more:
+        got[what] = call()
+        print(f"{what}: {digest(got[what])}", flush=True)
+
+
+def device_forms(engine, rows, lens, which):
+    """dist_cluster at 0.05 or dist_mst of the set with everything on the device; the tree's edges sorted, since they arrive in any order"""
+    import numpy as np
+    import torch
+
+    dev = torch.device("cuda")
+    n, stride = rows.shape
+    d_rows = torch.from_numpy(np.ascontiguousarray(rows).view(np.int64)).to(dev)
+    d_len = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.uint32).view(np.int32)).to(dev)
+    if which == "cluster":
+        label, degree = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        counts = engine.dist_cluster_device(d_rows.data_ptr(), d_len.data_ptr(), n, stride, 21, 1000, 0.05, label.data_ptr(), degree.data_ptr())
+        return [counts, label.cpu().numpy(), degree.cpu().numpy()]
+    out = [torch.zeros(n - 1, dtype=torch.int32, device=dev) for _ in range(4)]
+    m = engine.dist_mst_device(d_rows.data_ptr(), d_len.data_ptr(), n, stride, 21, 1000, *[o.data_ptr() for o in out])
+    return [m, sorted(zip(*[o.cpu().numpy().tolist() for o in out]))]
 
 
 def query_sets():
