@@ -1,4 +1,5 @@
-"""`python -m auriclass_amd.contain [-w | -n TOP [-c MIN_SHARED]] [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N] REF.msh QUERY.msh [QUERY.msh ...]`: which share of
+"""`python -m auriclass_amd.contain [-w | -n TOP [-c MIN_SHARED] | --all [-c MIN_SHARED] [--order best|ref]] [-i MIN_IDENTITY] [-v MAX_P] [-C] [-p N]
+REF.msh QUERY.msh [QUERY.msh ...]`: which share of
 each reference sketch of REF.msh every query sketch holds, from the sketch files alone (engine.contain_files).  One row per
 (query, reference): reference, query, identity, p-value, shared/n_ref, shared/n_qry -- within the window in which both
 sketches are complete, n_ref hashes of the reference and n_qry of the query lie, `shared` of them in both.  A sample that
@@ -14,7 +15,11 @@ then no longer repeat one another's row.
 exactly, then the larger `shared`, then the order in REF.msh -- best first; a query without hits prints nothing.  -i and -c
 (a hit shares at least MIN_SHARED hashes, default 1: a one-hash reference inside a tiny window reaches 1/1) say what a hit
 is and act before the cut; -v drops rows from the result already chosen and promotes none.  Not with -w, whose ranking is
-per hash, not per pair; -c needs -n."""
+per hash, not per pair; -c needs -n or --all.
+--all: per query EVERY reference that is a hit by -i and -c, with no cap, taken out on the device as CSR
+(engine.dist_contain_within): what -n cannot give when one mixed culture or one clade of near-identical references passes 64
+rows.  --order best (the default) prints a query's hits in the order of -n, --order ref in the order of REF.msh; -v drops
+rows; a query without hits prints nothing.  Not with -n or -w; --order needs --all."""
 from __future__ import annotations
 
 import argparse
@@ -30,7 +35,9 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("-v", dest="max_p_value", type=float, default=1.0, help="maximum p-value to report [1]")
     ap.add_argument("-w", dest="winner", action="store_true", help="winner-take-all: credit each shared hash to its best reference")
     ap.add_argument("-n", dest="top", type=int, default=None, help="per query only the TOP (1 .. 64) best references, ranked by shared/n_ref")
-    ap.add_argument("-c", dest="min_shared", type=int, default=None, help="with -n: a hit shares at least this many hashes [1]")
+    ap.add_argument("-c", dest="min_shared", type=int, default=None, help="with -n or --all: a hit shares at least this many hashes [1]")
+    ap.add_argument("--all", dest="all_hits", action="store_true", help="per query every reference that is a hit by -i and -c, with no cap")
+    ap.add_argument("--order", dest="order", choices=("best", "ref"), default=None, help="with --all: a query's hits best first or in reference order [best]")
     ap.add_argument("-C", dest="comment", action="store_true", help="show comment fields in place of the names")
     ap.add_argument("-p", dest="threads", type=int, default=1, help="ignored")
     ap.add_argument("reference", metavar="REF.msh")
@@ -46,7 +53,13 @@ def main(argv: List[str] = None) -> int:
     if args.top is not None and args.winner:
         sys.stderr.write("ERROR: contain -n ranks pairs and -w credits every hash to one reference: not both\n")
         return 1
-    if args.min_shared is not None and args.top is None:
+    if args.all_hits and (args.top is not None or args.winner):
+        sys.stderr.write("ERROR: contain --all lists every hit; -n cuts the list and -w credits every hash to one reference: not together\n")
+        return 1
+    if args.order is not None and not args.all_hits:
+        sys.stderr.write("ERROR: contain --order (the order of a query's hits) needs --all\n")
+        return 1
+    if args.min_shared is not None and args.top is None and not args.all_hits:
         sys.stderr.write("ERROR: contain -c (minimum shared hashes of a hit) needs -n\n")
         return 1
     if args.top is not None and not 1 <= args.top <= 64:
@@ -58,6 +71,8 @@ def main(argv: List[str] = None) -> int:
     more = {"winner": True} if args.winner else {}
     if args.top is not None:
         more = {"top": args.top, "min_shared": 1 if args.min_shared is None else args.min_shared}
+    if args.all_hits:
+        more = {"all_hits": True, "order": 0 if args.order == "ref" else 1, "min_shared": 1 if args.min_shared is None else args.min_shared}
     try:
         text = engine.contain_files(args.reference, args.queries, min_identity=args.min_identity, max_p_value=args.max_p_value, comment=args.comment, **more)
     except engine.EngineError as exc:

@@ -466,4 +466,36 @@ struct ContainSearchOut {
 };
 hipError_t launch_contain_take(const ContainSearchOut &o, hipStream_t st);
 
+// all references a query holds, as CSR (rules: mhx_contain_within.h, kernels: mhx_contain_within.hip).  A block's three counts
+// lie block-local as for the containment search; the queries of a super-batch have one cell per slice of 32 references in
+// mask / base [queries][nslices] as in WithinOut, which the take-out pass of every block fills: the ballot of
+// shared >= need[n_ref], and where the cell's keepers begin in the arrival list arr_shared / arr_n_ref / arr_n_qry [room]
+// (appended through *count, zero before the first block of the super-batch; at or beyond room they are only counted).
+// base null: the counting form, no list.
+struct ContainWithinOut {
+    const uint32_t *loc_shared, *loc_n_qry, *loc_n_ref;
+    const uint32_t *flag;    // non-zero: nothing is done
+    uint32_t r0, nr, q0, nq; // the block (mhx_search.h: SearchBlock); q0 counts from the super-batch's first query
+    const uint32_t *need;
+    uint32_t need_limit, nslices;
+    uint32_t *mask, *base;
+    uint32_t *arr_shared, *arr_n_ref, *arr_n_qry;
+    uint32_t room;
+    uint32_t *count;
+};
+hipError_t launch_contain_within_take(const ContainWithinOut &o, hipStream_t st);
+// Behind the last block, the last fallback and launch_within_scan of a super-batch of nq queries: every cell's keepers from
+// the arrival list to their final place (mhx_within.h: within_dest); places at or beyond cap are left out.  row_off points at
+// the entry of the super-batch's first query.
+struct ContainWithinRows {
+    const uint32_t *mask, *base;
+    uint32_t nq, nslices;
+    const uint64_t *row_off; // [nq + 1]
+    const uint32_t *arr_shared, *arr_n_ref, *arr_n_qry;
+    uint32_t room;
+    uint32_t *hit_ref, *hit_shared, *hit_n_ref, *hit_n_qry; // [cap] of the call
+    uint64_t cap;
+};
+hipError_t launch_contain_within_gather(const ContainWithinRows &o, hipStream_t st);
+
 } // namespace mhx

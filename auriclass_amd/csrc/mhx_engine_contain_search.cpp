@@ -28,10 +28,13 @@ struct ContainSearchCall { // everything on the device but `need`
     uint32_t *hit_ref, *hit_shared, *hit_n_ref, *hit_n_qry, *n_hits;
 };
 
+} // namespace
+
+namespace mhx {
 // The need table of the last call stays in the engine state, on the host, like the workspace it goes into: a bound between 0
 // and 1 costs about three pow per entry (some milliseconds at 50 000 entries), and the batches of a file-level call, or a
 // caller that searches set after set, ask for the same table again.  A call with another bound builds it anew.
-const uint32_t *need_table(uint32_t limit, int k, double min_identity, uint32_t min_shared)
+const uint32_t *contain_need_table(uint32_t limit, int k, double min_identity, uint32_t min_shared)
 {
     if (g.contain_need.size() != (size_t)limit + 1 || g.contain_need_k != k || g.contain_need_min_identity != min_identity ||
         g.contain_need_min_shared != min_shared) {
@@ -42,6 +45,18 @@ const uint32_t *need_table(uint32_t limit, int k, double min_identity, uint32_t 
     }
     return g.contain_need.data();
 }
+
+int contain_hit_check(uint32_t s_q, uint32_t s_r, uint32_t stride, int k, double min_identity, uint32_t min_shared)
+{
+    if (min_shared == 0) return fail(MHX_E_ARG, "min_shared must be at least 1");
+    if (!(min_identity == min_identity)) return fail(MHX_E_ARG, "min_identity is not a number");
+    if (k < 1 || k > 32) return fail(MHX_E_ARG, "bad k");
+    if (s_q == 0 || s_r == 0 || stride == 0) return fail(MHX_E_ARG, "bad s_q / s_r / stride");
+    return MHX_OK;
+}
+} // namespace mhx
+
+namespace {
 
 // Launches the whole call on the engine's stream and waits for it, on the schedule of mhx_engine_sets.h with the containment's
 // geometry.  The containment's finish pass and pair kernel write a block's [queries][32] counts block-local, and the take-out
@@ -99,11 +114,7 @@ int contain_search_device(ContainSearchCall &c)
 int contain_search_check(uint32_t s_q, uint32_t s_r, uint32_t stride, int k, double min_identity, uint32_t min_shared, uint32_t top)
 {
     if (top < 1 || top > kSearchMaxTop) return fail(MHX_E_ARG, "top must be 1 .. %u", kSearchMaxTop);
-    if (min_shared == 0) return fail(MHX_E_ARG, "min_shared must be at least 1");
-    if (!(min_identity == min_identity)) return fail(MHX_E_ARG, "min_identity is not a number");
-    if (k < 1 || k > 32) return fail(MHX_E_ARG, "bad k");
-    if (s_q == 0 || s_r == 0 || stride == 0) return fail(MHX_E_ARG, "bad s_q / s_r / stride");
-    return MHX_OK;
+    return contain_hit_check(s_q, s_r, stride, k, min_identity, min_shared);
 }
 
 // Host queries against references that are on the device already (refs) or on the host (r / r_len, refs null).  The lists
@@ -126,7 +137,7 @@ int contain_search_host(const uint64_t *q, const uint64_t *const *q_rows, const 
     for (uint32_t i = 0; i < nq; ++i) c.longest = std::max(c.longest, contain_eff_len(q_len[i], stride, s_q));
     if (!refs) for (uint32_t i = 0; i < nr; ++i) c.longest = std::max(c.longest, contain_eff_len(r_len[i], stride, s_r));
     c.need_limit = std::min(stride, s_r);
-    c.need = need_table(c.need_limit, k, min_identity, min_shared);
+    c.need = contain_need_table(c.need_limit, k, min_identity, min_shared);
     c.hit_ref = (uint32_t *)(in.room + o_ref); c.hit_shared = (uint32_t *)(in.room + o_shared); c.hit_n_ref = (uint32_t *)(in.room + o_nref);
     c.hit_n_qry = (uint32_t *)(in.room + o_nqry); c.n_hits = (uint32_t *)(in.room + o_n);
     rc = contain_search_device(c);
@@ -178,7 +189,7 @@ extern "C" int mhx_dist_contain_search(const uint64_t *q, const uint32_t *q_len,
         c.q = q; c.q_len = q_len; c.r = r; c.r_len = r_len; c.nq = nq; c.nr = nr; c.stride = stride; c.s_q = s_q; c.s_r = s_r; c.top = top;
         c.longest = std::min(stride, std::max(s_q, s_r));
         c.need_limit = std::min(stride, s_r);
-        c.need = need_table(c.need_limit, k, min_identity, min_shared);
+        c.need = contain_need_table(c.need_limit, k, min_identity, min_shared);
         c.hit_ref = hit_ref; c.hit_shared = hit_shared; c.hit_n_ref = hit_n_ref; c.hit_n_qry = hit_n_qry; c.n_hits = n_hits;
         return contain_search_device(c);
     });

@@ -133,7 +133,8 @@ struct Engine {
     int last_dist_fallbacks = 0;
     uint64_t last_contain_winner_pairs = 0; // pairs the claim pass of the last mhx_dist_contain_winner call walked
     int last_dist_ranges = 0;    // value ranges per block of the last distance call (0: generic kernel only)
-    // the need table of the last containment search (mhx_engine_contain_search.cpp: need_table), on the host, and what it was built from
+    // the need table of the last containment search or contain-within call (mhx_engine_contain_search.cpp: contain_need_table), on
+    // the host, and what it was built from
     std::vector<uint32_t> contain_need;
     int contain_need_k = 0;
     double contain_need_min_identity = 0.0;
@@ -213,6 +214,18 @@ uint32_t contain_ranges(uint32_t longest);
 int contain_search_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const SearchRefs &refs, uint32_t s_r, int k,
                         double min_identity, uint32_t min_shared, uint32_t top, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
                         uint32_t *hit_n_qry, uint32_t *n_hits);
+// What the containment search and mhx_dist_contain_within share (mhx_engine_contain_search.cpp): the argument checks that
+// both make (MHX_E_ARG with the message set), and the need table of a bound -- [limit + 1] on the host, kept in the engine
+// state until another (limit, k, min_identity, min_shared) comes.
+int contain_hit_check(uint32_t s_q, uint32_t s_r, uint32_t stride, int k, double min_identity, uint32_t min_shared);
+const uint32_t *contain_need_table(uint32_t limit, int k, double min_identity, uint32_t min_shared);
+// All references a query holds (mhx_engine_contain_within.cpp) of host queries, every row where it lies (q_len[i] <=
+// refs.stride entries each), against a reference set that the caller has put on the device (SearchRefs as for search_rows).
+// Outputs as the host form of mhx_dist_contain_within, the capacity protocol included.  What mhx_contain_files_within runs per
+// batch of queries.
+int contain_within_rows(const uint64_t *const *q_rows, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const SearchRefs &refs, uint32_t s_r, int k,
+                        double min_identity, uint32_t min_shared, uint64_t *row_off, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
+                        uint32_t *hit_n_qry, uint64_t cap, uint64_t *n_out);
 // Jackknife support of search hits (mhx_engine_support.cpp) with everything on the device: what mhx_dist_support's device form
 // runs, and mhx_search_files_support on the rows its search has staged.  first [nq][top] is a device pointer; the rep_*
 // outputs (each may be null) are device pointers too, or host pointers with host_out.  Uses g.dist_ws, not g.dist_in.

@@ -1,7 +1,7 @@
 // mhx_files_sets.cpp -- the file-level commands over sets of sketches (.msh files): `mash dist` (mhx_dist_files*), `mash
 // triangle` (mhx_triangle_files), the dereplication (mhx_cluster_files, mhx_cluster_reps_files), the single-linkage tree (mhx_tree_files), complete
 // and average linkage (mhx_linkage_files), neighbour joining (mhx_nj_files) and the reference-set search
-// (mhx_search_files), the bounded neighbourhood (mhx_within_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
+// (mhx_search_files), the bounded neighbourhood (mhx_within_files) and the containment from sketches (mhx_contain_files, mhx_contain_files_search, mhx_contain_files_within).  They read sketch files, call the device paths of the engine files and write Mash's text; the ingest
 // of sequence files is in mhx_files.cpp.  The commands of query files against one reference file (search, within, contain)
 // share their path check, the staging of the references on the device and the walk over the query files in batches
 // (set_paths_check, stage_refs, walk_query_files): a command supplies what follows its first query file and what a batch prints.
@@ -22,6 +22,7 @@
 
 #include "mhx_triangle.h"
 #include "mhx_within.h"
+#include "mhx_contain_search.h"
 #include "mhx_engine_internal.h"
 #include "mhx_internal.h"
 
@@ -1107,6 +1108,83 @@ extern "C" int mhx_contain_files_search(const char *ref_msh, const char *const *
                             fmt_g(pv) + "\t" + std::to_string(hs[p]) + "/" + std::to_string(hnr[p]) + "\t" + std::to_string(hs[p]) + "/" +
                             std::to_string(hnq[p]) + "\n";
                 }
+            return MHX_OK;
+        };
+        rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);
+        if (rc) return rc;
+        return put_text(text, stdout_buf, cap, need);
+    });
+}
+
+// Every reference a query holds, at file level: the reference file is read, checked and staged on the device ONCE, as
+// mhx_contain_files_search does; the query files are read one after the other and go to contain_within_rows in batches of
+// sketches, whose CSR the host prints row by row -- in reference order, or every row of the CSR sorted best first by
+// contain_better.  A batch whose hits exceed its buffers is repeated once with the size it reported.
+extern "C" int mhx_contain_files_within(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_within_opts *opts, char *stdout_buf,
+                                        size_t cap, size_t *need)
+{
+    return entry("mhx_contain_files_within", [&]() -> int {
+        mhx_contain_within_opts o{(uint32_t)sizeof(mhx_contain_within_opts), 0, 1, 0.0, 1, 1.0};
+        int rc = ref_msh && qry_msh && n_qry >= 1 ? take_opts("contain_within", opts, o) : MHX_OK;
+        if (rc) return rc;
+        rc = set_paths_check("contain", ref_msh, qry_msh, n_qry);
+        if (rc) return rc;
+        if (!(o.min_identity == o.min_identity) || !(o.max_p_value == o.max_p_value)) return fail(MHX_E_ARG, "contain: min_identity / max_p_value is not a number");
+        if (o.order > 1) return fail(MHX_E_ARG, "contain: order must be 0 (reference order) or 1 (best first)");
+        if (o.min_shared < 1) return fail(MHX_E_ARG, "contain: min_shared must be at least 1");
+        SketchSet R;
+        rc = msh_read_file(ref_msh, R); // (checks that every hash list ascends: MHX_E_FORMAT)
+        if (rc) return rc;
+        const int k = (int)R.kmer_size;
+        const uint32_t nr = (uint32_t)R.refs.size(), s_r = std::max<uint32_t>(1, R.sketch_size);
+        ResidentRefs resident;
+        const SearchRefs &refs = resident.refs;
+        uint32_t s_q = 1;
+        std::string text;
+        constexpr uint64_t kFirstRoom = 4096; // hits the buffers hold before a batch has asked for more
+        std::vector<uint32_t> hr, hs, hnr, hnq, order;
+        auto on_first_file = [&](const SketchSet &Q) { // the queries' sketch size, the references on the device, cut at theirs
+            s_q = std::max<uint32_t>(1, Q.sketch_size);
+            return stage_refs(R, s_r, s_q, "contain --all", resident);
+        };
+        auto flush = [&](const std::vector<const RefSketch *> &qs) -> int {
+            const uint32_t nq = (uint32_t)qs.size();
+            std::vector<const uint64_t *> qrows(nq);
+            std::vector<uint32_t> ql(nq);
+            std::vector<uint64_t> row_off((size_t)nq + 1);
+            for (uint32_t i = 0; i < nq; ++i) { // a list is the first s_q entries of its sketch at most
+                qrows[i] = qs[i]->hash_data(); ql[i] = (uint32_t)std::min<size_t>(qs[i]->hash_count(), s_q);
+            }
+            uint64_t found = 0, room = std::max<uint64_t>(hr.size(), std::min<uint64_t>((uint64_t)nq * nr, kFirstRoom));
+            int rc2 = MHX_OK;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                if (hr.size() < room) { hr.resize(room); hs.resize(room); hnr.resize(room); hnq.resize(room); }
+                rc2 = contain_within_rows(qrows.data(), ql.data(), nq, s_q, refs, s_r, k, o.min_identity, o.min_shared, row_off.data(), hr.data(), hs.data(),
+                                          hnr.data(), hnq.data(), hr.size(), &found);
+                if (rc2 != MHX_E_CAPACITY) break;
+                room = found;
+            }
+            if (rc2) return rc2;
+            clear_error();
+            for (uint32_t qi = 0; qi < nq; ++qi) {
+                const uint64_t lo = row_off[qi], hi = row_off[qi + 1];
+                order.resize((size_t)(hi - lo));
+                for (uint64_t t = lo; t < hi; ++t) order[(size_t)(t - lo)] = (uint32_t)(t - lo);
+                if (o.order == 1)
+                    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+                        return contain_better(ContainHit{hr[lo + a], hs[lo + a], hnr[lo + a], hnq[lo + a]}, ContainHit{hr[lo + b], hs[lo + b], hnr[lo + b], hnq[lo + b]});
+                    });
+                for (const uint32_t t : order) {
+                    const size_t p = (size_t)(lo + t);
+                    const RefSketch &ref = R.refs[hr[p]];
+                    const double identity = mhx_screen_identity(hs[p], hnr[p], k);
+                    const double pv = mhx_screen_p_value(hs[p], hnr[p], (double)qs[qi]->length, k);
+                    if (!(pv <= o.max_p_value)) continue;
+                    text += (o.comment ? ref.comment : ref.name) + "\t" + (o.comment ? qs[qi]->comment : qs[qi]->name) + "\t" + fmt_g(identity) + "\t" +
+                            fmt_g(pv) + "\t" + std::to_string(hs[p]) + "/" + std::to_string(hnr[p]) + "\t" + std::to_string(hs[p]) + "/" +
+                            std::to_string(hnq[p]) + "\n";
+                }
+            }
             return MHX_OK;
         };
         rc = walk_query_files(R, qry_msh, n_qry, on_first_file, flush);

@@ -238,6 +238,12 @@ def load() -> ctypes.CDLL:
                                               c.c_int]
         L.mhx_contain_files_search.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ContainSearchOpts), c.c_char_p, c.c_size_t,
                                                c.POINTER(c.c_size_t)]
+    if hasattr(L, "mhx_dist_contain_within"):   # (or older than contain --all)
+        L.mhx_dist_contain_within.argtypes = [c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_void_p, c.c_void_p, c.c_uint32, c.c_uint32, c.c_uint32,
+                                              c.c_int, c.c_double, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, u64p,
+                                              c.c_int]
+        L.mhx_contain_files_within.argtypes = [c.c_char_p, c.POINTER(c.c_char_p), c.c_int, c.POINTER(ContainWithinOpts), c.c_char_p, c.c_size_t,
+                                               c.POINTER(c.c_size_t)]
     _lib = L
     return L
 
@@ -442,8 +448,14 @@ class ContainSearchOpts(ctypes.Structure):
                 ("min_identity", ctypes.c_double), ("max_p_value", ctypes.c_double)]
 
 
+class ContainWithinOpts(ctypes.Structure):
+    """mhx_contain_within_opts of include/mhx.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("comment", ctypes.c_int32), ("order", ctypes.c_uint32), ("min_identity", ctypes.c_double),
+                ("min_shared", ctypes.c_uint32), ("max_p_value", ctypes.c_double)]
+
+
 def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p_value: float = 1.0, comment: bool = False,
-                  winner: bool = False, top=None, min_shared: int = 1) -> str:
+                  winner: bool = False, top=None, min_shared: int = 1, all_hits: bool = False, order: int = 1) -> str:
     """Which share of each reference sketch of REF.msh every query sketch holds, from the sketches alone (mhx_contain_files):
     one row "reference\\tquery\\tidentity\\tp-value\\tshared/n_ref\\tshared/n_qry" per (query, reference), the queries in
     argument then file order, the references in file order.  The sketch size of REF.msh may differ from the queries'.
@@ -453,10 +465,20 @@ def contain_files(ref_msh, qry_paths: Sequence, min_identity: float = 0.0, max_p
     stands in the place of `shared` in every column and in both filters.
     top = 1 .. 64 (mhx_contain_files_search): per query only the `top` references it holds the largest share of, ranked on the
     device (share, then `shared`, then file order), best first; min_identity and min_shared (>= 1) say what a hit is and act
-    before the cut, max_p_value drops rows from the result already chosen.  Not with `winner`.  top=None: the full table."""
+    before the cut, max_p_value drops rows from the result already chosen.  Not with `winner`.  top=None: the full table.
+    all_hits (mhx_contain_files_within): per query EVERY reference that is a hit by min_identity and min_shared, with no cap,
+    taken out on the device as CSR; order 1: best first as with `top`, order 0: in the order of REF.msh; max_p_value drops rows.
+    A query without hits prints nothing.  Not with `winner` or `top`."""
     init()
     files = [os.fsencode(str(p)) for p in qry_paths]
     arr = (ctypes.c_char_p * len(files))(*files)
+    if all_hits:
+        if winner or top is not None:
+            raise EngineError(MHX_E_ARG, "contain: all_hits lists every hit of a pair rule: not with winner or top")
+        wopts = ContainWithinOpts(ctypes.sizeof(ContainWithinOpts), int(bool(comment)), _count(order), float(min_identity), _count(min_shared),
+                                  float(max_p_value))
+        return _text_call(lambda buf, cap, need: load().mhx_contain_files_within(os.fsencode(str(ref_msh)), arr, len(files), ctypes.byref(wopts), buf,
+                                                                                 cap, need), guess=1 << 20)
     if top is not None:
         if winner:
             raise EngineError(MHX_E_ARG, "contain: top ranks pairs, the winner-take-all form ranks per hash: not both")
@@ -1558,6 +1580,64 @@ def dist_contain_search_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_
     _check(load().mhx_dist_contain_search(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, int(k), float(min_identity),
                                           _count(min_shared), _count(top), v(ref_ptr), v(shared_ptr), v(n_ref_ptr), v(n_qry_ptr), v(n_hits_ptr), 1))
     return load().mhx_last_dist_kernel_ms()
+
+
+def dist_contain_within(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int, k: int, min_identity: float = 0.0,
+                        min_shared: int = 1, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """For every query list ALL references it holds (mhx_dist_contain_within), as CSR: (row_off [nq + 1], ref, shared, n_ref,
+    n_qry); the hits of query i are [row_off[i], row_off[i + 1]) of the four arrays, ascending by reference index.  A hit is
+    dist_contain_search's: it shares at least min_shared (>= 1) hashes and has identity(shared, n_ref, k) >= min_identity.
+    Exact and the same from run to run.  Rows and lengths as dist_contain takes them; no [nq, nr] array exists anywhere.
+    cap: room for that many hits (default 65 536); when it is too small the call is repeated once with the size the library
+    reported."""
+    init()
+    q, q_len, r, r_len = _within_rows(q, q_len, r, r_len)
+    nq, nr, stride = q.shape[0], r.shape[0], q.shape[1]
+    cap = 1 << 16 if cap is None else int(cap)
+    row_off = np.zeros(nq + 1, dtype=np.uint64)
+    found = ctypes.c_uint64(0)
+    for _ in range(2):
+        ref, shared, n_ref, n_qry = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
+        rc = load().mhx_dist_contain_within(q.ctypes.data, q_len.ctypes.data, nq, int(s_q), r.ctypes.data, r_len.ctypes.data, nr, int(s_r), stride, int(k),
+                                            float(min_identity), _count(min_shared), row_off.ctypes.data, ref.ctypes.data, shared.ctypes.data,
+                                            n_ref.ctypes.data, n_qry.ctypes.data, cap, ctypes.byref(found), 0)
+        if rc != MHX_E_CAPACITY or found.value <= cap:
+            break
+        cap = found.value
+    _check(rc)
+    m = found.value
+    return row_off, ref[:m].copy(), shared[:m].copy(), n_ref[:m].copy(), n_qry[:m].copy()
+
+
+def dist_contain_within_counts(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int, k: int,
+                               min_identity: float = 0.0, min_shared: int = 1) -> np.ndarray:
+    """The counting form of dist_contain_within: row_off [nq + 1] alone (row_off[nq] the number of hits), no hit is stored."""
+    init()
+    q, q_len, r, r_len = _within_rows(q, q_len, r, r_len)
+    nq = q.shape[0]
+    row_off = np.zeros(nq + 1, dtype=np.uint64)
+    found = ctypes.c_uint64(0)
+    _check(load().mhx_dist_contain_within(q.ctypes.data, q_len.ctypes.data, nq, int(s_q), r.ctypes.data, r_len.ctypes.data, r.shape[0], int(s_r), q.shape[1],
+                                          int(k), float(min_identity), _count(min_shared), row_off.ctypes.data, None, None, None, None, 0,
+                                          ctypes.byref(found), 0))
+    return row_off
+
+
+def dist_contain_within_device(q_ptr: int, q_len_ptr: int, nq: int, s_q: int, r_ptr: int, r_len_ptr: int, nr: int, s_r: int, stride: int, k: int,
+                               min_identity: float, min_shared: int, row_off_ptr: int, ref_ptr: int, shared_ptr: int, n_ref_ptr: int, n_qry_ptr: int,
+                               cap: int) -> int:
+    """Device pointers in and out (row_off [nq + 1] of 64-bit words, the hit arrays [cap]; a sketch_segments_device result goes
+    straight in on either side): the CSR stays on the device, exact and in its final order -- the integers are those of
+    dist_contain_within bit for bit.  Lengths the host cannot see are clipped to the stride and the sketch size.  All four hit
+    pointers 0 with cap == 0 only counts.  Returns the number of hits; EngineError(MHX_E_CAPACITY) when it exceeds cap (row_off
+    is complete then, the message names the number)."""
+    init()
+    v = ctypes.c_void_p
+    found = ctypes.c_uint64(0)
+    _check(load().mhx_dist_contain_within(v(q_ptr), v(q_len_ptr), nq, int(s_q), v(r_ptr), v(r_len_ptr), nr, int(s_r), stride, int(k), float(min_identity),
+                                          _count(min_shared), v(row_off_ptr), v(ref_ptr or None), v(shared_ptr or None), v(n_ref_ptr or None),
+                                          v(n_qry_ptr or None), int(cap), ctypes.byref(found), 1))
+    return int(found.value)
 
 
 def dist_contain_winner(q: np.ndarray, q_len: np.ndarray, r: np.ndarray, r_len: np.ndarray, s_q: int, s_r: int, ref_length=None

@@ -30,6 +30,9 @@
  *   mhx_contain_files_search <- no mash command: mhx_contain_files followed by a sort per query, for a reference set too
  *                        large to print in full -- per query sketch the `top` references it holds the largest share of
  *                        (python -m auriclass_amd.contain -n TOP; buffer level: mhx_dist_contain_search)
+ *   mhx_contain_files_within <- no mash command: mhx_contain_files followed by a filter, for a reference set too large for
+ *                        the full table -- per query sketch EVERY reference it holds, with no cap, as CSR
+ *                        (python -m auriclass_amd.contain --all; buffer level: mhx_dist_contain_within)
  *   mhx_cluster_files <- no mash command: `mash triangle -E -d D` followed by a union-find over its edge list -- which
  *                        references of a set are the same thing within distance D, and one representative of each, as a
  *                        table and as a dereplicated sketch file (python -m auriclass_amd.cluster)
@@ -946,7 +949,8 @@ int mhx_contain_files_winner(const char *ref_msh, const char *const *qry_msh, in
  * block with the same take-out.  Nothing of size nq x nr exists anywhere.  MHX_SEARCH_GEOMETRY and MHX_SEARCH_QBATCH are
  * honoured; mhx_last_dist_kernel_ms, mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report this call too.
  * Not pinned by mash output (mash has no such command): pinned by the restated rule.
- * Not built: more than 64 hits per query, the ranking for the winner-take-all form, and what mhx_dist_contain lists. */
+ * More than 64 hits per query: mhx_dist_contain_within below.  Not built: the ranking for the winner-take-all form, and what
+ * mhx_dist_contain lists. */
 int mhx_dist_contain_search(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r,
                             const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, int k, double min_identity,
                             uint32_t min_shared, uint32_t top, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
@@ -966,6 +970,58 @@ typedef struct mhx_contain_search_opts {
     double max_p_value;   /* print rows with p <= max_p_value (1: all) */
 } mhx_contain_search_opts;
 int mhx_contain_files_search(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_search_opts *opts,
+                             char *stdout_buf, size_t cap, size_t *need);
+
+/* ALL REFERENCES A QUERY HOLDS, AS CSR: the containment search without its ceiling of 64 hits -- "which of the 100 000
+ * plasmids, marker loci or genomes we know are IN this sample, all of them" -- and without a cell per pair; no [nq][nr] array
+ * exists anywhere.  A Jaccard bound (mhx_dist_within) cannot stand in, for the reason given at mhx_dist_contain_search.
+ * q / q_len / r / r_len / stride / s_q / s_r as mhx_dist_contain takes them, whose three integers a pair's are.
+ * Rule (auriclass_amd/csrc/mhx_contain_within.h, restated in tests/contain_within_rule.py): a pair (q, r) is a hit iff it is
+ * one for mhx_dist_contain_search -- shared >= min_shared (>= 1) and identity(shared, n_ref, k) >= min_identity in host libm
+ * doubles.  min_identity <= 0 keeps every pair that shares at least min_shared hashes, min_identity > 1 none.
+ * Outputs: the hits of query q are hit_ref / hit_shared / hit_n_ref / hit_n_qry [row_off[q] .. row_off[q + 1]), ascending by
+ * reference index; row_off [nq + 1], row_off[0] == 0, row_off[nq] == *n_out (host, always).
+ * Exact in both forms, which return the same integers bit for bit, and the same from run to run, whatever the batch sizes are
+ * and whenever a flagged block is redone: the bound reaches the kernels as the need table of mhx_dist_contain_search, there is
+ * no prefilter and no host post-filter.  device_ptrs != 0: all pointers but n_out are device pointers (a result of
+ * mhx_sketch_segments goes straight in on either side), and lengths the host cannot see are clipped as mhx_dist_contain does.
+ * Capacity: cap is the room of the hit arrays in entries.  *n_out > cap: MHX_E_CAPACITY; row_off and *n_out are complete and
+ * correct then (the hit arrays hold nothing of use), so the caller sizes the arrays exactly and calls once more.
+ * All four hit arrays NULL with cap == 0 is the counting form: MHX_OK, only row_off and *n_out are written; it keeps no
+ * arrival list and does no atomic.
+ * nq == 0: MHX_OK, nothing written but *n_out = 0.  nr == 0: MHX_OK, row_off zeroed, *n_out = 0.  MHX_E_ARG, before anything
+ * is launched: min_shared == 0, min_identity not a number, k outside 1 .. 32, s_q, s_r or stride zero, a null required
+ * pointer, a len > stride (host form).
+ * On the device: the schedule of mhx_dist_contain_search inside the super-batches of mhx_dist_within;
+ * behind every block one half-wave per (query, slice of 32 references) ballots shared >= need[n_ref] into one mask word and
+ * appends its keepers (shared, n_ref, n_qry) to an arrival list with one atomic per wave; behind the last block of a
+ * super-batch the scan of mhx_dist_within gives row_off and a gather puts every hit in its final place.  Tiny calls,
+ * MHX_DIST_GENERIC and lists above 65 536 entries go through the pair kernel per block with the same take-out.
+ * MHX_SEARCH_GEOMETRY, MHX_SEARCH_QBATCH and MHX_WITHIN_CELLS are honoured; mhx_last_dist_kernel_ms,
+ * mhx_last_dist_fallback_blocks and mhx_last_dist_ranges report this call too.
+ * Not pinned by mash output (mash has no such command): pinned by the restated rule.
+ * Not built: max-containment or the query-in-reference identity as hit rule, the winner-take-all form, support values, a
+ * p-value filter on the device. */
+int mhx_dist_contain_within(const uint64_t *q, const uint32_t *q_len, uint32_t nq, uint32_t s_q, const uint64_t *r,
+                            const uint32_t *r_len, uint32_t nr, uint32_t s_r, uint32_t stride, int k, double min_identity,
+                            uint32_t min_shared, uint64_t *row_off, uint32_t *hit_ref, uint32_t *hit_shared, uint32_t *hit_n_ref,
+                            uint32_t *hit_n_qry, uint64_t cap, uint64_t *n_out, int device_ptrs);
+/* The same at file level: for every query sketch, in argument order and then file order, EVERY reference it holds as one
+ * mhx_contain_files row (the same six columns, the same %g); a query without hits prints nothing.  order 0: the hits of a
+ * query in reference order; order 1: best first in the order of mhx_dist_contain_search (the host sorts each row of the CSR).
+ * Rows with p > max_p_value are dropped on the host.  opts == NULL means {sizeof, 0, 1, 0, 1, 1}.  Checks and messages are
+ * mhx_contain_files_search's; order outside 0 .. 1 or min_shared == 0 is MHX_E_ARG.  The reference file is read, checked and
+ * staged on the device once; the query files go there in batches of 4096 sketches with room for 4096 hits at first, and a
+ * batch whose hits exceed its buffers is repeated once with the size the device reported (the buffers stay that large). */
+typedef struct mhx_contain_within_opts {
+    uint32_t struct_size; /* sizeof(mhx_contain_within_opts) */
+    int32_t comment;      /* comment fields in place of names */
+    uint32_t order;       /* 0: reference order, 1: best first */
+    double min_identity;  /* a hit has identity >= min_identity (0: all) */
+    uint32_t min_shared;  /* a hit shares at least this many hashes, >= 1 */
+    double max_p_value;   /* print rows with p <= max_p_value (1: all) */
+} mhx_contain_within_opts;
+int mhx_contain_files_within(const char *ref_msh, const char *const *qry_msh, int n_qry, const mhx_contain_within_opts *opts,
                              char *stdout_buf, size_t cap, size_t *need);
 
 /* Segmented sketch: one bottom-s list per segment of ONE dense stream (`mash sketch -i` at buffer level).
